@@ -12,7 +12,10 @@ launches the N ranks ITSELF (one child per GPU, LOCAL_RANK = GPU index, rendezvo
 torchrun / torch.distributed.run it uses the ranks it was given.  `n_gpus` in the output is the world size RCCL saw,
 and a WORLD_SIZE that differs from --gpus is an error (exit status 2), never a silent single-GPU run.
 
-Prints ONE JSON line (rank 0).  Besides the driver's fields it carries
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up, priming, --warmup steps, the
+--steps timed steps (`value`, `ms_per_step`, `timing.per_step_ms`) and, with --dump-outputs DIR, the enhanced PCM of the last
+timed step (a fixed, seeded sample of the streams, float32) as DIR/*.npy.  The handle's stream state is reset in front of the
+warm-up, so the same arguments give the same outputs from run to run.  With --full the line also carries
   roofline      dominant kernel (by device time) priced against its bound: algorithmic work per launch / mean launch
                 duration measured with HIP events on the engine's stream in a second, identical pass
   stages        the same for every kernel class (HBM-bound stages also against the bytes they were measured to move)
@@ -24,6 +27,8 @@ Prints ONE JSON line (rank 0).  Besides the driver's fields it carries
                 4096 streams, the host-pointer (PCIe-inclusive) paths -- synchronous calls on pageable and page-locked
                 buffers, asynchronous calls rotating over three page-locked buffer pairs -- and the |GPU - oracle|
                 histogram of the timed batch's first call
+  parity        the timed batch's first call against the oracle; a run that misses its bars exits with status 3
+and the sustained sclk / board power (--sustain-seconds), the board state before the timed region and a device copy rate.
 """
 import argparse
 import json
@@ -67,7 +72,12 @@ def parse_args():
                          'leave its idle clocks (sclk ~100 MHz), and the workload then runs against the 1400 W board power cap')
     ap.add_argument('--sustain-seconds', type=float, default=4.0,
                     help='untimed stretch of the same step after the timed region during which the sustained sclk / board power '
-                         'are sampled (0: skip)')
+                         'are sampled (0: skip; --full only)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything besides the headline: per-kernel pass, sustained clock, CPU baseline, '
+                         'parity against the oracle, HBM traffic, the other operating points')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the enhanced PCM of the last timed step (a fixed, seeded sample of the streams) as DIR/*.npy')
     ap.add_argument('--streams', type=int, default=4096, help='streams per GPU')
     ap.add_argument('--frames', type=int, default=64, help='frames per stream per call (64 = 1.02 s of audio)')
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp32'])
@@ -79,7 +89,27 @@ def parse_args():
     ap.add_argument('--library', default=None, help='alternative libpv_koala.so (developer A/B runs)')
     ap.add_argument('--dist-backend', default='nccl', help='nccl (= RCCL over xGMI) for real runs; gloo only to test the '
                     'multi-rank code path on a single-GPU box together with KOALA_BENCH_SHARE_GPU=1')
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return a
+
+
+_MODEL_DIR = []
+
+
+def seeded_model(kind, seed=1234):
+    """The seeded random parameter file of `kind` (15-16 MB, ~50 ms to write), written by this process into a temporary directory
+    that is removed when it exits: the bench writes nothing into the tree, which may be read-only to the user who runs it, and
+    never picks up a file that another revision of the generator left behind."""
+    import atexit
+    import shutil
+    import tempfile
+    from koala_amd import params
+    if not _MODEL_DIR:
+        _MODEL_DIR.append(tempfile.mkdtemp(prefix='koala_bench_'))
+        atexit.register(shutil.rmtree, _MODEL_DIR[0], True)
+    return params.ensure_params(os.path.join(_MODEL_DIR[0], '%s_%d.kns' % (kind, seed)), kind, seed)
 
 
 def launch_ranks(args):
@@ -253,10 +283,9 @@ def cpu_leg_child(T, distinct):
     """The cpu_baseline leg proper, in its own process (started by main() with the OpenMP binding in its environment): the oracle
     ("port") on a bounded sample of the bench workload -- calibrated for ~15 s -- plus one thread for scale.  Prints one JSON line."""
     import numpy as np
-    from koala_amd import params
     from koala_amd.workload import synth_streams
     from oracle import oracle
-    model = params.ensure_params(os.path.join(ROOT, 'build', 'random_1234.kns'), 'random', 1234)
+    model = seeded_model('random', 1234)
     native = oracle.build_native()
     threads = int(os.environ.get('OMP_NUM_THREADS', '0')) or (os.cpu_count() or 1)
     base = synth_streams(distinct, T, seed=1234)
@@ -310,9 +339,58 @@ def machine_state():
     return st
 
 
+DUMP_STREAMS = 512        # streams of the last timed step's output that --dump-outputs writes (32 MiB at 64 frames per call)
+DUMP_BYTES = 48 << 20     # ... fewer for longer calls
+
+
+def dump_outputs(path, dy, np):
+    """What a caller of the timed path receives -- the enhanced int16 PCM [streams, frames * 256] -- after the last timed step, as
+    float32: a fixed, seeded sample of the streams (the same ones in every run with the same --streams, in stream order) and their
+    indices."""
+    import torch
+    B, n = dy.shape
+    rows = min(B, DUMP_STREAMS, max(1, DUMP_BYTES // (4 * n)))
+    idx = np.sort(np.random.default_rng(1234).choice(B, size=rows, replace=False))
+    pcm = dy[torch.from_numpy(idx).to(dy.device)].cpu().numpy().astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'enhanced_pcm.npy'), pcm)
+    np.save(os.path.join(path, 'enhanced_pcm_streams.npy'), idx.astype(np.float64))
+
+
+def headline(args, value, elapsed_max, world, collective, cores_per_rank, timing):
+    """The fields of the result line that every run reports."""
+    B, T = args.streams, args.frames
+    return {
+        'metric': '16 kHz frames/sec (batch 4096 streams per GPU)',
+        'value': round(value, 1),
+        'unit': 'frames/s',
+        'n_gpus': world,
+        'steps': args.steps,
+        'warmup': args.warmup,
+        'ms_per_step': round(elapsed_max / args.steps * 1e3, 4),
+        'higher_is_better': True,
+        'scaling': 'weak',
+        'vs_baseline': None,
+        'dtype': args.precision,
+        'data': 'synthetic (seeded AR(2)+AM speech-like int16 streams; seeded random KNS1 parameters)',
+        'config': {
+            'workload': 'BASELINE configs[2]: batch=%d streams/GPU x %d frames/call, %s mask GEMMs on MFMA + fp32 FFT'
+                        % (B, T, args.precision),
+            'streams_per_gpu': B, 'frames_per_call': T, 'global_streams': B * world,
+            'parallelism': 'streams sharded over %d GPU(s), no data-path collective' % world,
+            'throughput_all_reduce': collective,  # 'nccl' (= RCCL) under a launcher, None for a plain single-process run
+            'host_cores_per_rank': cores_per_rank,
+        },
+        'real_time_factor': round(elapsed_max / (args.steps * T * 256 / 16000.0) / B, 9),
+        'frames_per_sec_per_gpu': round(value / world, 1),
+        'full': bool(args.full),
+        # HIP-event time of every timed step, what priming did (and with --full the board's clock / power right before the timed region)
+        'timing': timing,
+    }
+
+
 def extra_points(args, torch, np, koala_amd, model, kb, x, dx, dy, base, local_rank):
     """The other BASELINE operating points, on the same box in the same run (rank 0 of a single-GPU run)."""
-    from koala_amd import params
     from koala_amd.workload import synth_streams
     B, T = args.streams, args.frames
     out = {}
@@ -371,7 +449,7 @@ def extra_points(args, torch, np, koala_amd, model, kb, x, dx, dy, base, local_r
 
     # -- KNS-v1.1: the same batch with the reference model file's front-end topology (a linear layer over FIVE stacked feature
     # frames, koala_params.pv record [1285, 271]: + 4 x 257 x 271 = 278 588 MAC per stream-frame, 3 992 914 in all)
-    m5 = params.ensure_params(os.path.join(ROOT, 'build', 'random5_1234.kns'), 'random5', 1234)
+    m5 = seeded_model('random5', 1234)
     k5 = koala_amd.create_batch('bench', B, T, args.precision, model_path=m5, device=dev, library_path=args.library)
     k5.set_stream(torch.cuda.current_stream().cuda_stream)
     dt = time_steps(lambda: k5.process_device(T, dx.data_ptr(), dy.data_ptr()), sync, 100, 10)
@@ -532,7 +610,6 @@ def main():
     import torch
 
     import koala_amd
-    from koala_amd import params
     from koala_amd.sharding import aggregate_throughput, shard_range
     from koala_amd.workload import synth_streams
 
@@ -578,7 +655,7 @@ def main():
             pass
 
     koala_amd.build_native()
-    model = params.ensure_params(os.path.join(ROOT, 'build', 'random_1234.kns'), 'random', 1234)
+    model = seeded_model('random', 1234)
     B, T = args.streams, args.frames
     first, _ = shard_range(B * world, rank, world)
 
@@ -607,12 +684,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # the first call after creation is also the parity sample (checked against the oracle further down)
+    # the first call after creation is also the parity sample (checked against the oracle further down, --full)
     step()
     torch.cuda.synchronize()
-    first_call = dy[:distinct].cpu().numpy() if (rank == 0 and world == 1) else None
+    first_call = dy[:distinct].cpu().numpy() if (args.full and rank == 0 and world == 1) else None
     # ... and its masks (the mask head's output buffer, read back through the debug tap; only the parity leg uses them)
-    first_mask = kb.debug_read('mask', T)[:, :distinct] if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    first_mask = kb.debug_read('mask', T)[:, :distinct] if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
 
     # ---- priming, untimed (see --prime-seconds): the board's clock / power state follows the load with a lag of tens of milliseconds,
     # and a burst that starts from an idle or half-ramped board runs its first steps 5-10 % slower than steady state (round 5: the
@@ -635,7 +712,7 @@ def main():
     board_before = None
     t_prime = time.perf_counter()
     if args.prime_seconds > 0:
-        sampler = BoardSampler(local_rank) if rank == 0 else None
+        sampler = BoardSampler(local_rank) if (args.full and rank == 0) else None
         if sampler:
             sampler.__enter__()
         pending, hist = timed_group(8), []
@@ -676,6 +753,9 @@ def main():
         for _ in range(24):
             step()
         prime['steps'] += 24
+    # every stream starts from silence again (one kernel on the bench stream, no host synchronisation): how many steps priming
+    # took depends on the board, and the outputs of the timed steps must depend on --warmup and --steps only
+    kb.reset()
     for _ in range(args.warmup):
         step()
     barrier()
@@ -687,6 +767,20 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     per_step_ms = [round(v, 4) for v in group_ms(timed_ev)] if timed_ev else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dy, np)
+    if not args.full:
+        frames_total, elapsed_max = aggregate_throughput(B * T * args.steps, elapsed)
+        kb.delete()
+        if collective:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(headline(args, frames_total / elapsed_max, elapsed_max, world, collective, cores_per_rank,
+                                      {'per_step_ms': per_step_ms, 'prime': prime})))
+            sys.stdout.flush()
+        return
     # A further untimed stretch of the same step gives the figures the MFMA fractions are also quoted against
     # (`frac_at_sustained_sclk`: the board runs this workload AT its 1.4 kW cap, ~2.0 GHz instead of 2.4) and the throughput over
     # four seconds; since round 6's priming the timed region starts from that same state.
@@ -903,29 +997,9 @@ def main():
         dist.destroy_process_group()
     if rank != 0:
         return
-    line = {
-        'metric': '16 kHz frames/sec (batch 4096 streams per GPU)',
-        'value': round(value, 1),
-        'unit': 'frames/s',
-        'n_gpus': world,
-        'steps': args.steps,
-        'warmup': args.warmup,
-        'ms_per_step': round(elapsed_max / args.steps * 1e3, 4),
-        'higher_is_better': True,
-        'scaling': 'weak',
-        'vs_baseline': None,
-        'dtype': args.precision,
-        'data': 'synthetic (seeded AR(2)+AM speech-like int16 streams; seeded random KNS1 parameters)',
-        'config': {
-            'workload': 'BASELINE configs[2]: batch=%d streams/GPU x %d frames/call, %s mask GEMMs on MFMA + fp32 FFT'
-                        % (B, T, args.precision),
-            'streams_per_gpu': B, 'frames_per_call': T, 'global_streams': B * world,
-            'parallelism': 'streams sharded over %d GPU(s), no data-path collective' % world,
-            'throughput_all_reduce': collective,  # 'nccl' (= RCCL) under a launcher, None for a plain single-process run
-            'host_cores_per_rank': cores_per_rank,
-        },
-        'real_time_factor': round(elapsed_max / (args.steps * T * 256 / 16000.0) / B, 9),
-        'frames_per_sec_per_gpu': round(value / world, 1),
+    line = headline(args, value, elapsed_max, world, collective, cores_per_rank,
+                    {'per_step_ms': per_step_ms, 'prime': prime, 'board_before_t0': board_before})
+    line.update({
         'roofline': roofline,
         'peaks': peaks,
         'stages': stages,
@@ -933,12 +1007,10 @@ def main():
         # cent slower than the timed one (the events serialise the launches): both step times, so the shares can be scaled
         'stages_pass': {'ms_per_step': round(instrumented_ms_per_step, 4), 'sum_of_class_ms': round(dev_ms, 4),
                         'timed_ms_per_step': round(elapsed_max / args.steps * 1e3, 4)},
-        # HIP-event time of every timed step, what priming did, and the board's clock / power right before the timed region
-        'timing': {'per_step_ms': per_step_ms, 'prime': prime, 'board_before_t0': board_before},
         'cpu_baseline': cpu,
         'parity': parity,
         'extra': extra,
-    }
+    })
     print(json.dumps(line))
     sys.stdout.flush()
     if parity is not None and not parity['pass']:

@@ -6,7 +6,7 @@ Bars (BASELINE.json north_star / DESIGN.md section 5):
                 for value (since round 4 the spec's FFT is the transform the kernels evaluate, operation for operation)
   bf16 engine : mask within 1e-3 RMS of the fp32 oracle; PCM within 5 LSB of the oracle run with the same
                 rounding points (bf16 GEMM operands, fp16 pre-activations); share of samples within 1 LSB: >= 99 % on the real-speech
-                histogram of this file (102 400 samples: 99.1 % measured), >= 99.9 % on the bench's timed batch (enforced by bench.py)
+                histogram of this file (102 400 samples: 99.1 % measured), >= 99.9 % on the bench's timed batch (enforced by bench.py --full)
                 and on the default-model soak below
 Size-independent properties are checked at BASELINE's full batch (4096 streams).
 """
@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 # Bar 5 LSB (the same as __graft_entry__.smoke(), whose white-noise sample measures 4; this suite's own maximum is 3) plus the
 # distribution checked wherever a histogram is taken.  Constants, not knobs: nothing in the environment can loosen them.
 BF16_TOL = 5
-# share of samples within 1 LSB: 99.99 % over the bench's 16.8 M samples of synthetic streams (bench.py fails its run below
+# share of samples within 1 LSB: 99.99 % over the bench's 16.8 M samples of synthetic streams (bench.py --full fails its run below
 # 99.9 %); on real speech through the random-weight model (test_bf16_against_both_oracles, 102 400 samples) 99.1 % measured
 BF16_WITHIN_1 = 0.99
 # fp32 engine: the oracle's values, every one of them

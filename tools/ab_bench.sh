@@ -28,7 +28,7 @@ for v in "$@"; do
 done
 for rep in 1 2; do
   for j in $(seq 0 $((i-1))); do
-    python bench.py --library $PWD/build/ab/libv$j.so --no-cpu-baseline --steps ${AB_STEPS:-600} 2>/dev/null | python -c "
+    python bench.py --full --library $PWD/build/ab/libv$j.so --no-cpu-baseline --steps ${AB_STEPS:-600} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('variant $j rep $rep: %.2f Mframes/s  %.4f ms/step | ' % (d['value']/1e6, d['ms_per_step']) + '  '.join('%s %.1f' % (k, v['avg_launch_ms']*1e3) for k,v in d['stages'].items()))"

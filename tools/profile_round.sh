@@ -13,5 +13,5 @@ rm -rf $OUT/stats
 bash $ROOT/tools/pmc_run.sh $TAG > /dev/null 2>&1
 python $ROOT/tools/pmc_to_json.py $ROOT/gpurun_out/pmc_$TAG $OUT/pmc.json "$(cat $ROOT/build/head_commit.txt 2>/dev/null)" > /dev/null
 cp $ROOT/gpurun_out/pmc_$TAG/summary.txt $OUT/pmc_summary.txt
-cd $ROOT && cp $OUT/pmc.json profiles/${TAG}_pmc.json && python bench.py > $OUT/bench.json 2> $OUT/bench.err
+cd $ROOT && cp $OUT/pmc.json profiles/${TAG}_pmc.json && python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
