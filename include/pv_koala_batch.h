@@ -56,6 +56,34 @@ PV_API pv_status_t pv_koala_batch_process_chunk(pv_koala_batch_t *object, int32_
 PV_API pv_status_t pv_koala_batch_process_chunk_async(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
                                                       int16_t *enhanced);
 
+/* pv_koala_batch_process_chunk with PER-FRAME STREAM RESETS.  `reset` is HOST memory, uint8 [num_streams][num_frames] (row-major, one
+ * row per stream); NULL means no resets.  If reset[b][t] != 0, stream b is set to the fresh state (analysis history, overlap-add tail and
+ * the eight GRU hidden states, as pv_koala_batch_reset would leave them) immediately before frame t of this call, and its output from
+ * frame t on is exactly what a freshly reset stream produces.  A stream may reset at any number of frames of one call, adjacent ones,
+ * frame 0 and frame num_frames - 1 included, so utterances shorter than a call can be packed back to back into one stream.
+ * Equivalent definition: the call gives the same result as cutting it at each stream's reset frames into consecutive sub-calls with
+ * pv_koala_batch_reset of exactly those streams between them -- fp32: the same samples; bf16: within the same bar as against the bf16
+ * oracle.  A NULL or all-zero mask makes the call pv_koala_batch_process_chunk, route and bits.  Resets at frame 0 only are carried out
+ * by the reset kernel in front of the call, which then keeps its route; resets at a later frame put the call (host calls of 4 MiB or more:
+ * each sub-chunk that holds one) on the chunked kernels' reset arms at every batch size.
+ * Pointers as for pv_koala_batch_process_chunk: host pointers synchronous, device pointers enqueued on the handle's stream without a host
+ * wait (a caller that runs more than four such calls ahead of the GPU waits for the oldest one's mask upload).  `reset` is read before the
+ * function returns.  Arguments: as pv_koala_batch_process_chunk (PV_STATUS_INVALID_ARGUMENT: NULL object / pcm / enhanced, num_frames
+ * outside [1, max_frames_per_call]); in addition PV_STATUS_INVALID_ARGUMENT, with a message on the error stack, for a model with a
+ * several-frame front-end (KNS-v1.1, front_taps > 1) and a non-zero reset[b][t] at any t > 0: nothing is processed and the state is
+ * unchanged.
+ * A corpus job (many independent files on one handle, koala_amd/corpus.py): every stream is a slot that plays one file after the other;
+ * each file is laid out as ceil(samples / 256) + 1 frames (the last one a zero flush frame: delay_sample is one frame) and its first
+ * frame carries the reset bit; the output of file f is its frames' output from sample delay_sample on, trimmed to its length. */
+PV_API pv_status_t pv_koala_batch_process_chunk_resets(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
+                                                       int16_t *enhanced, const uint8_t *reset);
+
+/* The same for page-locked host buffers, asynchronous: the rules of pv_koala_batch_process_chunk_async (at most three calls in flight,
+ * `enhanced` valid once the call has completed).  `reset` is copied before the function returns into storage of the call's own in-flight
+ * slot: the caller may overwrite it at once. */
+PV_API pv_status_t pv_koala_batch_process_chunk_resets_async(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
+                                                             int16_t *enhanced, const uint8_t *reset);
+
 /* Blocks until at most `max_in_flight` asynchronous calls of the handle are still in flight (0: all have completed; calls complete in
  * order).  The triple-buffering loop of a host caller:  for call n:  pv_koala_batch_async_wait(o, 2)  -- call n - 3 is complete: take its
  * `enhanced`, refill its `pcm` --  then pv_koala_batch_process_chunk_async(o, frames, pcm[n % 3], enhanced[n % 3]). */

@@ -362,6 +362,15 @@ __device__ __forceinline__ void buf_store_f32x4(__amdgpu_buffer_rsrc_t r, unsign
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, 0);
 }
+// Per-frame stream resets (the reset arms of the analysis, synthesis and recurrent kernels): the rows of m-tile `mt` that restart at frame
+// `t`, bit r = row r.  The word is the same for the whole workgroup and read through the constant address space, so it arrives in an
+// SGPR by a scalar load (the table is written before the launch and only read during it): a step with no reset pays one scalar load
+// and one uniform branch.
+__device__ __forceinline__ unsigned reset_rows(const unsigned *resets, int pitch, int mt, int t) {
+    typedef const __attribute__((address_space(4))) unsigned *cptr_t;
+    return __builtin_amdgcn_readfirstlane(((cptr_t) resets)[(size_t) mt * pitch + t]);
+}
+
 // `gi` is written once and read once (428 MB per layer at the bench shape, more than the 256 MB memory-side cache): both sides
 // mark it non-temporal (aux = 2), which leaves the cache to the hidden sequences the next kernels re-read -- +0.5 % on the step, the
 // narrow heads 42 -> 39 us (round 4; either side alone measured -0.2 ... -0.4 %)

@@ -709,6 +709,10 @@ Engine::~Engine() {
     if (h_frame_word_) (void) hipHostFree(h_frame_word_);
     if (h_in_) (void) hipHostFree(h_in_);
     if (h_out_) (void) hipHostFree(h_out_);
+    for (int i = 0; i < kResetRing; ++i) {
+        if (h_rs_[i]) (void) hipHostFree(h_rs_[i]);
+        if (rs_ev_[i]) (void) hipEventDestroy(rs_ev_[i]);
+    }
     for (int i = 0; i < 4; ++i)
         if (aev_out_[i]) (void) hipEventDestroy(aev_out_[i]);
     for (int i = 0; i < 2; ++i) {
@@ -800,9 +804,7 @@ bool Engine::synchronize(std::string *err) {
     return true;
 }
 
-bool Engine::reset(const uint8_t *host_mask, std::string *err) {
-    (void) hipSetDevice(device_);
-    // (the reset kernel is ordered behind every enqueued call on the handle's stream; nothing to drain)
+ResetArgs Engine::reset_args(const uint8_t *d_mask) const {
     ResetArgs r;
     r.hist = d_hist_[0];
     r.hist2 = d_hist_[1];
@@ -815,7 +817,14 @@ bool Engine::reset(const uint8_t *host_mask, std::string *err) {
     r.silent = d_silent_;
     r.fhist_frames = taps_ > 1 ? taps_ : 0;
     r.nbf = nbf_;
-    r.mask = nullptr;
+    r.mask = d_mask;
+    return r;
+}
+
+bool Engine::reset(const uint8_t *host_mask, std::string *err) {
+    (void) hipSetDevice(device_);
+    // (the reset kernel is ordered behind every enqueued call on the handle's stream; nothing to drain)
+    ResetArgs r = reset_args(nullptr);
     if (host_mask) {
         std::vector<uint8_t> m((size_t) Bpad_, 0);
         memcpy(m.data(), host_mask, (size_t) B_);
@@ -834,6 +843,92 @@ bool Engine::reset(const uint8_t *host_mask, std::string *err) {
         *err = std::string("HIP error: ") + hipGetErrorString(e);
         return false;
     }
+    return true;
+}
+
+// Per-frame stream resets of the call about to run (the mask parked by park_resets, uint8 [B][T] host memory), before anything of the call
+// is enqueued.  Resets at frame 0 only: the reset kernel in front of the call, which then takes its normal route.  Resets at some frame
+// t > 0 (refused for a several-frame front-end, whose feature history the reset arms do not rebuild): the mask is packed per (m-tile,
+// frame) into a page-locked ring slot -- bit r of word [mt][t] = stream 16 mt + r restarts right before frame t -- which run_device uploads
+// on the stream of the call's kernels and reads through the kernels' reset arms (kRouteChunkedResets).  A slot is reused four calls
+// later, after the copy that read it has completed (an event): the asynchronous window is three calls, and a device-pointer caller waits
+// only when it is four calls ahead of the GPU.
+bool Engine::begin_resets(int T, const uint8_t *mask, std::string *err) {
+    rs_active_ = false;
+    rs_t0_ = 0;
+    if (!mask) return true;
+    bool first = false, late = false;
+    for (int b = 0; b < B_; ++b) {
+        const uint8_t *row = mask + (size_t) b * T;
+        first = first || row[0];
+        for (int t = 1; t < T && !late; ++t) late = row[t] != 0;
+    }
+    if (!first && !late) return true;  // (an all-zero mask: the plain call, same route and bits)
+    if (late && taps_ > 1) {
+        *err = "per-frame stream resets after frame 0 are not supported for models with a several-frame front-end (front_taps > 1).";
+        return false;
+    }
+    const int mtb = Bpad_ / 16;
+    const size_t slot_bytes = std::max((size_t) mtb * Tmax_ * 4, (size_t) Bpad_);
+    if (!d_rs_) {  // first use: the ring and the device table
+        bool ok = true;
+        for (int i = 0; i < kResetRing && ok; ++i) {
+            ok = hipHostMalloc((void **) &h_rs_[i], slot_bytes, hipHostMallocDefault) == hipSuccess;
+            ok = ok && hipEventCreateWithFlags(&rs_ev_[i], hipEventDisableTiming) == hipSuccess;
+        }
+        unsigned *d = ok ? (unsigned *) dalloc((size_t) mtb * Tmax_ * 4, false) : nullptr;
+        if (!d) {
+            (void) hipGetLastError();
+            for (int i = 0; i < kResetRing; ++i) {
+                if (h_rs_[i]) (void) hipHostFree(h_rs_[i]);
+                if (rs_ev_[i]) (void) hipEventDestroy(rs_ev_[i]);
+                h_rs_[i] = nullptr;
+                rs_ev_[i] = nullptr;
+            }
+            *err = "Failed to allocate the buffers of per-frame stream resets.";
+            return false;
+        }
+        d_rs_ = d;
+    }
+    const int k = (int) (rs_n_ % kResetRing);
+    if (rs_ev_set_[k] && hipEventSynchronize(rs_ev_[k]) != hipSuccess) {
+        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+        return false;
+    }
+    rs_ev_set_[k] = false;
+    ++rs_n_;
+    if (!late) {  // frame 0 only: the reset kernel on the call's stream, right in front of it
+        uint8_t *bytes = (uint8_t *) h_rs_[k];
+        memset(bytes, 0, (size_t) Bpad_);
+        for (int b = 0; b < B_; ++b) bytes[b] = mask[(size_t) b * T] != 0;
+        bool ok = hipMemcpyAsync(d_rmask_, bytes, (size_t) Bpad_, hipMemcpyHostToDevice, stream_) == hipSuccess;
+        ok = ok && hipEventRecord(rs_ev_[k], stream_) == hipSuccess;
+        rs_ev_set_[k] = ok;
+        if (ok) launch_reset(reset_args(d_rmask_), stream_);
+        const hipError_t e = hipGetLastError();
+        if (!ok || e != hipSuccess) {
+            *err = std::string("HIP error: ") + hipGetErrorString(e);
+            return false;
+        }
+        return true;
+    }
+    unsigned *w = h_rs_[k];
+    memset(w, 0, (size_t) mtb * T * 4);
+    rs_frame_.assign((size_t) T, 0);
+    for (int b = 0; b < B_; ++b) {
+        const uint8_t *row = mask + (size_t) b * T;
+        unsigned *wm = w + (size_t) (b >> 4) * T;
+        const unsigned bit = 1u << (b & 15);
+        for (int t = 0; t < T; ++t)
+            if (row[t]) {
+                wm[t] |= bit;
+                rs_frame_[t] = 1;
+            }
+    }
+    rs_slot_ = k;
+    rs_T_ = T;
+    rs_uploaded_ = false;
+    rs_active_ = true;
     return true;
 }
 
@@ -1010,6 +1105,11 @@ void Engine::run_wave(int T, int mtb) {
 //   |               |          |   switch, debug taps)                 |                                                              |
 //   |               |          |                                       |   per layer; the chunked recurrence would occupy mtb CUs)     |
 //   | fp32          | > 1      | > 192                                 | kRouteChunked                                                 |
+//   | both          | any      | any: a call (host-pointer calls: a    | kRouteChunkedResets: the chunked kernels' reset arms          |
+//   |               |          |   sub-chunk) with per-frame stream    |   (analysis_kernel, synthesis_kernel, gru_resident8_kernel /  |
+//   |               |          |   resets at some frame t > 0 (t = 0   |   gru_kernel<PF32, 8>: kResets) read the rows that restart    |
+//   |               |          |   only: reset kernel + normal route)  |   per (m-tile, frame); GEMMs and heads unchanged; developer   |
+//   |               |          |                                       |   A/B switches of the recurrent kernel not honoured           |
 //
 //   Around them (all configurations)
 //   | what                          | T = 1, bf16                                         | otherwise                            |
@@ -1024,11 +1124,20 @@ void Engine::run_wave(int T, int mtb) {
 //   | mask head                     | inside the synthesis launch                         | gemm_wsr_kernel                      |
 //   | analysis / synthesis segments | one                                                 | ~4 / ~2 workgroups per CU (>= 1 frame)  |
 //   Host-pointer calls: >= 4 MiB and more than min(16, max_frames / 2) frames -> sub-chunks on three streams; T = 1 -> hipGraph replay.
-enum Route { kRouteChunked = 0, kRouteSmall = 1, kRouteSmallSteps = 2, kRouteQuad1 = 3, kRouteWave = 4, kRoutePipelined = 5 };
+enum Route { kRouteChunked = 0, kRouteSmall = 1, kRouteSmallSteps = 2, kRouteQuad1 = 3, kRouteWave = 4, kRoutePipelined = 5, kRouteChunkedResets = 6 };
 
 bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string *err, bool allow_recompute) {
     const int mtb = Bpad_ / 16;
     last_T_ = T;
+    // per-frame stream resets in these frames (begin_resets): the chunked route with the kernels' reset arms, whatever the batch size
+    const bool resets = rs_active_ && std::any_of(rs_frame_.begin() + rs_t0_, rs_frame_.begin() + rs_t0_ + T, [](uint8_t v) { return v != 0; });
+    if (resets && !rs_uploaded_) {  // the call's table, on the stream of its kernels (its first sub-chunk that needs it)
+        (void) hipMemcpyAsync(d_rs_, h_rs_[rs_slot_], (size_t) mtb * rs_T_ * 4, hipMemcpyHostToDevice, stream_);
+        (void) hipEventRecord(rs_ev_[rs_slot_], stream_);
+        rs_ev_set_[rs_slot_] = true;
+        rs_uploaded_ = true;
+    }
+    const unsigned *rs = resets ? d_rs_ : nullptr;
 
     AnalysisArgs an;
     an.pcm = d_pcm;
@@ -1060,6 +1169,9 @@ bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string
     an.T = T;
     an.nbf = nbf_;
     an.precision = prec_;
+    an.resets = rs;
+    an.rs_pitch = rs_T_;
+    an.rs_t0 = rs_t0_;
     // The spectrum makes its round trip through HBM only where it has to: in single-frame calls (the history is updated in
     // place there, so the synthesis kernel cannot rebuild it) and when the debug taps are on.  Otherwise the synthesis
     // kernel recomputes it from the PCM.
@@ -1137,6 +1249,9 @@ bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string
         g.mtiles = mtb;
         g.precision = prec_;
         g.dev = dev_variant_;
+        g.resets = rs;
+        g.rs_pitch = rs_T_;
+        g.rs_t0 = rs_t0_;
         tick(kClsGru);
         if (only < 0 || only == kClsGru) launch_gru(g, c_stream);
         tock(kClsGru);
@@ -1152,7 +1267,7 @@ bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string
     // 512 to 1 536 streams, 96 at 2 048, 106 at 4 096 (222 with the chunked kernels); the low-latency kernel below 79 us at 512
     // streams, 81 at 704, 99 at 1 024, 120 at 1 536)
     const int small_mt = small_env > 0 ? small_env : (prec_ == kBf16 ? (use_quad_ ? 59 : 192) : 256);
-    const bool small = T == 1 && mtb <= small_mt && !no_small_;
+    const bool small = T == 1 && mtb <= small_mt && !no_small_ && !resets;
     // Fewer than 256 m-tiles: the chunked recurrent kernels would occupy mtb workgroups, so the layers run frame
     // by frame through the low-latency kernel instead (17 x mtb workgroups of three waves per frame, input GEMM included):
     // in fp32 at 256 streams x 32 frames 8 x 32 launches of ~13 us beat 8 x (0.1 + 0.75) ms (2.8 vs 1.2 M frames/s; 5.5 vs
@@ -1173,11 +1288,12 @@ bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string
     // (32 frames x 512 streams: 0.49 against 0.68 ms; 768: 0.66 against 0.73; 1 024: equal at best -- beyond, the chunked kernels'
     // resident weights win -- except in calls of 2-4 frames)
     const bool wave_wins = prec_ == kBf16 ? (mtb <= 48 || (mtb <= 64 && T <= 4)) : mtb <= 256;
-    const bool wave = T > 1 && (dev_wave_mt_ >= 0 ? mtb <= dev_wave_mt_ : wave_wins) && !no_small_ && !debug_taps_ && (only < 0 || only == kClsGru) && wave_fits();
+    const bool wave = T > 1 && (dev_wave_mt_ >= 0 ? mtb <= dev_wave_mt_ : wave_wins) && !no_small_ && !debug_taps_ && (only < 0 || only == kClsGru) && wave_fits() &&
+                      !resets;
     // One-frame bf16 calls whose m-tiles come in whole quads (from 60 m-tiles on): a GRU layer is ONE launch (kns_gruq.hip) -- input
     // GEMM, recurrent GEMM and gates fused over CU quads.  Same arithmetic as the two-kernel form, bit for bit
     // (tests/test_gpu_parity.py::test_alternative_kernels_give_identical_pcm).
-    const bool quad = use_quad_ && !small && T == 1;
+    const bool quad = use_quad_ && !small && T == 1 && !resets;
     auto gru_quad = [&](const void *a0, int nb0, const void *a1, const void *wih, const float *bih, const void *whh,
                         const float *bhh, int layer, void *hseq, const StageDev *head = nullptr) {
         GruQuadArgs g;
@@ -1205,15 +1321,15 @@ bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string
         tock(kClsGru);
     };
 
-    const bool small_steps = T > 1 && mtb <= steps_mt && prec_ != kBf16 && !no_small_ && !wave;
-    last_route_ = small ? kRouteSmall : wave ? kRouteWave : small_steps ? kRouteSmallSteps : quad ? kRouteQuad1 : kRouteChunked;
+    const bool small_steps = T > 1 && mtb <= steps_mt && prec_ != kBf16 && !no_small_ && !wave && !resets;
+    last_route_ = resets ? kRouteChunkedResets : small ? kRouteSmall : wave ? kRouteWave : small_steps ? kRouteSmallSteps : quad ? kRouteQuad1 : kRouteChunked;
     // ---- mid-size batches: the layer pipeline over sub-chunks of frames (see the chunk loop below)
     const int pipe_chunk = dev_pipe_chunk_ > 0 ? dev_pipe_chunk_ : (T + 1) / 2;
     const int pipe_mt = dev_pipe_mt_ >= 0 ? dev_pipe_mt_ : 144;
     const int pipe_grid = dev_pipe_grid_ > 0 ? dev_pipe_grid_ : 128;
     const int pipe_streams = dev_pipe_streams_ > 0 && dev_pipe_streams_ <= kPipeStreams ? dev_pipe_streams_ : 2;
     const bool pipelined = !wave && !small && !small_steps && !quad && prec_ == kBf16 && mtb <= pipe_mt && T >= 32 && T >= 2 * pipe_chunk - 1 && !profiling_ &&
-                           !debug_taps_ && only < 0 && pipe_ready();
+                           !debug_taps_ && only < 0 && !resets && pipe_ready();
     int nchunks = 1;
     if (pipelined) {
         nchunks = (T + pipe_chunk - 1) / pipe_chunk;
@@ -1258,7 +1374,7 @@ bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string
     // layer launch instead of in a launch of its own (kns_gruq.hip, kHead): 15 launches per frame step become 12.
     // ... and the mask head in the synthesis launch (bf16, stored spectrum -- what a one-frame call uses; kns_stft.hip, kMaskIn)
     const bool mask_in_synthesis = T == 1 && prec_ == kBf16 && fuse_front_ && !debug_taps_ && !recompute &&
-                                   sd_[kStages - 1].head_tiles == kMaskTiles;
+                                   sd_[kStages - 1].head_tiles == kMaskTiles && !resets;
     mask_valid_ = !mask_in_synthesis;
     bool head_in_next = false;  // stage s - 1's head has been left to this stage's first layer
     bool head_in_recurrent = false;  // this stage's head was computed by its layer-B recurrent launch
@@ -1312,6 +1428,9 @@ bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string
         sy.T = Tc;
         sy.pitch = T;
         sy.prev_in_pcm = t0c > 0 ? 1 : 0;
+        sy.resets = rs;
+        sy.rs_pitch = rs_T_;
+        sy.rs_t0 = rs_t0_ + t0c;
         launch_synthesis(sy, st);
     };
     if (pipelined) (void) hipEventRecord(pipe_fork_, stream_);
@@ -1509,6 +1628,7 @@ bool Engine::process_host_pipelined(int T, const int16_t *pcm, int16_t *out, boo
         // ---- kernels (d_out_ slot s was last drained by the D2H of chunk c - 2)
         check(hipStreamWaitEvent(stream_, ev_in_[s], 0));
         if (c >= 2) check(hipStreamWaitEvent(stream_, ev_out_[s], 0));
+        rs_t0_ = first[c];  // (per-frame stream resets: the sub-chunk's frames of the call's table)
         if (ok && !run_device(tc, d_in_ + s * slot, d_out_ + s * slot, err)) {
             // copies of earlier sub-chunks may still be writing into the caller's buffers: let them finish first
             (void) hipStreamSynchronize(copy_in_);
@@ -1584,6 +1704,13 @@ bool Engine::async_wait(int max_in_flight, std::string *err) {
     return true;
 }
 
+// per-frame stream resets apply to one call: whichever way it leaves, the packed table is no longer the next call's
+struct Engine::ResetScope {
+    Engine *e;
+    explicit ResetScope(Engine *engine) : e(engine) {}
+    ~ResetScope() { e->rs_active_ = false, e->rs_t0_ = 0; }
+};
+
 // One asynchronous host call = H2D on copy_in_, the kernels on the handle's stream, D2H on copy_out_, chained by events.  Up to
 // THREE calls are in flight: with two, a caller alternating between two buffer pairs cannot issue call n + 2 before call n's copy-out has
 // finished, which puts a slot's copy-in, kernels and copy-out in series (measured: 4.03 ms per 4096 x 64 frames = (2.8 + 2.6 + 2.8) / 2);
@@ -1592,6 +1719,8 @@ bool Engine::async_wait(int max_in_flight, std::string *err) {
 // once call n - 2's copy-out has -- both waited for on the device, by the stream that needs it.  A synchronous call of that size cannot
 // hide its first copy-in and last copy-out and has to cut its kernels into short, less efficient sub-chunks (process_host_pipelined).
 bool Engine::process_host_async(int T, const int16_t *pcm, int16_t *out, std::string *err) {
+    const uint8_t *resets = parked_resets_;  // (taken first: consumed by this call whatever happens below)
+    parked_resets_ = nullptr;
     (void) hipSetDevice(device_);
     if (pointer_kind(pcm) != kPtrPinned || pointer_kind(out) != kPtrPinned) {
         *err = "asynchronous host calls need page-locked `pcm` and `enhanced` (pv_koala_batch_host_alloc, hipHostMalloc or hipHostRegister).";
@@ -1632,6 +1761,8 @@ bool Engine::process_host_async(int T, const int16_t *pcm, int16_t *out, std::st
         }
         async_busy_[ring3] = false;
     }
+    if (!begin_resets(T, resets, err)) return false;  // (the mask is packed into a ring slot of this call: the caller may overwrite it now)
+    ResetScope rs_scope(this);
     int16_t *din = s ? d_in2_ : d_in_, *dout = s ? d_out2_ : d_out_;
     bool ok = true;
     if (n >= 2) ok = hipStreamWaitEvent(copy_in_, aev_done_[s], 0) == hipSuccess;  // the kernels of call n - 2 have read this slot's input
@@ -1666,8 +1797,11 @@ bool Engine::process_host_async(int T, const int16_t *pcm, int16_t *out, std::st
 }
 
 bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, bool host_pointers) {
+    const uint8_t *resets = parked_resets_;  // (taken first: consumed by this call whatever happens below)
+    parked_resets_ = nullptr;
     (void) hipSetDevice(device_);
     if (async_n_ && !drain_async(err)) return false;
+    ResetScope rs_scope(this);
     const size_t bytes = (size_t) B_ * T * kFrame * 2;
     // (the single-stream ABI takes host buffers by contract: no driver query per frame on the latency path)
     const PointerKind kin = host_pointers ? kPtrPageable : pointer_kind(pcm), kout = host_pointers ? kPtrPageable : pointer_kind(out);
@@ -1678,7 +1812,7 @@ bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, 
     if (kin == kPtrDevice) {
         const size_t n = (size_t) B_ * T * kFrame;
         const bool overlap = pcm < out + n && out < pcm + n;
-        return run_device(T, pcm, out, err, !overlap);
+        return begin_resets(T, resets, err) && run_device(T, pcm, out, err, !overlap);
     }
     if (T > host_chunk_ && bytes >= host_pipeline_min_bytes_) {
         const char *pa = (const char *) pcm, *pb = (const char *) out;
@@ -1689,6 +1823,7 @@ bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, 
                    "disjoint buffers.";
             return false;
         }
+        if (!begin_resets(T, resets, err)) return false;
         // On a caller's stream the kernels of the sub-chunks still run on the handle's OWN stream, fenced behind whatever the caller
         // has enqueued (the call is synchronous, so everything the caller enqueues later is behind it anyway): the handle's three
         // streams were created together and sit on three different hardware queues, while a foreign stream may share its queue with
@@ -1706,6 +1841,7 @@ bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, 
         stream_ = user;
         return done;
     }
+    if (!begin_resets(T, resets, err)) return false;
     memcpy(h_in_, pcm, bytes);
     if (T == 1 && use_graph_ && stream_ == own_stream_ && !profiling_) {
         // frame-by-frame streaming: (copy-in,) the kernels of one frame (and copy-out) replayed as one hipGraph

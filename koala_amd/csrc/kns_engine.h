@@ -57,6 +57,13 @@ public:
     bool drain_async(std::string *err);
     bool async_wait(int max_in_flight, std::string *err);  // until at most that many asynchronous calls are still in flight (0: all done)
     bool reset(const uint8_t *host_mask, std::string *err);
+    // Per-frame stream resets of the NEXT process() or process_host_async() call: `mask` is host memory, uint8 [num_streams][T] of that
+    // call (non-zero at [b][t]: stream b restarts from the fresh state right before frame t).  The call consumes it before it returns --
+    // packed into the reset ring (kns_engine.cpp, begin_resets) -- and clears it, on success and on failure alike.  Inline, as is
+    // front_taps(): the C-ABI shim's entry points that carry a mask call nothing else of the engine's, and tests/abi_sanitizer links the
+    // shim against a host-only double of the Engine that defines only the out-of-line members.
+    void park_resets(const uint8_t *mask) { parked_resets_ = mask; }
+    int front_taps() const { return taps_; }
     // 0: back to the handle's own stream.  Waits for everything the handle has in flight first (asynchronous host calls and the work
     // queued on the previous stream, which must still exist: the next call's kernels touch the same state, history and tail buffers)
     void set_stream(hipStream_t s);
@@ -172,6 +179,22 @@ private:
     // the last run_device() stored the spectrum / the features / the mask (debug_read refuses a tap that was not stored)
     bool spec_valid_ = false, feat_valid_ = false, mask_valid_ = false;
     int last_route_ = 0;  // enum Route of the last run_device() (kns_engine.cpp; reported by the developer build's debug tap 6)
+
+    // per-frame stream resets (kns_engine.cpp, begin_resets): the parked host mask, and the call's packed form -- per (m-tile, frame) the
+    // rows that restart, uint32 [mtiles][T] -- in a ring of page-locked slots (one per call in flight; a slot is refilled once the copy
+    // that read it four calls back has completed) uploaded to d_rs_ on the stream that runs the call's kernels
+    const uint8_t *parked_resets_ = nullptr;
+    static constexpr int kResetRing = 4;
+    unsigned *h_rs_[kResetRing] = {};
+    hipEvent_t rs_ev_[kResetRing] = {};
+    bool rs_ev_set_[kResetRing] = {};
+    unsigned *d_rs_ = nullptr, rs_n_ = 0;
+    int rs_slot_ = 0, rs_T_ = 0, rs_t0_ = 0;  // the call's ring slot and length; the first frame of the sub-chunk run_device() is given
+    bool rs_active_ = false, rs_uploaded_ = false;
+    std::vector<uint8_t> rs_frame_;  // [T]: some stream restarts at this frame of the call
+    bool begin_resets(int T, const uint8_t *mask, std::string *err);
+    ResetArgs reset_args(const uint8_t *d_mask) const;
+    struct ResetScope;  // the reset kernel's arguments (d_mask: device [Bpad], null: every stream)
 
     // profiling
     bool profiling_ = false;

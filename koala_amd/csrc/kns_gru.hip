@@ -8,7 +8,9 @@ namespace kns {
 
 // Weights streamed from L2 every step (fp32 parity path; bf16 only as an A/B switch).  W waves per workgroup share the
 // 17 unit tiles round-robin; the B fragments of a tile are fetched four k-blocks (twelve fragments) ahead of their MFMAs, and with W = 8 two waves per SIMD cover each other's latencies.
-template <class P, int W>
+// kResets (fp32 only, GruArgs::resets): before step t the rows that restart at t get h_{t-1} = 0, in the registers and in the operand
+// image, after that image has gone out as frame t - 1's hidden vector
+template <class P, int W, bool kResets = false>
 __global__ __launch_bounds__(64 * W, W / 4) void gru_kernel(GruArgs g) {
     typedef typename P::frag_t frag_t;
     typedef typename P::elem_t elem_t;
@@ -64,6 +66,26 @@ __global__ __launch_bounds__(64 * W, W / 4) void gru_kernel(GruArgs g) {
         if (t > 0) {  // what is in LDS now is h_{t-1}: publish it as the next layer's A operand
             frag_t *hs = (frag_t *) g.hseq + ((size_t) (t - 1) * g.mtiles + mt) * NBH * 64;
             for (int blk = wave; blk < NBH; blk += W) hs[blk * 64 + lane] = ha[blk * 64 + lane];
+        }
+        if (kResets) {
+            const unsigned rm = reset_rows(g.resets, g.rs_pitch, mt, g.rs_t0 + t);
+            if (rm) {  // (wave-uniform: most steps have no reset in this m-tile)
+                __syncthreads();  // h_{t-1}'s image has been read by every wave
+#pragma unroll
+                for (int q = 0; q < TPW; ++q) {
+                    const int u = wave + W * q;
+                    if (u < kUnitTiles) {
+                        const int k = u * 16 + colq;
+                        elem_t *dst = (elem_t *) hbuf[cur] + (k / P::KB) * 64 * P::EPL;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            hreg[q][i] = (rm >> (rowq + i)) & 1u ? 0.0f : hreg[q][i];
+                            dst[P::off(rowq + i, k % P::KB)] = operand_of(hreg[q][i], u);
+                        }
+                    }
+                }
+                __syncthreads();
+            }
         }
         const typename P::gi_t *gi = (const typename P::gi_t *) g.gi + ((size_t) t * g.mtiles + mt) * kGateTiles * 64;
 #pragma unroll
@@ -644,6 +666,10 @@ constexpr int kR8HeadLds = PBF16::NBH * 1024;          // (kYHead) the narrow he
 #ifndef R8_APF
 #define R8_APF 2  // gru_resident8_kernel<false> (six of the bench's eight recurrent launches): fits 256 registers without a spill
 #endif
+#ifndef R8_APF_R
+#define R8_APF_R 0  // gru_resident8_kernel<false, true> (per-frame resets): with the reset step's selects and image rewrite a distance of 2 or 1
+                    // spills 20 bytes inside the step
+#endif
 #ifndef R8_APF_Y
 #define R8_APF_Y 0  // gru_resident8_kernel<true>: the head's chain and epilogue leave no registers (a distance of 1 spills inside the step)
 #endif
@@ -693,12 +719,16 @@ __device__ __forceinline__ f16x4 buf_load_gi(__amdgpu_buffer_rsrc_t r, unsigned 
 // (profiles/r04_recurrent_stamps.txt) -- carries its nine MFMAs through its first tile's loop as a fourth accumulator, on the same A
 // fragments (the image of h_{t-1} it multiplies anyway), then the sigmoid and sixteen 2-byte stores: y_{t-1} leaves one step late,
 // y_{T-1} after the loop.  The chain is k-ascending from 0 with the bias after, like gemm_head_kernel's: the same bits.
-template <bool kYHead>
+// kResets (GruArgs::resets): before step t the rows that restart at t get h_{t-1} = 0 -- hreg, h16 and their rows of the operand image
+// (column 15 of tile 16 stays the bias constant) -- after the image has gone out as frame t - 1's hidden vector.  With kYHead the head's
+// y_{t-1} belongs to frame t - 1, the last frame before the reset: in such a step wave 0 computes it from the image BEFORE the rows are
+// zeroed and the chain's value (on the zeroed image) is not stored.  A step without a reset in the m-tile pays a scalar load and a branch.
+template <bool kYHead, bool kResets = false>
 __global__ __launch_bounds__(64 * kR8Waves, 2) void gru_resident8_kernel(GruArgs g) {
     typedef PBF16 P;
     typedef P::frag_t frag_t;
     constexpr int NBH = P::NBH;
-    constexpr int kApf = kYHead ? R8_APF_Y : R8_APF;  // A fragments requested this many k-blocks ahead
+    constexpr int kApf = kYHead ? R8_APF_Y : kResets ? R8_APF_R : R8_APF;  // A fragments requested this many k-blocks ahead
     __shared__ __attribute__((aligned(16))) char smem[kR8Lds + 3 * 1024 + 16 + (kYHead ? kR8HeadLds : 0)];
     frag_t *wlh = (frag_t *) (smem + kR8Lds + 3 * 1024 + 16);  // (kYHead) [9][64]: the head's n-tile 0
     char *hbuf0 = smem, *hbuf1 = smem + NBH * 1024;
@@ -839,10 +869,37 @@ __global__ __launch_bounds__(64 * kR8Waves, 2) void gru_resident8_kernel(GruArgs
         KNS_STAMP(0);
         KNS_STAMP_AT(9, 8);  // steady-state step length = (stamp 10 - stamp 9) / 16
         KNS_STAMP_AT(10, 24);
-        const char *hc = (t & 1) ? hbuf1 : hbuf0;
+        char *hc = (t & 1) ? hbuf1 : hbuf0;
         char *hn = (t & 1) ? hbuf0 : hbuf1;
         const frag_t *ha = (const frag_t *) hc;
         publish(ha, hs_base);  // LDS holds h_{t-1}
+        bool reset_step = false;
+        if (kResets) {
+            const unsigned rm = reset_rows(g.resets, g.rs_pitch, mt, g.rs_t0 + t);
+            reset_step = rm != 0;
+            if (reset_step) {
+                if (kYHead && wave == 0 && t > 0) {  // y_{t-1} from h_{t-1} as it is (the chain below multiplies the reset image)
+                    f32x4 ya = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma nounroll
+                    for (int blk = 0; blk < NBH; ++blk) ya = P::mma(ha[blk * 64 + lane], wlh[blk * 64 + lane], ya);  // (rolled: registers)
+                    emit_y(ya, t - 1);
+                }
+                __syncthreads();  // every wave has read the image of h_{t-1}
+            }
+            // (selects outside the branch: with them inside, hipcc kept both versions of hreg alive across the join and spilled)
+            const unsigned rb = rm >> rowq;  // this lane's four rows
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) hreg[q][i] = (rb >> i) & 1u ? 0.0f : hreg[q][i];
+            h16 = (rb >> e16) & 1u ? 0.0f : h16;
+            if (reset_step) {
+                put_h(hc, u0, hreg[0]);
+                put_h(hc, u1, hreg[1]);
+                if (q16) put_h16(hc, h16);
+                __syncthreads();
+            }
+        }
         const __amdgpu_buffer_rsrc_t gnext = make_rsrc(gn_base, kGateTiles * 512);
         hs_base += t > 0 ? hs_stride : 0;
         gn_base += t + 2 < g.T ? gi_stride : 0;
@@ -872,7 +929,7 @@ __global__ __launch_bounds__(64 * kR8Waves, 2) void gru_resident8_kernel(GruArgs
         if (kYHead && wave == 0) {  // ... with the head's chain on h_{t-1} (at t = 0: h_{-1}, into frame 0's slot, rewritten at t = 1)
             f32x4 ya = f32x4{0.f, 0.f, 0.f, 0.f};
             r8_tile_mma<kR8RegFrags0, R8C_Q, kR8RegFrags0, true, 1, kApf>(acc, ha, w0, wl0w, lane, &ya, wlh + lane);
-            emit_y(ya, t > 0 ? t - 1 : 0);
+            if (!reset_step) emit_y(ya, t > 0 ? t - 1 : 0);
         } else {
             r8_tile_mma<kR8RegFrags0, R8C_Q, kR8RegFrags0, false, 3, kApf>(acc, ha, w0, wl0w, lane);
         }
@@ -937,7 +994,14 @@ __global__ __launch_bounds__(64 * kR8Waves, 2) void gru_resident8_kernel(GruArgs
 // profiles/r05_gate_lut.txt).)
 void launch_gru(const GruArgs &a, hipStream_t s) {
     const bool stream_weights = (a.dev & kDevGruStream) != 0;  // A/B switch (developer build only)
-    if (a.precision == kBf16 && !stream_weights && a.yw)
+    if (a.resets) {  // calls with per-frame stream resets: the reset arms (the A/B switch is not honoured)
+        if (a.precision == kBf16 && a.yw)
+            hipLaunchKernelGGL((gru_resident8_kernel<true, true>), dim3(a.mtiles), dim3(64 * kR8Waves), 0, s, a);
+        else if (a.precision == kBf16)
+            hipLaunchKernelGGL((gru_resident8_kernel<false, true>), dim3(a.mtiles), dim3(64 * kR8Waves), 0, s, a);
+        else
+            hipLaunchKernelGGL((gru_kernel<PF32, 8, true>), dim3(a.mtiles), dim3(512), 0, s, a);
+    } else if (a.precision == kBf16 && !stream_weights && a.yw)
         hipLaunchKernelGGL(gru_resident8_kernel<true>, dim3(a.mtiles), dim3(64 * kR8Waves), 0, s, a);
     else if (a.precision == kBf16 && !stream_weights)
         hipLaunchKernelGGL(gru_resident8_kernel<false>, dim3(a.mtiles), dim3(64 * kR8Waves), 0, s, a);

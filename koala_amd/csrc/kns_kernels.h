@@ -57,6 +57,11 @@ struct AnalysisArgs {
     // rows are `pitch` frames apart (0: T), the frame in front of the slice is read from the row itself instead of `hist_in`, and only the
     // call's last slice leaves the history behind
     int pitch = 0, prev_in_pcm = 0, write_hist = 1;
+    // optional (calls with per-frame stream resets): the rows that restart at frame t of this launch are the set bits of
+    // resets[mtile * rs_pitch + rs_t0 + t] (bit r = stream 16 mtile + r, kns_engine.cpp, ResetRing); in such a frame a row's previous
+    // frame is zero.  Selects the kernels' reset arms (a null pointer: the arms are not instantiated in the launch)
+    const unsigned *resets = nullptr;
+    int rs_pitch = 0, rs_t0 = 0;
 };
 void launch_analysis(const AnalysisArgs &a, hipStream_t s);
 
@@ -83,6 +88,10 @@ struct SynthesisArgs {
     const void *mask_h = nullptr;    // A-packed hidden sequence of the last stage's layer B [mtiles][9]
     const void *mask_w = nullptr;    // B-packed [17][9]
     const float *mask_b = nullptr;   // [17 * 16]
+    // optional: per-frame stream resets, as in AnalysisArgs -- a resetting row's overlap-add tail and (recompute) previous frame are
+    // zero in its reset frame
+    const unsigned *resets = nullptr;
+    int rs_pitch = 0, rs_t0 = 0;
 };
 void launch_synthesis(const SynthesisArgs &a, hipStream_t s);
 
@@ -137,6 +146,10 @@ struct GruArgs {
     const float *yb = nullptr;   // [16]
     void *yout = nullptr;
     int yvalid = 0, y_nb = 0, y_blk = 0, y_kk0 = 0;
+    // optional: per-frame stream resets, as in AnalysisArgs -- before step t, h_{t-1} of the rows that restart at t is zero (bf16:
+    // gru_resident8_kernel, fp32: gru_kernel<PF32, 8>; developer A/B switches are not honoured then)
+    const unsigned *resets = nullptr;
+    int rs_pitch = 0, rs_t0 = 0;
 };
 void launch_gru(const GruArgs &a, hipStream_t s);
 

@@ -103,7 +103,9 @@ __device__ __forceinline__ float feature_log(float x) {
 
 // grid (stream tiles, time segments): a workgroup walks the frames [t0, t1) of its 16 streams, so every PCM sample is
 // read once (the previous frame stays in registers) and the per-lane constants are set up once per segment.
-template <class P, bool kSpec>
+// kResets: calls with per-frame stream resets (AnalysisArgs::resets): in a row's reset frame the previous frame is zero -- the block
+// [0 | frame t] a fresh stream sees -- and a segment whose first frame is one does not read the frame in front of it
+template <class P, bool kSpec, bool kResets = false>
 __global__ __launch_bounds__(256, 3) void analysis_kernel(AnalysisArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *lmean = (float *) (smem + kOffAEnd), *lscale = lmean + 272;
@@ -134,7 +136,12 @@ __global__ __launch_bounds__(256, 3) void analysis_kernel(AnalysisArgs g) {
     }
     int prev[8], cur[8], nxt[8];
     // (a slice of a longer call, prev_in_pcm: the frame in front of frame 0 sits in the row itself, at t = -1)
-    load_frame(prev, t0 == 0 && !g.prev_in_pcm ? g.hist_in + (size_t) b * kFrame : pcm_row + ((ptrdiff_t) t0 - 1) * kFrame, c);
+    if (kResets && ((reset_rows(g.resets, g.rs_pitch, mt, g.rs_t0 + t0) >> row) & 1u)) {
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) prev[jj] = 0;
+    } else {
+        load_frame(prev, t0 == 0 && !g.prev_in_pcm ? g.hist_in + (size_t) b * kFrame : pcm_row + ((ptrdiff_t) t0 - 1) * kFrame, c);
+    }
     load_frame(cur, pcm_row + (size_t) t0 * kFrame, c);
     StftTables tbl;
     stft_request_tables(tbl, g.twiddle, g.window, tid);
@@ -174,6 +181,14 @@ __global__ __launch_bounds__(256, 3) void analysis_kernel(AnalysisArgs g) {
     for (int t = t0; t < t1; ++t) {
         // next frame's samples are requested before this frame is transformed (clamped, never skipped)
         load_frame(nxt, pcm_row + (size_t) (t + 1 < t1 ? t + 1 : t) * kFrame, c);
+        if (kResets && t > t0) {  // (the segment's first frame was taken care of above)
+            const unsigned rm = reset_rows(g.resets, g.rs_pitch, mt, g.rs_t0 + t);
+            if (rm) {
+                const bool r = (rm >> row) & 1u;
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) prev[jj] = r ? 0 : prev[jj];
+            }
+        }
         cpx v[16];
         window_block(v, prev, cur, win_c);
         fft256_rows(v, twl_c, xw, xr);
@@ -230,7 +245,12 @@ void launch_analysis(const AnalysisArgs &a, hipStream_t s) {
         if (bytes > 48 * 1024) (void) hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
         hipLaunchKernelGGL(kernel, grid, dim3(threads), bytes, s, a);
     };
-    if (a.precision == kBf16) {
+    if (a.resets) {  // (calls with per-frame stream resets: the reset arm)
+        if (a.precision == kBf16)
+            a.write_spec ? go(analysis_kernel<PBF16, true, true>, 256, lds) : go(analysis_kernel<PBF16, false, true>, 256, lds);
+        else
+            a.write_spec ? go(analysis_kernel<PF32, true, true>, 256, lds) : go(analysis_kernel<PF32, false, true>, 256, lds);
+    } else if (a.precision == kBf16) {
         if (a.write_spec)
             go(analysis_kernel<PBF16, true>, 256, lds);
         else
@@ -255,10 +275,14 @@ void launch_analysis(const AnalysisArgs &a, hipStream_t s) {
 // three come close to the pipe's 2; the register budget of 168 is what decides which loads are prefetched below)
 // kMaskIn (one-frame calls, bf16): waves 4..7 are the mask head -- sigmoid(h . W_mask + b_mask) of the workgroup's m-tile as fp16 C
 // fragments in LDS (what gemm_kernel<kOutMask> stores), complete at the workgroup's one barrier; the STFT waves read it from there.
-template <bool kRecompute, bool kMaskH, bool kMaskIn>  // kMaskH: the mask travels as fp16 C fragments (bf16 configuration), else fp32
+// kResets (calls with per-frame stream resets, SynthesisArgs::resets): in a row's reset frame its overlap-add tail is zero and, recomputed,
+// its spectrum is that of [0 | frame t].  This holds for the replayed frame t0 - 1 as well, and a reset at t0 zeroes the tail the replay
+// left: nothing of the frames before a reset reaches the output.
+template <bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets = false>  // kMaskH: the mask travels as fp16 C fragments (bf16 configuration), else fp32
 __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_kernel(SynthesisArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!kMaskIn || (kMaskH && !kRecompute), "mask head inside: bf16, stored spectrum");
+    static_assert(!kMaskIn || !kResets, "resets: multi-frame form only");
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (kMaskIn && wave >= 4) {
@@ -379,6 +403,18 @@ __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesi
             mask_fetch(mk, t);
         else
             mask_fetch(mkn, tn);
+        if (kResets) {
+            const unsigned rm = reset_rows(g.resets, g.rs_pitch, mt, g.rs_t0 + t);
+            if (rm) {
+                const bool r = (rm >> row) & 1u;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) tl[j] = r ? cpx{0.0f, 0.0f} : tl[j];
+                if (kRecompute) {
+#pragma unroll
+                    for (int jj = 0; jj < 8; ++jj) prev[jj] = r ? 0 : prev[jj];
+                }
+            }
+        }
         cpx x[16];
         if (kRecompute) {
             load_frame(nxt, pcm_row + (size_t) tn * kFrame, c);
@@ -472,7 +508,16 @@ void launch_synthesis(const SynthesisArgs &a, hipStream_t s) {
 #if KNS_STFT_LDS_PAD
     (void) hipFuncSetAttribute((const void *) synthesis_kernel<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
 #endif
-    if (a.mask_w && !a.recompute && a.mask_fp16 && a.T == 1)
+    if (a.resets) {  // (calls with per-frame stream resets: the reset arm; the engine does not put the mask head inside then)
+        if (a.recompute && a.mask_fp16)
+            hipLaunchKernelGGL((synthesis_kernel<true, true, false, true>), grid, dim3(256), lds, s, a);
+        else if (a.recompute)
+            hipLaunchKernelGGL((synthesis_kernel<true, false, false, true>), grid, dim3(256), lds, s, a);
+        else if (a.mask_fp16)
+            hipLaunchKernelGGL((synthesis_kernel<false, true, false, true>), grid, dim3(256), lds, s, a);
+        else
+            hipLaunchKernelGGL((synthesis_kernel<false, false, false, true>), grid, dim3(256), lds, s, a);
+    } else if (a.mask_w && !a.recompute && a.mask_fp16 && a.T == 1)
         hipLaunchKernelGGL((synthesis_kernel<false, true, true>), grid, dim3(512), lds + kMaskTiles * 512, s, a);
     else if (a.recompute && a.mask_fp16)
         hipLaunchKernelGGL((synthesis_kernel<true, true, false>), grid, dim3(256), lds, s, a);

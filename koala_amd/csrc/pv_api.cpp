@@ -453,6 +453,55 @@ PV_API pv_status_t pv_koala_batch_process_chunk_async(pv_koala_batch_t *object, 
     });
 }
 
+// ---- per-frame stream resets.  These entry points reach the engine only through members that are inline in kns_engine.h (front_taps,
+// park_resets: the mask is parked on the Engine and consumed by the call that follows) and the process / process_host_async calls that
+// pv_koala_batch_process_chunk* make: tests/abi_sanitizer links this file against a host-only double that defines no other member.
+namespace {
+// argument checks shared by both forms; PV_STATUS_SUCCESS: the mask is parked, the engine's call consumes it
+pv_status_t park_reset_mask(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm, int16_t *enhanced, const uint8_t *reset) {
+    if (!object) {
+        push_error(0x64, "Argument `object` is NULL.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (!pcm || !enhanced) {
+        push_error(0x64, "Argument `%s` is NULL.", pcm ? "enhanced" : "pcm");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (num_frames <= 0 || num_frames > object->engine->max_frames()) {
+        push_error(0x66, "`num_frames` %d is outside [1, %d].", num_frames, object->engine->max_frames());
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (reset && object->engine->front_taps() > 1) {  // the five-frame front-end: resets at frame 0 only (the reset kernel)
+        const int32_t B = object->engine->num_streams();
+        for (int32_t b = 0; b < B; ++b)
+            for (int32_t t = 1; t < num_frames; ++t)
+                if (reset[(size_t) b * num_frames + t]) {
+                    push_error(0x66, "`reset[%d][%d]` is set: a model with a %d-frame front-end takes per-frame stream resets at frame 0 only.",
+                               b, t, object->engine->front_taps());
+                    return PV_STATUS_INVALID_ARGUMENT;
+                }
+    }
+    object->engine->park_resets(reset);
+    return PV_STATUS_SUCCESS;
+}
+}  // namespace
+
+PV_API pv_status_t pv_koala_batch_process_chunk_resets(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
+                                                       int16_t *enhanced, const uint8_t *reset) {
+    t_stack.clear();
+    const pv_status_t st = park_reset_mask(object, num_frames, pcm, enhanced, reset);
+    if (st != PV_STATUS_SUCCESS) return st;
+    return pv_koala_batch_process_chunk(object, num_frames, pcm, enhanced);
+}
+
+PV_API pv_status_t pv_koala_batch_process_chunk_resets_async(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
+                                                             int16_t *enhanced, const uint8_t *reset) {
+    t_stack.clear();
+    const pv_status_t st = park_reset_mask(object, num_frames, pcm, enhanced, reset);
+    if (st != PV_STATUS_SUCCESS) return st;
+    return pv_koala_batch_process_chunk_async(object, num_frames, pcm, enhanced);
+}
+
 PV_API pv_status_t pv_koala_batch_async_wait(pv_koala_batch_t *object, int32_t max_in_flight) {
     t_stack.clear();
     if (!object) {

@@ -101,6 +101,10 @@ def main():
     p.add_argument('--frames_per_call', type=int, default=32)
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'])
     p.add_argument('--asynchronous', action='store_true', help='many-files mode: asynchronous calls over three page-locked buffer pairs')
+    p.add_argument('--refill', action='store_true',
+                   help='many-files mode: a fixed number of slots, each playing one file after the other with per-frame stream resets '
+                        '(koala_amd/corpus.py) instead of one stream per file zero-padded to the longest')
+    p.add_argument('--num_slots', type=int, help='--refill: streams of the handle (default: the number of files, at most 4096)')
     p.add_argument('--show_inference_devices', action='store_true')
     args = p.parse_args()
     if args.show_inference_devices:
@@ -124,12 +128,17 @@ def main():
         if not args.output_dir:
             raise SystemExit('--output_dir is required for several inputs')
         os.makedirs(args.output_dir, exist_ok=True)
-        batch = koala_amd.create_batch(args.access_key, len(args.input_path), args.frames_per_call, args.precision,
+        slots = (args.num_slots or min(len(args.input_path), 4096)) if args.refill else len(args.input_path)
+        batch = koala_amd.create_batch(args.access_key, slots, args.frames_per_call, args.precision,
                                        model_path=args.model_path, device=args.device, library_path=args.library_path)
         try:
             signals = [read_wav(pth, batch.sample_rate) for pth in args.input_path]
             t0 = time.perf_counter()
-            outs = enhance_batch(batch, signals, args.frames_per_call, args.asynchronous)
+            if args.refill:
+                from koala_amd import corpus
+                outs = corpus.enhance_corpus(batch, signals, args.frames_per_call, 'async' if args.asynchronous else 'host')
+            else:
+                outs = enhance_batch(batch, signals, args.frames_per_call, args.asynchronous)
             dt = time.perf_counter() - t0
             for pth, o in zip(args.input_path, outs):
                 write_wav(os.path.join(args.output_dir, os.path.basename(pth)), o, batch.sample_rate)

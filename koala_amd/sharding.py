@@ -1,10 +1,13 @@
 """
 Multi-GPU host logic: streams are independent, so a job of N streams is cut into contiguous
-per-rank ranges, one process and one engine per GPU, and nothing crosses GPUs on the data path.  The only
+per-rank ranges (or, for a ragged corpus of utterances, balanced by duration: balanced_assignment), one process and one engine per GPU, and nothing crosses GPUs on the data path.  The only
 collective is the final reduction of {frames processed (sum), elapsed seconds (max)} for the aggregate rate.
 """
 
-from typing import Optional, Tuple
+import heapq
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
 
 
 def shard_range(num_streams: int, rank: int, world_size: int) -> Tuple[int, int]:
@@ -14,6 +17,28 @@ def shard_range(num_streams: int, rank: int, world_size: int) -> Tuple[int, int]
     base, extra = divmod(num_streams, world_size)
     begin = rank * base + min(rank, extra)
     return begin, begin + base + (1 if rank < extra else 0)
+
+
+def balanced_assignment(durations: Sequence[float], world_size: int) -> List[List[int]]:
+    """
+    Utterances of a ragged corpus onto `world_size` ranks by duration, longest-processing-time first: each utterance, longest first
+    (ties: lower index first), goes to the rank with the least audio so far (ties: lower rank).  Returns per rank the ascending list of
+    its utterance indices.  Deterministic; ranks may be empty when there are fewer utterances than ranks.  (`shard_range` cuts by
+    stream COUNT: on a ragged corpus the rank holding the longest files would set the wall time.)
+    """
+    if world_size <= 0:
+        raise ValueError("bad world_size")
+    d = np.asarray(durations, dtype=np.float64).reshape(-1)
+    if d.size and (not np.all(np.isfinite(d)) or d.min() < 0):
+        raise ValueError("durations must be finite and non-negative")
+    order = np.lexsort((np.arange(d.size), -d))  # longest first, then by index
+    heap = [(0.0, r) for r in range(world_size)]
+    ranks: List[List[int]] = [[] for _ in range(world_size)]
+    for i in order:
+        load, r = heapq.heappop(heap)
+        ranks[r].append(int(i))
+        heapq.heappush(heap, (load + float(d[i]), r))
+    return [sorted(x) for x in ranks]
 
 
 def aggregate_throughput(frames_local: int, elapsed_local: float, device: Optional[str] = None) -> Tuple[int, float]:
@@ -37,4 +62,4 @@ def aggregate_throughput(frames_local: int, elapsed_local: float, device: Option
     return int(frames.item()), float(elapsed.item())
 
 
-__all__ = ["shard_range", "aggregate_throughput"]
+__all__ = ["shard_range", "balanced_assignment", "aggregate_throughput"]
