@@ -92,6 +92,45 @@ PV_API pv_status_t pv_koala_batch_async_wait(pv_koala_batch_t *object, int32_t m
 /* Resets the streams whose byte in `stream_mask[num_streams]` (host memory) is non-zero; NULL resets all. */
 PV_API pv_status_t pv_koala_batch_reset(pv_koala_batch_t *object, const uint8_t *stream_mask);
 
+/* PER-STREAM STATE AS RECORDS: move a stream to another slot, another handle (any num_streams / max_frames_per_call), another GPU or
+ * another process; drain a handle for a restart; park a stream that is on hold and give its slot away.  A record is plain bytes,
+ * self-contained and position-independent, little-endian, pv_koala_batch_state_size() bytes for a given model:
+ *
+ *     header, 32 bytes   magic "KNSS", uint32 version = 1, uint32 front_taps, uint32 precision, uint64 model content hash,
+ *                        8 reserved zero bytes
+ *     hist   int16[256]                  the previous frame's input samples
+ *     tail   float[256]                  overlap-add tail
+ *     h      float[8][271]               the eight GRU hidden vectors, layer-major (the order of debug tap 3)
+ *     fctx   float[front_taps - 1][257]  the front-end's feature context, oldest frame first (KNS-v1.1 models only)
+ *
+ * 10 240 bytes for a model with a one-frame front-end (padded with zero bytes to a multiple of 16 for front_taps 2 ... 4).  It does not
+ * depend on num_streams, the slot or anything else of the handle that wrote it.  A record belongs to one model and one precision:
+ * importing it into a handle of another model, another front_taps or the OTHER PRECISION is refused (a bf16 stream does not continue
+ * as an fp32 stream).
+ *
+ * `records` is HOST memory (pageable or page-locked), count x state_size bytes; record i belongs to stream streams[i]; streams == NULL
+ * means slots 0 .. count - 1.  Both calls first wait for asynchronous host calls in flight and then run on the handle's stream, behind
+ * everything enqueued on it.  Export returns when the records are filled.  Import returns when `records` may be reused, and the streams
+ * continue from the imported state in the next call; a freshly created or reset stream's record imports as a reset.
+ * PV_STATUS_INVALID_ARGUMENT, with a message on the error stack: NULL object / records, count outside [1, num_streams], an index outside
+ * [0, num_streams), a slot listed twice, and on import any header that does not match the handle (the message names the record and the
+ * field, "record 3: model hash ...").  Everything is checked before anything is written: a refused call leaves all state as it was.
+ * PV_STATUS_RUNTIME_ERROR: a HIP failure.  The first such call allocates a device staging buffer of num_streams records. */
+PV_API pv_status_t pv_koala_batch_state_size(const pv_koala_batch_t *object, int32_t *num_bytes);
+PV_API pv_status_t pv_koala_batch_export_state(pv_koala_batch_t *object, int32_t count, const int32_t *streams, void *records);
+PV_API pv_status_t pv_koala_batch_import_state(pv_koala_batch_t *object, int32_t count, const int32_t *streams,
+                                               const void *records);
+
+/* pv_koala_batch_process_chunk with HELD STREAMS.  `hold` is HOST memory, uint8 [num_streams], read before the function returns; NULL
+ * means none.  A stream with hold[b] != 0 is NOT ADVANCED by the call: afterwards its state is bit for bit what it was before, as if the
+ * call had not happened for it (a live stream whose next frames have not arrived).  Its rows of `pcm` are read but meaningless, its rows
+ * of `enhanced` are unspecified.  Every other stream behaves exactly as in pv_koala_batch_process_chunk.  A NULL or all-zero mask makes
+ * the call pv_koala_batch_process_chunk: same route, same launches, same bits.  Otherwise the held streams' records are set aside in
+ * device memory in front of the call and put back behind it -- two more launches on the handle's stream, no host wait for device
+ * pointers.  Not combined with per-frame resets or the asynchronous host path. */
+PV_API pv_status_t pv_koala_batch_process_chunk_hold(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
+                                                     int16_t *enhanced, const uint8_t *hold);
+
 PV_API pv_status_t pv_koala_batch_num_streams(const pv_koala_batch_t *object, int32_t *num_streams);
 PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, int32_t *delay_sample);
 

@@ -39,7 +39,11 @@ class KoalaBatch(object):
                            ('profile_read', [c_void_p, POINTER(c_double), POINTER(c_int64)]),
                            ('delay_sample', [c_void_p, POINTER(c_int32)]),
                            ('process_chunk_resets', [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
-                           ('process_chunk_resets_async', [c_void_p, c_int32, c_void_p, c_void_p, c_void_p])):
+                           ('process_chunk_resets_async', [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+                           ('state_size', [c_void_p, POINTER(c_int32)]),
+                           ('export_state', [c_void_p, c_int32, c_void_p, c_void_p]),
+                           ('import_state', [c_void_p, c_int32, c_void_p, c_void_p]),
+                           ('process_chunk_hold', [c_void_p, c_int32, c_void_p, c_void_p, c_void_p])):
             fn = getattr(lib, 'pv_koala_batch_' + name)
             fn.argtypes = args
             fn.restype = PicovoiceStatuses
@@ -67,6 +71,8 @@ class KoalaBatch(object):
         d = c_int32()
         self._check(lib.pv_koala_batch_delay_sample(self._handle, byref(d)), 'Failed to get delay samples')
         self.delay_sample = d.value
+        self._check(lib.pv_koala_batch_state_size(self._handle, byref(d)), 'Failed to get the state size')
+        self.state_size = d.value  # bytes of one stream record (export_state / import_state)
 
     def _check(self, status, what):
         if status is not PicovoiceStatuses.SUCCESS:
@@ -163,6 +169,69 @@ class KoalaBatch(object):
         work is enqueued on the handle's stream."""
         m, mp = self._reset_mask(reset, num_frames)
         self._check(self._lib.pv_koala_batch_process_chunk_resets(self._handle, num_frames, c_void_p(pcm_ptr), c_void_p(enhanced_ptr), mp),
+                    'Processing failed')
+
+    def _stream_list(self, streams, n):
+        """(int32 array kept alive by the caller's frame, pointer, count) for a list of stream indices (None: 0 .. n - 1)"""
+        if streams is None:
+            return None, None, self.num_streams if n is None else n
+        s = np.ascontiguousarray(streams)
+        if s.ndim != 1 or s.size == 0 or not np.issubdtype(s.dtype, np.integer):
+            raise KoalaInvalidArgumentError("`streams` must be a non-empty list of stream indices")
+        if n is not None and s.size != n:
+            raise KoalaInvalidArgumentError("`streams` has %d entries for %d records" % (s.size, n))
+        s = s.astype(np.int32)
+        return s, s.ctypes.data, int(s.size)
+
+    def export_state(self, streams=None) -> np.ndarray:
+        """The state of the listed streams (None: all) as records: uint8 [n, state_size], record i = stream streams[i].  A record is
+        plain bytes (include/pv_koala_batch.h): `bytes(blob[i])` can go to a database and come back in another process, into any
+        slot of any handle on the same model and precision."""
+        s, sp, n = self._stream_list(streams, None)
+        out = np.empty((n, self.state_size), np.uint8)
+        self._check(self._lib.pv_koala_batch_export_state(self._handle, n, sp, out.ctypes.data), 'export_state failed')
+        return out
+
+    def import_state(self, blobs, streams=None) -> None:
+        """Continues the listed streams (None: slots 0 .. n - 1) from records: `blobs` is uint8 [n, state_size], a list of n `bytes`
+        objects of state_size each, or one such object."""
+        if isinstance(blobs, (bytes, bytearray, memoryview)):
+            blobs = [blobs]
+        if isinstance(blobs, (list, tuple)):
+            if any(not isinstance(b, (bytes, bytearray, memoryview, np.ndarray)) or len(b) != self.state_size for b in blobs):
+                raise KoalaInvalidArgumentError("every record must be %d bytes" % self.state_size)
+            blobs = np.frombuffer(b''.join(bytes(b) for b in blobs), np.uint8).reshape(len(blobs), self.state_size)
+        a = np.ascontiguousarray(blobs)
+        if a.dtype != np.uint8 or a.ndim != 2 or a.shape[1] != self.state_size:
+            raise KoalaInvalidArgumentError("expected uint8 records of shape [n, %d]" % self.state_size)
+        s, sp, n = self._stream_list(streams, a.shape[0])
+        self._check(self._lib.pv_koala_batch_import_state(self._handle, n, sp, a.ctypes.data), 'import_state failed')
+
+    def _hold_mask(self, hold):
+        if hold is None:
+            return None, None
+        m = np.ascontiguousarray(hold, dtype=np.uint8)
+        if m.shape != (self.num_streams,):
+            raise KoalaInvalidArgumentError("`hold` must have one entry per stream")
+        return m, m.ctypes.data
+
+    def process_hold(self, pcm: np.ndarray, hold: Optional[np.ndarray]) -> np.ndarray:
+        """`process()` in which the streams with hold[b] != 0 are not advanced (their state stays bit for bit what it was; their rows of
+        the result are unspecified).  `hold`: [num_streams] (None: nobody)."""
+        a = np.ascontiguousarray(pcm, dtype=np.int16)
+        if a.ndim != 2 or a.shape[0] != self.num_streams or a.shape[1] % self.frame_length:
+            raise KoalaInvalidArgumentError("expected int16 array of shape [%d, T*%d]" % (self.num_streams, self.frame_length))
+        m, mp = self._hold_mask(hold)
+        out = np.empty_like(a)
+        self._check(self._lib.pv_koala_batch_process_chunk_hold(self._handle, a.shape[1] // self.frame_length, a.ctypes.data,
+                                                                out.ctypes.data, mp), 'Processing failed')
+        return out
+
+    def process_device_hold(self, num_frames: int, pcm_ptr: int, enhanced_ptr: int, hold: Optional[np.ndarray]) -> None:
+        """`process_device()` with held streams: the host mask [num_streams] is read before the call returns, the work is enqueued on
+        the handle's stream."""
+        m, mp = self._hold_mask(hold)
+        self._check(self._lib.pv_koala_batch_process_chunk_hold(self._handle, num_frames, c_void_p(pcm_ptr), c_void_p(enhanced_ptr), mp),
                     'Processing failed')
 
     def reset(self, stream_mask: Optional[np.ndarray] = None) -> None:

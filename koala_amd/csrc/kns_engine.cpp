@@ -573,7 +573,8 @@ bool Engine::init(const Params &p, int device, int B, int Tmax, int precision, s
     // ---- tables and weights: shared with every other handle open on the same model, device and precision
     {
         std::lock_guard<std::mutex> lock(g_image_mutex);
-        const ImageKey key{params_key(p), device, precision};
+        model_key_ = params_key(p);
+        const ImageKey key{model_key_, device, precision};
         std::shared_ptr<void> held = g_images[key].lock();
         // (KOALA_AMD_NO_WEIGHT_CACHE, developer build: every handle builds its own image, as in rounds 1-5)
         if (held && !dev_env("KOALA_AMD_NO_WEIGHT_CACHE")) {
@@ -712,6 +713,10 @@ Engine::~Engine() {
     for (int i = 0; i < kResetRing; ++i) {
         if (h_rs_[i]) (void) hipHostFree(h_rs_[i]);
         if (rs_ev_[i]) (void) hipEventDestroy(rs_ev_[i]);
+    }
+    for (int i = 0; i < kResetRing; ++i) {
+        if (h_recof_[i]) (void) hipHostFree(h_recof_[i]);
+        if (recof_ev_[i]) (void) hipEventDestroy(recof_ev_[i]);
     }
     for (int i = 0; i < 4; ++i)
         if (aev_out_[i]) (void) hipEventDestroy(aev_out_[i]);
@@ -1934,6 +1939,184 @@ bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, 
 fail:
     *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
     return false;
+}
+
+// ------------------------------------------------------------------------------------------------ stream records
+
+namespace {
+struct StateHeader {  // the first 32 bytes of a record (kns_kernels.h)
+    uint32_t magic, version, front_taps, precision;
+    uint64_t model;
+    uint64_t reserved;
+};
+static_assert(sizeof(StateHeader) == kStateHeaderBytes, "record header");
+}  // namespace
+
+bool Engine::state_ready(std::string *err) {
+    if (d_state_) return true;
+    (void) hipSetDevice(device_);
+    uint8_t *d = (uint8_t *) dalloc((size_t) B_ * state_bytes(), false);
+    int32_t *t = d ? (int32_t *) dalloc((size_t) Bpad_ * 4, false) : nullptr;
+    bool ok = d && t;
+    for (int i = 0; i < kResetRing && ok; ++i)
+        ok = hipHostMalloc((void **) &h_recof_[i], (size_t) Bpad_ * 4, hipHostMallocDefault) == hipSuccess &&
+             hipEventCreateWithFlags(&recof_ev_[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {  // (what was allocated stays on the handle's lists and goes with the handle; the next call tries the rest again)
+        (void) hipGetLastError();
+        for (int i = 0; i < kResetRing; ++i) {
+            if (h_recof_[i]) (void) hipHostFree(h_recof_[i]);
+            if (recof_ev_[i]) (void) hipEventDestroy(recof_ev_[i]);
+            h_recof_[i] = nullptr;
+            recof_ev_[i] = nullptr;
+        }
+        *err = "Failed to allocate the staging buffers of stream records.";
+        return false;
+    }
+    d_recof_ = t;
+    d_state_ = d;
+    return true;
+}
+
+// Checks a stream list (nullptr: 0 .. count - 1) and uploads its inverse -- stream -> record, -1 = not listed -- on the handle's stream
+// from the next slot of a page-locked ring (a slot is rewritten once the copy that read it four uploads back has completed).
+bool Engine::state_list(int count, const int32_t *streams, std::string *err) {
+    state_bad_arg_ = true;
+    if (count < 1 || count > B_) {
+        *err = "`count` " + std::to_string(count) + " is outside [1, " + std::to_string(B_) + "].";
+        return false;
+    }
+    for (int i = 0; streams && i < count; ++i)
+        if (streams[i] < 0 || streams[i] >= B_) {
+            *err = "`streams[" + std::to_string(i) + "]` = " + std::to_string(streams[i]) + " is outside [0, " + std::to_string(B_) + ").";
+            return false;
+        }
+    std::vector<int32_t> inv((size_t) Bpad_, -1);
+    for (int i = 0; i < count; ++i) {
+        const int b = streams ? streams[i] : i;
+        if (inv[b] >= 0) {  // (refused for export too: one stream -> record table serves both directions)
+            *err = "`streams[" + std::to_string(i) + "]`: slot " + std::to_string(b) + " is listed twice.";
+            return false;
+        }
+        inv[b] = i;
+    }
+    state_bad_arg_ = false;
+    if (!state_ready(err)) return false;
+    const int k = (int) (recof_n_++ % kResetRing);
+    if (hipEventSynchronize(recof_ev_[k]) != hipSuccess) {  // (an event never recorded is complete)
+        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+        return false;
+    }
+    memcpy(h_recof_[k], inv.data(), (size_t) Bpad_ * 4);
+    if (hipMemcpyAsync(d_recof_, h_recof_[k], (size_t) Bpad_ * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+        hipEventRecord(recof_ev_[k], stream_) != hipSuccess) {
+        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+        return false;
+    }
+    return true;
+}
+
+StateArgs Engine::state_args() const {
+    StateArgs a;
+    a.hist[0] = d_hist_[hist_cur_], a.hist[1] = d_hist_[hist_cur_ ^ 1];
+    a.tail[0] = d_tail_[tail_cur_], a.tail[1] = d_tail_[tail_cur_ ^ 1];
+    a.hstate[0] = d_hstate_[hs_cur_], a.hstate[1] = d_hstate_[hs_cur_ ^ 1];
+    a.fhist = d_fhist_;
+    a.rec_of = d_recof_;
+    a.records = d_state_;
+    const StateHeader h{kStateMagic, kStateVersion, (uint32_t) taps_, (uint32_t) prec_, model_key_, 0};
+    memcpy(&a.hdr0, &h, 16);
+    memcpy(&a.hdr1, (const char *) &h + 16, 16);
+    a.state_bytes = (uint32_t) state_bytes();
+    a.Bpad = Bpad_;
+    a.nbf = nbf_;
+    a.precision = prec_;
+    a.taps = taps_;
+    return a;
+}
+
+bool Engine::export_state(int count, const int32_t *streams, void *host_records, std::string *err) {
+    (void) hipSetDevice(device_);
+    state_bad_arg_ = false;
+    if (async_n_ && !drain_async(err)) return false;
+    if (!state_list(count, streams, err)) return false;
+    launch_state_export(state_args(), stream_);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(host_records, d_state_, (size_t) count * state_bytes(), hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        *err = std::string("HIP error: ") + hipGetErrorString(e);
+        return false;
+    }
+    return true;
+}
+
+bool Engine::import_state(int count, const int32_t *streams, const void *host_records, std::string *err) {
+    (void) hipSetDevice(device_);
+    state_bad_arg_ = false;
+    if (async_n_ && !drain_async(err)) return false;
+    // every header before anything is written (the list is checked by state_list, which writes only the table)
+    const size_t S = state_bytes();
+    for (int i = 0; i < count && count <= B_; ++i) {
+        StateHeader h;
+        memcpy(&h, (const char *) host_records + (size_t) i * S, sizeof(h));
+        std::string what;
+        if (h.magic != kStateMagic) what = "magic is not `KNSS`";
+        else if (h.version != kStateVersion) what = "version " + std::to_string(h.version) + " is not " + std::to_string(kStateVersion);
+        else if (h.front_taps != (uint32_t) taps_)
+            what = "front_taps " + std::to_string(h.front_taps) + " does not match the handle's model (" + std::to_string(taps_) + ")";
+        else if (h.precision != (uint32_t) prec_)
+            what = std::string("precision is ") + (h.precision == kBf16 ? "bf16" : h.precision == kFp32 ? "fp32" : "unknown") +
+                   ", the handle's is " + (prec_ == kBf16 ? "bf16" : "fp32") + " (records do not cross precisions)";
+        else if (h.model != model_key_) what = "model hash does not match the handle's model";
+        if (!what.empty()) {
+            state_bad_arg_ = true;
+            *err = "record " + std::to_string(i) + ": " + what + ".";
+            return false;
+        }
+    }
+    if (!state_list(count, streams, err)) return false;
+    hipError_t e = hipMemcpyAsync(d_state_, host_records, (size_t) count * S, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess) {
+        launch_state_import(state_args(), stream_);
+        e = hipGetLastError();
+    }
+    // (the copy may read pageable records when it runs, not when it is enqueued: the call returns once the stream has passed it)
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        *err = std::string("HIP error: ") + hipGetErrorString(e);
+        return false;
+    }
+    return true;
+}
+
+// Held streams: export the held rows' records to the device scratch, run the call unchanged, import them back -- around the WHOLE call
+// (outside the one-frame graph and the sub-chunks of large host calls), all on the handle's stream, so a device-pointer call stays
+// enqueued without a host wait.  The import restores both ping-pong copies, whichever parity the call has left current.
+bool Engine::process_hold(int T, const int16_t *pcm, int16_t *out, const uint8_t *host_hold, bool host_pointers, std::string *err) {
+    state_bad_arg_ = false;
+    std::vector<int32_t> held;
+    for (int b = 0; host_hold && b < B_; ++b)
+        if (host_hold[b]) held.push_back(b);
+    if (held.empty()) return process(T, pcm, out, err, host_pointers);
+    (void) hipSetDevice(device_);
+    if (async_n_ && !drain_async(err)) return false;
+    if (!state_list((int) held.size(), held.data(), err)) return false;
+    launch_state_export(state_args(), stream_);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        *err = std::string("HIP error: ") + hipGetErrorString(e);
+        return false;
+    }
+    if (!process(T, pcm, out, err, host_pointers)) return false;  // (a refused call has advanced nothing)
+    launch_state_import(state_args(), stream_);
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        *err = std::string("HIP error: ") + hipGetErrorString(e);
+        return false;
+    }
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------ debug taps

@@ -39,6 +39,7 @@ public:
     ~Engine();
 
     // bytes of device memory this handle allocated itself / bytes of the weight image it shares (first handle on a model: it built it)
+    // (own: grows by the stream-record staging buffer, num_streams x state_bytes(), at the first export / import / held call)
     size_t own_device_bytes() const { return own_bytes_; }
     size_t shared_device_bytes() const;
     bool weights_were_cached() const { return weights_cached_; }
@@ -68,6 +69,23 @@ public:
     // queued on the previous stream, which must still exist: the next call's kernels touch the same state, history and tail buffers)
     void set_stream(hipStream_t s);
     bool synchronize(std::string *err);
+
+    // ---- per-stream state as stream records (kns_kernels.h, StateArgs: the record; kns_state.hip: the kernels).  `records` is HOST memory
+    // (pageable or page-locked), count x state_bytes(), record i = stream streams[i] (streams == nullptr: slots 0 .. count - 1).  Both
+    // calls first wait for asynchronous host calls in flight, then run on the handle's current stream, through a device staging buffer of
+    // num_streams records allocated on first use (it counts into own_device_bytes()).  export_state returns when the records are filled.
+    // import_state checks every header (magic, version, front_taps, precision, model hash -- a record of the other precision is refused:
+    // its feature context is the other engine's) and every index (outside [0, num_streams), the same slot twice) BEFORE anything is written,
+    // returns when the host records may be reused, and its scatter is ordered on the stream in front of the next call.  A failed call
+    // leaves all state as it was; state_bad_argument() then tells a refused argument from a HIP failure.
+    size_t state_bytes() const { return state_record_bytes(taps_); }
+    bool export_state(int count, const int32_t *streams, void *host_records, std::string *err);
+    bool import_state(int count, const int32_t *streams, const void *host_records, std::string *err);
+    // process() in which the streams with host_hold[b] != 0 are not advanced: their state after the call is bit for bit what it was before
+    // it (exported to a device scratch in front of the whole call and imported back behind it); their rows of `out` are unspecified.
+    // nullptr or all zero: process() itself.  Not combined with per-frame resets or the asynchronous host path.
+    bool process_hold(int T, const int16_t *pcm, int16_t *out, const uint8_t *host_hold, bool host_pointers, std::string *err);
+    bool state_bad_argument() const { return state_bad_arg_; }
 
     void profile_enable(bool on);
     bool profile_read(double *ms, int64_t *launches, std::string *err);
@@ -195,6 +213,18 @@ private:
     bool begin_resets(int T, const uint8_t *mask, std::string *err);
     ResetArgs reset_args(const uint8_t *d_mask) const;
     struct ResetScope;  // the reset kernel's arguments (d_mask: device [Bpad], null: every stream)
+
+    // stream records (export_state / import_state / process_hold): the device staging buffer [B_][state_bytes()], the stream -> record
+    // table on the device [Bpad_] and its page-locked upload ring (one slot per call that may still be in flight, as the reset ring)
+    uint64_t model_key_ = 0;  // content hash of the parameters: the key of the shared weight image, the `model hash` of a record
+    uint8_t *d_state_ = nullptr;
+    int32_t *d_recof_ = nullptr, *h_recof_[kResetRing] = {};
+    hipEvent_t recof_ev_[kResetRing] = {};
+    unsigned recof_n_ = 0;
+    bool state_bad_arg_ = false;
+    bool state_ready(std::string *err);
+    bool state_list(int count, const int32_t *streams, std::string *err);  // checks the list, uploads its inverse table
+    StateArgs state_args() const;
 
     // profiling
     bool profiling_ = false;

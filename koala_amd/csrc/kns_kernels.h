@@ -247,6 +247,37 @@ struct ResetArgs {
     int fhist_frames = 0, nbf = 0;
 };
 void launch_reset(const ResetArgs &a, hipStream_t s);
+// ---- per-stream state <-> stream records (kns_state.hip).  A record is self-contained and position-independent (little-endian):
+//   header, 32 bytes: magic "KNSS", uint32 version (1), uint32 front_taps, uint32 precision, uint64 model content hash (the hash the
+//                     shared weight image is keyed on), 8 reserved zero bytes
+//   hist   int16[256]                    the previous frame's samples (the analysis kernel's hist_in)
+//   tail   float[256]                    overlap-add tail
+//   h      float[8][271]                 hidden state, layer-major, logical unit order (the order of debug tap 3)
+//   fctx   float[front_taps - 1][257]    feature context, oldest first (absent for front_taps == 1); bf16 features widened to float
+// 10 240 bytes for front_taps == 1.  It does not depend on the batch size, the slot, the m-tile, the ping-pong parity or the route;
+// padding rows and columns of the packed layouts never enter it and are left alone on import.  A record belongs to one model and one
+// precision: importing into a handle of the other precision is refused (a bf16 handle's feature context is not an fp32 handle's).
+constexpr uint32_t kStateMagic = 0x53534e4bu;  // "KNSS"
+constexpr uint32_t kStateVersion = 1;
+constexpr int kStateHeaderBytes = 32, kStateHistOff = 32, kStateTailOff = kStateHistOff + kFrame * 2,
+              kStateHOff = kStateTailOff + kFrame * 4, kStateFctxOff = kStateHOff + kGruLayers * kHidden * 4;
+static_assert(kStateFctxOff == 10240 && kStateFctxOff % 16 == 0 && (kBins * 4 * 4) % 16 == 0, "stream record layout");
+KNS_HD size_t state_record_bytes(int front_taps) {  // whole 16-byte words (front_taps 2 ... 4: up to 12 trailing zero bytes)
+    return ((size_t) kStateFctxOff + (size_t) (front_taps - 1) * kBins * 4 + 15) / 16 * 16;
+}
+struct StateArgs {
+    int16_t *hist[2];   // [Bpad][256]; [0] = the current ping-pong copy (export reads it; import writes both)
+    float *tail[2];     // [Bpad][256]
+    float *hstate[2];   // C-packed [8][mtiles][17][64][4]
+    void *fhist;        // A-packed [front_taps][mtiles][nbf] blocks (slot 0 is the one-frame roll's spare: not part of the state)
+    const int32_t *rec_of;  // [Bpad]: the record of stream b in `records`, -1 = not listed (the inverse of the caller's stream list)
+    uint8_t *records;   // [count][state_bytes], device memory
+    uint4 hdr0, hdr1;   // the 32 header bytes (export)
+    uint32_t state_bytes;
+    int Bpad, nbf, precision, taps;
+};
+void launch_state_export(const StateArgs &a, hipStream_t s);
+void launch_state_import(const StateArgs &a, hipStream_t s);
 // last node of a captured one-frame replay: ++*counter (device memory), published to *host_word (page-locked host memory)
 void launch_frame_done(unsigned *counter, unsigned *host_word, hipStream_t s);
 

@@ -17,9 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pv_koala.h"
-#include "../../include/pv_koala_batch.h"
-#include "kns_engine.h"
+#include "pv_api_internal.h"
 
 #ifdef KNS_TIMING
 namespace kns {
@@ -33,7 +31,12 @@ const char kBuildId[] = "a355c0a";  // 7 hex digits, as the reference prints in 
 
 thread_local std::vector<std::string> t_stack;
 
-void push_error(unsigned code, const char *fmt, ...) {
+}  // namespace
+
+// (these two are shared with the shim's other translation unit, pv_api_state.cpp, through pv_api_internal.h)
+void pv_api::clear_errors() { t_stack.clear(); }
+
+void pv_api::push_error(unsigned code, const char *fmt, ...) {
     char text[768];
     va_list ap;
     va_start(ap, fmt);
@@ -43,6 +46,11 @@ void push_error(unsigned code, const char *fmt, ...) {
     snprintf(line, sizeof(line), "%s %08X: %s", kBuildId, code, text);
     if (t_stack.size() < 8) t_stack.push_back(line);
 }
+
+namespace {
+
+using pv_api::guarded;
+using pv_api::push_error;
 
 std::mutex g_sdk_mutex;
 std::string g_sdk = "c";
@@ -99,27 +107,6 @@ bool parse_device(const char *text, DeviceSpec *out) {
         return true;
     }
     return false;
-}
-
-// No C++ exception may cross the C ABI (the callers are ctypes / dlsym hosts: an escaping exception is std::terminate).  Every
-// entry point that reaches engine code runs it through this: bad_alloc -> OUT_OF_MEMORY, anything else -> RUNTIME_ERROR.
-template <class F>
-pv_status_t guarded(F &&body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        push_error(0x65, "Failed to allocate memory.");
-        return PV_STATUS_OUT_OF_MEMORY;
-    } catch (const std::length_error &) {
-        push_error(0x65, "Failed to allocate memory.");
-        return PV_STATUS_OUT_OF_MEMORY;
-    } catch (const std::exception &e) {
-        push_error(0x339, "Unexpected failure: %s", e.what());
-        return PV_STATUS_RUNTIME_ERROR;
-    } catch (...) {
-        push_error(0x339, "Unexpected failure.");
-        return PV_STATUS_RUNTIME_ERROR;
-    }
 }
 
 // shared front half of pv_koala_init / pv_koala_batch_init
@@ -206,13 +193,6 @@ int default_precision() {
 }
 
 }  // namespace
-
-struct pv_koala {
-    kns::Engine *engine;
-};
-struct pv_koala_batch {
-    kns::Engine *engine;
-};
 
 extern "C" {
 

@@ -1,0 +1,146 @@
+"""
+Stream records (include/pv_koala_batch.h: pv_koala_batch_state_size / export_state / import_state / process_chunk_hold) without a GPU:
+the symbols, their argument checks, the gfx950 build of the two kernels (koala_amd/csrc/kns_state.hip), and a pure-numpy statement of
+the record layout that tests/test_gpu_stream_state.py reuses to read records.
+"""
+import ctypes
+import os
+import re
+import shutil
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import koala_amd
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+SYMBOLS = ('pv_koala_batch_state_size', 'pv_koala_batch_export_state', 'pv_koala_batch_import_state',
+           'pv_koala_batch_process_chunk_hold')
+PV_STATUS_INVALID_ARGUMENT = 3
+
+# ---- the record: header 32 | hist int16[256] | tail float[256] | h float[8][271] | fctx float[taps - 1][257]
+MAGIC = b'KNSS'
+VERSION = 1
+HEADER = struct.Struct('<4sIIIQ8s')  # magic, version, front_taps, precision, model hash, reserved
+OFF_HIST, OFF_TAIL, OFF_H, OFF_FCTX = 32, 32 + 512, 32 + 512 + 1024, 32 + 512 + 1024 + 8 * 271 * 4
+
+
+def record_size(front_taps):
+    """bytes of a record; whole 16-byte words (front_taps 1 and 5, the models that exist, need no padding)"""
+    return (OFF_FCTX + (front_taps - 1) * 257 * 4 + 15) // 16 * 16
+
+
+def pack_record(front_taps, precision, model_hash, hist, tail, h, fctx=None):
+    out = np.zeros(record_size(front_taps), np.uint8)
+    out[:32] = np.frombuffer(HEADER.pack(MAGIC, VERSION, front_taps, precision, model_hash, bytes(8)), np.uint8)
+    out[OFF_HIST:OFF_TAIL] = np.ascontiguousarray(hist, '<i2').reshape(256).view(np.uint8)
+    out[OFF_TAIL:OFF_H] = np.ascontiguousarray(tail, '<f4').reshape(256).view(np.uint8)
+    out[OFF_H:OFF_FCTX] = np.ascontiguousarray(h, '<f4').reshape(8 * 271).view(np.uint8)
+    if front_taps > 1:
+        out[OFF_FCTX:OFF_FCTX + (front_taps - 1) * 1028] = np.ascontiguousarray(fctx, '<f4').reshape((front_taps - 1) * 257).view(np.uint8)
+    return out
+
+
+def unpack_record(blob):
+    """-> dict(front_taps, precision, model_hash, hist [256] int16, tail [256] float32, h [8, 271] float32, fctx [taps - 1, 257] float32)"""
+    raw = bytes(blob)
+    magic, version, taps, precision, model_hash, reserved = HEADER.unpack(raw[:32])
+    assert magic == MAGIC and version == VERSION and reserved == bytes(8), (magic, version, reserved)
+    assert len(raw) == record_size(taps), (len(raw), taps)
+    return dict(front_taps=taps, precision=precision, model_hash=model_hash,
+                hist=np.frombuffer(raw, '<i2', 256, OFF_HIST), tail=np.frombuffer(raw, '<f4', 256, OFF_TAIL),
+                h=np.frombuffer(raw, '<f4', 8 * 271, OFF_H).reshape(8, 271),
+                fctx=np.frombuffer(raw, '<f4', (taps - 1) * 257, OFF_FCTX).reshape(taps - 1, 257))
+
+
+def test_record_layout_round_trips():
+    assert (OFF_HIST, OFF_TAIL, OFF_H, OFF_FCTX) == (32, 544, 1568, 10240)
+    assert record_size(1) == 10240 and record_size(5) == 10240 + 4 * 257 * 4
+    rng = np.random.default_rng(5)
+    for taps in (1, 5):
+        hist = rng.integers(-32768, 32768, 256).astype(np.int16)
+        tail, h = rng.standard_normal(256).astype(np.float32), rng.standard_normal((8, 271)).astype(np.float32)
+        fctx = rng.standard_normal((taps - 1, 257)).astype(np.float32)
+        blob = pack_record(taps, 1, 0x0123456789abcdef, hist, tail, h, fctx)
+        assert blob.size == record_size(taps)
+        assert bytes(blob[:4]) == b'KNSS' and bytes(blob[4:8]) == b'\x01\0\0\0' and bytes(blob[24:32]) == bytes(8)
+        assert bytes(blob[16:24]) == bytes.fromhex('efcdab8967452301')  # little-endian
+        r = unpack_record(bytes(blob))
+        assert (r['front_taps'], r['precision'], r['model_hash']) == (taps, 1, 0x0123456789abcdef)
+        assert np.array_equal(r['hist'], hist) and np.array_equal(r['tail'], tail) and np.array_equal(r['h'], h)
+        assert np.array_equal(r['fctx'], fctx)
+        assert np.array_equal(pack_record(taps, 1, 0x0123456789abcdef, r['hist'], r['tail'], r['h'], r['fctx']), blob)
+
+
+def test_symbols_are_exported_and_declared(native_library):
+    header = open(os.path.join(ROOT, 'include', 'pv_koala_batch.h')).read()
+    for path in (native_library, koala_amd.developer_library_path()):
+        lib = ctypes.CDLL(path)
+        for sym in SYMBOLS:
+            assert hasattr(lib, sym), (path, sym)
+    for sym in SYMBOLS:
+        assert re.search(r'PV_API pv_status_t %s\(' % sym, header), sym
+
+
+def _stack(lib):
+    msgs, depth = ctypes.POINTER(ctypes.c_char_p)(), ctypes.c_int32()
+    status = lib.pv_get_error_stack(ctypes.byref(msgs), ctypes.byref(depth))
+    if depth.value == 0:  # (nothing pending: PV_STATUS_INVALID_STATE and nothing to free)
+        return []
+    assert status == 0
+    out = [msgs[i].decode() for i in range(depth.value)]
+    lib.pv_free_error_stack(msgs)
+    return out
+
+
+def test_null_arguments_are_refused_without_a_gpu(native_library):
+    lib = ctypes.CDLL(native_library)
+    lib.pv_get_error_stack.argtypes = [ctypes.POINTER(ctypes.POINTER(ctypes.c_char_p)), ctypes.POINTER(ctypes.c_int32)]
+    lib.pv_free_error_stack.argtypes = [ctypes.POINTER(ctypes.c_char_p)]
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    lib.pv_koala_batch_state_size.argtypes = [vp, vp]
+    lib.pv_koala_batch_export_state.argtypes = [vp, i32, vp, vp]
+    lib.pv_koala_batch_import_state.argtypes = [vp, i32, vp, vp]
+    lib.pv_koala_batch_process_chunk_hold.argtypes = [vp, i32, vp, vp, vp]
+    n = ctypes.c_int32(-7)
+    buf = (ctypes.c_uint8 * 16)()
+    calls = [lambda: lib.pv_koala_batch_state_size(None, ctypes.byref(n)),
+             lambda: lib.pv_koala_batch_state_size(None, None),
+             lambda: lib.pv_koala_batch_export_state(None, 1, None, buf),
+             lambda: lib.pv_koala_batch_export_state(None, 1, None, None),
+             lambda: lib.pv_koala_batch_import_state(None, 1, None, buf),
+             lambda: lib.pv_koala_batch_import_state(None, 1, None, None),
+             lambda: lib.pv_koala_batch_process_chunk_hold(None, 1, buf, buf, buf),
+             lambda: lib.pv_koala_batch_process_chunk_hold(None, 1, None, None, None)]
+    for call in calls:
+        assert call() == PV_STATUS_INVALID_ARGUMENT
+        msgs = _stack(lib)
+        assert len(msgs) == 1 and 'NULL' in msgs[0], msgs
+        assert _stack(lib) == []  # drained
+    assert n.value == -7
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not available')
+def test_state_kernels_build_for_gfx950_without_spills(tmp_path):
+    import isa_scan
+    src = 'kns_state.hip'
+    out = tmp_path / (src + '.s')
+    mk = open(os.path.join(ROOT, 'koala_amd', 'Makefile')).read()
+    assert 'csrc/' + src in mk and 'obj/kns_state.o' in mk
+    cxx = re.search(r'^CXXFLAGS\s*=\s*(.*)$', mk, re.M).group(1).split()
+    m = re.search(r'^FLAGS_%s\s*=\s*(.*)$' % src.split('.')[0], mk, re.M)
+    flags = [f for f in cxx if f not in ('-fPIC',)] + (m.group(1).split() if m else [])
+    subprocess.check_call([HIPCC, '--offload-arch=gfx950'] + flags +
+                          ['-S', '--cuda-device-only', '-x', 'hip', os.path.join(ROOT, 'koala_amd', 'csrc', src), '-o', str(out)],
+                          stderr=subprocess.DEVNULL)
+    text = out.read_text()
+    assert isa_scan.scan(text) == []
+    found = dict(re.findall(r'\.set (\S+)\.has_indirect_call, \d+\n[^\n]*\n; Kernel info:\n(?:;[^\n]*\n)*?; ScratchSize: (\d+)', text))
+    assert any('state_export_kernel' in k for k in found) and any('state_import_kernel' in k for k in found), list(found)
+    spills = {k: int(v) for k, v in found.items() if int(v) > 16}
+    assert not spills, 'kernels spill registers to scratch: %r' % spills
