@@ -245,7 +245,6 @@ std::string gpu_name(int device) {
 
 struct Engine::WeightImage {
     int device = 0;
-    size_t bytes = 0;
     std::vector<void *> allocs;
     float *window = nullptr, *twiddle = nullptr, *mean = nullptr, *scale = nullptr, *b_in = nullptr;
     void *w_in = nullptr;
@@ -291,9 +290,11 @@ struct ImageKey {
 };
 std::mutex g_image_mutex;
 std::map<ImageKey, std::weak_ptr<void>> g_images;  // (weak: an image lives as long as a handle holds it)
-}  // namespace
 
-size_t Engine::shared_device_bytes() const { return weights_ ? weights_->bytes : 0; }
+// every HIP failure the engine reports reads "HIP error: <the runtime's text>"
+std::string hip_error(hipError_t e) { return std::string("HIP error: ") + hipGetErrorString(e); }
+std::string hip_last_error() { return hip_error(hipGetLastError()); }
+}  // namespace
 
 void *Engine::dalloc(size_t bytes, bool zero) {
     void *p = nullptr;
@@ -302,13 +303,7 @@ void *Engine::dalloc(size_t bytes, bool zero) {
         alloc_failed_ = true;
         return nullptr;
     }
-    if (alloc_sink_) {
-        alloc_sink_->push_back(p);
-        weights_->bytes += bytes ? bytes : 16;
-    } else {
-        allocs_.push_back(p);
-        own_bytes_ += bytes ? bytes : 16;
-    }
+    (alloc_sink_ ? *alloc_sink_ : allocs_).push_back(p);
     // (on the handle's own non-blocking stream: a legacy-stream operation would collide with another handle's graph capture)
     if (zero) (void) hipMemsetAsync(p, 0, bytes, own_stream_);
     return p;
@@ -579,7 +574,6 @@ bool Engine::init(const Params &p, int device, int B, int Tmax, int precision, s
         // (KOALA_AMD_NO_WEIGHT_CACHE, developer build: every handle builds its own image, as in rounds 1-5)
         if (held && !dev_env("KOALA_AMD_NO_WEIGHT_CACHE")) {
             weights_ = std::static_pointer_cast<WeightImage>(held);
-            weights_cached_ = true;
         } else {
             weights_ = std::make_shared<WeightImage>();
             weights_->device = device;
@@ -710,14 +704,8 @@ Engine::~Engine() {
     if (h_frame_word_) (void) hipHostFree(h_frame_word_);
     if (h_in_) (void) hipHostFree(h_in_);
     if (h_out_) (void) hipHostFree(h_out_);
-    for (int i = 0; i < kResetRing; ++i) {
-        if (h_rs_[i]) (void) hipHostFree(h_rs_[i]);
-        if (rs_ev_[i]) (void) hipEventDestroy(rs_ev_[i]);
-    }
-    for (int i = 0; i < kResetRing; ++i) {
-        if (h_recof_[i]) (void) hipHostFree(h_recof_[i]);
-        if (recof_ev_[i]) (void) hipEventDestroy(recof_ev_[i]);
-    }
+    rs_ring_.release();
+    recof_ring_.release();
     for (int i = 0; i < 4; ++i)
         if (aev_out_[i]) (void) hipEventDestroy(aev_out_[i]);
     for (int i = 0; i < 2; ++i) {
@@ -781,7 +769,7 @@ void Engine::profile_enable(bool on) {
 
 bool Engine::profile_read(double *ms, int64_t *launches, std::string *err) {
     if (hipStreamSynchronize(stream_) != hipSuccess) {
-        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+        *err = hip_last_error();
         return false;
     }
     for (Span &s : spans_) {
@@ -803,7 +791,7 @@ bool Engine::profile_read(double *ms, int64_t *launches, std::string *err) {
 bool Engine::synchronize(std::string *err) {
     if (async_n_ && !drain_async(err)) return false;
     if (hipStreamSynchronize(stream_) != hipSuccess) {
-        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+        *err = hip_last_error();
         return false;
     }
     return true;
@@ -837,7 +825,7 @@ bool Engine::reset(const uint8_t *host_mask, std::string *err) {
         if (ce == hipSuccess) ce = hipStreamSynchronize(stream_);  // `m` goes out of scope
         if (ce != hipSuccess) {  // a stale mask would reset the wrong streams: report, do not launch
             (void) hipGetLastError();
-            *err = std::string("HIP error: ") + hipGetErrorString(ce);
+            *err = hip_error(ce);
             return false;
         }
         r.mask = d_rmask_;
@@ -845,22 +833,56 @@ bool Engine::reset(const uint8_t *host_mask, std::string *err) {
     launch_reset(r, stream_);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        *err = std::string("HIP error: ") + hipGetErrorString(e);
+        *err = hip_error(e);
         return false;
     }
     return true;
 }
 
-// Per-frame stream resets of the call about to run (the mask parked by park_resets, uint8 [B][T] host memory), before anything of the call
-// is enqueued.  Resets at frame 0 only: the reset kernel in front of the call, which then takes its normal route.  Resets at some frame
-// t > 0 (refused for a several-frame front-end, whose feature history the reset arms do not rebuild): the mask is packed per (m-tile,
-// frame) into a page-locked ring slot -- bit r of word [mt][t] = stream 16 mt + r restarts right before frame t -- which run_device uploads
-// on the stream of the call's kernels and reads through the kernels' reset arms (kRouteChunkedResets).  A slot is reused four calls
-// later, after the copy that read it has completed (an event): the asynchronous window is three calls, and a device-pointer caller waits
-// only when it is four calls ahead of the GPU.
-bool Engine::begin_resets(int T, const uint8_t *mask, std::string *err) {
-    rs_active_ = false;
-    rs_t0_ = 0;
+bool Engine::UploadRing::ready(size_t slot_bytes) {
+    if (host[0]) return true;
+    bool ok = true;
+    for (int i = 0; i < kResetRing && ok; ++i)
+        ok = hipHostMalloc(&host[i], slot_bytes, hipHostMallocDefault) == hipSuccess &&
+             hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        (void) hipGetLastError();
+        release();
+    }
+    return ok;
+}
+
+int Engine::UploadRing::acquire() {
+    const int k = (int) (n % kResetRing);
+    if (pending[k] && hipEventSynchronize(ev[k]) != hipSuccess) return -1;
+    pending[k] = false;
+    ++n;
+    return k;
+}
+
+bool Engine::UploadRing::uploaded(int slot, hipStream_t stream) {
+    pending[slot] = hipEventRecord(ev[slot], stream) == hipSuccess;
+    return pending[slot];
+}
+
+void Engine::UploadRing::release() {
+    for (int i = 0; i < kResetRing; ++i) {
+        if (host[i]) (void) hipHostFree(host[i]);
+        if (ev[i]) (void) hipEventDestroy(ev[i]);
+        host[i] = nullptr;
+        ev[i] = nullptr;
+        pending[i] = false;
+    }
+}
+
+// Per-frame stream resets of the call about to run (Call::resets, uint8 [B][T] host memory), before anything of the call is enqueued;
+// `table` is the caller's, fresh.  Resets at frame 0 only: the reset kernel in front of the call, which then takes its normal route.
+// Resets at some frame t > 0 (refused for a several-frame front-end, whose feature history the reset arms do not rebuild): the mask is
+// packed per (m-tile, frame) into a page-locked ring slot -- bit r of word [mt][t] = stream 16 mt + r restarts right before frame t -- and
+// `table` says so; run_device uploads the slot on the stream of the call's kernels and reads it through the kernels' reset arms
+// (kRouteChunkedResets).  A slot is reused four calls later, after the copy that read it has completed (an event): the asynchronous
+// window is three calls, and a device-pointer caller waits only when it is four calls ahead of the GPU.
+bool Engine::begin_resets(int T, const uint8_t *mask, ResetTable *table, std::string *err) {
     if (!mask) return true;
     bool first = false, late = false;
     for (int b = 0; b < B_; ++b) {
@@ -874,52 +896,37 @@ bool Engine::begin_resets(int T, const uint8_t *mask, std::string *err) {
         return false;
     }
     const int mtb = Bpad_ / 16;
-    const size_t slot_bytes = std::max((size_t) mtb * Tmax_ * 4, (size_t) Bpad_);
     if (!d_rs_) {  // first use: the ring and the device table
-        bool ok = true;
-        for (int i = 0; i < kResetRing && ok; ++i) {
-            ok = hipHostMalloc((void **) &h_rs_[i], slot_bytes, hipHostMallocDefault) == hipSuccess;
-            ok = ok && hipEventCreateWithFlags(&rs_ev_[i], hipEventDisableTiming) == hipSuccess;
-        }
+        const bool ok = rs_ring_.ready(std::max((size_t) mtb * Tmax_ * 4, (size_t) Bpad_));
         unsigned *d = ok ? (unsigned *) dalloc((size_t) mtb * Tmax_ * 4, false) : nullptr;
         if (!d) {
-            (void) hipGetLastError();
-            for (int i = 0; i < kResetRing; ++i) {
-                if (h_rs_[i]) (void) hipHostFree(h_rs_[i]);
-                if (rs_ev_[i]) (void) hipEventDestroy(rs_ev_[i]);
-                h_rs_[i] = nullptr;
-                rs_ev_[i] = nullptr;
-            }
             *err = "Failed to allocate the buffers of per-frame stream resets.";
             return false;
         }
         d_rs_ = d;
     }
-    const int k = (int) (rs_n_ % kResetRing);
-    if (rs_ev_set_[k] && hipEventSynchronize(rs_ev_[k]) != hipSuccess) {
-        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+    const int k = rs_ring_.acquire();
+    if (k < 0) {
+        *err = hip_last_error();
         return false;
     }
-    rs_ev_set_[k] = false;
-    ++rs_n_;
     if (!late) {  // frame 0 only: the reset kernel on the call's stream, right in front of it
-        uint8_t *bytes = (uint8_t *) h_rs_[k];
+        uint8_t *bytes = (uint8_t *) rs_ring_.host[k];
         memset(bytes, 0, (size_t) Bpad_);
         for (int b = 0; b < B_; ++b) bytes[b] = mask[(size_t) b * T] != 0;
-        bool ok = hipMemcpyAsync(d_rmask_, bytes, (size_t) Bpad_, hipMemcpyHostToDevice, stream_) == hipSuccess;
-        ok = ok && hipEventRecord(rs_ev_[k], stream_) == hipSuccess;
-        rs_ev_set_[k] = ok;
+        const bool ok = hipMemcpyAsync(d_rmask_, bytes, (size_t) Bpad_, hipMemcpyHostToDevice, stream_) == hipSuccess &&
+                        rs_ring_.uploaded(k, stream_);
         if (ok) launch_reset(reset_args(d_rmask_), stream_);
         const hipError_t e = hipGetLastError();
         if (!ok || e != hipSuccess) {
-            *err = std::string("HIP error: ") + hipGetErrorString(e);
+            *err = hip_error(e);
             return false;
         }
         return true;
     }
-    unsigned *w = h_rs_[k];
+    unsigned *w = (unsigned *) rs_ring_.host[k];
     memset(w, 0, (size_t) mtb * T * 4);
-    rs_frame_.assign((size_t) T, 0);
+    table->frame.assign((size_t) T, 0);
     for (int b = 0; b < B_; ++b) {
         const uint8_t *row = mask + (size_t) b * T;
         unsigned *wm = w + (size_t) (b >> 4) * T;
@@ -927,13 +934,11 @@ bool Engine::begin_resets(int T, const uint8_t *mask, std::string *err) {
         for (int t = 0; t < T; ++t)
             if (row[t]) {
                 wm[t] |= bit;
-                rs_frame_[t] = 1;
+                table->frame[t] = 1;
             }
     }
-    rs_slot_ = k;
-    rs_T_ = T;
-    rs_uploaded_ = false;
-    rs_active_ = true;
+    table->slot = k;
+    table->T = T;
     return true;
 }
 
@@ -1131,18 +1136,23 @@ void Engine::run_wave(int T, int mtb) {
 //   Host-pointer calls: >= 4 MiB and more than min(16, max_frames / 2) frames -> sub-chunks on three streams; T = 1 -> hipGraph replay.
 enum Route { kRouteChunked = 0, kRouteSmall = 1, kRouteSmallSteps = 2, kRouteQuad1 = 3, kRouteWave = 4, kRoutePipelined = 5, kRouteChunkedResets = 6 };
 
-bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string *err, bool allow_recompute) {
+bool Engine::run_device(const Slice &slice, std::string *err) {
+    const int T = slice.T;
+    const int16_t *d_pcm = slice.d_pcm;
+    int16_t *d_out = slice.d_out;
+    const bool allow_recompute = slice.allow_recompute;
     const int mtb = Bpad_ / 16;
     last_T_ = T;
     // per-frame stream resets in these frames (begin_resets): the chunked route with the kernels' reset arms, whatever the batch size
-    const bool resets = rs_active_ && std::any_of(rs_frame_.begin() + rs_t0_, rs_frame_.begin() + rs_t0_ + T, [](uint8_t v) { return v != 0; });
-    if (resets && !rs_uploaded_) {  // the call's table, on the stream of its kernels (its first sub-chunk that needs it)
-        (void) hipMemcpyAsync(d_rs_, h_rs_[rs_slot_], (size_t) mtb * rs_T_ * 4, hipMemcpyHostToDevice, stream_);
-        (void) hipEventRecord(rs_ev_[rs_slot_], stream_);
-        rs_ev_set_[rs_slot_] = true;
-        rs_uploaded_ = true;
+    ResetTable *table = slice.resets && slice.resets->slot >= 0 ? slice.resets : nullptr;
+    const bool resets = table && std::any_of(table->frame.begin() + slice.t0, table->frame.begin() + slice.t0 + T, [](uint8_t v) { return v != 0; });
+    if (resets && !table->uploaded) {  // the call's table, on the stream of its kernels (its first sub-chunk that needs it)
+        (void) hipMemcpyAsync(d_rs_, rs_ring_.host[table->slot], (size_t) mtb * table->T * 4, hipMemcpyHostToDevice, stream_);
+        (void) rs_ring_.uploaded(table->slot, stream_);
+        table->uploaded = true;
     }
     const unsigned *rs = resets ? d_rs_ : nullptr;
+    const int rs_pitch = table ? table->T : 0, rs_t0 = slice.t0;  // (where these frames are in the table)
 
     AnalysisArgs an;
     an.pcm = d_pcm;
@@ -1175,8 +1185,8 @@ bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string
     an.nbf = nbf_;
     an.precision = prec_;
     an.resets = rs;
-    an.rs_pitch = rs_T_;
-    an.rs_t0 = rs_t0_;
+    an.rs_pitch = rs_pitch;
+    an.rs_t0 = rs_t0;
     // The spectrum makes its round trip through HBM only where it has to: in single-frame calls (the history is updated in
     // place there, so the synthesis kernel cannot rebuild it) and when the debug taps are on.  Otherwise the synthesis
     // kernel recomputes it from the PCM.
@@ -1255,8 +1265,8 @@ bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string
         g.precision = prec_;
         g.dev = dev_variant_;
         g.resets = rs;
-        g.rs_pitch = rs_T_;
-        g.rs_t0 = rs_t0_;
+        g.rs_pitch = rs_pitch;
+        g.rs_t0 = rs_t0;
         tick(kClsGru);
         if (only < 0 || only == kClsGru) launch_gru(g, c_stream);
         tock(kClsGru);
@@ -1434,8 +1444,8 @@ bool Engine::run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string
         sy.pitch = T;
         sy.prev_in_pcm = t0c > 0 ? 1 : 0;
         sy.resets = rs;
-        sy.rs_pitch = rs_T_;
-        sy.rs_t0 = rs_t0_ + t0c;
+        sy.rs_pitch = rs_pitch;
+        sy.rs_t0 = rs_t0 + t0c;
         launch_synthesis(sy, st);
     };
     if (pipelined) (void) hipEventRecord(pipe_fork_, stream_);
@@ -1601,7 +1611,10 @@ std::vector<int> Engine::host_schedule(int T) const {
     return sched;
 }
 
-bool Engine::process_host_pipelined(int T, const int16_t *pcm, int16_t *out, bool pinned, std::string *err) {
+bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *resets, std::string *err) {
+    const int T = call.T;
+    const int16_t *pcm = call.pcm;
+    int16_t *out = call.out;
     const std::vector<int> sched = host_schedule(T);
     const int n = (int) sched.size();
     std::vector<int> first(n + 1, 0);  // first frame of chunk c
@@ -1633,8 +1646,7 @@ bool Engine::process_host_pipelined(int T, const int16_t *pcm, int16_t *out, boo
         // ---- kernels (d_out_ slot s was last drained by the D2H of chunk c - 2)
         check(hipStreamWaitEvent(stream_, ev_in_[s], 0));
         if (c >= 2) check(hipStreamWaitEvent(stream_, ev_out_[s], 0));
-        rs_t0_ = first[c];  // (per-frame stream resets: the sub-chunk's frames of the call's table)
-        if (ok && !run_device(tc, d_in_ + s * slot, d_out_ + s * slot, err)) {
+        if (ok && !run_device({first[c], tc, d_in_ + s * slot, d_out_ + s * slot, true, resets}, err)) {
             // copies of earlier sub-chunks may still be writing into the caller's buffers: let them finish first
             (void) hipStreamSynchronize(copy_in_);
             (void) hipStreamSynchronize(copy_out_);
@@ -1663,7 +1675,7 @@ bool Engine::process_host_pipelined(int T, const int16_t *pcm, int16_t *out, boo
     }
     if (ok) check(hipStreamSynchronize(stream_));
     if (!ok) {
-        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+        *err = hip_last_error();
         (void) hipDeviceSynchronize();
         return false;
     }
@@ -1688,7 +1700,7 @@ bool Engine::drain_async(std::string *err) {
         async_busy_[i] = false;
     }
     if (!ok) {
-        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+        *err = hip_last_error();
         (void) hipDeviceSynchronize();
     }
     return ok;
@@ -1701,20 +1713,13 @@ bool Engine::async_wait(int max_in_flight, std::string *err) {
         const int ring = (int) ((async_n_ - (unsigned) j) & 3u);
         if (!async_busy_[ring]) continue;
         if (hipEventSynchronize(aev_out_[ring]) != hipSuccess) {
-            *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+            *err = hip_last_error();
             return false;
         }
         async_busy_[ring] = false;
     }
     return true;
 }
-
-// per-frame stream resets apply to one call: whichever way it leaves, the packed table is no longer the next call's
-struct Engine::ResetScope {
-    Engine *e;
-    explicit ResetScope(Engine *engine) : e(engine) {}
-    ~ResetScope() { e->rs_active_ = false, e->rs_t0_ = 0; }
-};
 
 // One asynchronous host call = H2D on copy_in_, the kernels on the handle's stream, D2H on copy_out_, chained by events.  Up to
 // THREE calls are in flight: with two, a caller alternating between two buffer pairs cannot issue call n + 2 before call n's copy-out has
@@ -1723,20 +1728,25 @@ struct Engine::ResetScope {
 // staging alternates between two slots: the input half of slot s is free once the kernels of call n - 2 have read it, the output half
 // once call n - 2's copy-out has -- both waited for on the device, by the stream that needs it.  A synchronous call of that size cannot
 // hide its first copy-in and last copy-out and has to cut its kernels into short, less efficient sub-chunks (process_host_pipelined).
-bool Engine::process_host_async(int T, const int16_t *pcm, int16_t *out, std::string *err) {
-    const uint8_t *resets = parked_resets_;  // (taken first: consumed by this call whatever happens below)
-    parked_resets_ = nullptr;
+Status Engine::process_host_async(const Call &c, std::string *err) {
+    if (c.hold) {
+        *err = "asynchronous host calls take no held streams.";
+        return Status::kBadArgument;
+    }
+    const int T = c.T;
+    const int16_t *pcm = c.pcm;
+    int16_t *out = c.out;
     (void) hipSetDevice(device_);
     if (pointer_kind(pcm) != kPtrPinned || pointer_kind(out) != kPtrPinned) {
         *err = "asynchronous host calls need page-locked `pcm` and `enhanced` (pv_koala_batch_host_alloc, hipHostMalloc or hipHostRegister).";
-        return false;
+        return Status::kRuntime;
     }
     const size_t bytes = (size_t) B_ * T * kFrame * 2;
     {
         const char *pa = (const char *) pcm, *pb = (const char *) out;
         if (pa != pb && pa < pb + bytes && pb < pa + bytes) {
             *err = "`pcm` and `enhanced` overlap partially.";
-            return false;
+            return Status::kRuntime;
         }
     }
     if (!async_ready_) {  // set only once EVERY event and both buffers exist: a partial failure is retried by the next call
@@ -1753,7 +1763,7 @@ bool Engine::process_host_async(int T, const int16_t *pcm, int16_t *out, std::st
         if (!ok) {
             (void) hipGetLastError();
             *err = "Failed to allocate the second staging slot of asynchronous host calls.";
-            return false;
+            return Status::kRuntime;
         }
         async_ready_ = true;
     }
@@ -1761,13 +1771,13 @@ bool Engine::process_host_async(int T, const int16_t *pcm, int16_t *out, std::st
     const int s = (int) (n & 1u), ring = (int) (n & 3u), ring3 = (int) ((n - 3u) & 3u), ring2 = (int) ((n - 2u) & 3u);
     if (n >= 3 && async_busy_[ring3]) {  // the window: the call three back has completed before this one is accepted
         if (hipEventSynchronize(aev_out_[ring3]) != hipSuccess) {
-            *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
-            return false;
+            *err = hip_last_error();
+            return Status::kRuntime;
         }
         async_busy_[ring3] = false;
     }
-    if (!begin_resets(T, resets, err)) return false;  // (the mask is packed into a ring slot of this call: the caller may overwrite it now)
-    ResetScope rs_scope(this);
+    ResetTable table;
+    if (!begin_resets(T, c.resets, &table, err)) return Status::kRuntime;  // (the mask is packed into a ring slot of this call: the caller may overwrite it now)
     int16_t *din = s ? d_in2_ : d_in_, *dout = s ? d_out2_ : d_out_;
     bool ok = true;
     if (n >= 2) ok = hipStreamWaitEvent(copy_in_, aev_done_[s], 0) == hipSuccess;  // the kernels of call n - 2 have read this slot's input
@@ -1776,13 +1786,13 @@ bool Engine::process_host_async(int T, const int16_t *pcm, int16_t *out, std::st
     ok = ok && hipStreamWaitEvent(stream_, aev_in_[s], 0) == hipSuccess;
     if (n >= 2) ok = ok && hipStreamWaitEvent(stream_, aev_out_[ring2], 0) == hipSuccess;  // ... and its copy-out this slot's output
     if (!ok) {
-        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+        *err = hip_last_error();
         (void) hipDeviceSynchronize();  // (a copy-in may have been enqueued: nothing of this call stays in flight)
-        return false;
+        return Status::kRuntime;
     }
-    if (!run_device(T, din, dout, err)) {
+    if (!run_device({0, T, din, dout, true, &table}, err)) {
         (void) hipDeviceSynchronize();
-        return false;
+        return Status::kRuntime;
     }
     ok = hipEventRecord(aev_done_[s], stream_) == hipSuccess;
     ok = ok && hipStreamWaitEvent(copy_out_, aev_done_[s], 0) == hipSuccess;
@@ -1792,24 +1802,25 @@ bool Engine::process_host_async(int T, const int16_t *pcm, int16_t *out, std::st
                                 copy_out_) == hipSuccess;
     ok = ok && hipEventRecord(aev_out_[ring], copy_out_) == hipSuccess;
     if (!ok) {
-        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+        *err = hip_last_error();
         (void) hipDeviceSynchronize();
-        return false;
+        return Status::kRuntime;
     }
     async_busy_[ring] = true;
     ++async_n_;
-    return true;
+    return Status::kOk;
 }
 
-bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, bool host_pointers) {
-    const uint8_t *resets = parked_resets_;  // (taken first: consumed by this call whatever happens below)
-    parked_resets_ = nullptr;
+bool Engine::run_call(const Call &c, std::string *err) {
+    const int T = c.T;
+    const int16_t *pcm = c.pcm;
+    int16_t *out = c.out;
     (void) hipSetDevice(device_);
     if (async_n_ && !drain_async(err)) return false;
-    ResetScope rs_scope(this);
+    ResetTable table;  // (this call's, filled by begin_resets: nothing of it outlives the call)
     const size_t bytes = (size_t) B_ * T * kFrame * 2;
     // (the single-stream ABI takes host buffers by contract: no driver query per frame on the latency path)
-    const PointerKind kin = host_pointers ? kPtrPageable : pointer_kind(pcm), kout = host_pointers ? kPtrPageable : pointer_kind(out);
+    const PointerKind kin = c.host_contract ? kPtrPageable : pointer_kind(pcm), kout = c.host_contract ? kPtrPageable : pointer_kind(out);
     if ((kin == kPtrDevice) != (kout == kPtrDevice)) {
         *err = "`pcm` and `enhanced` must both be host or both be device memory.";
         return false;
@@ -1817,7 +1828,7 @@ bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, 
     if (kin == kPtrDevice) {
         const size_t n = (size_t) B_ * T * kFrame;
         const bool overlap = pcm < out + n && out < pcm + n;
-        return begin_resets(T, resets, err) && run_device(T, pcm, out, err, !overlap);
+        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table}, err);
     }
     if (T > host_chunk_ && bytes >= host_pipeline_min_bytes_) {
         const char *pa = (const char *) pcm, *pb = (const char *) out;
@@ -1828,7 +1839,7 @@ bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, 
                    "disjoint buffers.";
             return false;
         }
-        if (!begin_resets(T, resets, err)) return false;
+        if (!begin_resets(T, c.resets, &table, err)) return false;
         // On a caller's stream the kernels of the sub-chunks still run on the handle's OWN stream, fenced behind whatever the caller
         // has enqueued (the call is synchronous, so everything the caller enqueues later is behind it anyway): the handle's three
         // streams were created together and sit on three different hardware queues, while a foreign stream may share its queue with
@@ -1842,11 +1853,11 @@ bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, 
             if (host_fork_ && hipEventRecord(host_fork_, user) == hipSuccess && hipStreamWaitEvent(own_stream_, host_fork_, 0) == hipSuccess)
                 stream_ = own_stream_;
         }
-        const bool done = process_host_pipelined(T, pcm, out, kin == kPtrPinned && kout == kPtrPinned, err);
+        const bool done = process_host_pipelined(c, kin == kPtrPinned && kout == kPtrPinned, &table, err);
         stream_ = user;
         return done;
     }
-    if (!begin_resets(T, resets, err)) return false;
+    if (!begin_resets(T, c.resets, &table, err)) return false;
     memcpy(h_in_, pcm, bytes);
     if (T == 1 && use_graph_ && stream_ == own_stream_ && !profiling_) {
         // frame-by-frame streaming: (copy-in,) the kernels of one frame (and copy-out) replayed as one hipGraph
@@ -1866,7 +1877,9 @@ bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, 
                 // pinned host staging buffers directly (device-visible memory): two copy nodes of ~4 us each less per frame
                 const bool zero_copy = bytes <= 64 * 1024 && !no_zero_copy_;
                 ok = zero_copy || hipMemcpyAsync(d_in_, h_in_, bytes, hipMemcpyHostToDevice, stream_) == hipSuccess;
-                ok = ok && run_device(1, zero_copy ? h_in_ : d_in_, zero_copy ? h_out_ : d_out_, err);
+                // (no reset table in the captured frame, whichever call happens to capture it: a one-frame call can restart a stream
+                // at frame 0 only, and that is the reset kernel begin_resets has already put in front of the graph)
+                ok = ok && run_device({0, 1, zero_copy ? h_in_ : d_in_, zero_copy ? h_out_ : d_out_, true, nullptr}, err);
                 ok = ok && (zero_copy || hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream_) == hipSuccess);
                 // zero-copy frames end with the completion word (the output is already in host memory when that node runs)
                 frame_graph_signals_[parity] = ok && zero_copy && spin_wait_ && h_frame_word_ && d_frame_count_;
@@ -1931,13 +1944,13 @@ bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, 
         }
     }
     if (hipMemcpyAsync(d_in_, h_in_, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) goto fail;
-    if (!run_device(T, d_in_, d_out_, err)) return false;
+    if (!run_device({0, T, d_in_, d_out_, true, &table}, err)) return false;
     if (hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
     if (hipStreamSynchronize(stream_) != hipSuccess) goto fail;
     memcpy(out, h_out_, bytes);
     return true;
 fail:
-    *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+    *err = hip_last_error();
     return false;
 }
 
@@ -1957,18 +1970,9 @@ bool Engine::state_ready(std::string *err) {
     (void) hipSetDevice(device_);
     uint8_t *d = (uint8_t *) dalloc((size_t) B_ * state_bytes(), false);
     int32_t *t = d ? (int32_t *) dalloc((size_t) Bpad_ * 4, false) : nullptr;
-    bool ok = d && t;
-    for (int i = 0; i < kResetRing && ok; ++i)
-        ok = hipHostMalloc((void **) &h_recof_[i], (size_t) Bpad_ * 4, hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&recof_ev_[i], hipEventDisableTiming) == hipSuccess;
-    if (!ok) {  // (what was allocated stays on the handle's lists and goes with the handle; the next call tries the rest again)
+    if (!d || !t || !recof_ring_.ready((size_t) Bpad_ * 4)) {
+        // (what was allocated stays on the handle's lists and goes with the handle; the next call tries the rest again)
         (void) hipGetLastError();
-        for (int i = 0; i < kResetRing; ++i) {
-            if (h_recof_[i]) (void) hipHostFree(h_recof_[i]);
-            if (recof_ev_[i]) (void) hipEventDestroy(recof_ev_[i]);
-            h_recof_[i] = nullptr;
-            recof_ev_[i] = nullptr;
-        }
         *err = "Failed to allocate the staging buffers of stream records.";
         return false;
     }
@@ -1979,40 +1983,34 @@ bool Engine::state_ready(std::string *err) {
 
 // Checks a stream list (nullptr: 0 .. count - 1) and uploads its inverse -- stream -> record, -1 = not listed -- on the handle's stream
 // from the next slot of a page-locked ring (a slot is rewritten once the copy that read it four uploads back has completed).
-bool Engine::state_list(int count, const int32_t *streams, std::string *err) {
-    state_bad_arg_ = true;
+Status Engine::state_list(int count, const int32_t *streams, std::string *err) {
     if (count < 1 || count > B_) {
         *err = "`count` " + std::to_string(count) + " is outside [1, " + std::to_string(B_) + "].";
-        return false;
+        return Status::kBadArgument;
     }
     for (int i = 0; streams && i < count; ++i)
         if (streams[i] < 0 || streams[i] >= B_) {
             *err = "`streams[" + std::to_string(i) + "]` = " + std::to_string(streams[i]) + " is outside [0, " + std::to_string(B_) + ").";
-            return false;
+            return Status::kBadArgument;
         }
     std::vector<int32_t> inv((size_t) Bpad_, -1);
     for (int i = 0; i < count; ++i) {
         const int b = streams ? streams[i] : i;
         if (inv[b] >= 0) {  // (refused for export too: one stream -> record table serves both directions)
             *err = "`streams[" + std::to_string(i) + "]`: slot " + std::to_string(b) + " is listed twice.";
-            return false;
+            return Status::kBadArgument;
         }
         inv[b] = i;
     }
-    state_bad_arg_ = false;
-    if (!state_ready(err)) return false;
-    const int k = (int) (recof_n_++ % kResetRing);
-    if (hipEventSynchronize(recof_ev_[k]) != hipSuccess) {  // (an event never recorded is complete)
-        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
-        return false;
+    if (!state_ready(err)) return Status::kRuntime;
+    const int k = recof_ring_.acquire();
+    if (k >= 0) memcpy(recof_ring_.host[k], inv.data(), (size_t) Bpad_ * 4);
+    if (k < 0 || hipMemcpyAsync(d_recof_, recof_ring_.host[k], (size_t) Bpad_ * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+        !recof_ring_.uploaded(k, stream_)) {
+        *err = hip_last_error();
+        return Status::kRuntime;
     }
-    memcpy(h_recof_[k], inv.data(), (size_t) Bpad_ * 4);
-    if (hipMemcpyAsync(d_recof_, h_recof_[k], (size_t) Bpad_ * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-        hipEventRecord(recof_ev_[k], stream_) != hipSuccess) {
-        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
-        return false;
-    }
-    return true;
+    return Status::kOk;
 }
 
 StateArgs Engine::state_args() const {
@@ -2034,27 +2032,26 @@ StateArgs Engine::state_args() const {
     return a;
 }
 
-bool Engine::export_state(int count, const int32_t *streams, void *host_records, std::string *err) {
+Status Engine::export_state(int count, const int32_t *streams, void *host_records, std::string *err) {
     (void) hipSetDevice(device_);
-    state_bad_arg_ = false;
-    if (async_n_ && !drain_async(err)) return false;
-    if (!state_list(count, streams, err)) return false;
+    if (async_n_ && !drain_async(err)) return Status::kRuntime;
+    const Status listed = state_list(count, streams, err);
+    if (listed != Status::kOk) return listed;
     launch_state_export(state_args(), stream_);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(host_records, d_state_, (size_t) count * state_bytes(), hipMemcpyDeviceToHost, stream_);
     if (e == hipSuccess) e = hipStreamSynchronize(stream_);
     if (e != hipSuccess) {
         (void) hipGetLastError();
-        *err = std::string("HIP error: ") + hipGetErrorString(e);
-        return false;
+        *err = hip_error(e);
+        return Status::kRuntime;
     }
-    return true;
+    return Status::kOk;
 }
 
-bool Engine::import_state(int count, const int32_t *streams, const void *host_records, std::string *err) {
+Status Engine::import_state(int count, const int32_t *streams, const void *host_records, std::string *err) {
     (void) hipSetDevice(device_);
-    state_bad_arg_ = false;
-    if (async_n_ && !drain_async(err)) return false;
+    if (async_n_ && !drain_async(err)) return Status::kRuntime;
     // every header before anything is written (the list is checked by state_list, which writes only the table)
     const size_t S = state_bytes();
     for (int i = 0; i < count && count <= B_; ++i) {
@@ -2070,12 +2067,12 @@ bool Engine::import_state(int count, const int32_t *streams, const void *host_re
                    ", the handle's is " + (prec_ == kBf16 ? "bf16" : "fp32") + " (records do not cross precisions)";
         else if (h.model != model_key_) what = "model hash does not match the handle's model";
         if (!what.empty()) {
-            state_bad_arg_ = true;
             *err = "record " + std::to_string(i) + ": " + what + ".";
-            return false;
+            return Status::kBadArgument;
         }
     }
-    if (!state_list(count, streams, err)) return false;
+    const Status listed = state_list(count, streams, err);
+    if (listed != Status::kOk) return listed;
     hipError_t e = hipMemcpyAsync(d_state_, host_records, (size_t) count * S, hipMemcpyHostToDevice, stream_);
     if (e == hipSuccess) {
         launch_state_import(state_args(), stream_);
@@ -2085,38 +2082,42 @@ bool Engine::import_state(int count, const int32_t *streams, const void *host_re
     if (e == hipSuccess) e = hipStreamSynchronize(stream_);
     if (e != hipSuccess) {
         (void) hipGetLastError();
-        *err = std::string("HIP error: ") + hipGetErrorString(e);
-        return false;
+        *err = hip_error(e);
+        return Status::kRuntime;
     }
-    return true;
+    return Status::kOk;
 }
 
-// Held streams: export the held rows' records to the device scratch, run the call unchanged, import them back -- around the WHOLE call
-// (outside the one-frame graph and the sub-chunks of large host calls), all on the handle's stream, so a device-pointer call stays
-// enqueued without a host wait.  The import restores both ping-pong copies, whichever parity the call has left current.
-bool Engine::process_hold(int T, const int16_t *pcm, int16_t *out, const uint8_t *host_hold, bool host_pointers, std::string *err) {
-    state_bad_arg_ = false;
+// A call and its held streams: export the held rows' records to the device scratch, run the call unchanged, import them back -- around the
+// WHOLE call (outside the one-frame graph and the sub-chunks of large host calls), all on the handle's stream, so a device-pointer call
+// stays enqueued without a host wait.  The import restores both ping-pong copies, whichever parity the call has left current.
+Status Engine::process(const Call &c, std::string *err) {
+    if (c.hold && c.resets) {
+        *err = "held streams are not combined with per-frame stream resets in one call.";
+        return Status::kBadArgument;
+    }
     std::vector<int32_t> held;
-    for (int b = 0; host_hold && b < B_; ++b)
-        if (host_hold[b]) held.push_back(b);
-    if (held.empty()) return process(T, pcm, out, err, host_pointers);
+    for (int b = 0; c.hold && b < B_; ++b)
+        if (c.hold[b]) held.push_back(b);
+    if (held.empty()) return run_call(c, err) ? Status::kOk : Status::kRuntime;
     (void) hipSetDevice(device_);
-    if (async_n_ && !drain_async(err)) return false;
-    if (!state_list((int) held.size(), held.data(), err)) return false;
+    if (async_n_ && !drain_async(err)) return Status::kRuntime;
+    const Status listed = state_list((int) held.size(), held.data(), err);
+    if (listed != Status::kOk) return listed;
     launch_state_export(state_args(), stream_);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        *err = std::string("HIP error: ") + hipGetErrorString(e);
-        return false;
+        *err = hip_error(e);
+        return Status::kRuntime;
     }
-    if (!process(T, pcm, out, err, host_pointers)) return false;  // (a refused call has advanced nothing)
+    if (!run_call(c, err)) return Status::kRuntime;  // (a refused call has advanced nothing)
     launch_state_import(state_args(), stream_);
     e = hipGetLastError();
     if (e != hipSuccess) {
-        *err = std::string("HIP error: ") + hipGetErrorString(e);
-        return false;
+        *err = hip_error(e);
+        return Status::kRuntime;
     }
-    return true;
+    return Status::kOk;
 }
 
 // ------------------------------------------------------------------------------------------------ debug taps
@@ -2148,7 +2149,7 @@ static float bf16_to_float(uint16_t h) {
 int64_t Engine::debug_read(int what, float *out, int64_t capacity, std::string *err) {
     (void) hipSetDevice(device_);
     if (hipStreamSynchronize(stream_) != hipSuccess) {
-        *err = std::string("HIP error: ") + hipGetErrorString(hipGetLastError());
+        *err = hip_last_error();
         return -1;
     }
     const int T = last_T_, mtb = Bpad_ / 16;

@@ -31,6 +31,27 @@ LoadResult load_params(const char *path, Params *out, std::string *err);
 constexpr int kNumKernelClasses = 5;
 enum KernelClass { kClsAnalysis = 0, kClsGemmIn = 1, kClsGru = 2, kClsGemmHead = 3, kClsSynthesis = 4 };
 
+// One call that advances the streams, with everything it carries.  pcm/out: [B][T*256], host or device pointers (both of the same kind).
+struct Call {
+    int T;
+    const int16_t *pcm;
+    int16_t *out;
+    // Per-frame stream resets: host memory, uint8 [num_streams][T] (non-zero at [b][t]: stream b restarts from the fresh state right before
+    // frame t).  Consumed before the call returns -- packed into the reset ring (kns_engine.cpp, begin_resets) -- so the caller may
+    // overwrite it then.  nullptr or all zero: the plain call.
+    const uint8_t *resets = nullptr;
+    // Held streams: host memory, uint8 [num_streams].  The streams with hold[b] != 0 are not advanced: their state after the call is bit for
+    // bit what it was before it (exported to a device scratch in front of the whole call and imported back behind it); their rows of `out`
+    // are unspecified.  nullptr or all zero: the plain call.  Not combined with `resets`, not taken by process_host_async.
+    const uint8_t *hold = nullptr;
+    bool host_contract = false;  // pcm/out are host memory by the entry point's contract: no driver query per frame on the latency path
+};
+
+// kBadArgument: a stream list, a record or a combination of Call members that the engine refused before it touched anything (the C ABI
+// reports INVALID_ARGUMENT).  kRuntime: a HIP failure, and the refusals the ABI has always reported as a runtime error (pointer kinds,
+// overlapping buffers).
+enum class Status { kOk, kBadArgument, kRuntime };
+
 class Engine {
 public:
     // returns nullptr and fills *err on failure (*oom set when the failure was an allocation)
@@ -38,33 +59,21 @@ public:
                           std::string *err, bool *oom);
     ~Engine();
 
-    // bytes of device memory this handle allocated itself / bytes of the weight image it shares (first handle on a model: it built it)
-    // (own: grows by the stream-record staging buffer, num_streams x state_bytes(), at the first export / import / held call)
-    size_t own_device_bytes() const { return own_bytes_; }
-    size_t shared_device_bytes() const;
-    bool weights_were_cached() const { return weights_cached_; }
-
     int num_streams() const { return B_; }
     int max_frames() const { return Tmax_; }
     int device() const { return device_; }
+    int front_taps() const { return taps_; }
 
-    // pcm/out: [B][T*256]; host or device pointers (both of the same kind).  Host: synchronous.  Device: enqueued.
-    bool process(int T, const int16_t *pcm, int16_t *out, std::string *err, bool host_pointers = false);
+    // The two entries that advance the streams.  Host pointers: synchronous.  Device pointers: enqueued.
+    Status process(const Call &c, std::string *err);
     // Page-locked host buffers, asynchronous: the call's copy-in, kernels and copy-out are enqueued on three streams and the function
     // returns; up to three such calls are in flight (a fourth first waits for the oldest), so the copies of one call run under the
     // kernels of its neighbours.  `drain_async` (also reached through synchronize(), and entered by every other entry point) waits
     // for all of them.
-    bool process_host_async(int T, const int16_t *pcm, int16_t *out, std::string *err);
+    Status process_host_async(const Call &c, std::string *err);
     bool drain_async(std::string *err);
     bool async_wait(int max_in_flight, std::string *err);  // until at most that many asynchronous calls are still in flight (0: all done)
     bool reset(const uint8_t *host_mask, std::string *err);
-    // Per-frame stream resets of the NEXT process() or process_host_async() call: `mask` is host memory, uint8 [num_streams][T] of that
-    // call (non-zero at [b][t]: stream b restarts from the fresh state right before frame t).  The call consumes it before it returns --
-    // packed into the reset ring (kns_engine.cpp, begin_resets) -- and clears it, on success and on failure alike.  Inline, as is
-    // front_taps(): the C-ABI shim's entry points that carry a mask call nothing else of the engine's, and tests/abi_sanitizer links the
-    // shim against a host-only double of the Engine that defines only the out-of-line members.
-    void park_resets(const uint8_t *mask) { parked_resets_ = mask; }
-    int front_taps() const { return taps_; }
     // 0: back to the handle's own stream.  Waits for everything the handle has in flight first (asynchronous host calls and the work
     // queued on the previous stream, which must still exist: the next call's kernels touch the same state, history and tail buffers)
     void set_stream(hipStream_t s);
@@ -73,19 +82,14 @@ public:
     // ---- per-stream state as stream records (kns_kernels.h, StateArgs: the record; kns_state.hip: the kernels).  `records` is HOST memory
     // (pageable or page-locked), count x state_bytes(), record i = stream streams[i] (streams == nullptr: slots 0 .. count - 1).  Both
     // calls first wait for asynchronous host calls in flight, then run on the handle's current stream, through a device staging buffer of
-    // num_streams records allocated on first use (it counts into own_device_bytes()).  export_state returns when the records are filled.
+    // num_streams records allocated on first use.  export_state returns when the records are filled.
     // import_state checks every header (magic, version, front_taps, precision, model hash -- a record of the other precision is refused:
     // its feature context is the other engine's) and every index (outside [0, num_streams), the same slot twice) BEFORE anything is written,
     // returns when the host records may be reused, and its scatter is ordered on the stream in front of the next call.  A failed call
-    // leaves all state as it was; state_bad_argument() then tells a refused argument from a HIP failure.
+    // leaves all state as it was.
     size_t state_bytes() const { return state_record_bytes(taps_); }
-    bool export_state(int count, const int32_t *streams, void *host_records, std::string *err);
-    bool import_state(int count, const int32_t *streams, const void *host_records, std::string *err);
-    // process() in which the streams with host_hold[b] != 0 are not advanced: their state after the call is bit for bit what it was before
-    // it (exported to a device scratch in front of the whole call and imported back behind it); their rows of `out` are unspecified.
-    // nullptr or all zero: process() itself.  Not combined with per-frame resets or the asynchronous host path.
-    bool process_hold(int T, const int16_t *pcm, int16_t *out, const uint8_t *host_hold, bool host_pointers, std::string *err);
-    bool state_bad_argument() const { return state_bad_arg_; }
+    Status export_state(int count, const int32_t *streams, void *host_records, std::string *err);
+    Status import_state(int count, const int32_t *streams, const void *host_records, std::string *err);
 
     void profile_enable(bool on);
     bool profile_read(double *ms, int64_t *launches, std::string *err);
@@ -94,14 +98,24 @@ public:
 private:
     Engine() {}
     bool init(const Params &p, int device, int B, int Tmax, int precision, std::string *err, bool *oom);
-    bool run_device(int T, const int16_t *d_pcm, int16_t *d_out, std::string *err, bool allow_recompute = true);
+    bool run_call(const Call &c, std::string *err);  // process() without the held streams
+    // what run_device is given: the frames [t0, t0 + T) of a call, their device buffers, and the call's reset table if it has one
+    struct ResetTable;
+    struct Slice {
+        int t0, T;
+        const int16_t *d_pcm;
+        int16_t *d_out;
+        bool allow_recompute;  // the synthesis kernel may rebuild the spectrum from d_pcm (false: d_out overlaps it)
+        ResetTable *resets;
+    };
+    bool run_device(const Slice &s, std::string *err);
     void *dalloc(size_t bytes, bool zero);
     void *upload(const void *src, size_t bytes);
     void tick(int cls);
     void tock(int cls);
 
-    // The immutable part of a handle -- tables and every packed weight matrix -- is built once per (model content, device, precision,
-    // developer switches) and SHARED by all handles that are open on it (round 6: the reference's contract is one handle per stream,
+    // The immutable part of a handle -- tables and every packed weight matrix -- is built once per (model content, device, precision)
+    // and SHARED by all handles that are open on it (round 6: the reference's contract is one handle per stream,
     // include/pv_koala.h:26-63; a caller with N handles used to get N folds, N packings and N weight images).  Ref-counted: freed with the
     // last handle.  A handle copies the image's pointers into its own members below; only its allocations differ.
     struct WeightImage;
@@ -113,8 +127,7 @@ private:
     PrecInfo pi_{};
     int nbf_ = 0, nbh_ = 0, nby_[kStages] = {0, 0, 0, 0};
     hipStream_t own_stream_ = nullptr, stream_ = nullptr;
-    bool alloc_failed_ = false, weights_cached_ = false;
-    size_t own_bytes_ = 0;
+    bool alloc_failed_ = false;
     std::vector<void *> allocs_;
 
     // parameters on device
@@ -150,7 +163,7 @@ private:
     // staging for host-pointer calls: [B][Tmax * 256] each; chunked calls use them as two slots of [B][Tc * 256]
     int16_t *d_in_ = nullptr, *d_out_ = nullptr, *h_in_ = nullptr, *h_out_ = nullptr;
     // host-pointer calls with more than one sub-chunk: copy-in, compute and copy-out run on three streams
-    bool process_host_pipelined(int T, const int16_t *pcm, int16_t *out, bool pinned, std::string *err);
+    bool process_host_pipelined(const Call &c, bool pinned, ResetTable *resets, std::string *err);
     std::vector<int> host_schedule(int T) const;  // its sub-chunk lengths
     std::vector<int> dev_host_sched_;             // developer override (KOALA_AMD_HOST_SCHED)
     // calls of several frames as a wavefront over (stage, frame): kns_engine.cpp, run_wave
@@ -198,32 +211,40 @@ private:
     bool spec_valid_ = false, feat_valid_ = false, mask_valid_ = false;
     int last_route_ = 0;  // enum Route of the last run_device() (kns_engine.cpp; reported by the developer build's debug tap 6)
 
-    // per-frame stream resets (kns_engine.cpp, begin_resets): the parked host mask, and the call's packed form -- per (m-tile, frame) the
-    // rows that restart, uint32 [mtiles][T] -- in a ring of page-locked slots (one per call in flight; a slot is refilled once the copy
-    // that read it four calls back has completed) uploaded to d_rs_ on the stream that runs the call's kernels
-    const uint8_t *parked_resets_ = nullptr;
+    // A ring of page-locked upload slots, one per call that may still be in flight: a slot is handed out again once the copy that read
+    // it kResetRing uses ago has completed (an event per slot).  Allocated at first use, all slots or none; release() frees it (~Engine).
     static constexpr int kResetRing = 4;
-    unsigned *h_rs_[kResetRing] = {};
-    hipEvent_t rs_ev_[kResetRing] = {};
-    bool rs_ev_set_[kResetRing] = {};
-    unsigned *d_rs_ = nullptr, rs_n_ = 0;
-    int rs_slot_ = 0, rs_T_ = 0, rs_t0_ = 0;  // the call's ring slot and length; the first frame of the sub-chunk run_device() is given
-    bool rs_active_ = false, rs_uploaded_ = false;
-    std::vector<uint8_t> rs_frame_;  // [T]: some stream restarts at this frame of the call
-    bool begin_resets(int T, const uint8_t *mask, std::string *err);
-    ResetArgs reset_args(const uint8_t *d_mask) const;
-    struct ResetScope;  // the reset kernel's arguments (d_mask: device [Bpad], null: every stream)
+    struct UploadRing {
+        void *host[kResetRing] = {};
+        hipEvent_t ev[kResetRing] = {};
+        bool pending[kResetRing] = {};  // a copy out of the slot has been enqueued since the slot was handed out
+        unsigned n = 0;
+        bool ready(size_t slot_bytes);
+        int acquire();                                // the next slot, once its last copy has completed; -1: HIP failure
+        bool uploaded(int slot, hipStream_t stream);  // a copy out of `slot` has just been enqueued on `stream`
+        void release();
+    };
+    // Per-frame stream resets (kns_engine.cpp, begin_resets).  A call's packed table -- per (m-tile, frame) the rows that restart, uint32
+    // [mtiles][T] -- goes through a slot of rs_ring_ to d_rs_ on the stream that runs the call's kernels, a frame-0 mask to d_rmask_.
+    // The table belongs to its call: process*() own it and hand it to run_device with every slice.
+    UploadRing rs_ring_;
+    unsigned *d_rs_ = nullptr;
+    struct ResetTable {
+        int slot = -1, T = 0;        // the call's ring slot (-1: no stream restarts after frame 0, there is no table) and its length
+        bool uploaded = false;       // by the call's first run_device() that needed it
+        std::vector<uint8_t> frame;  // [T]: some stream restarts at this frame of the call
+    };
+    bool begin_resets(int T, const uint8_t *mask, ResetTable *table, std::string *err);
+    ResetArgs reset_args(const uint8_t *d_mask) const;  // the reset kernel's arguments (d_mask: device [Bpad], null: every stream)
 
-    // stream records (export_state / import_state / process_hold): the device staging buffer [B_][state_bytes()], the stream -> record
-    // table on the device [Bpad_] and its page-locked upload ring (one slot per call that may still be in flight, as the reset ring)
+    // stream records (export_state / import_state / held streams): the device staging buffer [B_][state_bytes()], the stream -> record
+    // table on the device [Bpad_] and its upload ring
     uint64_t model_key_ = 0;  // content hash of the parameters: the key of the shared weight image, the `model hash` of a record
     uint8_t *d_state_ = nullptr;
-    int32_t *d_recof_ = nullptr, *h_recof_[kResetRing] = {};
-    hipEvent_t recof_ev_[kResetRing] = {};
-    unsigned recof_n_ = 0;
-    bool state_bad_arg_ = false;
+    int32_t *d_recof_ = nullptr;
+    UploadRing recof_ring_;
     bool state_ready(std::string *err);
-    bool state_list(int count, const int32_t *streams, std::string *err);  // checks the list, uploads its inverse table
+    Status state_list(int count, const int32_t *streams, std::string *err);  // checks the list, uploads its inverse table
     StateArgs state_args() const;
 
     // profiling

@@ -17,7 +17,9 @@
 #include <string>
 #include <vector>
 
-#include "pv_api_internal.h"
+#include "../../include/pv_koala.h"
+#include "../../include/pv_koala_batch.h"
+#include "kns_engine.h"
 
 #ifdef KNS_TIMING
 namespace kns {
@@ -25,18 +27,21 @@ void read_timing(unsigned long long *out);
 }
 #endif
 
+struct pv_koala {
+    kns::Engine *engine;
+};
+struct pv_koala_batch {
+    kns::Engine *engine;
+};
+
 namespace {
 
 const char kBuildId[] = "a355c0a";  // 7 hex digits, as the reference prints in front of every message
 
+// the calling thread's error stack (at most 8 messages, drained by pv_get_error_stack): every entry point clears it first
 thread_local std::vector<std::string> t_stack;
 
-}  // namespace
-
-// (these two are shared with the shim's other translation unit, pv_api_state.cpp, through pv_api_internal.h)
-void pv_api::clear_errors() { t_stack.clear(); }
-
-void pv_api::push_error(unsigned code, const char *fmt, ...) {
+void push_error(unsigned code, const char *fmt, ...) {
     char text[768];
     va_list ap;
     va_start(ap, fmt);
@@ -47,10 +52,95 @@ void pv_api::push_error(unsigned code, const char *fmt, ...) {
     if (t_stack.size() < 8) t_stack.push_back(line);
 }
 
-namespace {
+// No C++ exception may cross the C ABI (the callers are ctypes / dlsym hosts: an escaping exception is std::terminate).  Every
+// entry point that reaches engine code runs it through this: bad_alloc -> OUT_OF_MEMORY, anything else -> RUNTIME_ERROR.
+template <class F>
+pv_status_t guarded(F &&body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        push_error(0x65, "Failed to allocate memory.");
+        return PV_STATUS_OUT_OF_MEMORY;
+    } catch (const std::length_error &) {
+        push_error(0x65, "Failed to allocate memory.");
+        return PV_STATUS_OUT_OF_MEMORY;
+    } catch (const std::exception &e) {
+        push_error(0x339, "Unexpected failure: %s", e.what());
+        return PV_STATUS_RUNTIME_ERROR;
+    } catch (...) {
+        push_error(0x339, "Unexpected failure.");
+        return PV_STATUS_RUNTIME_ERROR;
+    }
+}
 
-using pv_api::guarded;
-using pv_api::push_error;
+// ---- the argument checks that several entry points share: the first failure's message and status, in this order
+pv_status_t check_object(const void *object) {
+    if (!object) {
+        push_error(0x64, "Argument `object` is NULL.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    return PV_STATUS_SUCCESS;
+}
+
+pv_status_t check_call(const pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm, const int16_t *enhanced) {
+    if (!object) return check_object(object);
+    if (!pcm || !enhanced) {
+        push_error(0x64, "Argument `%s` is NULL.", pcm ? "enhanced" : "pcm");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (num_frames <= 0 || num_frames > object->engine->max_frames()) {
+        push_error(0x66, "`num_frames` %d is outside [1, %d].", num_frames, object->engine->max_frames());
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    return PV_STATUS_SUCCESS;
+}
+
+// the five-frame front-end takes per-frame stream resets at frame 0 only (the reset kernel)
+pv_status_t check_resets(const pv_koala_batch_t *object, int32_t num_frames, const uint8_t *reset) {
+    if (!reset || object->engine->front_taps() <= 1) return PV_STATUS_SUCCESS;
+    const int32_t B = object->engine->num_streams();
+    for (int32_t b = 0; b < B; ++b)
+        for (int32_t t = 1; t < num_frames; ++t)
+            if (reset[(size_t) b * num_frames + t]) {
+                push_error(0x66, "`reset[%d][%d]` is set: a model with a %d-frame front-end takes per-frame stream resets at frame 0 only.",
+                           b, t, object->engine->front_taps());
+                return PV_STATUS_INVALID_ARGUMENT;
+            }
+    return PV_STATUS_SUCCESS;
+}
+
+pv_status_t check_list(const pv_koala_batch_t *object, int32_t count, const void *records) {
+    if (!object) return check_object(object);
+    if (!records) {
+        push_error(0x64, "Argument `records` is NULL.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (count < 1 || count > object->engine->num_streams()) {
+        push_error(0x66, "`count` %d is outside [1, %d].", count, object->engine->num_streams());
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    return PV_STATUS_SUCCESS;
+}
+
+// what an engine call that did not succeed leaves on the stack: a refused argument, or a failure under the entry point's own code
+pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std::string &err) {
+    if (status == kns::Status::kBadArgument) {
+        push_error(0x66, "%s", err.c_str());
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    push_error(runtime_code, "%s", err.c_str());
+    push_error(0x12C, "Picovoice Error.");
+    return PV_STATUS_RUNTIME_ERROR;
+}
+
+// one call that advances the streams (arguments already checked)
+pv_status_t advance(kns::Engine *engine, const kns::Call &call, bool async = false) {
+    return guarded([&] {
+        std::string err;
+        const kns::Status status = async ? engine->process_host_async(call, &err) : engine->process(call, &err);
+        return status == kns::Status::kOk ? PV_STATUS_SUCCESS : engine_failure(status, async ? 0x33A : 0x337, err);
+    });
+}
 
 std::mutex g_sdk_mutex;
 std::string g_sdk = "c";
@@ -124,10 +214,7 @@ pv_status_t open_engine_unguarded(const char *access_key, const char *model_path
         push_error(0x64, "Argument `device` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    if (!object) {
-        push_error(0x64, "Argument `object` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
+    if (!object) return check_object(object);
     kns::Params params;
     std::string err;
     kns::LoadResult lr = kns::load_params(model_path, &params, &err);
@@ -271,10 +358,7 @@ PV_API void pv_koala_delete(pv_koala_t *object) {
 
 PV_API pv_status_t pv_koala_process(pv_koala_t *object, const int16_t *pcm, int16_t *enhanced_pcm) {
     t_stack.clear();
-    if (!object) {
-        push_error(0x64, "Argument `object` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
+    if (!object) return check_object(object);
     if (!pcm) {
         push_error(0x64, "Argument `pcm` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
@@ -283,15 +367,7 @@ PV_API pv_status_t pv_koala_process(pv_koala_t *object, const int16_t *pcm, int1
         push_error(0x64, "Argument `enhanced_pcm` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    return guarded([&] {
-        std::string err;
-        if (!object->engine->process(1, pcm, enhanced_pcm, &err, /*host_pointers=*/true)) {
-            push_error(0x337, "%s", err.c_str());
-            push_error(0x12C, "Picovoice Error.");
-            return PV_STATUS_RUNTIME_ERROR;
-        }
-        return PV_STATUS_SUCCESS;
-    });
+    return advance(object->engine, {1, pcm, enhanced_pcm, nullptr, nullptr, /*host_contract=*/true});
 }
 
 PV_API pv_status_t pv_koala_reset(pv_koala_t *object) {
@@ -309,10 +385,7 @@ PV_API pv_status_t pv_koala_reset(pv_koala_t *object) {
 
 PV_API pv_status_t pv_koala_delay_sample(const pv_koala_t *object, int32_t *delay_sample) {
     t_stack.clear();
-    if (!object) {
-        push_error(0x64, "Argument `object` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
+    if (!object) return check_object(object);
     if (!delay_sample) {
         push_error(0x64, "Argument `delay_sample` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
@@ -384,110 +457,83 @@ PV_API void pv_koala_batch_delete(pv_koala_batch_t *object) {
 PV_API pv_status_t pv_koala_batch_process_chunk(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
                                                 int16_t *enhanced) {
     t_stack.clear();
-    if (!object) {
-        push_error(0x64, "Argument `object` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    if (!pcm || !enhanced) {
-        push_error(0x64, "Argument `%s` is NULL.", pcm ? "enhanced" : "pcm");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    if (num_frames <= 0 || num_frames > object->engine->max_frames()) {
-        push_error(0x66, "`num_frames` %d is outside [1, %d].", num_frames, object->engine->max_frames());
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    return guarded([&] {
-        std::string err;
-        if (!object->engine->process(num_frames, pcm, enhanced, &err)) {
-            push_error(0x337, "%s", err.c_str());
-            push_error(0x12C, "Picovoice Error.");
-            return PV_STATUS_RUNTIME_ERROR;
-        }
-        return PV_STATUS_SUCCESS;
-    });
+    const pv_status_t st = check_call(object, num_frames, pcm, enhanced);
+    if (st != PV_STATUS_SUCCESS) return st;
+    return advance(object->engine, {num_frames, pcm, enhanced});
 }
 
 PV_API pv_status_t pv_koala_batch_process_chunk_async(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
                                                       int16_t *enhanced) {
     t_stack.clear();
-    if (!object) {
-        push_error(0x64, "Argument `object` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    if (!pcm || !enhanced) {
-        push_error(0x64, "Argument `%s` is NULL.", pcm ? "enhanced" : "pcm");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    if (num_frames <= 0 || num_frames > object->engine->max_frames()) {
-        push_error(0x66, "`num_frames` %d is outside [1, %d].", num_frames, object->engine->max_frames());
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    return guarded([&] {
-        std::string err;
-        if (!object->engine->process_host_async(num_frames, pcm, enhanced, &err)) {
-            push_error(0x33A, "%s", err.c_str());
-            push_error(0x12C, "Picovoice Error.");
-            return PV_STATUS_RUNTIME_ERROR;
-        }
-        return PV_STATUS_SUCCESS;
-    });
+    const pv_status_t st = check_call(object, num_frames, pcm, enhanced);
+    if (st != PV_STATUS_SUCCESS) return st;
+    return advance(object->engine, {num_frames, pcm, enhanced}, /*async=*/true);
 }
-
-// ---- per-frame stream resets.  These entry points reach the engine only through members that are inline in kns_engine.h (front_taps,
-// park_resets: the mask is parked on the Engine and consumed by the call that follows) and the process / process_host_async calls that
-// pv_koala_batch_process_chunk* make: tests/abi_sanitizer links this file against a host-only double that defines no other member.
-namespace {
-// argument checks shared by both forms; PV_STATUS_SUCCESS: the mask is parked, the engine's call consumes it
-pv_status_t park_reset_mask(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm, int16_t *enhanced, const uint8_t *reset) {
-    if (!object) {
-        push_error(0x64, "Argument `object` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    if (!pcm || !enhanced) {
-        push_error(0x64, "Argument `%s` is NULL.", pcm ? "enhanced" : "pcm");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    if (num_frames <= 0 || num_frames > object->engine->max_frames()) {
-        push_error(0x66, "`num_frames` %d is outside [1, %d].", num_frames, object->engine->max_frames());
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    if (reset && object->engine->front_taps() > 1) {  // the five-frame front-end: resets at frame 0 only (the reset kernel)
-        const int32_t B = object->engine->num_streams();
-        for (int32_t b = 0; b < B; ++b)
-            for (int32_t t = 1; t < num_frames; ++t)
-                if (reset[(size_t) b * num_frames + t]) {
-                    push_error(0x66, "`reset[%d][%d]` is set: a model with a %d-frame front-end takes per-frame stream resets at frame 0 only.",
-                               b, t, object->engine->front_taps());
-                    return PV_STATUS_INVALID_ARGUMENT;
-                }
-    }
-    object->engine->park_resets(reset);
-    return PV_STATUS_SUCCESS;
-}
-}  // namespace
 
 PV_API pv_status_t pv_koala_batch_process_chunk_resets(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
                                                        int16_t *enhanced, const uint8_t *reset) {
     t_stack.clear();
-    const pv_status_t st = park_reset_mask(object, num_frames, pcm, enhanced, reset);
+    pv_status_t st = check_call(object, num_frames, pcm, enhanced);
+    if (st == PV_STATUS_SUCCESS) st = check_resets(object, num_frames, reset);
     if (st != PV_STATUS_SUCCESS) return st;
-    return pv_koala_batch_process_chunk(object, num_frames, pcm, enhanced);
+    return advance(object->engine, {num_frames, pcm, enhanced, reset});
 }
 
 PV_API pv_status_t pv_koala_batch_process_chunk_resets_async(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
                                                              int16_t *enhanced, const uint8_t *reset) {
     t_stack.clear();
-    const pv_status_t st = park_reset_mask(object, num_frames, pcm, enhanced, reset);
+    pv_status_t st = check_call(object, num_frames, pcm, enhanced);
+    if (st == PV_STATUS_SUCCESS) st = check_resets(object, num_frames, reset);
     if (st != PV_STATUS_SUCCESS) return st;
-    return pv_koala_batch_process_chunk_async(object, num_frames, pcm, enhanced);
+    return advance(object->engine, {num_frames, pcm, enhanced, reset}, /*async=*/true);
+}
+
+PV_API pv_status_t pv_koala_batch_process_chunk_hold(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
+                                                     int16_t *enhanced, const uint8_t *hold) {
+    t_stack.clear();
+    const pv_status_t st = check_call(object, num_frames, pcm, enhanced);
+    if (st != PV_STATUS_SUCCESS) return st;
+    return advance(object->engine, {num_frames, pcm, enhanced, nullptr, hold});
+}
+
+// ---- stream records
+
+PV_API pv_status_t pv_koala_batch_state_size(const pv_koala_batch_t *object, int32_t *num_bytes) {
+    t_stack.clear();
+    if (!object || !num_bytes) {
+        push_error(0x64, "Argument `%s` is NULL.", object ? "num_bytes" : "object");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    *num_bytes = (int32_t) object->engine->state_bytes();
+    return PV_STATUS_SUCCESS;
+}
+
+PV_API pv_status_t pv_koala_batch_export_state(pv_koala_batch_t *object, int32_t count, const int32_t *streams, void *records) {
+    t_stack.clear();
+    const pv_status_t st = check_list(object, count, records);
+    if (st != PV_STATUS_SUCCESS) return st;
+    return guarded([&] {
+        std::string err;
+        const kns::Status status = object->engine->export_state(count, streams, records, &err);
+        return status == kns::Status::kOk ? PV_STATUS_SUCCESS : engine_failure(status, 0x33C, err);
+    });
+}
+
+PV_API pv_status_t pv_koala_batch_import_state(pv_koala_batch_t *object, int32_t count, const int32_t *streams,
+                                               const void *records) {
+    t_stack.clear();
+    const pv_status_t st = check_list(object, count, records);
+    if (st != PV_STATUS_SUCCESS) return st;
+    return guarded([&] {
+        std::string err;
+        const kns::Status status = object->engine->import_state(count, streams, records, &err);
+        return status == kns::Status::kOk ? PV_STATUS_SUCCESS : engine_failure(status, 0x33C, err);
+    });
 }
 
 PV_API pv_status_t pv_koala_batch_async_wait(pv_koala_batch_t *object, int32_t max_in_flight) {
     t_stack.clear();
-    if (!object) {
-        push_error(0x64, "Argument `object` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
+    if (!object) return check_object(object);
     if (max_in_flight < 0) {
         push_error(0x66, "`max_in_flight` %d is negative.", max_in_flight);
         return PV_STATUS_INVALID_ARGUMENT;
@@ -508,10 +554,7 @@ PV_API pv_status_t pv_koala_batch_process(pv_koala_batch_t *object, const int16_
 
 PV_API pv_status_t pv_koala_batch_reset(pv_koala_batch_t *object, const uint8_t *stream_mask) {
     t_stack.clear();
-    if (!object) {
-        push_error(0x64, "Argument `object` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
+    if (!object) return check_object(object);
     return guarded([&] {
         std::string err;
         if (!object->engine->reset(stream_mask, &err)) {
@@ -544,10 +587,7 @@ PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, i
 
 PV_API pv_status_t pv_koala_batch_set_stream(pv_koala_batch_t *object, void *hip_stream) {
     t_stack.clear();
-    if (!object) {
-        push_error(0x64, "Argument `object` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
+    if (!object) return check_object(object);
     object->engine->set_stream((hipStream_t) hip_stream);
     return PV_STATUS_SUCCESS;
 }
@@ -582,10 +622,7 @@ PV_API void pv_koala_batch_host_free(void *memory) {
 
 PV_API pv_status_t pv_koala_batch_synchronize(pv_koala_batch_t *object) {
     t_stack.clear();
-    if (!object) {
-        push_error(0x64, "Argument `object` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
+    if (!object) return check_object(object);
     std::string err;
     if (!object->engine->synchronize(&err)) {
         push_error(0x339, "%s", err.c_str());
@@ -596,10 +633,7 @@ PV_API pv_status_t pv_koala_batch_synchronize(pv_koala_batch_t *object) {
 
 PV_API pv_status_t pv_koala_batch_profile_enable(pv_koala_batch_t *object, int32_t enable) {
     t_stack.clear();
-    if (!object) {
-        push_error(0x64, "Argument `object` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
+    if (!object) return check_object(object);
     object->engine->profile_enable(enable != 0);
     return PV_STATUS_SUCCESS;
 }

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <thread>
 #include <vector>
@@ -176,10 +177,91 @@ static void batch(const char *model) {
     pv_koala_batch_delete(nullptr);
 }
 
+// the calls that carry a mask or stream records: per-frame resets (both forms), held streams, state size / export / import
+static void batch_calls_with_arguments(const char *model) {
+    const int B = 3, T = 4;
+    pv_koala_batch_t *b = nullptr;
+    EXPECT(pv_koala_batch_init("k", model, "best", B, T, PV_KOALA_PRECISION_BF16, &b) == PV_STATUS_SUCCESS && b != nullptr);
+    std::vector<int16_t> in(B * T * 256, 7), out(B * T * 256, 0);
+    std::vector<uint8_t> reset(B * T, 0), hold(B, 0);
+    reset[1 * T + 2] = 1;  // stream 1 restarts before frame 2
+    hold[2] = 1;
+    std::string msg;
+    typedef pv_status_t (*masked_call)(pv_koala_batch_t *, int32_t, const int16_t *, int16_t *, const uint8_t *);
+    const masked_call calls[3] = {pv_koala_batch_process_chunk_resets, pv_koala_batch_process_chunk_resets_async, pv_koala_batch_process_chunk_hold};
+    for (int i = 0; i < 3; ++i) {
+        const masked_call call = calls[i];
+        const uint8_t *mask = i < 2 ? reset.data() : hold.data();
+        EXPECT(call(nullptr, T, in.data(), out.data(), mask) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && msg.find("`object`") != std::string::npos);
+        EXPECT(call(b, T, nullptr, out.data(), mask) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && msg.find("`pcm`") != std::string::npos);
+        EXPECT(call(b, T, in.data(), nullptr, mask) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && msg.find("`enhanced`") != std::string::npos);
+        EXPECT(call(b, 0, in.data(), out.data(), mask) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && msg.find("`num_frames` 0") != std::string::npos);
+        EXPECT(call(b, T + 1, in.data(), out.data(), mask) == PV_STATUS_INVALID_ARGUMENT && drain() == 1);
+        std::fill(out.begin(), out.end(), 0);
+        EXPECT(call(b, T, in.data(), out.data(), mask) == PV_STATUS_SUCCESS && out == in && drain() == 0);
+        EXPECT(call(b, T, in.data(), out.data(), nullptr) == PV_STATUS_SUCCESS && drain() == 0);  // no mask: the plain call
+        setenv("STUB_FAIL_PROCESS", "1", 1);
+        EXPECT(call(b, T, in.data(), out.data(), mask) == PV_STATUS_RUNTIME_ERROR && drain(&msg) == 2 &&
+               msg.find(i == 1 ? "0000033A" : "00000337") != std::string::npos);
+        unsetenv("STUB_FAIL_PROCESS");
+        setenv("STUB_THROW", "1", 1);
+        EXPECT(call(b, T, in.data(), out.data(), mask) == PV_STATUS_OUT_OF_MEMORY && drain() == 1);
+        unsetenv("STUB_THROW");
+    }
+    // a refused call leaves nothing behind for the next one (the mask travels with its call)
+    EXPECT(pv_koala_batch_process_chunk_resets(b, T + 1, in.data(), out.data(), reset.data()) == PV_STATUS_INVALID_ARGUMENT && drain() == 1);
+    EXPECT(pv_koala_batch_process_chunk(b, T, in.data(), out.data()) == PV_STATUS_SUCCESS && drain() == 0);
+
+    int32_t size = -1;
+    EXPECT(pv_koala_batch_state_size(nullptr, &size) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && msg.find("`object`") != std::string::npos);
+    EXPECT(pv_koala_batch_state_size(b, nullptr) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && msg.find("`num_bytes`") != std::string::npos);
+    EXPECT(pv_koala_batch_state_size(b, &size) == PV_STATUS_SUCCESS && size > 0 && size % 16 == 0 && drain() == 0);
+    std::vector<uint8_t> records((size_t) B * size, 0xAB);
+    const int32_t two[2] = {2, 0}, outside[2] = {0, B};
+    EXPECT(pv_koala_batch_export_state(nullptr, 2, two, records.data()) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && msg.find("`object`") != std::string::npos);
+    EXPECT(pv_koala_batch_export_state(b, 2, two, nullptr) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && msg.find("`records`") != std::string::npos);
+    EXPECT(pv_koala_batch_export_state(b, 0, two, records.data()) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && msg.find("`count` 0") != std::string::npos);
+    EXPECT(pv_koala_batch_export_state(b, B + 1, nullptr, records.data()) == PV_STATUS_INVALID_ARGUMENT && drain() == 1);
+    EXPECT(pv_koala_batch_export_state(b, 2, outside, records.data()) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && msg.find("00000066") != std::string::npos);
+    EXPECT(pv_koala_batch_export_state(b, 2, two, records.data()) == PV_STATUS_SUCCESS && records[0] == 0 && records[2 * size - 1] == 0 &&
+           records[2 * size] == 0xAB && drain() == 0);
+    EXPECT(pv_koala_batch_export_state(b, B, nullptr, records.data()) == PV_STATUS_SUCCESS && records.back() == 0 && drain() == 0);
+    EXPECT(pv_koala_batch_import_state(nullptr, 2, two, records.data()) == PV_STATUS_INVALID_ARGUMENT && drain() == 1);
+    EXPECT(pv_koala_batch_import_state(b, 2, two, nullptr) == PV_STATUS_INVALID_ARGUMENT && drain() == 1);
+    EXPECT(pv_koala_batch_import_state(b, 0, two, records.data()) == PV_STATUS_INVALID_ARGUMENT && drain() == 1);
+    EXPECT(pv_koala_batch_import_state(b, B + 1, nullptr, records.data()) == PV_STATUS_INVALID_ARGUMENT && drain() == 1);
+    EXPECT(pv_koala_batch_import_state(b, 2, outside, records.data()) == PV_STATUS_INVALID_ARGUMENT && drain() == 1);
+    EXPECT(pv_koala_batch_import_state(b, 2, two, records.data()) == PV_STATUS_SUCCESS && drain() == 0);
+    EXPECT(pv_koala_batch_import_state(b, B, nullptr, records.data()) == PV_STATUS_SUCCESS && drain() == 0);
+    setenv("STUB_FAIL_PROCESS", "1", 1);
+    EXPECT(pv_koala_batch_export_state(b, 2, two, records.data()) == PV_STATUS_RUNTIME_ERROR && drain(&msg) == 2 && msg.find("0000033C") != std::string::npos);
+    EXPECT(pv_koala_batch_import_state(b, 2, two, records.data()) == PV_STATUS_RUNTIME_ERROR && drain(&msg) == 2 && msg.find("0000033C") != std::string::npos);
+    unsetenv("STUB_FAIL_PROCESS");
+    setenv("STUB_THROW", "1", 1);
+    EXPECT(pv_koala_batch_export_state(b, 2, two, records.data()) == PV_STATUS_OUT_OF_MEMORY && drain() == 1);
+    EXPECT(pv_koala_batch_import_state(b, 2, two, records.data()) == PV_STATUS_OUT_OF_MEMORY && drain() == 1);
+    unsetenv("STUB_THROW");
+    pv_koala_batch_delete(b);
+
+    // a model with a five-frame front-end takes per-frame resets at frame 0 only: a later one is refused before the engine sees the call
+    setenv("STUB_FRONT_TAPS", "5", 1);
+    EXPECT(pv_koala_batch_init("k", model, "best", B, T, PV_KOALA_PRECISION_BF16, &b) == PV_STATUS_SUCCESS && b != nullptr);
+    unsetenv("STUB_FRONT_TAPS");
+    EXPECT(pv_koala_batch_process_chunk_resets(b, T, in.data(), out.data(), reset.data()) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 &&
+           msg.find("`reset[1][2]`") != std::string::npos);
+    EXPECT(pv_koala_batch_process_chunk_resets_async(b, T, in.data(), out.data(), reset.data()) == PV_STATUS_INVALID_ARGUMENT && drain() == 1);
+    reset[1 * T + 2] = 0;
+    reset[1 * T] = 1;  // frame 0: accepted
+    EXPECT(pv_koala_batch_process_chunk_resets(b, T, in.data(), out.data(), reset.data()) == PV_STATUS_SUCCESS && drain() == 0);
+    EXPECT(pv_koala_batch_state_size(b, &size) == PV_STATUS_SUCCESS && size % 16 == 0);
+    pv_koala_batch_delete(b);
+}
+
 int main(int argc, char **argv) {
     if (argc < 3) return 2;
     single_stream(argv[1], argv[2]);
     batch(argv[1]);
+    batch_calls_with_arguments(argv[1]);
     // the error stack is per thread: failures on other threads leave this one's untouched, and eight threads hammering the
     // argument checks must not race (the stack is thread_local, the SDK string is behind a mutex)
     EXPECT(pv_koala_process(nullptr, nullptr, nullptr) == PV_STATUS_INVALID_ARGUMENT);

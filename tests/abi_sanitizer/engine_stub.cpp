@@ -1,7 +1,8 @@
 // Stand-in for kns_engine.cpp in the sanitizer build of the C-ABI shim (tests/test_abi_sanitized.py; SURVEY.md section 5: "ASan/UBSan
 // build of the shim").  Only koala_amd/csrc/pv_api.cpp is under test here -- argument checks, the thread-local error stack, string
 // and list ownership -- so the engine behind it is a host-only double: parameters "load" when the file exists, a handle is a plain
-// object, process() copies its input, and no HIP call reaches a GPU.  TEST INFRASTRUCTURE: never linked into the product.
+// object, process() copies its input, and no HIP call reaches a GPU.  It defines every out-of-line public member of kns::Engine: a new
+// one gets a trivial body here, the engine's interface is not shaped around this file.  TEST INFRASTRUCTURE: never linked into the product.
 #include <stdio.h>
 #include <string.h>
 
@@ -44,25 +45,57 @@ Engine *Engine::create(const Params &, int device, int num_streams, int max_fram
     e->B_ = num_streams;
     e->Tmax_ = max_frames;
     e->prec_ = precision;
+    if (const char *taps = getenv("STUB_FRONT_TAPS")) e->taps_ = atoi(taps);  // (a model with a several-frame front-end)
     return e;
 }
 Engine::~Engine() {}
-bool Engine::process(int T, const int16_t *pcm, int16_t *out, std::string *err, bool) {
+static bool stub_fails(std::string *err) {
     if (getenv("STUB_FAIL_PROCESS")) {
         *err = "HIP error: stub";
-        return false;
+        return true;
     }
     if (getenv("STUB_THROW")) throw std::bad_alloc();
-    memmove(out, pcm, (size_t) B_ * T * kFrame * 2);
+    return false;
+}
+// a stream list as the engine checks it: an index outside the handle is a refused argument, not a failure
+static bool stub_list_ok(int count, const int32_t *streams, int B, std::string *err) {
+    for (int i = 0; streams && i < count; ++i)
+        if (streams[i] < 0 || streams[i] >= B) {
+            *err = "`streams[" + std::to_string(i) + "]` is outside the handle.";
+            return false;
+        }
     return true;
 }
-bool Engine::process_host_async(int T, const int16_t *pcm, int16_t *out, std::string *err) { return process(T, pcm, out, err, true); }
+Status Engine::process(const Call &c, std::string *err) {
+    if (stub_fails(err)) return Status::kRuntime;
+    // (every mask is read to its end, as the engine does: a short buffer is the sanitizer's to find)
+    unsigned marks = 0;
+    for (size_t i = 0; c.resets && i < (size_t) B_ * c.T; ++i) marks += c.resets[i];
+    for (int b = 0; c.hold && b < B_; ++b) marks += c.hold[b];
+    (void) marks;
+    memmove(c.out, c.pcm, (size_t) B_ * c.T * kFrame * 2);
+    return Status::kOk;
+}
+Status Engine::process_host_async(const Call &c, std::string *err) { return process(c, err); }
+Status Engine::export_state(int count, const int32_t *streams, void *host_records, std::string *err) {
+    if (stub_fails(err)) return Status::kRuntime;
+    if (!stub_list_ok(count, streams, B_, err)) return Status::kBadArgument;
+    memset(host_records, 0, (size_t) count * state_bytes());
+    return Status::kOk;
+}
+Status Engine::import_state(int count, const int32_t *streams, const void *host_records, std::string *err) {
+    if (stub_fails(err)) return Status::kRuntime;
+    if (!stub_list_ok(count, streams, B_, err)) return Status::kBadArgument;
+    unsigned sum = 0;
+    for (size_t i = 0; i < (size_t) count * state_bytes(); ++i) sum += ((const uint8_t *) host_records)[i];
+    (void) sum;
+    return Status::kOk;
+}
 bool Engine::drain_async(std::string *) { return true; }
 bool Engine::async_wait(int, std::string *) { return true; }
 bool Engine::reset(const uint8_t *, std::string *) { return true; }
 bool Engine::synchronize(std::string *) { return true; }
 void Engine::set_stream(hipStream_t s) { stream_ = s ? s : own_stream_; }
-size_t Engine::shared_device_bytes() const { return 0; }
 void Engine::profile_enable(bool on) { profiling_ = on; }
 bool Engine::profile_read(double *ms, int64_t *launches, std::string *) {
     for (int i = 0; i < kNumKernelClasses; ++i) ms[i] = 0.0, launches[i] = 0;

@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 lib = os.path.join(ROOT, 'build', 'libpv_koala_timing%s.so' % os.environ.get('TIMING_TAG', ''))
 os.makedirs(os.path.dirname(lib), exist_ok=True)
-src = [os.path.join(ROOT, 'koala_amd', 'csrc', f) for f in ('kns_stft.hip', 'kns_gemm.hip', 'kns_gru.hip', 'kns_gruq.hip', 'kns_state.hip', 'kns_engine.cpp', 'pv_api.cpp', 'pv_api_state.cpp')]
+src = [os.path.join(ROOT, 'koala_amd', 'csrc', f) for f in ('kns_stft.hip', 'kns_gemm.hip', 'kns_gru.hip', 'kns_gruq.hip', 'kns_state.hip', 'kns_engine.cpp', 'pv_api.cpp')]
 if not (os.environ.get('TIMING_NOBUILD') and os.path.exists(lib)):
     subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden',
                        '-ffp-contract=off', '-DKNS_TIMING'] + os.environ.get('TIMING_FLAGS', '').split() + ['-x', 'hip'] + src + ['-shared', '-o', lib])

@@ -8,7 +8,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 lib = os.path.join(ROOT, 'build', 'libpv_koala_wtiming.so')
 os.makedirs(os.path.dirname(lib), exist_ok=True)
-src = [os.path.join(ROOT, 'koala_amd', 'csrc', f) for f in ('kns_stft.hip', 'kns_gemm.hip', 'kns_gru.hip', 'kns_gruq.hip', 'kns_state.hip', 'kns_engine.cpp', 'pv_api.cpp', 'pv_api_state.cpp')]
+src = [os.path.join(ROOT, 'koala_amd', 'csrc', f) for f in ('kns_stft.hip', 'kns_gemm.hip', 'kns_gru.hip', 'kns_gruq.hip', 'kns_state.hip', 'kns_engine.cpp', 'pv_api.cpp')]
 subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden',
                        '-ffp-contract=off', '-Xarch_host', '-mfma', '-Xarch_host', '-mavx2', '-DKNS_TIMING', '-DKNS_DEV', '-x', 'hip'] + src + ['-shared', '-o', lib])
 import koala_amd
