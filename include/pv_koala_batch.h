@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "picovoice.h"
+#include "pv_koala.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -130,6 +131,37 @@ PV_API pv_status_t pv_koala_batch_import_state(pv_koala_batch_t *object, int32_t
  * pointers.  Not combined with per-frame resets or the asynchronous host path. */
 PV_API pv_status_t pv_koala_batch_process_chunk_hold(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
                                                      int16_t *enhanced, const uint8_t *hold);
+
+/* PER-STREAM ATTENUATION LIMIT: how hard the suppressor may bite, stream by stream.  Every stream b has a MINIMUM MASK GAIN g_b, an fp32
+ * value in [0, 1]; a new handle has g_b = 0 for every stream.  In every frame processed while g_b is in force, the mask value m of each of
+ * the 257 bins (DC and Nyquist included) becomes
+ *
+ *     m' = g_b + (1 - g_b) * m        fp32: u = 1 - g_b, then the product u * m rounded, then the sum rounded (two roundings, no fma)
+ *
+ * and the frame is synthesised from m' exactly as it is from m otherwise.  g = 0 is the handle without a limit (m' = m: the same samples,
+ * and when EVERY stream's gain is 0 also the same route and kernels); g = 1 is a pure delay by delay_sample samples (m' = 1: the output is
+ * the input, bit for bit, in both precisions, for any model) -- a bypass that keeps the stream's latency; in between no bin is attenuated by
+ * more than -20 log10(g) dB: g = 0.25 is "at most 12 dB".  The mask network never sees its own output: a stream's hidden state, history and
+ * feature context evolve exactly as without a limit, so the limit may be changed between any two calls without disturbing what the stream
+ * has adapted to.  A change takes effect with the next call and holds for every frame of that call (the first output frame after a change
+ * overlap-adds a tail made under the old gain: this is the definition, nothing is smoothed).
+ * The limit is CONFIGURATION, NOT STATE: pv_koala_batch_reset, per-frame resets, held streams and export_state / import_state neither change
+ * nor carry it (the stream record is unchanged); a caller that moves a stream sets its limit at the destination.  It applies to every
+ * entry point that advances streams -- process, process_chunk, _async, _resets, _resets_async, _hold -- for host and device pointers alike.
+ *
+ * pv_koala_batch_set_min_gain: gains[i] is the minimum gain of stream streams[i]; streams == NULL means slots 0 .. count - 1; streams not
+ * listed keep theirs.  Both arrays are HOST memory, read before the function returns.  No device work and no wait: the gains travel with
+ * the next call (asynchronous host calls in flight keep the gains they were issued under).  PV_STATUS_INVALID_ARGUMENT, with a message
+ * on the error stack and NOTHING changed: NULL object / gains, count outside [1, num_streams], an index outside [0, num_streams), a slot
+ * listed twice, a gain that is NaN or outside [0, 1] (the message names the entry, "gain 3: ...").
+ * pv_koala_batch_get_min_gain: the gains in force, gains[num_streams]. */
+PV_API pv_status_t pv_koala_batch_set_min_gain(pv_koala_batch_t *object, int32_t count, const int32_t *streams, const float *gains);
+PV_API pv_status_t pv_koala_batch_get_min_gain(const pv_koala_batch_t *object, float *gains /*[num_streams]*/);
+
+/* The same for the single-stream handle of pv_koala.h (an extension: the reference library has no such control): the limit of
+ * pv_koala_process from the next frame on.  PV_STATUS_INVALID_ARGUMENT for a NULL argument, a NaN or a gain outside [0, 1]. */
+PV_API pv_status_t pv_koala_set_min_gain(pv_koala_t *object, float gain);
+PV_API pv_status_t pv_koala_get_min_gain(const pv_koala_t *object, float *gain);
 
 PV_API pv_status_t pv_koala_batch_num_streams(const pv_koala_batch_t *object, int32_t *num_streams);
 PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, int32_t *delay_sample);

@@ -10,7 +10,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._koala import (KoalaError, KoalaInvalidArgumentError, KoalaIOError, PicovoiceStatuses, load_library,
+from ._koala import (KoalaError, KoalaInvalidArgumentError, KoalaIOError, PicovoiceStatuses, attenuation_limit_to_gain, load_library,
                      raise_status)
 
 PRECISION_FP32 = 0
@@ -43,7 +43,9 @@ class KoalaBatch(object):
                            ('state_size', [c_void_p, POINTER(c_int32)]),
                            ('export_state', [c_void_p, c_int32, c_void_p, c_void_p]),
                            ('import_state', [c_void_p, c_int32, c_void_p, c_void_p]),
-                           ('process_chunk_hold', [c_void_p, c_int32, c_void_p, c_void_p, c_void_p])):
+                           ('process_chunk_hold', [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+                           ('set_min_gain', [c_void_p, c_int32, c_void_p, c_void_p]),
+                           ('get_min_gain', [c_void_p, c_void_p])):
             fn = getattr(lib, 'pv_koala_batch_' + name)
             fn.argtypes = args
             fn.restype = PicovoiceStatuses
@@ -233,6 +235,31 @@ class KoalaBatch(object):
         m, mp = self._hold_mask(hold)
         self._check(self._lib.pv_koala_batch_process_chunk_hold(self._handle, num_frames, c_void_p(pcm_ptr), c_void_p(enhanced_ptr), mp),
                     'Processing failed')
+
+    def set_min_gain(self, gains, streams=None) -> None:
+        """Per-stream attenuation limit as a minimum mask gain in [0, 1] (include/pv_koala_batch.h, pv_koala_batch_set_min_gain): 0 = no
+        limit, 1 = bypass with unchanged latency, in between no bin of the stream is attenuated by more than -20 log10(gain) dB.
+        `gains`: one value per listed stream, or a scalar for all of them; `streams`: indices (None: every stream, in order).  Holds from
+        the next call on; configuration, not state: resets, held streams and stream records neither change nor carry it."""
+        g = np.asarray(gains, dtype=np.float32)
+        if g.ndim == 0:
+            g = np.full(self.num_streams if streams is None else np.size(streams), g, np.float32)
+        g = np.ascontiguousarray(g)
+        if g.ndim != 1 or g.size == 0 or (streams is None and g.size != self.num_streams):
+            raise KoalaInvalidArgumentError("`gains` must be a scalar or one value per listed stream")
+        s, sp, n = self._stream_list(streams, g.size)
+        self._check(self._lib.pv_koala_batch_set_min_gain(self._handle, n, sp, g.ctypes.data), 'set_min_gain failed')
+
+    def set_attenuation_limit(self, db, streams=None) -> None:
+        """`set_min_gain` in dB: the listed streams are suppressed by at most `db` dB (scalar or one value per stream; None or inf:
+        unlimited; 0: bypass).  Negative or NaN limits raise ValueError."""
+        self.set_min_gain(attenuation_limit_to_gain(db), streams)
+
+    def min_gain(self) -> np.ndarray:
+        """The minimum gains in force, float32 [num_streams]."""
+        out = np.empty(self.num_streams, np.float32)
+        self._check(self._lib.pv_koala_batch_get_min_gain(self._handle, out.ctypes.data), 'min_gain failed')
+        return out
 
     def reset(self, stream_mask: Optional[np.ndarray] = None) -> None:
         ptr = None

@@ -8,9 +8,12 @@ Differences from the reference binding, on purpose:
   * `process` also accepts numpy int16 arrays and converts them without a per-sample Python loop.
 """
 
+import math
 import os
-from ctypes import (POINTER, Structure, byref, c_char_p, c_int, c_int16, c_int32, c_short, c_void_p, cdll)
-from typing import Sequence
+from ctypes import (POINTER, Structure, byref, c_char_p, c_float, c_int, c_int16, c_int32, c_short, c_void_p, cdll)
+from typing import Optional, Sequence
+
+import numpy as np
 
 from ._errors import *  # noqa: F401,F403  (re-exported: the reference keeps the exceptions in this module)
 from ._errors import STATUS_TO_EXCEPTION as _STATUS_TO_EXCEPTION
@@ -47,6 +50,16 @@ def fetch_error_stack(library) -> Sequence[str]:
 
 def raise_status(library, status: PicovoiceStatuses, message: str) -> None:
     raise _STATUS_TO_EXCEPTION[status](message=message, message_stack=fetch_error_stack(library))
+
+
+def attenuation_limit_to_gain(db) -> np.ndarray:
+    """Attenuation limit(s) in dB -> minimum mask gain(s), float32, same shape: `None` or `inf` = unlimited = gain 0, 0 dB = bypass = gain
+    1, otherwise float32(10 ** (-db / 20)) computed in double precision.  Negative or NaN limits raise ValueError."""
+    a = np.asarray(np.inf if db is None else db, dtype=np.float64)
+    if np.isnan(a).any() or (a < 0).any():
+        raise ValueError("an attenuation limit is a number of dB >= 0 (None or inf: unlimited)")
+    flat = [0.0 if math.isinf(v) else 10.0 ** (-v / 20.0) for v in a.ravel().tolist()]
+    return np.array(flat, np.float64).reshape(a.shape).astype(np.float32)
 
 
 class Koala(object):
@@ -103,6 +116,13 @@ class Koala(object):
         self._reset_func.argtypes = [POINTER(self.CKoala)]
         self._reset_func.restype = PicovoiceStatuses
 
+        self._set_min_gain_func = library.pv_koala_set_min_gain
+        self._set_min_gain_func.argtypes = [POINTER(self.CKoala), c_float]
+        self._set_min_gain_func.restype = PicovoiceStatuses
+        self._get_min_gain_func = library.pv_koala_get_min_gain
+        self._get_min_gain_func.argtypes = [POINTER(self.CKoala), POINTER(c_float)]
+        self._get_min_gain_func.restype = PicovoiceStatuses
+
         self._sample_rate = library.pv_sample_rate()
         self._frame_length = library.pv_koala_frame_length()
         self._version = library.pv_koala_version().decode('utf-8')
@@ -133,6 +153,25 @@ class Koala(object):
         status = self._reset_func(self._handle)
         if status is not PicovoiceStatuses.SUCCESS:
             raise_status(self._library, status, 'Reset failed')
+
+    def set_min_gain(self, gain: float) -> None:
+        """Minimum mask gain in [0, 1] from the next frame on (an extension: include/pv_koala_batch.h, pv_koala_set_min_gain): 0 = no
+        limit, 1 = bypass with unchanged latency, in between no bin is attenuated by more than -20 log10(gain) dB.  The stream's
+        adapted state is not disturbed; `reset()` does not change the limit."""
+        status = self._set_min_gain_func(self._handle, float(gain))
+        if status is not PicovoiceStatuses.SUCCESS:
+            raise_status(self._library, status, 'set_min_gain failed')
+
+    def set_attenuation_limit(self, db: Optional[float]) -> None:
+        """`set_min_gain` in dB: at most `db` dB of suppression (None or inf: unlimited; 0: bypass)."""
+        self.set_min_gain(float(attenuation_limit_to_gain(db)))
+
+    def min_gain(self) -> float:
+        gain = c_float()
+        status = self._get_min_gain_func(self._handle, byref(gain))
+        if status is not PicovoiceStatuses.SUCCESS:
+            raise_status(self._library, status, 'min_gain failed')
+        return gain.value
 
     def delete(self) -> None:
         """Releases the native stream."""
@@ -180,5 +219,5 @@ def list_hardware_devices(library_path: str) -> Sequence[str]:
 
 from . import _errors  # noqa: E402
 
-__all__ = ['Koala', 'list_hardware_devices', 'load_library', 'fetch_error_stack', 'raise_status'] + [
+__all__ = ['Koala', 'attenuation_limit_to_gain', 'list_hardware_devices', 'load_library', 'fetch_error_stack', 'raise_status'] + [
     n for n in _errors.__all__ if n != 'STATUS_TO_EXCEPTION']

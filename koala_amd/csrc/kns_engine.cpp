@@ -706,6 +706,7 @@ Engine::~Engine() {
     if (h_out_) (void) hipHostFree(h_out_);
     rs_ring_.release();
     recof_ring_.release();
+    mg_ring_.release();
     for (int i = 0; i < 4; ++i)
         if (aev_out_[i]) (void) hipEventDestroy(aev_out_[i]);
     for (int i = 0; i < 2; ++i) {
@@ -939,6 +940,44 @@ bool Engine::begin_resets(int T, const uint8_t *mask, ResetTable *table, std::st
     }
     table->slot = k;
     table->T = T;
+    return true;
+}
+
+// The attenuation limit of the call about to run (Call::min_gain, float [B] host memory), before anything of the call is enqueued and outside
+// any capture.  No limit: *table = nullptr and nothing else happens.  Otherwise *table = the device table [Bpad]; when the call's revision is
+// not the one the table holds, the gains go through a slot of mg_ring_ (rows past B: 0) to the device on the handle's stream, where every
+// kernel of the previous call is in front of the copy and every kernel of this one behind it.  The caller's vector has been read when this
+// returns; a device-pointer caller waits only when it is four changed tables ahead of the GPU.
+bool Engine::begin_min_gain(const Call &c, const float **table, std::string *err) {
+    *table = nullptr;
+    if (!c.min_gain) return true;
+    if (!d_min_gain_) {  // first use: the ring and the device table
+        const bool ok = mg_ring_.ready((size_t) Bpad_ * 4);
+        float *d = ok ? (float *) dalloc((size_t) Bpad_ * 4, true) : nullptr;
+        if (!d) {
+            (void) hipGetLastError();
+            *err = "Failed to allocate the buffers of the per-stream attenuation limit.";
+            return false;
+        }
+        d_min_gain_ = d;
+    }
+    if (!mg_valid_ || mg_rev_ != c.min_gain_rev) {
+        const int k = mg_ring_.acquire();
+        if (k >= 0) {
+            float *slot = (float *) mg_ring_.host[k];
+            memcpy(slot, c.min_gain, (size_t) B_ * 4);
+            for (int b = B_; b < Bpad_; ++b) slot[b] = 0.0f;
+        }
+        if (k < 0 || hipMemcpyAsync(d_min_gain_, mg_ring_.host[k], (size_t) Bpad_ * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+            !mg_ring_.uploaded(k, stream_)) {
+            *err = hip_last_error();
+            mg_valid_ = false;
+            return false;
+        }
+        mg_rev_ = c.min_gain_rev;
+        mg_valid_ = true;
+    }
+    *table = d_min_gain_;
     return true;
 }
 
@@ -1446,6 +1485,7 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
         sy.resets = rs;
         sy.rs_pitch = rs_pitch;
         sy.rs_t0 = rs_t0 + t0c;
+        sy.min_gain = slice.min_gain;
         launch_synthesis(sy, st);
     };
     if (pipelined) (void) hipEventRecord(pipe_fork_, stream_);
@@ -1611,7 +1651,7 @@ std::vector<int> Engine::host_schedule(int T) const {
     return sched;
 }
 
-bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *resets, std::string *err) {
+bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *resets, const float *min_gain, std::string *err) {
     const int T = call.T;
     const int16_t *pcm = call.pcm;
     int16_t *out = call.out;
@@ -1646,7 +1686,7 @@ bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *r
         // ---- kernels (d_out_ slot s was last drained by the D2H of chunk c - 2)
         check(hipStreamWaitEvent(stream_, ev_in_[s], 0));
         if (c >= 2) check(hipStreamWaitEvent(stream_, ev_out_[s], 0));
-        if (ok && !run_device({first[c], tc, d_in_ + s * slot, d_out_ + s * slot, true, resets}, err)) {
+        if (ok && !run_device({first[c], tc, d_in_ + s * slot, d_out_ + s * slot, true, resets, min_gain}, err)) {
             // copies of earlier sub-chunks may still be writing into the caller's buffers: let them finish first
             (void) hipStreamSynchronize(copy_in_);
             (void) hipStreamSynchronize(copy_out_);
@@ -1778,6 +1818,8 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
     }
     ResetTable table;
     if (!begin_resets(T, c.resets, &table, err)) return Status::kRuntime;  // (the mask is packed into a ring slot of this call: the caller may overwrite it now)
+    const float *min_gain = nullptr;  // (the gains are copied into an upload slot of this call: the caller may change them now)
+    if (!begin_min_gain(c, &min_gain, err)) return Status::kRuntime;
     int16_t *din = s ? d_in2_ : d_in_, *dout = s ? d_out2_ : d_out_;
     bool ok = true;
     if (n >= 2) ok = hipStreamWaitEvent(copy_in_, aev_done_[s], 0) == hipSuccess;  // the kernels of call n - 2 have read this slot's input
@@ -1790,7 +1832,7 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
         (void) hipDeviceSynchronize();  // (a copy-in may have been enqueued: nothing of this call stays in flight)
         return Status::kRuntime;
     }
-    if (!run_device({0, T, din, dout, true, &table}, err)) {
+    if (!run_device({0, T, din, dout, true, &table, min_gain}, err)) {
         (void) hipDeviceSynchronize();
         return Status::kRuntime;
     }
@@ -1825,10 +1867,12 @@ bool Engine::run_call(const Call &c, std::string *err) {
         *err = "`pcm` and `enhanced` must both be host or both be device memory.";
         return false;
     }
+    const float *min_gain = nullptr;  // (this call's attenuation limit on the device, on the handle's stream in front of everything below)
+    if (!begin_min_gain(c, &min_gain, err)) return false;
     if (kin == kPtrDevice) {
         const size_t n = (size_t) B_ * T * kFrame;
         const bool overlap = pcm < out + n && out < pcm + n;
-        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table}, err);
+        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table, min_gain}, err);
     }
     if (T > host_chunk_ && bytes >= host_pipeline_min_bytes_) {
         const char *pa = (const char *) pcm, *pb = (const char *) out;
@@ -1853,7 +1897,7 @@ bool Engine::run_call(const Call &c, std::string *err) {
             if (host_fork_ && hipEventRecord(host_fork_, user) == hipSuccess && hipStreamWaitEvent(own_stream_, host_fork_, 0) == hipSuccess)
                 stream_ = own_stream_;
         }
-        const bool done = process_host_pipelined(c, kin == kPtrPinned && kout == kPtrPinned, &table, err);
+        const bool done = process_host_pipelined(c, kin == kPtrPinned && kout == kPtrPinned, &table, min_gain, err);
         stream_ = user;
         return done;
     }
@@ -1865,7 +1909,9 @@ bool Engine::run_call(const Call &c, std::string *err) {
         // ping-pong indices.  (A single-frame call leaves history and tail in place and flips the hidden state only, but
         // multi-frame calls in between flip the other two as well.)
         const int hs = hs_cur_;
-        const int parity = hs | (hist_cur_ << 1) | (tail_cur_ << 2);
+        // (... and one set for the plain synthesis kernel, one for its kMinGain form: a handle that crosses between "no limit" and "some
+        // limit" changes sets, a change of values only re-uploads the table, which begin_min_gain has put on the stream in front of the replay)
+        const int parity = hs | (hist_cur_ << 1) | (tail_cur_ << 2) | (min_gain ? 8 : 0);
         if (!frame_graph_[parity]) {
             hipGraph_t graph = nullptr;
             // (relaxed mode and one capture at a time in the process: other threads -- other handles being created, the
@@ -1879,7 +1925,7 @@ bool Engine::run_call(const Call &c, std::string *err) {
                 ok = zero_copy || hipMemcpyAsync(d_in_, h_in_, bytes, hipMemcpyHostToDevice, stream_) == hipSuccess;
                 // (no reset table in the captured frame, whichever call happens to capture it: a one-frame call can restart a stream
                 // at frame 0 only, and that is the reset kernel begin_resets has already put in front of the graph)
-                ok = ok && run_device({0, 1, zero_copy ? h_in_ : d_in_, zero_copy ? h_out_ : d_out_, true, nullptr}, err);
+                ok = ok && run_device({0, 1, zero_copy ? h_in_ : d_in_, zero_copy ? h_out_ : d_out_, true, nullptr, min_gain}, err);
                 ok = ok && (zero_copy || hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream_) == hipSuccess);
                 // zero-copy frames end with the completion word (the output is already in host memory when that node runs)
                 frame_graph_signals_[parity] = ok && zero_copy && spin_wait_ && h_frame_word_ && d_frame_count_;
@@ -1944,7 +1990,7 @@ bool Engine::run_call(const Call &c, std::string *err) {
         }
     }
     if (hipMemcpyAsync(d_in_, h_in_, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) goto fail;
-    if (!run_device({0, T, d_in_, d_out_, true, &table}, err)) return false;
+    if (!run_device({0, T, d_in_, d_out_, true, &table, min_gain}, err)) return false;
     if (hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
     if (hipStreamSynchronize(stream_) != hipSuccess) goto fail;
     memcpy(out, h_out_, bytes);

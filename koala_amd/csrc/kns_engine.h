@@ -45,6 +45,12 @@ struct Call {
     // are unspecified.  nullptr or all zero: the plain call.  Not combined with `resets`, not taken by process_host_async.
     const uint8_t *hold = nullptr;
     bool host_contract = false;  // pcm/out are host memory by the entry point's contract: no driver query per frame on the latency path
+    // Per-stream attenuation limit: host memory, float [num_streams], every value in [0, 1] (checked by the owner, the C ABI's handle).
+    // Stream b's mask value m becomes min_gain[b] + (1 - min_gain[b]) m in every frame of the call.  Read before
+    // the call returns (copied into an upload slot of the call when `min_gain_rev` differs from the one the engine's device table holds: the
+    // owner counts its changes).  nullptr: every gain is 0, the plain call -- same route, same kernels, same bits.
+    const float *min_gain = nullptr;
+    unsigned min_gain_rev = 0;
 };
 
 // kBadArgument: a stream list, a record or a combination of Call members that the engine refused before it touched anything (the C ABI
@@ -107,6 +113,7 @@ private:
         int16_t *d_out;
         bool allow_recompute;  // the synthesis kernel may rebuild the spectrum from d_pcm (false: d_out overlaps it)
         ResetTable *resets;
+        const float *min_gain;  // the call's per-stream minimum gains on the device [Bpad] (begin_min_gain), nullptr: no limit in force
     };
     bool run_device(const Slice &s, std::string *err);
     void *dalloc(size_t bytes, bool zero);
@@ -163,7 +170,7 @@ private:
     // staging for host-pointer calls: [B][Tmax * 256] each; chunked calls use them as two slots of [B][Tc * 256]
     int16_t *d_in_ = nullptr, *d_out_ = nullptr, *h_in_ = nullptr, *h_out_ = nullptr;
     // host-pointer calls with more than one sub-chunk: copy-in, compute and copy-out run on three streams
-    bool process_host_pipelined(const Call &c, bool pinned, ResetTable *resets, std::string *err);
+    bool process_host_pipelined(const Call &c, bool pinned, ResetTable *resets, const float *min_gain, std::string *err);
     std::vector<int> host_schedule(int T) const;  // its sub-chunk lengths
     std::vector<int> dev_host_sched_;             // developer override (KOALA_AMD_HOST_SCHED)
     // calls of several frames as a wavefront over (stage, frame): kns_engine.cpp, run_wave
@@ -191,12 +198,13 @@ private:
     size_t host_pipeline_min_bytes_ = 0;
 
     // hipGraph of one host-pointer frame (copy-in, 23 kernels, copy-out); built on first use
-    hipGraphExec_t frame_graph_[8] = {};  // one per combination of the hidden-state / history / tail ping-pong indices
+    hipGraphExec_t frame_graph_[16] = {};  // one per combination of the hidden-state / history / tail ping-pong indices, and (bit 3) of
+                                           // "an attenuation limit is in force": the captured synthesis kernel is the plain or the kMinGain form
     // completion word of the zero-copy one-frame replays (kns_stft.hip, frame_done_kernel): the host spins on a word in page-locked
     // memory instead of sleeping in hipStreamSynchronize, whose wake-up is what made p99 drift away from p50 on a busy host
     unsigned *d_frame_count_ = nullptr, *h_frame_word_ = nullptr;
     unsigned frame_seq_ = 0;
-    bool frame_graph_signals_[8] = {};
+    bool frame_graph_signals_[16] = {};
     bool spin_wait_ = true;
     bool use_graph_ = true, no_small_ = false, no_zero_copy_ = false, no_recompute_ = false, debug_taps_ = false;
     // developer switches (all read once in init() through dev_env(): compiled out of the product library)
@@ -243,6 +251,14 @@ private:
     uint8_t *d_state_ = nullptr;
     int32_t *d_recof_ = nullptr;
     UploadRing recof_ring_;
+    // Per-stream attenuation limit (Call::min_gain): the one device table float [Bpad] and its upload ring.  The table is configuration, not
+    // state: no reset, record or held stream touches it.  begin_min_gain: the device table a call's synthesis kernels read (nullptr: no
+    // limit), uploaded on the handle's stream -- in front of the call's kernels or graph replay -- when the call's revision is not the table's
+    float *d_min_gain_ = nullptr;
+    UploadRing mg_ring_;
+    unsigned mg_rev_ = 0;
+    bool mg_valid_ = false;
+    bool begin_min_gain(const Call &c, const float **table, std::string *err);
     bool state_ready(std::string *err);
     Status state_list(int count, const int32_t *streams, std::string *err);  // checks the list, uploads its inverse table
     StateArgs state_args() const;

@@ -92,6 +92,9 @@ struct SynthesisArgs {
     // zero in its reset frame
     const unsigned *resets = nullptr;
     int rs_pitch = 0, rs_t0 = 0;
+    // optional: per-stream minimum mask gain, float [Bpad] in [0, 1] (rows past B: 0).  Row b's mask value m becomes g_b + (1 - g_b) m, two
+    // roundings, in all 257 bins, before Y = mask . X.  Selects the kernels' kMinGain arm (a null pointer: today's instantiations)
+    const float *min_gain = nullptr;
 };
 void launch_synthesis(const SynthesisArgs &a, hipStream_t s);
 

@@ -278,7 +278,16 @@ void launch_analysis(const AnalysisArgs &a, hipStream_t s) {
 // kResets (calls with per-frame stream resets, SynthesisArgs::resets): in a row's reset frame its overlap-add tail is zero and, recomputed,
 // its spectrum is that of [0 | frame t].  This holds for the replayed frame t0 - 1 as well, and a reset at t0 zeroes the tail the replay
 // left: nothing of the frames before a reset reaches the output.
-template <bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets = false>  // kMaskH: the mask travels as fp16 C fragments (bf16 configuration), else fp32
+// kMinGain (handles with a per-stream attenuation limit in force, SynthesisArgs::min_gain): the mask value m of every bin becomes
+// m' = g + (1 - g) m, g the row's minimum gain -- one (g, 1 - g) pair per lane, loaded in front of the frame loop; DESIGN.md section 2, step 4.
+// m' = g + u m of the spec: the product rounded, then the sum -- never one fused operation, whatever the build's flags say
+__device__ __forceinline__ float min_gain_mask(float g, float u, float m) {
+#pragma clang fp contract(off)
+    const float p = u * m;
+    return g + p;
+}
+
+template <bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets = false, bool kMinGain = false>  // kMaskH: the mask travels as fp16 C fragments (bf16 configuration), else fp32
 __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_kernel(SynthesisArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!kMaskIn || (kMaskH && !kRecompute), "mask head inside: bf16, stored spectrum");
@@ -324,6 +333,12 @@ __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesi
     const bool valid = b < g.B;
     const size_t row_len = (size_t) (g.pitch ? g.pitch : g.T) * kFrame;
     const int16_t *pcm_row = g.pcm + (size_t) (valid ? b : g.B - 1) * row_len;  // (ragged tile: see analysis_kernel)
+    // this row's minimum gain and its complement (the table has Bpad entries: rows past the last stream read their own, a zero)
+    float mg = 0.0f, mu = 1.0f;
+    if (kMinGain) {
+        mg = g.min_gain[b];
+        mu = 1.0f - mg;
+    }
 
     int prev[8], cur[8], nxt[8];
     if (kRecompute) {
@@ -429,6 +444,11 @@ __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesi
         }
         // Y = mask . X; bin 0 holds DC and Nyquist (both real): its slot travels as {m[0] X[0], m[256] X[256]} and is taken
         // apart again below
+        // (kMinGain: on m' -- formed here, where the frame's mask is first used, so the request above stays in flight as long as before)
+        if (kMinGain) {
+#pragma unroll
+            for (int k2 = 0; k2 < 17; ++k2) mk[k2] = min_gain_mask(mg, mu, mk[k2]);
+        }
         cpx y[16];
 #pragma unroll
         for (int k2 = 0; k2 < 16; ++k2) y[k2] = cpx{mk[k2] * x[k2].x, mk[k2] * x[k2].y};
@@ -502,31 +522,40 @@ __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesi
     }
 }
 
+// the forms of one arm (kMinGain: with or without the per-stream minimum gain); the plain arm's are the kernels of a handle without a limit
+template <bool kMinGain>
+static void launch_synthesis_arm(const SynthesisArgs &a, const dim3 grid, size_t lds, hipStream_t s) {
+    if (a.resets) {  // (calls with per-frame stream resets: the reset arm; the engine does not put the mask head inside then)
+        if (a.recompute && a.mask_fp16)
+            hipLaunchKernelGGL((synthesis_kernel<true, true, false, true, kMinGain>), grid, dim3(256), lds, s, a);
+        else if (a.recompute)
+            hipLaunchKernelGGL((synthesis_kernel<true, false, false, true, kMinGain>), grid, dim3(256), lds, s, a);
+        else if (a.mask_fp16)
+            hipLaunchKernelGGL((synthesis_kernel<false, true, false, true, kMinGain>), grid, dim3(256), lds, s, a);
+        else
+            hipLaunchKernelGGL((synthesis_kernel<false, false, false, true, kMinGain>), grid, dim3(256), lds, s, a);
+    } else if (a.mask_w && !a.recompute && a.mask_fp16 && a.T == 1)
+        hipLaunchKernelGGL((synthesis_kernel<false, true, true, false, kMinGain>), grid, dim3(512), lds + kMaskTiles * 512, s, a);
+    else if (a.recompute && a.mask_fp16)
+        hipLaunchKernelGGL((synthesis_kernel<true, true, false, false, kMinGain>), grid, dim3(256), lds, s, a);
+    else if (a.recompute)
+        hipLaunchKernelGGL((synthesis_kernel<true, false, false, false, kMinGain>), grid, dim3(256), lds, s, a);
+    else if (a.mask_fp16)
+        hipLaunchKernelGGL((synthesis_kernel<false, true, false, false, kMinGain>), grid, dim3(256), lds, s, a);
+    else
+        hipLaunchKernelGGL((synthesis_kernel<false, false, false, false, kMinGain>), grid, dim3(256), lds, s, a);
+}
+
 void launch_synthesis(const SynthesisArgs &a, hipStream_t s) {
     const size_t lds = kOffStftEnd + KNS_STFT_LDS_PAD;
     const dim3 grid(a.Bpad / 16, (a.T + a.seg - 1) / a.seg);
 #if KNS_STFT_LDS_PAD
     (void) hipFuncSetAttribute((const void *) synthesis_kernel<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
 #endif
-    if (a.resets) {  // (calls with per-frame stream resets: the reset arm; the engine does not put the mask head inside then)
-        if (a.recompute && a.mask_fp16)
-            hipLaunchKernelGGL((synthesis_kernel<true, true, false, true>), grid, dim3(256), lds, s, a);
-        else if (a.recompute)
-            hipLaunchKernelGGL((synthesis_kernel<true, false, false, true>), grid, dim3(256), lds, s, a);
-        else if (a.mask_fp16)
-            hipLaunchKernelGGL((synthesis_kernel<false, true, false, true>), grid, dim3(256), lds, s, a);
-        else
-            hipLaunchKernelGGL((synthesis_kernel<false, false, false, true>), grid, dim3(256), lds, s, a);
-    } else if (a.mask_w && !a.recompute && a.mask_fp16 && a.T == 1)
-        hipLaunchKernelGGL((synthesis_kernel<false, true, true>), grid, dim3(512), lds + kMaskTiles * 512, s, a);
-    else if (a.recompute && a.mask_fp16)
-        hipLaunchKernelGGL((synthesis_kernel<true, true, false>), grid, dim3(256), lds, s, a);
-    else if (a.recompute)
-        hipLaunchKernelGGL((synthesis_kernel<true, false, false>), grid, dim3(256), lds, s, a);
-    else if (a.mask_fp16)
-        hipLaunchKernelGGL((synthesis_kernel<false, true, false>), grid, dim3(256), lds, s, a);
+    if (a.min_gain)
+        launch_synthesis_arm<true>(a, grid, lds, s);
     else
-        hipLaunchKernelGGL((synthesis_kernel<false, false, false>), grid, dim3(256), lds, s, a);
+        launch_synthesis_arm<false>(a, grid, lds, s);
 }
 
 // ------------------------------------------------------------------------------------------------ reset

@@ -27,11 +27,20 @@ void read_timing(unsigned long long *out);
 }
 #endif
 
+// The attenuation limit of a handle (include/pv_koala_batch.h, pv_koala_batch_set_min_gain): configuration that the handle owns and every
+// call carries to the engine (kns::Call::min_gain) -- the engine keeps nothing of it between calls but its device table.
+struct MinGain {
+    std::vector<float> gain;  // [num_streams], every value in [0, 1]
+    unsigned rev = 0;         // counts the accepted changes: the engine uploads the table when it has not seen this one
+    bool any = false;         // some gain is non-zero (none: the calls are the plain calls, no table at all)
+};
 struct pv_koala {
     kns::Engine *engine;
+    MinGain limit;
 };
 struct pv_koala_batch {
     kns::Engine *engine;
+    MinGain limit;
 };
 
 namespace {
@@ -133,8 +142,12 @@ pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std:
     return PV_STATUS_RUNTIME_ERROR;
 }
 
-// one call that advances the streams (arguments already checked)
-pv_status_t advance(kns::Engine *engine, const kns::Call &call, bool async = false) {
+// one call that advances the streams (arguments already checked), under the handle's attenuation limit
+pv_status_t advance(kns::Engine *engine, const MinGain &limit, kns::Call call, bool async = false) {
+    if (limit.any) {
+        call.min_gain = limit.gain.data();
+        call.min_gain_rev = limit.rev;
+    }
     return guarded([&] {
         std::string err;
         const kns::Status status = async ? engine->process_host_async(call, &err) : engine->process(call, &err);
@@ -273,6 +286,66 @@ pv_status_t open_engine(const char *access_key, const char *model_path, const ch
     return guarded([&] { return open_engine_unguarded(access_key, model_path, device, object, num_streams, max_frames, precision, engine); });
 }
 
+// the handle around a new engine (takes the engine over: deleted when the handle cannot be made)
+template <class H>
+pv_status_t make_handle(kns::Engine *e, H **object) {
+    H *o = nullptr;
+    try {
+        o = new H();
+        o->engine = e;
+        o->limit.gain.assign((size_t) e->num_streams(), 0.0f);
+    } catch (...) {
+        delete o;
+        o = nullptr;
+    }
+    if (!o) {
+        delete e;
+        push_error(0x65, "Failed to allocate memory.");
+        return PV_STATUS_OUT_OF_MEMORY;
+    }
+    *object = o;
+    return PV_STATUS_SUCCESS;
+}
+
+// pv_koala_batch_set_min_gain / pv_koala_set_min_gain: every entry is checked before anything is changed
+pv_status_t set_min_gain(MinGain *limit, int32_t B, int32_t count, const int32_t *streams, const float *gains) {
+    if (!gains) {
+        push_error(0x64, "Argument `gains` is NULL.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (count < 1 || count > B) {
+        push_error(0x66, "`count` %d is outside [1, %d].", count, B);
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    return guarded([&] {
+        std::vector<float> next(limit->gain);
+        std::vector<uint8_t> listed((size_t) B, 0);
+        for (int32_t i = 0; i < count; ++i) {
+            const int32_t b = streams ? streams[i] : i;
+            if (b < 0 || b >= B) {
+                push_error(0x66, "`streams[%d]` = %d is outside [0, %d).", i, b, B);
+                return PV_STATUS_INVALID_ARGUMENT;
+            }
+            if (listed[b]) {
+                push_error(0x66, "`streams[%d]`: slot %d is listed twice.", i, b);
+                return PV_STATUS_INVALID_ARGUMENT;
+            }
+            listed[b] = 1;
+            if (!(gains[i] >= 0.0f && gains[i] <= 1.0f)) {  // (NaN fails both comparisons)
+                push_error(0x66, "gain %d: %g is not a minimum gain in [0, 1].", i, (double) gains[i]);
+                return PV_STATUS_INVALID_ARGUMENT;
+            }
+            next[b] = gains[i] + 0.0f;  // (-0 -> +0: "no limit" is one bit pattern)
+        }
+        bool any = false;
+        for (float g : next) any = any || g != 0.0f;
+        limit->gain.swap(next);
+        limit->any = any;
+        ++limit->rev;
+        return PV_STATUS_SUCCESS;
+    });
+}
+
 int default_precision() {
     const char *p = getenv("KOALA_AMD_PRECISION");
     if (p && !strcmp(p, "bf16")) return kns::kBf16;
@@ -339,21 +412,13 @@ PV_API pv_status_t pv_koala_init(const char *access_key, const char *model_path,
     kns::Engine *e = nullptr;
     pv_status_t st = open_engine(access_key, model_path, device, object, 1, 1, default_precision(), &e);
     if (st != PV_STATUS_SUCCESS) return st;
-    pv_koala_t *o = (pv_koala_t *) malloc(sizeof(pv_koala_t));
-    if (!o) {
-        delete e;
-        push_error(0x65, "Failed to allocate memory.");
-        return PV_STATUS_OUT_OF_MEMORY;
-    }
-    o->engine = e;
-    *object = o;
-    return PV_STATUS_SUCCESS;
+    return make_handle(e, object);
 }
 
 PV_API void pv_koala_delete(pv_koala_t *object) {
     if (!object) return;
     delete object->engine;
-    free(object);
+    delete object;
 }
 
 PV_API pv_status_t pv_koala_process(pv_koala_t *object, const int16_t *pcm, int16_t *enhanced_pcm) {
@@ -367,7 +432,7 @@ PV_API pv_status_t pv_koala_process(pv_koala_t *object, const int16_t *pcm, int1
         push_error(0x64, "Argument `enhanced_pcm` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    return advance(object->engine, {1, pcm, enhanced_pcm, nullptr, nullptr, /*host_contract=*/true});
+    return advance(object->engine, object->limit, {1, pcm, enhanced_pcm, nullptr, nullptr, /*host_contract=*/true});
 }
 
 PV_API pv_status_t pv_koala_reset(pv_koala_t *object) {
@@ -437,21 +502,13 @@ PV_API pv_status_t pv_koala_batch_init(const char *access_key, const char *model
     pv_status_t st = open_engine(access_key, model_path, device, object, num_streams, max_frames_per_call,
                                  precision == PV_KOALA_PRECISION_BF16 ? kns::kBf16 : kns::kFp32, &e);
     if (st != PV_STATUS_SUCCESS) return st;
-    pv_koala_batch_t *o = (pv_koala_batch_t *) malloc(sizeof(pv_koala_batch_t));
-    if (!o) {
-        delete e;
-        push_error(0x65, "Failed to allocate memory.");
-        return PV_STATUS_OUT_OF_MEMORY;
-    }
-    o->engine = e;
-    *object = o;
-    return PV_STATUS_SUCCESS;
+    return make_handle(e, object);
 }
 
 PV_API void pv_koala_batch_delete(pv_koala_batch_t *object) {
     if (!object) return;
     delete object->engine;
-    free(object);
+    delete object;
 }
 
 PV_API pv_status_t pv_koala_batch_process_chunk(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
@@ -459,7 +516,7 @@ PV_API pv_status_t pv_koala_batch_process_chunk(pv_koala_batch_t *object, int32_
     t_stack.clear();
     const pv_status_t st = check_call(object, num_frames, pcm, enhanced);
     if (st != PV_STATUS_SUCCESS) return st;
-    return advance(object->engine, {num_frames, pcm, enhanced});
+    return advance(object->engine, object->limit, {num_frames, pcm, enhanced});
 }
 
 PV_API pv_status_t pv_koala_batch_process_chunk_async(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
@@ -467,7 +524,7 @@ PV_API pv_status_t pv_koala_batch_process_chunk_async(pv_koala_batch_t *object, 
     t_stack.clear();
     const pv_status_t st = check_call(object, num_frames, pcm, enhanced);
     if (st != PV_STATUS_SUCCESS) return st;
-    return advance(object->engine, {num_frames, pcm, enhanced}, /*async=*/true);
+    return advance(object->engine, object->limit, {num_frames, pcm, enhanced}, /*async=*/true);
 }
 
 PV_API pv_status_t pv_koala_batch_process_chunk_resets(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
@@ -476,7 +533,7 @@ PV_API pv_status_t pv_koala_batch_process_chunk_resets(pv_koala_batch_t *object,
     pv_status_t st = check_call(object, num_frames, pcm, enhanced);
     if (st == PV_STATUS_SUCCESS) st = check_resets(object, num_frames, reset);
     if (st != PV_STATUS_SUCCESS) return st;
-    return advance(object->engine, {num_frames, pcm, enhanced, reset});
+    return advance(object->engine, object->limit, {num_frames, pcm, enhanced, reset});
 }
 
 PV_API pv_status_t pv_koala_batch_process_chunk_resets_async(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
@@ -485,7 +542,7 @@ PV_API pv_status_t pv_koala_batch_process_chunk_resets_async(pv_koala_batch_t *o
     pv_status_t st = check_call(object, num_frames, pcm, enhanced);
     if (st == PV_STATUS_SUCCESS) st = check_resets(object, num_frames, reset);
     if (st != PV_STATUS_SUCCESS) return st;
-    return advance(object->engine, {num_frames, pcm, enhanced, reset}, /*async=*/true);
+    return advance(object->engine, object->limit, {num_frames, pcm, enhanced, reset}, /*async=*/true);
 }
 
 PV_API pv_status_t pv_koala_batch_process_chunk_hold(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
@@ -493,7 +550,41 @@ PV_API pv_status_t pv_koala_batch_process_chunk_hold(pv_koala_batch_t *object, i
     t_stack.clear();
     const pv_status_t st = check_call(object, num_frames, pcm, enhanced);
     if (st != PV_STATUS_SUCCESS) return st;
-    return advance(object->engine, {num_frames, pcm, enhanced, nullptr, hold});
+    return advance(object->engine, object->limit, {num_frames, pcm, enhanced, nullptr, hold});
+}
+
+// ---- attenuation limit
+
+PV_API pv_status_t pv_koala_batch_set_min_gain(pv_koala_batch_t *object, int32_t count, const int32_t *streams, const float *gains) {
+    t_stack.clear();
+    if (!object) return check_object(object);
+    return set_min_gain(&object->limit, object->engine->num_streams(), count, streams, gains);
+}
+
+PV_API pv_status_t pv_koala_batch_get_min_gain(const pv_koala_batch_t *object, float *gains) {
+    t_stack.clear();
+    if (!object || !gains) {
+        push_error(0x64, "Argument `%s` is NULL.", object ? "gains" : "object");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    memcpy(gains, object->limit.gain.data(), object->limit.gain.size() * sizeof(float));
+    return PV_STATUS_SUCCESS;
+}
+
+PV_API pv_status_t pv_koala_set_min_gain(pv_koala_t *object, float gain) {
+    t_stack.clear();
+    if (!object) return check_object(object);
+    return set_min_gain(&object->limit, 1, 1, nullptr, &gain);
+}
+
+PV_API pv_status_t pv_koala_get_min_gain(const pv_koala_t *object, float *gain) {
+    t_stack.clear();
+    if (!object || !gain) {
+        push_error(0x64, "Argument `%s` is NULL.", object ? "gain" : "object");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    *gain = object->limit.gain[0];
+    return PV_STATUS_SUCCESS;
 }
 
 // ---- stream records

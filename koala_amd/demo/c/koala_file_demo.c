@@ -36,6 +36,8 @@ typedef struct {
     status_t (*batch_init)(const char *, const char *, const char *, int32_t, int32_t, int32_t, void **);
     status_t (*batch_process_chunk)(void *, int32_t, const int16_t *, int16_t *);
     void (*batch_delete)(void *);
+    status_t (*set_min_gain)(void *, float);                                          /* extensions: include/pv_koala_batch.h */
+    status_t (*batch_set_min_gain)(void *, int32_t, const int32_t *, const float *);
 } api_t;
 
 static void *must_sym(void *lib, const char *name) {
@@ -66,6 +68,8 @@ static void bind(api_t *a, const char *path) {
     *(void **) &a->batch_init = must_sym(a->lib, "pv_koala_batch_init");
     *(void **) &a->batch_process_chunk = must_sym(a->lib, "pv_koala_batch_process_chunk");
     *(void **) &a->batch_delete = must_sym(a->lib, "pv_koala_batch_delete");
+    *(void **) &a->set_min_gain = must_sym(a->lib, "pv_koala_set_min_gain");
+    *(void **) &a->batch_set_min_gain = must_sym(a->lib, "pv_koala_batch_set_min_gain");
 }
 
 static void die_with_stack(const api_t *a, const char *what, status_t st) {
@@ -147,9 +151,22 @@ static double now_s(void) {
     return (double) t.tv_sec + 1e-9 * (double) t.tv_nsec;
 }
 
+/* 10^(-db / 20) without libm (the build line above links -ldl only): e^x by its series on an argument halved until it is small, squared back */
+static double db_to_gain(double db) {
+    if (db > 400.0) return 0.0;
+    double x = -db * 0.11512925464970229; /* ln(10) / 20 */
+    int halvings = 0;
+    for (; x < -0.5; x *= 0.5) ++halvings;
+    double term = 1.0, sum = 1.0;
+    for (int i = 1; i < 20; ++i) sum += (term *= x / i);
+    while (halvings--) sum *= sum;
+    return sum;
+}
+
 int main(int argc, char **argv) {
     const char *lib = NULL, *model = NULL, *in = NULL, *out = NULL, *device = "best", *key = "koala-amd";
     int streams = 1, frames = 8;
+    double limit_db = -1.0; /* < 0: no attenuation limit */
     for (int i = 1; i < argc; ++i) {
         const char *v = i + 1 < argc ? argv[i + 1] : NULL;
         if (!strcmp(argv[i], "-l") && v) lib = v, ++i;
@@ -160,11 +177,17 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-a") && v) key = v, ++i;
         else if (!strcmp(argv[i], "--streams") && v) streams = atoi(v), ++i;
         else if (!strcmp(argv[i], "--frames") && v) frames = atoi(v), ++i;
+        else if (!strcmp(argv[i], "--attenuation_limit_db") && v) limit_db = atof(v), ++i;
         else {
-            fprintf(stderr, "usage: %s -l LIBRARY -m MODEL -i IN.wav -o OUT.wav [-d DEVICE] [-a KEY] [--streams N --frames T]\n", argv[0]);
+            fprintf(stderr,
+                    "usage: %s -l LIBRARY -m MODEL -i IN.wav -o OUT.wav [-d DEVICE] [-a KEY] [--streams N --frames T] "
+                    "[--attenuation_limit_db DB]\n",
+                    argv[0]);
             return 2;
         }
     }
+    /* at most DB decibels of suppression: the minimum mask gain 10^(-DB / 20) (0 dB: bypass with unchanged latency) */
+    const float min_gain = limit_db >= 0.0 ? (float) db_to_gain(limit_db) : 0.0f;
     if (!lib || !model || !in || !out || streams < 1 || frames < 1) {
         fprintf(stderr, "missing -l / -m / -i / -o\n");
         return 2;
@@ -185,6 +208,7 @@ int main(int argc, char **argv) {
         status_t st = a.init(key, model, device, &k);
         if (st) die_with_stack(&a, "pv_koala_init", st);
         if ((st = a.delay_sample(k, &delay))) die_with_stack(&a, "pv_koala_delay_sample", st);
+        if (limit_db >= 0.0 && (st = a.set_min_gain(k, min_gain))) die_with_stack(&a, "pv_koala_set_min_gain", st);
         total = (len + delay + n - 1) / n;
         enh = (int16_t *) calloc((size_t) total * n, 2);
         int16_t *frame = (int16_t *) calloc((size_t) n, 2);
@@ -202,6 +226,12 @@ int main(int argc, char **argv) {
         void *k = NULL;
         status_t st = a.batch_init(key, model, device, streams, frames, 0 /* fp32 */, &k);
         if (st) die_with_stack(&a, "pv_koala_batch_init", st);
+        if (limit_db >= 0.0) {
+            float *gains = (float *) malloc((size_t) streams * sizeof(float));
+            for (int s = 0; s < streams; ++s) gains[s] = min_gain;
+            if ((st = a.batch_set_min_gain(k, streams, NULL, gains))) die_with_stack(&a, "pv_koala_batch_set_min_gain", st);
+            free(gains);
+        }
         delay = 256;
         total = (len + delay + n - 1) / n;
         total = (total + frames - 1) / frames * frames;

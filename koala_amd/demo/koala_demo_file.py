@@ -105,6 +105,8 @@ def main():
                    help='many-files mode: a fixed number of slots, each playing one file after the other with per-frame stream resets '
                         '(koala_amd/corpus.py) instead of one stream per file zero-padded to the longest')
     p.add_argument('--num_slots', type=int, help='--refill: streams of the handle (default: the number of files, at most 4096)')
+    p.add_argument('--attenuation_limit_db', type=float,
+                   help='suppress by at most this many dB (every file alike; 0: bypass with unchanged latency; default: unlimited)')
     p.add_argument('--show_inference_devices', action='store_true')
     args = p.parse_args()
     if args.show_inference_devices:
@@ -115,6 +117,7 @@ def main():
         koala = koala_amd.create(args.access_key, model_path=args.model_path, device=args.device,
                                  library_path=args.library_path)
         try:
+            koala.set_attenuation_limit(args.attenuation_limit_db)
             pcm = read_wav(args.input_path[0], koala.sample_rate)
             t0 = time.perf_counter()
             out = enhance_single(koala, pcm)
@@ -132,6 +135,7 @@ def main():
         batch = koala_amd.create_batch(args.access_key, slots, args.frames_per_call, args.precision,
                                        model_path=args.model_path, device=args.device, library_path=args.library_path)
         try:
+            batch.set_attenuation_limit(args.attenuation_limit_db)  # (a slot keeps its limit from file to file)
             signals = [read_wav(pth, batch.sample_rate) for pth in args.input_path]
             t0 = time.perf_counter()
             if args.refill:

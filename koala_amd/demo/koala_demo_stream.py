@@ -65,6 +65,8 @@ def main(argv=None):
     ap.add_argument('--precision', default=None, choices=['fp32', 'bf16'],
                     help='mask network arithmetic (default: the library default, fp32, or $KOALA_AMD_PRECISION)')
     ap.add_argument('--realtime', action='store_true', help='pace a replayed file at 16 ms per frame, like a recorder')
+    ap.add_argument('--attenuation_limit_db', type=float, default=None,
+                    help='suppress by at most this many dB (0: bypass with unchanged latency; default: unlimited)')
     ap.add_argument('--show_devices', action='store_true')
     args = ap.parse_args(argv)
 
@@ -82,6 +84,7 @@ def main(argv=None):
         os.environ['KOALA_AMD_PRECISION'] = args.precision
     koala = koala_amd.create(access_key=args.access_key, model_path=args.model_path, device=args.device,
                              library_path=args.library_path)
+    koala.set_attenuation_limit(args.attenuation_limit_db)
     print('Koala version: %s' % koala.version)
     n = koala.frame_length
     source = (frames_from_wav(args.input_path, n, koala.sample_rate) if args.input_path
