@@ -163,6 +163,48 @@ PV_API pv_status_t pv_koala_batch_get_min_gain(const pv_koala_batch_t *object, f
 PV_API pv_status_t pv_koala_set_min_gain(pv_koala_t *object, float gain);
 PV_API pv_status_t pv_koala_get_min_gain(const pv_koala_t *object, float *gain);
 
+/* FRAME REPORT: what the suppressor did to every stream in every frame -- for voice activity and talker detection, for a "this caller is
+ * being gated to nothing" alarm (the moment to raise pv_koala_batch_set_min_gain), for per-file figures of a corpus job.  Four fp32 values per
+ * stream and frame, formed by the synthesis kernel from what it holds anyway (fixes every operation and the
+ * summation order; fp32 handles are bit-exact against it):
+ *
+ *     report[b][t][0]  e_in      sum over the 257 bins of |X[k]|^2, X the spectrum of the 512-sample analysis block whose second half is
+ *                                input frame t (sqrt-Hann window, samples / 32768)
+ *     report[b][t][1]  e_out     the same sum over Y[k] = m'[k] X[k], the spectrum that is synthesised (m': the mask under the stream's
+ *                                attenuation limit)
+ *     report[b][t][2]  mask_sum  sum of the network's RAW mask m[k] (before the attenuation limit: the speech cue does not depend on a
+ *                                tenant's limit); mask_sum / 257 is the mean gain the model asked for
+ *     report[b][t][3]  reserved, 0
+ *
+ * The block of report row t leaves as output frame t (its first half, overlap-added).  Exact in both precisions: a stream with minimum
+ * gain 1 has e_out == e_in; a block of digital silence reports zeros; in a reset frame the report is that of the block [0 | frame t].  The
+ * report is an output only: samples and stream state are bit for bit the same whether or not it is asked for, and a call that does not ask
+ * runs the kernels it always ran.  Held streams' rows are unspecified.  koala_amd/report.py turns rows into dBFS, suppression in dB and
+ * mean gain.
+ *
+ * pv_koala_batch_process_call: ONE entry point for every way of advancing the streams; the members select what the dedicated entry points
+ * select.  With report == NULL the call is exactly the existing entry point its other members name -- pv_koala_batch_process_chunk,
+ * _async, _resets, _resets_async or _hold: same route, same bits.  `report` is memory of the same kind as `enhanced` (host with host,
+ * device with device; asynchronous calls: page-locked, valid once the call has completed) -- anything else is PV_STATUS_RUNTIME_ERROR like
+ * the other pointer-kind refusals.  PV_STATUS_INVALID_ARGUMENT, with a message on the error stack and nothing processed: a NULL object /
+ * call / pcm / enhanced, num_frames outside [1, max_frames_per_call], a struct_size that is not sizeof(pv_koala_batch_call_t), hold together
+ * with reset, hold together with asynchronous, and a KNS-v1.1 model with a reset at a frame t > 0. */
+typedef struct {
+    int32_t struct_size;      /* sizeof(pv_koala_batch_call_t): lets the struct grow */
+    int32_t num_frames;
+    const int16_t *pcm;       /* [num_streams][num_frames * 256] */
+    int16_t *enhanced;        /* [num_streams][num_frames * 256] */
+    const uint8_t *reset;     /* [num_streams][num_frames] or NULL (pv_koala_batch_process_chunk_resets) */
+    const uint8_t *hold;      /* [num_streams] or NULL (pv_koala_batch_process_chunk_hold) */
+    float *report;            /* [num_streams][num_frames][4] or NULL */
+    int32_t asynchronous;     /* non-zero: the rules of pv_koala_batch_process_chunk_async */
+} pv_koala_batch_call_t;
+PV_API pv_status_t pv_koala_batch_process_call(pv_koala_batch_t *object, const pv_koala_batch_call_t *call);
+
+/* pv_koala_process of the single-stream handle of pv_koala.h with the frame's report (an extension: the reference library has no such
+ * call).  Calls with and without a report may be mixed freely: the samples are those of a handle that never asked. */
+PV_API pv_status_t pv_koala_process_report(pv_koala_t *object, const int16_t *pcm, int16_t *enhanced_pcm, float report[4]);
+
 PV_API pv_status_t pv_koala_batch_num_streams(const pv_koala_batch_t *object, int32_t *num_streams);
 PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, int32_t *delay_sample);
 

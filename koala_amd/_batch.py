@@ -5,7 +5,7 @@ sample-for-sample what its own `Koala` instance would produce.
 """
 
 import os
-from ctypes import POINTER, byref, c_char_p, c_double, c_int16, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int16, c_int32, c_int64, c_void_p, sizeof
 from typing import Optional
 
 import numpy as np
@@ -16,6 +16,12 @@ from ._koala import (KoalaError, KoalaInvalidArgumentError, KoalaIOError, Picovo
 PRECISION_FP32 = 0
 PRECISION_BF16 = 1
 KERNEL_CLASSES = ('analysis', 'gemm_input', 'gru_recurrent', 'gemm_head', 'synthesis')
+
+
+class BatchCall(Structure):
+    """pv_koala_batch_call_t (include/pv_koala_batch.h)"""
+    _fields_ = [('struct_size', c_int32), ('num_frames', c_int32), ('pcm', c_void_p), ('enhanced', c_void_p), ('reset', c_void_p),
+                ('hold', c_void_p), ('report', c_void_p), ('asynchronous', c_int32)]
 
 
 class KoalaBatch(object):
@@ -45,7 +51,8 @@ class KoalaBatch(object):
                            ('import_state', [c_void_p, c_int32, c_void_p, c_void_p]),
                            ('process_chunk_hold', [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
                            ('set_min_gain', [c_void_p, c_int32, c_void_p, c_void_p]),
-                           ('get_min_gain', [c_void_p, c_void_p])):
+                           ('get_min_gain', [c_void_p, c_void_p]),
+                           ('process_call', [c_void_p, POINTER(BatchCall)])):
             fn = getattr(lib, 'pv_koala_batch_' + name)
             fn.argtypes = args
             fn.restype = PicovoiceStatuses
@@ -172,6 +179,62 @@ class KoalaBatch(object):
         m, mp = self._reset_mask(reset, num_frames)
         self._check(self._lib.pv_koala_batch_process_chunk_resets(self._handle, num_frames, c_void_p(pcm_ptr), c_void_p(enhanced_ptr), mp),
                     'Processing failed')
+
+    # ---- one call with everything it may carry, the frame report included (include/pv_koala_batch.h, pv_koala_batch_process_call)
+
+    def _call(self, num_frames, pcm_ptr, enhanced_ptr, reset, hold, report_ptr, asynchronous):
+        m, mp = self._reset_mask(reset, num_frames)
+        h, hp = self._hold_mask(hold)
+        call = BatchCall(sizeof(BatchCall), num_frames, pcm_ptr, enhanced_ptr, mp, hp, report_ptr or None, 1 if asynchronous else 0)
+        self._check(self._lib.pv_koala_batch_process_call(self._handle, byref(call)), 'Processing failed')
+
+    def _audio(self, *arrays):
+        for a in arrays:
+            if (not isinstance(a, np.ndarray) or a.dtype != np.int16 or not a.flags['C_CONTIGUOUS'] or a.ndim != 2 or
+                    a.shape[0] != self.num_streams or a.shape[1] == 0 or a.shape[1] % self.frame_length or a.shape != arrays[0].shape):
+                raise KoalaInvalidArgumentError(
+                    "expected C-contiguous int16 arrays of shape [%d, T*%d]" % (self.num_streams, self.frame_length))
+        return arrays[0].shape[1] // self.frame_length
+
+    def _report_array(self, report, num_frames):
+        if (not isinstance(report, np.ndarray) or report.dtype != np.float32 or not report.flags['C_CONTIGUOUS'] or
+                report.shape != (self.num_streams, num_frames, 4)):
+            raise KoalaInvalidArgumentError("`report` must be a C-contiguous float32 array of shape [%d, %d, 4]" % (self.num_streams, num_frames))
+        return report.ctypes.data
+
+    def process_call(self, pcm: np.ndarray, reset: Optional[np.ndarray] = None, hold: Optional[np.ndarray] = None, report: bool = False):
+        """`process()` with any of: per-frame resets ([num_streams, T]), held streams ([num_streams]; not together with resets), and the
+        FRAME REPORT.  Returns `enhanced`, or `(enhanced, report)` when `report` is true: float32 [num_streams, T, 4] = e_in, e_out,
+        mask_sum, 0 of every stream and frame (include/pv_koala_batch.h; koala_amd.report turns rows into dBFS, dB of suppression and
+        mean gain).  The samples do not depend on whether the report is asked for."""
+        a = np.ascontiguousarray(pcm, dtype=np.int16)
+        T = self._audio(a)
+        out = np.empty_like(a)
+        rep = np.empty((self.num_streams, T, 4), np.float32) if report else None
+        self._call(T, a.ctypes.data, out.ctypes.data, reset, hold, rep.ctypes.data if report else None, False)
+        return (out, rep) if report else out
+
+    def process_device_call(self, num_frames: int, pcm_ptr: int, enhanced_ptr: int, report_ptr: int = 0, reset: Optional[np.ndarray] = None,
+                            hold: Optional[np.ndarray] = None) -> None:
+        """`process_device()` with any of resets, held streams (host masks, read before the call returns) and the frame report:
+        `report_ptr` is a device pointer of float32 [num_streams, num_frames, 4] (0: none), written on the handle's stream."""
+        self._call(num_frames, c_void_p(pcm_ptr), c_void_p(enhanced_ptr), reset, hold, c_void_p(report_ptr) if report_ptr else None, False)
+
+    def alloc_host_report(self, num_frames: int) -> np.ndarray:
+        """float32 [num_streams, num_frames, 4] in page-locked host memory (freed by `delete()`): the report array of `process_async_call`."""
+        n = self.num_streams * num_frames * 4
+        p = c_void_p()
+        self._check(self._lib.pv_koala_batch_host_alloc(4 * n, byref(p)), 'Host allocation failed')
+        self._pinned.append(p)
+        return np.frombuffer((c_float * n).from_address(p.value), dtype=np.float32).reshape(self.num_streams, num_frames, 4)
+
+    def process_async_call(self, pcm: np.ndarray, enhanced: np.ndarray, report: Optional[np.ndarray] = None,
+                           reset: Optional[np.ndarray] = None) -> None:
+        """`process_async()` with per-frame resets and / or the frame report: `report` is a page-locked float32 [num_streams, T, 4]
+        (`alloc_host_report()`), valid when `enhanced` is -- after `synchronize()` or once `wait(k)` says the call has completed."""
+        T = self._audio(pcm, enhanced)
+        rp = None if report is None else self._report_array(report, T)
+        self._call(T, pcm.ctypes.data, enhanced.ctypes.data, reset, None, rp, True)
 
     def _stream_list(self, streams, n):
         """(int32 array kept alive by the caller's frame, pointer, count) for a list of stream indices (None: 0 .. n - 1)"""
@@ -312,4 +375,4 @@ class KoalaBatch(object):
             pass
 
 
-__all__ = ['KoalaBatch', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']
+__all__ = ['KoalaBatch', 'BatchCall', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']

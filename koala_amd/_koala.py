@@ -123,6 +123,10 @@ class Koala(object):
         self._get_min_gain_func.argtypes = [POINTER(self.CKoala), POINTER(c_float)]
         self._get_min_gain_func.restype = PicovoiceStatuses
 
+        self._process_report_func = library.pv_koala_process_report
+        self._process_report_func.argtypes = [POINTER(self.CKoala), POINTER(c_short), POINTER(c_short), POINTER(c_float)]
+        self._process_report_func.restype = PicovoiceStatuses
+
         self._sample_rate = library.pv_sample_rate()
         self._frame_length = library.pv_koala_frame_length()
         self._version = library.pv_koala_version().decode('utf-8')
@@ -147,6 +151,27 @@ class Koala(object):
         if status is not PicovoiceStatuses.SUCCESS:
             raise_status(self._library, status, 'Processing failed')
         return list(enhanced)
+
+    def process_with_report(self, pcm: Sequence[int]):
+        """`process()` that also returns the frame's report (an extension: include/pv_koala_batch.h, pv_koala_process_report): a float32
+        array [4] = e_in, e_out, mask_sum, 0 -- what came in, what goes out and how far the mask was open (koala_amd.report).  Calls with and
+        without a report may be mixed; the samples are the same either way.
+
+        :return: (enhanced samples as a list of ints, report)
+        """
+        if len(pcm) != self._frame_length:
+            raise KoalaInvalidArgumentError(
+                "Length of input frame %d does not match required frame length %d" % (len(pcm), self._frame_length))
+        if hasattr(pcm, 'ctypes') and getattr(pcm, 'dtype', None) == 'int16' and pcm.flags['C_CONTIGUOUS']:
+            frame = pcm.ctypes.data_as(POINTER(c_short))
+        else:
+            frame = self._frame_type(*pcm)
+        enhanced = self._frame_type()
+        report = np.zeros(4, np.float32)
+        status = self._process_report_func(self._handle, frame, enhanced, report.ctypes.data_as(POINTER(c_float)))
+        if status is not PicovoiceStatuses.SUCCESS:
+            raise_status(self._library, status, 'Processing failed')
+        return list(enhanced), report
 
     def reset(self) -> None:
         """Back to the state of a new instance; call between non-consecutive pieces of audio."""

@@ -118,7 +118,7 @@ def process_split(proc, pcm: np.ndarray, reset: Optional[np.ndarray]) -> np.ndar
 
 
 def enhance_corpus(batch, signals: Sequence[np.ndarray], frames_per_call: int, mode: str = 'device',
-                   plan: Optional[CorpusPlan] = None, table: Optional[np.ndarray] = None) -> List[np.ndarray]:
+                   plan: Optional[CorpusPlan] = None, table: Optional[np.ndarray] = None, report: bool = False):
     """Enhances every utterance of `signals` (int16 arrays of any length) on `batch` (a KoalaBatch whose streams are the slots, opened
     with max_frames_per_call >= frames_per_call) and returns one trimmed int16 array per utterance.  Modes:
       host    synchronous host calls (process_resets)
@@ -126,7 +126,9 @@ def enhance_corpus(batch, signals: Sequence[np.ndarray], frames_per_call: int, m
       device  the corpus uploaded once as a torch int16 [frames + 1, 256] tensor; each call's input gathered and its output scattered
               by frame index on the GPU, on torch's current stream (no per-call host copy of audio)
     The handle's streams need no reset before: every slot's first utterance starts with one.  `plan` / `table`: a plan_corpus() of the
-    signals' lengths and its corpus_table(), when the caller has them already."""
+    signals' lengths and its corpus_table(), when the caller has them already.
+    report=True: returns (arrays, reports), reports[u] = float32 [frames of u, 4], the frame report (koala_amd/report.py) of utterance u's
+    own frames and its flush frame -- what the same file reports when it is run alone from a fresh stream."""
     T = int(frames_per_call)
     if T > batch.max_frames_per_call:
         raise ValueError("frames_per_call %d exceeds the handle's max_frames_per_call %d" % (T, batch.max_frames_per_call))
@@ -137,18 +139,26 @@ def enhance_corpus(batch, signals: Sequence[np.ndarray], frames_per_call: int, m
         raise ValueError("plan shape %r does not match %d slots x %d frames" % (plan.src.shape[1:], S, T))
     if table is None:
         table = corpus_table(signals, plan)
+    rep = np.zeros((table.shape[0], 4), np.float32) if report else None  # by corpus frame, like `out`
     if mode == 'host':
         out = np.zeros_like(table)
         for c in range(plan.num_calls):
             idx = plan.src[c]
-            y = batch.process_resets(table[idx].reshape(S, T * FRAME), plan.reset[c])
+            if report:
+                y, r = batch.process_call(table[idx].reshape(S, T * FRAME), reset=plan.reset[c], report=True)
+                rep[idx] = r
+            else:
+                y = batch.process_resets(table[idx].reshape(S, T * FRAME), plan.reset[c])
             out[idx] = y.reshape(S, T, FRAME)
     elif mode == 'async':
         out = np.zeros_like(table)
         pins = [(batch.alloc_host(T), batch.alloc_host(T)) for _ in range(3)]
+        rpins = [batch.alloc_host_report(T) for _ in range(3)] if report else None
 
         def collect(c):
             out[plan.src[c]] = pins[c % 3][1].reshape(S, T, FRAME)
+            if report:
+                rep[plan.src[c]] = rpins[c % 3]
 
         for c in range(plan.num_calls):
             if c >= 3:
@@ -156,7 +166,10 @@ def enhance_corpus(batch, signals: Sequence[np.ndarray], frames_per_call: int, m
                 collect(c - 3)
             pin_in, pin_out = pins[c % 3]
             np.take(table, plan.src[c], axis=0, out=pin_in.reshape(S, T, FRAME))
-            batch.process_async_resets(pin_in, pin_out, plan.reset[c])
+            if report:
+                batch.process_async_call(pin_in, pin_out, report=rpins[c % 3], reset=plan.reset[c])
+            else:
+                batch.process_async_resets(pin_in, pin_out, plan.reset[c])
         batch.wait(0)
         for c in range(max(0, plan.num_calls - 3), plan.num_calls):
             collect(c)
@@ -165,6 +178,7 @@ def enhance_corpus(batch, signals: Sequence[np.ndarray], frames_per_call: int, m
         dev = torch.device('cuda')
         tab = torch.from_numpy(table).to(dev)
         res = torch.zeros_like(tab)
+        rres = torch.zeros((table.shape[0], 4), dtype=torch.float32, device=dev) if report else None
         src = torch.from_numpy(plan.src.astype(np.int64)).to(dev)
         # one stream of its own for torch's gathers / scatters and the engine's kernels, in order (torch's default stream is the null
         # stream, which the engine cannot be put on: set_stream(0) means the handle's own stream)
@@ -177,14 +191,24 @@ def enhance_corpus(batch, signals: Sequence[np.ndarray], frames_per_call: int, m
                     idx = src[c]
                     x = tab[idx].reshape(S, T * FRAME)
                     y = torch.empty_like(x)
-                    batch.process_device_resets(T, x.data_ptr(), y.data_ptr(), plan.reset[c])
+                    if report:
+                        r = torch.empty((S, T, 4), dtype=torch.float32, device=dev)
+                        batch.process_device_call(T, x.data_ptr(), y.data_ptr(), r.data_ptr(), reset=plan.reset[c])
+                        rres[idx.reshape(-1)] = r.reshape(S * T, 4)
+                    else:
+                        batch.process_device_resets(T, x.data_ptr(), y.data_ptr(), plan.reset[c])
                     res[idx.reshape(-1)] = y.reshape(S * T, FRAME)
                 out = res.cpu().numpy()
+                if report:
+                    rep = rres.cpu().numpy()
         finally:
             batch.set_stream(0)
     else:
         raise ValueError("mode must be 'host', 'async' or 'device'")
-    return trim(out, signals, plan, batch.delay_sample)
+    enhanced = trim(out, signals, plan, batch.delay_sample)
+    if not report:
+        return enhanced
+    return enhanced, [rep[int(o):int(o) + int(n)].copy() for o, n in zip(plan.offsets, plan.frames)]
 
 
 __all__ = ['CorpusPlan', 'plan_corpus', 'utterance_frames', 'corpus_table', 'trim', 'process_split', 'enhance_corpus']

@@ -704,6 +704,7 @@ Engine::~Engine() {
     if (h_frame_word_) (void) hipHostFree(h_frame_word_);
     if (h_in_) (void) hipHostFree(h_in_);
     if (h_out_) (void) hipHostFree(h_out_);
+    if (h_report_) (void) hipHostFree(h_report_);
     rs_ring_.release();
     recof_ring_.release();
     mg_ring_.release();
@@ -978,6 +979,20 @@ bool Engine::begin_min_gain(const Call &c, const float **table, std::string *err
         mg_valid_ = true;
     }
     *table = d_min_gain_;
+    return true;
+}
+
+// The staging of the frame report of host-pointer calls, before anything of the call is enqueued and outside any capture.
+bool Engine::report_ready(bool second_slot, std::string *err) {
+    const size_t bytes = (size_t) B_ * Tmax_ * 16;
+    if (!d_report_) d_report_ = (float *) dalloc(bytes, true);
+    if (d_report_ && !h_report_ && hipHostMalloc((void **) &h_report_, bytes, hipHostMallocDefault) != hipSuccess) h_report_ = nullptr;
+    if (second_slot && !d_report2_) d_report2_ = (float *) dalloc(bytes, true);
+    if (!d_report_ || !h_report_ || (second_slot && !d_report2_)) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the staging buffers of the frame report.";
+        return false;
+    }
     return true;
 }
 
@@ -1486,6 +1501,7 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
         sy.rs_pitch = rs_pitch;
         sy.rs_t0 = rs_t0 + t0c;
         sy.min_gain = slice.min_gain;
+        sy.report = slice.d_report ? slice.d_report + (size_t) t0c * 4 : nullptr;  // (like `out`: the slice's first frame, rows T frames apart)
         launch_synthesis(sy, st);
     };
     if (pipelined) (void) hipEventRecord(pipe_fork_, stream_);
@@ -1663,11 +1679,15 @@ bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *r
     const size_t slot = (size_t) B_ * host_chunk_ * kFrame;    // int16 elements per staging slot (the longest chunk fits)
     bool ok = true;
     auto check = [&](hipError_t e) { ok = ok && e == hipSuccess; };
+    // (the frame report, when asked for, travels beside the samples: staged per sub-chunk as [B][tc][4] in slot s of d_report_ / h_report_)
+    float *report = call.report;
+    const size_t rslot = (size_t) B_ * host_chunk_ * 4, rrow_user = (size_t) T * 16;
     auto drain_to_user = [&](int c) {  // chunk c's output: staging slot -> caller (pageable path)
         const int s = c & 1, tc = sched[c];
         check(hipEventSynchronize(ev_out_[s]));
         host_copy_2d((char *) out + (size_t) first[c] * kFrame * 2, row_user, h_out_ + s * slot, (size_t) tc * kFrame * 2,
                      (size_t) tc * kFrame * 2, B_);
+        if (report) host_copy_2d((char *) report + (size_t) first[c] * 16, rrow_user, h_report_ + s * rslot, (size_t) tc * 16, (size_t) tc * 16, B_);
     };
     for (int c = 0; c < n && ok; ++c) {
         const int s = c & 1, tc = sched[c];
@@ -1686,7 +1706,7 @@ bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *r
         // ---- kernels (d_out_ slot s was last drained by the D2H of chunk c - 2)
         check(hipStreamWaitEvent(stream_, ev_in_[s], 0));
         if (c >= 2) check(hipStreamWaitEvent(stream_, ev_out_[s], 0));
-        if (ok && !run_device({first[c], tc, d_in_ + s * slot, d_out_ + s * slot, true, resets, min_gain}, err)) {
+        if (ok && !run_device({first[c], tc, d_in_ + s * slot, d_out_ + s * slot, true, resets, min_gain, report ? d_report_ + s * rslot : nullptr}, err)) {
             // copies of earlier sub-chunks may still be writing into the caller's buffers: let them finish first
             (void) hipStreamSynchronize(copy_in_);
             (void) hipStreamSynchronize(copy_out_);
@@ -1699,9 +1719,13 @@ bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *r
         if (pinned) {
             check(hipMemcpy2DAsync((char *) out + (size_t) first[c] * kFrame * 2, row_user, d_out_ + s * slot, width, width, B_,
                                    hipMemcpyDeviceToHost, copy_out_));
+            if (report)
+                check(hipMemcpy2DAsync((char *) report + (size_t) first[c] * 16, rrow_user, d_report_ + s * rslot, (size_t) tc * 16, (size_t) tc * 16,
+                                       B_, hipMemcpyDeviceToHost, copy_out_));
         } else {
             if (c >= 2) drain_to_user(c - 2);  // frees staging slot s
             check(hipMemcpyAsync(h_out_ + s * slot, d_out_ + s * slot, width * B_, hipMemcpyDeviceToHost, copy_out_));
+            if (report) check(hipMemcpyAsync(h_report_ + s * rslot, d_report_ + s * rslot, (size_t) tc * 16 * B_, hipMemcpyDeviceToHost, copy_out_));
         }
         check(hipEventRecord(ev_out_[s], copy_out_));
     }
@@ -1781,6 +1805,10 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
         *err = "asynchronous host calls need page-locked `pcm` and `enhanced` (pv_koala_batch_host_alloc, hipHostMalloc or hipHostRegister).";
         return Status::kRuntime;
     }
+    if (c.report && pointer_kind(c.report) != kPtrPinned) {
+        *err = "asynchronous host calls need a page-locked `report` (pv_koala_batch_host_alloc, hipHostMalloc or hipHostRegister).";
+        return Status::kRuntime;
+    }
     const size_t bytes = (size_t) B_ * T * kFrame * 2;
     {
         const char *pa = (const char *) pcm, *pb = (const char *) out;
@@ -1789,6 +1817,7 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
             return Status::kRuntime;
         }
     }
+    if (c.report && !report_ready(true, err)) return Status::kRuntime;
     if (!async_ready_) {  // set only once EVERY event and both buffers exist: a partial failure is retried by the next call
         bool ok = true;
         for (int i = 0; i < 4 && ok; ++i)
@@ -1821,6 +1850,7 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
     const float *min_gain = nullptr;  // (the gains are copied into an upload slot of this call: the caller may change them now)
     if (!begin_min_gain(c, &min_gain, err)) return Status::kRuntime;
     int16_t *din = s ? d_in2_ : d_in_, *dout = s ? d_out2_ : d_out_;
+    float *drep = c.report ? (s ? d_report2_ : d_report_) : nullptr;  // (part of the call's staging slot: free when its samples' slot is)
     bool ok = true;
     if (n >= 2) ok = hipStreamWaitEvent(copy_in_, aev_done_[s], 0) == hipSuccess;  // the kernels of call n - 2 have read this slot's input
     ok = ok && hipMemcpyAsync(din, pcm, bytes, hipMemcpyHostToDevice, copy_in_) == hipSuccess;
@@ -1832,7 +1862,7 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
         (void) hipDeviceSynchronize();  // (a copy-in may have been enqueued: nothing of this call stays in flight)
         return Status::kRuntime;
     }
-    if (!run_device({0, T, din, dout, true, &table, min_gain}, err)) {
+    if (!run_device({0, T, din, dout, true, &table, min_gain, drep}, err)) {
         (void) hipDeviceSynchronize();
         return Status::kRuntime;
     }
@@ -1842,6 +1872,8 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
     // through its copy KERNEL, which took compute units from the engine's own kernels -- profiles/r05_host_async_trace.txt)
     ok = ok && hipMemcpy2DAsync(out, (size_t) T * kFrame * 2, dout, (size_t) T * kFrame * 2, (size_t) T * kFrame * 2, B_, hipMemcpyDeviceToHost,
                                 copy_out_) == hipSuccess;
+    if (drep)  // (in front of the call's completion event: the report is valid when the call has completed)
+        ok = ok && hipMemcpy2DAsync(c.report, (size_t) T * 16, drep, (size_t) T * 16, (size_t) T * 16, B_, hipMemcpyDeviceToHost, copy_out_) == hipSuccess;
     ok = ok && hipEventRecord(aev_out_[ring], copy_out_) == hipSuccess;
     if (!ok) {
         *err = hip_last_error();
@@ -1867,12 +1899,19 @@ bool Engine::run_call(const Call &c, std::string *err) {
         *err = "`pcm` and `enhanced` must both be host or both be device memory.";
         return false;
     }
+    float *report = c.report;
+    if (report && !c.host_contract && (pointer_kind(report) == kPtrDevice) != (kout == kPtrDevice)) {
+        *err = "`report` must be memory of the same kind as `enhanced`: host with host, device with device.";
+        return false;
+    }
+    if (report && kin != kPtrDevice && !report_ready(false, err)) return false;
+    const size_t rbytes = (size_t) B_ * T * 16;
     const float *min_gain = nullptr;  // (this call's attenuation limit on the device, on the handle's stream in front of everything below)
     if (!begin_min_gain(c, &min_gain, err)) return false;
     if (kin == kPtrDevice) {
         const size_t n = (size_t) B_ * T * kFrame;
         const bool overlap = pcm < out + n && out < pcm + n;
-        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table, min_gain}, err);
+        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table, min_gain, report}, err);
     }
     if (T > host_chunk_ && bytes >= host_pipeline_min_bytes_) {
         const char *pa = (const char *) pcm, *pb = (const char *) out;
@@ -1897,7 +1936,8 @@ bool Engine::run_call(const Call &c, std::string *err) {
             if (host_fork_ && hipEventRecord(host_fork_, user) == hipSuccess && hipStreamWaitEvent(own_stream_, host_fork_, 0) == hipSuccess)
                 stream_ = own_stream_;
         }
-        const bool done = process_host_pipelined(c, kin == kPtrPinned && kout == kPtrPinned, &table, min_gain, err);
+        const bool pinned = kin == kPtrPinned && kout == kPtrPinned && (!report || pointer_kind(report) == kPtrPinned);
+        const bool done = process_host_pipelined(c, pinned, &table, min_gain, err);
         stream_ = user;
         return done;
     }
@@ -1911,7 +1951,9 @@ bool Engine::run_call(const Call &c, std::string *err) {
         const int hs = hs_cur_;
         // (... and one set for the plain synthesis kernel, one for its kMinGain form: a handle that crosses between "no limit" and "some
         // limit" changes sets, a change of values only re-uploads the table, which begin_min_gain has put on the stream in front of the replay)
-        const int parity = hs | (hist_cur_ << 1) | (tail_cur_ << 2) | (min_gain ? 8 : 0);
+        // (... and the same again for calls that ask for the frame report: the kReport forms, writing into the report staging.  A handle that
+        // alternates between asking and not asking switches sets; a call without a report replays the plain graphs)
+        const int parity = hs | (hist_cur_ << 1) | (tail_cur_ << 2) | (min_gain ? 8 : 0) | (report ? 16 : 0);
         if (!frame_graph_[parity]) {
             hipGraph_t graph = nullptr;
             // (relaxed mode and one capture at a time in the process: other threads -- other handles being created, the
@@ -1925,8 +1967,10 @@ bool Engine::run_call(const Call &c, std::string *err) {
                 ok = zero_copy || hipMemcpyAsync(d_in_, h_in_, bytes, hipMemcpyHostToDevice, stream_) == hipSuccess;
                 // (no reset table in the captured frame, whichever call happens to capture it: a one-frame call can restart a stream
                 // at frame 0 only, and that is the reset kernel begin_resets has already put in front of the graph)
-                ok = ok && run_device({0, 1, zero_copy ? h_in_ : d_in_, zero_copy ? h_out_ : d_out_, true, nullptr, min_gain}, err);
+                float *rep = report ? (zero_copy ? h_report_ : d_report_) : nullptr;
+                ok = ok && run_device({0, 1, zero_copy ? h_in_ : d_in_, zero_copy ? h_out_ : d_out_, true, nullptr, min_gain, rep}, err);
                 ok = ok && (zero_copy || hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream_) == hipSuccess);
+                ok = ok && (zero_copy || !report || hipMemcpyAsync(h_report_, d_report_, rbytes, hipMemcpyDeviceToHost, stream_) == hipSuccess);
                 // zero-copy frames end with the completion word (the output is already in host memory when that node runs)
                 frame_graph_signals_[parity] = ok && zero_copy && spin_wait_ && h_frame_word_ && d_frame_count_;
                 if (frame_graph_signals_[parity]) launch_frame_done(d_frame_count_, h_frame_word_, stream_);
@@ -1986,14 +2030,17 @@ bool Engine::run_call(const Call &c, std::string *err) {
                 goto fail;
             }
             memcpy(out, h_out_, bytes);
+            if (report) memcpy(report, h_report_, rbytes);  // (written by the synthesis kernel in front of the completion word)
             return true;
         }
     }
     if (hipMemcpyAsync(d_in_, h_in_, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) goto fail;
-    if (!run_device({0, T, d_in_, d_out_, true, &table, min_gain}, err)) return false;
+    if (!run_device({0, T, d_in_, d_out_, true, &table, min_gain, report ? d_report_ : nullptr}, err)) return false;
     if (hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
+    if (report && hipMemcpyAsync(h_report_, d_report_, rbytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
     if (hipStreamSynchronize(stream_) != hipSuccess) goto fail;
     memcpy(out, h_out_, bytes);
+    if (report) memcpy(report, h_report_, rbytes);
     return true;
 fail:
     *err = hip_last_error();

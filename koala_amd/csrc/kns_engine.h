@@ -51,6 +51,11 @@ struct Call {
     // owner counts its changes).  nullptr: every gain is 0, the plain call -- same route, same kernels, same bits.
     const float *min_gain = nullptr;
     unsigned min_gain_rev = 0;
+    // Frame report: float [num_streams][T][4], memory of the same kind as `out` (host with host, device with device; process_host_async:
+    // page-locked).  Row [b][t] = e_in, e_out, mask_sum, 0 of stream b's frame t (three sums the synthesis kernel
+    // forms in a fixed order); complete when `out` is.  An output only: the streams' evolution and `out` do not depend on whether it was asked
+    // for.  Held streams' rows are unspecified.  nullptr: the plain call -- same route, same kernels, same bits.
+    float *report = nullptr;
 };
 
 // kBadArgument: a stream list, a record or a combination of Call members that the engine refused before it touched anything (the C ABI
@@ -114,6 +119,7 @@ private:
         bool allow_recompute;  // the synthesis kernel may rebuild the spectrum from d_pcm (false: d_out overlaps it)
         ResetTable *resets;
         const float *min_gain;  // the call's per-stream minimum gains on the device [Bpad] (begin_min_gain), nullptr: no limit in force
+        float *d_report = nullptr;  // the slice's frame report [B][T][4] (device-visible memory, rows T frames apart), nullptr: not asked for
     };
     bool run_device(const Slice &s, std::string *err);
     void *dalloc(size_t bytes, bool zero);
@@ -198,13 +204,14 @@ private:
     size_t host_pipeline_min_bytes_ = 0;
 
     // hipGraph of one host-pointer frame (copy-in, 23 kernels, copy-out); built on first use
-    hipGraphExec_t frame_graph_[16] = {};  // one per combination of the hidden-state / history / tail ping-pong indices, and (bit 3) of
-                                           // "an attenuation limit is in force": the captured synthesis kernel is the plain or the kMinGain form
+    hipGraphExec_t frame_graph_[32] = {};  // one per combination of the hidden-state / history / tail ping-pong indices, (bit 3) of
+                                           // "an attenuation limit is in force": the captured synthesis kernel is the plain or the kMinGain form,
+                                           // and (bit 4) of "a frame report is asked for": the kReport forms, writing to the report staging
     // completion word of the zero-copy one-frame replays (kns_stft.hip, frame_done_kernel): the host spins on a word in page-locked
     // memory instead of sleeping in hipStreamSynchronize, whose wake-up is what made p99 drift away from p50 on a busy host
     unsigned *d_frame_count_ = nullptr, *h_frame_word_ = nullptr;
     unsigned frame_seq_ = 0;
-    bool frame_graph_signals_[16] = {};
+    bool frame_graph_signals_[32] = {};
     bool spin_wait_ = true;
     bool use_graph_ = true, no_small_ = false, no_zero_copy_ = false, no_recompute_ = false, debug_taps_ = false;
     // developer switches (all read once in init() through dev_env(): compiled out of the product library)
@@ -259,6 +266,11 @@ private:
     unsigned mg_rev_ = 0;
     bool mg_valid_ = false;
     bool begin_min_gain(const Call &c, const float **table, std::string *err);
+    // Frame report (Call::report) of host-pointer calls: device and page-locked host staging [B][Tmax][4] each, used like d_out_ / h_out_ (two
+    // slots of [B][host_chunk_][4] by the sub-chunked calls; the one-frame graph writes into h_report_ or copies to it); d_report2_: the second
+    // slot of asynchronous host calls.  Allocated by the first call that asks for a report.
+    float *d_report_ = nullptr, *h_report_ = nullptr, *d_report2_ = nullptr;
+    bool report_ready(bool second_slot, std::string *err);
     bool state_ready(std::string *err);
     Status state_list(int count, const int32_t *streams, std::string *err);  // checks the list, uploads its inverse table
     StateArgs state_args() const;

@@ -95,6 +95,10 @@ struct SynthesisArgs {
     // optional: per-stream minimum mask gain, float [Bpad] in [0, 1] (rows past B: 0).  Row b's mask value m becomes g_b + (1 - g_b) m, two
     // roundings, in all 257 bins, before Y = mask . X.  Selects the kernels' kMinGain arm (a null pointer: today's instantiations)
     const float *min_gain = nullptr;
+    // optional: the frame report, float [B][T][4] in the caller's layout (e_in, e_out, mask_sum, 0 of every emitted
+    // frame).  Points at the slice's first frame like `out`, rows `pitch` frames apart (0: T).  Selects the kernels' kReport arm (a null
+    // pointer: today's instantiations)
+    float *report = nullptr;
 };
 void launch_synthesis(const SynthesisArgs &a, hipStream_t s);
 

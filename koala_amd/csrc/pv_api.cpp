@@ -435,6 +435,18 @@ PV_API pv_status_t pv_koala_process(pv_koala_t *object, const int16_t *pcm, int1
     return advance(object->engine, object->limit, {1, pcm, enhanced_pcm, nullptr, nullptr, /*host_contract=*/true});
 }
 
+PV_API pv_status_t pv_koala_process_report(pv_koala_t *object, const int16_t *pcm, int16_t *enhanced_pcm, float report[4]) {
+    t_stack.clear();
+    if (!object) return check_object(object);
+    if (!pcm || !enhanced_pcm || !report) {
+        push_error(0x64, "Argument `%s` is NULL.", !pcm ? "pcm" : !enhanced_pcm ? "enhanced_pcm" : "report");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    kns::Call call{1, pcm, enhanced_pcm, nullptr, nullptr, /*host_contract=*/true};
+    call.report = report;
+    return advance(object->engine, object->limit, call);
+}
+
 PV_API pv_status_t pv_koala_reset(pv_koala_t *object) {
     t_stack.clear();
     if (!object) return PV_STATUS_INVALID_ARGUMENT;  // the reference leaves no message for this one
@@ -551,6 +563,28 @@ PV_API pv_status_t pv_koala_batch_process_chunk_hold(pv_koala_batch_t *object, i
     const pv_status_t st = check_call(object, num_frames, pcm, enhanced);
     if (st != PV_STATUS_SUCCESS) return st;
     return advance(object->engine, object->limit, {num_frames, pcm, enhanced, nullptr, hold});
+}
+
+// ---- one extensible entry point (the frame report rides on it)
+
+PV_API pv_status_t pv_koala_batch_process_call(pv_koala_batch_t *object, const pv_koala_batch_call_t *call) {
+    t_stack.clear();
+    if (!object) return check_object(object);
+    if (!call) {
+        push_error(0x64, "Argument `call` is NULL.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (call->struct_size != (int32_t) sizeof(pv_koala_batch_call_t)) {
+        push_error(0x66, "`struct_size` %d is not sizeof(pv_koala_batch_call_t) = %d.", call->struct_size, (int) sizeof(pv_koala_batch_call_t));
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    pv_status_t st = check_call(object, call->num_frames, call->pcm, call->enhanced);
+    if (st == PV_STATUS_SUCCESS) st = check_resets(object, call->num_frames, call->reset);
+    if (st != PV_STATUS_SUCCESS) return st;
+    kns::Call c{call->num_frames, call->pcm, call->enhanced, call->reset, call->hold};
+    c.report = call->report;
+    // (hold with reset, hold with asynchronous: refused by the engine before it touches anything, as for the dedicated entry points)
+    return advance(object->engine, object->limit, c, call->asynchronous != 0);
 }
 
 // ---- attenuation limit

@@ -67,6 +67,8 @@ def main(argv=None):
     ap.add_argument('--realtime', action='store_true', help='pace a replayed file at 16 ms per frame, like a recorder')
     ap.add_argument('--attenuation_limit_db', type=float, default=None,
                     help='suppress by at most this many dB (0: bypass with unchanged latency; default: unlimited)')
+    ap.add_argument('--meter', type=int, default=0, metavar='N',
+                    help='every N frames print input level (dBFS), suppression (dB) and mean mask gain, from the frame report')
     ap.add_argument('--show_devices', action='store_true')
     args = ap.parse_args(argv)
 
@@ -91,6 +93,7 @@ def main(argv=None):
               else frames_from_raw(sys.stdin.buffer, n))
     lat = []
     frames = 0
+    meter = []  # report rows since the last printed line
     t_start = time.perf_counter()
     try:
         with contextlib.ExitStack() as stack:
@@ -110,8 +113,21 @@ def main(argv=None):
                     if due > now:
                         time.sleep(due - now)
                 t0 = time.perf_counter()
-                enhanced = koala.process(frame)
+                if args.meter > 0:
+                    enhanced, row = koala.process_with_report(frame)
+                else:
+                    enhanced = koala.process(frame)
                 lat.append(time.perf_counter() - t0)
+                if args.meter > 0:
+                    meter.append(row)
+                    if len(meter) == args.meter:
+                        from koala_amd import report
+                        total = np.sum(np.array(meter, np.float64), axis=0)  # (energies and mask sums add up over the N frames)
+                        total[2] /= len(meter)
+                        print('frame %6d  in %7.1f dBFS  suppression %6.1f dB  mean gain %.3f' %
+                              (frames + 1, report.input_dbfs(total / [len(meter), len(meter), 1, 1]), report.suppression_db(total),
+                               report.mean_gain(total)))
+                        meter = []
                 out.writeframes(struct.pack('%dh' % n, *enhanced))
                 if ref is not None:
                     ref.writeframes(struct.pack('%dh' % n, *[int(v) for v in frame]))
