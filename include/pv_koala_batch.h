@@ -32,6 +32,25 @@ PV_API pv_status_t pv_koala_batch_init(const char *access_key, const char *model
                                        pv_koala_precision_t precision, pv_koala_batch_t **object);
 PV_API void pv_koala_batch_delete(pv_koala_batch_t *object);
 
+/* A batch handle at a SAMPLE RATE of 8 000, 16 000, 32 000 or 48 000 Hz, fixed at creation (any other value: PV_STATUS_INVALID_ARGUMENT).
+ * 16 000 is pv_koala_batch_init's handle: same routes, launches, samples and stream records.  At the other rates a call converts the
+ * streams to 16 kHz on the device, runs the 16 kHz call unchanged and converts the enhanced samples back (third
+ * extension: a 48 R + 1 tap windowed-sinc low-pass, R = 2 or 3, evaluated in a fixed order; the converters' per-stream state lives in
+ * the handle, takes part in every kind of reset and in held streams, and travels in the stream record, which is version 2 then).
+ *   - a frame is pv_koala_batch_frame_length() = sample_rate * 256 / 16000 samples (128 / 256 / 512 / 768: 16 ms at every rate), and every
+ *     entry point that advances streams takes [num_streams][num_frames * frame_length] (process, process_chunk, _resets, _hold,
+ *     process_call with its frame report, whose rows are those of the inner 16 kHz stream, one per frame);
+ *   - pv_koala_batch_delay_sample() is 176 / 256 / 608 / 912 samples at the handle's rate: the engine's frame and both converters;
+ *   - host pointers: one copy in, the device route, one copy out, then synchronise; `pcm` and `enhanced` may overlap in any way, with
+ *     host and with device pointers (the input is consumed before the output is written);
+ *   - the asynchronous entry points, and `asynchronous != 0` in pv_koala_batch_process_call, are refused with PV_STATUS_INVALID_ARGUMENT on
+ *     a handle whose rate is not 16 000 (nothing processed). */
+PV_API pv_status_t pv_koala_batch_init_rate(const char *access_key, const char *model_path, const char *device,
+                                            int32_t num_streams, int32_t max_frames_per_call,
+                                            pv_koala_precision_t precision, int32_t sample_rate, pv_koala_batch_t **object);
+PV_API pv_status_t pv_koala_batch_sample_rate(const pv_koala_batch_t *object, int32_t *sample_rate);
+PV_API pv_status_t pv_koala_batch_frame_length(const pv_koala_batch_t *object, int32_t *frame_length);
+
 /* One frame per stream: pcm and enhanced are [num_streams][256] row-major int16.  Pointers may be host memory
  * (staged through pinned buffers, call returns when `enhanced` is filled) or device memory on the handle's GPU
  * (kernels are enqueued on the handle's stream and the call returns without synchronising). */

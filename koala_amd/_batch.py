@@ -26,13 +26,18 @@ class BatchCall(Structure):
 
 class KoalaBatch(object):
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
-                 max_frames_per_call: int = 1, precision: str = 'fp32') -> None:
+                 max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000) -> None:
+        """`sample_rate`: 8000, 16000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
+        array of samples is [num_streams, T * frame_length] with frame_length = sample_rate * 256 / 16000; at a rate other than 16000 the
+        handle converts on the device, `delay_sample` includes both converters, and the asynchronous calls are refused."""
         if not isinstance(access_key, str) or len(access_key) == 0:
             raise KoalaInvalidArgumentError("`access_key` should be a non-empty string.")
         if not os.path.exists(model_path):
             raise KoalaIOError("Could not find model file at `%s`." % model_path)
         if precision not in ('fp32', 'bf16'):
             raise KoalaInvalidArgumentError("`precision` should be `fp32` or `bf16`.")
+        if sample_rate not in (8000, 16000, 32000, 48000):
+            raise KoalaInvalidArgumentError("`sample_rate` should be 8000, 16000, 32000 or 48000.")
         lib = load_library(library_path)
         lib.pv_set_sdk(b'python')
         self._lib = lib
@@ -67,9 +72,15 @@ class KoalaBatch(object):
         lib.pv_koala_batch_debug_read.restype = c_int64
 
         self._handle = c_void_p()
-        status = lib.pv_koala_batch_init(access_key.encode(), model_path.encode(), device.encode(), num_streams,
-                                         max_frames_per_call, PRECISION_BF16 if precision == 'bf16' else PRECISION_FP32,
-                                         byref(self._handle))
+        prec = PRECISION_BF16 if precision == 'bf16' else PRECISION_FP32
+        if sample_rate == 16000:
+            status = lib.pv_koala_batch_init(access_key.encode(), model_path.encode(), device.encode(), num_streams, max_frames_per_call,
+                                             prec, byref(self._handle))
+        else:
+            lib.pv_koala_batch_init_rate.argtypes = [c_char_p, c_char_p, c_char_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)]
+            lib.pv_koala_batch_init_rate.restype = PicovoiceStatuses
+            status = lib.pv_koala_batch_init_rate(access_key.encode(), model_path.encode(), device.encode(), num_streams,
+                                                  max_frames_per_call, prec, sample_rate, byref(self._handle))
         if status is not PicovoiceStatuses.SUCCESS:
             raise_status(lib, status, 'Initialization failed')
         self.num_streams = num_streams
@@ -78,6 +89,13 @@ class KoalaBatch(object):
         self.frame_length = lib.pv_koala_frame_length()
         self.sample_rate = lib.pv_sample_rate()
         d = c_int32()
+        if sample_rate != 16000:
+            for name in ('sample_rate', 'frame_length'):
+                fn = getattr(lib, 'pv_koala_batch_' + name)
+                fn.argtypes = [c_void_p, POINTER(c_int32)]
+                fn.restype = PicovoiceStatuses
+                self._check(fn(self._handle, byref(d)), 'Failed to get the ' + name)
+                setattr(self, name, d.value)
         self._check(lib.pv_koala_batch_delay_sample(self._handle, byref(d)), 'Failed to get delay samples')
         self.delay_sample = d.value
         self._check(lib.pv_koala_batch_state_size(self._handle, byref(d)), 'Failed to get the state size')
@@ -88,7 +106,7 @@ class KoalaBatch(object):
             raise_status(self._lib, status, what)
 
     def process(self, pcm: np.ndarray) -> np.ndarray:
-        """pcm: int16 [num_streams, T*256] in host memory -> enhanced, same shape (synchronous)."""
+        """pcm: int16 [num_streams, T*frame_length] in host memory -> enhanced, same shape (synchronous)."""
         a = np.ascontiguousarray(pcm, dtype=np.int16)
         if a.ndim != 2 or a.shape[0] != self.num_streams or a.shape[1] % self.frame_length:
             raise KoalaInvalidArgumentError("expected int16 array of shape [%d, T*%d]" % (self.num_streams, self.frame_length))
@@ -98,7 +116,7 @@ class KoalaBatch(object):
         return out
 
     def alloc_host(self, num_frames: int) -> np.ndarray:
-        """int16 [num_streams, num_frames*256] in page-locked host memory (freed by `delete()`): `process()` on such arrays
+        """int16 [num_streams, num_frames*frame_length] in page-locked host memory (freed by `delete()`): `process()` on such arrays
         lets the GPU's copy engines move the audio directly instead of through a staging copy."""
         n = self.num_streams * num_frames * self.frame_length
         p = c_void_p()
@@ -135,7 +153,7 @@ class KoalaBatch(object):
         self._check(self._lib.pv_koala_batch_async_wait(self._handle, max_in_flight), 'wait failed')
 
     def process_device(self, num_frames: int, pcm_ptr: int, enhanced_ptr: int) -> None:
-        """Device pointers (e.g. torch_tensor.data_ptr()) of int16 [num_streams, num_frames*256]; asynchronous."""
+        """Device pointers (e.g. torch_tensor.data_ptr()) of int16 [num_streams, num_frames*frame_length]; asynchronous."""
         self._check(self._lib.pv_koala_batch_process_chunk(self._handle, num_frames, c_void_p(pcm_ptr),
                                                            c_void_p(enhanced_ptr)), 'Processing failed')
 

@@ -34,8 +34,9 @@ def create_batch(
         precision: str = 'fp32',
         model_path: Optional[str] = None,
         device: Optional[str] = None,
-        library_path: Optional[str] = None) -> KoalaBatch:
-    """`num_streams` independent streams advancing together on one GPU (see KoalaBatch)."""
+        library_path: Optional[str] = None,
+        sample_rate: int = 16000) -> KoalaBatch:
+    """`num_streams` independent streams advancing together on one GPU (see KoalaBatch), at 8000, 16000, 32000 or 48000 Hz."""
     return KoalaBatch(
         access_key=access_key,
         model_path=default_model_path() if model_path is None else model_path,
@@ -43,7 +44,8 @@ def create_batch(
         library_path=default_library_path() if library_path is None else library_path,
         num_streams=num_streams,
         max_frames_per_call=max_frames_per_call,
-        precision=precision)
+        precision=precision,
+        sample_rate=sample_rate)
 
 
 def available_devices(library_path: Optional[str] = None) -> Sequence[str]:

@@ -296,6 +296,29 @@ std::string hip_error(hipError_t e) { return std::string("HIP error: ") + hipGet
 std::string hip_last_error() { return hip_error(hipGetLastError()); }
 }  // namespace
 
+// The prototype low-pass of the sample-rate stages (third extension), in double, rounded once into the two tables.
+static void rs_prototype(int R, std::vector<float> *hd, std::vector<float> *hi) {
+    const int L = 2 * kRsHalf * R + 1, c = kRsHalf * R;
+    const double pi = 3.141592653589793;
+    std::vector<double> g0((size_t) L);
+    double sum = 0.0;
+    for (int i = 0; i < L; ++i) {
+        const double x = 0.94 * (i - c) / R, px = pi * x;
+        const double sinc = i == c ? 1.0 : sin(px) / px;
+        const double w = 0.35875 - 0.48829 * cos(2.0 * pi * i / (L - 1)) + 0.14128 * cos(4.0 * pi * i / (L - 1)) -
+                         0.01168 * cos(6.0 * pi * i / (L - 1));
+        g0[i] = sinc * w;
+        sum += g0[i];
+    }
+    hd->assign((size_t) kRsMaxTaps, 0.0f);
+    hi->assign((size_t) kRsMaxTaps, 0.0f);
+    for (int i = 0; i < L; ++i) {
+        const double g = g0[i] / sum;
+        (*hd)[i] = (float) g;
+        (*hi)[i] = (float) (R * g);
+    }
+}
+
 void *Engine::dalloc(size_t bytes, bool zero) {
     void *p = nullptr;
     if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) {
@@ -497,6 +520,11 @@ bool Engine::init(const Params &p, int device, int B, int Tmax, int precision, s
     nbf_ = ceil_div(kBins, pi_.kb);
     nbh_ = ceil_div(kHidden, pi_.kb);
     taps_ = p.front_taps;
+    if (!rs_rate_ok(p.sample_rate)) {
+        *err = "sample rate " + std::to_string(p.sample_rate) + " is not one of 8000, 16000, 32000, 48000.";
+        return false;
+    }
+    rate_ = p.sample_rate;
     fold_ = precision == kBf16 && taps_ == 1;  // the front-end rides in the stage-input GEMMs (see the packing below)
     if (hipStreamCreateWithFlags(&own_stream_, hipStreamNonBlocking) != hipSuccess) {
         (void) hipGetLastError();
@@ -608,6 +636,13 @@ bool Engine::init(const Params &p, int device, int B, int Tmax, int precision, s
     d_hstate_[1] = (float *) dalloc((size_t) kGruLayers * mtb * kUnitTiles * 1024, true);
     d_hprev_ = dalloc((size_t) kGruLayers * mtb * nbh_ * 1024, true);  // the state in operand form (wavefront calls, frame 0)
     d_rmask_ = (uint8_t *) dalloc((size_t) Bpad_, true);
+    if (rate_ != kRate16k) {  // the sample-rate stages: their tables and per-stream state (zeros: a fresh stream)
+        rs_prototype(rs_ratio(rate_), &rs_hd_, &rs_hi_);
+        for (int c = 0; c < 2; ++c) {
+            d_rs_state_[0][c] = (int16_t *) dalloc((size_t) Bpad_ * rs_in_hist(rate_) * 2, true);
+            d_rs_state_[1][c] = (int16_t *) dalloc((size_t) Bpad_ * rs_out_hist(rate_) * 2, true);
+        }
+    }
 
     // ---- activation workspace
     const size_t M = mtb * (size_t) Tmax_;  // m-tiles per call
@@ -706,6 +741,7 @@ Engine::~Engine() {
     if (h_out_) (void) hipHostFree(h_out_);
     if (h_report_) (void) hipHostFree(h_report_);
     rs_ring_.release();
+    rsf_ring_.release();
     recof_ring_.release();
     mg_ring_.release();
     for (int i = 0; i < 4; ++i)
@@ -833,6 +869,10 @@ bool Engine::reset(const uint8_t *host_mask, std::string *err) {
         r.mask = d_rmask_;
     }
     launch_reset(r, stream_);
+    if (rate_ != kRate16k) {
+        launch_resample_reset(d_rs_state_[0][0], d_rs_state_[0][1], rs_in_hist(rate_), r.mask, Bpad_, stream_);
+        launch_resample_reset(d_rs_state_[1][0], d_rs_state_[1][1], rs_out_hist(rate_), r.mask, Bpad_, stream_);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         *err = hip_error(e);
@@ -1793,6 +1833,10 @@ bool Engine::async_wait(int max_in_flight, std::string *err) {
 // once call n - 2's copy-out has -- both waited for on the device, by the stream that needs it.  A synchronous call of that size cannot
 // hide its first copy-in and last copy-out and has to cut its kernels into short, less efficient sub-chunks (process_host_pipelined).
 Status Engine::process_host_async(const Call &c, std::string *err) {
+    if (rate_ != kRate16k) {
+        *err = "asynchronous calls are not available on a handle whose sample rate is not 16000.";
+        return Status::kBadArgument;
+    }
     if (c.hold) {
         *err = "asynchronous host calls take no held streams.";
         return Status::kBadArgument;
@@ -2047,13 +2091,116 @@ fail:
     return false;
 }
 
+// ------------------------------------------------------------------------------------------------ handles that are not at 16 kHz
+
+bool Engine::rate_ready(bool host_staging, bool reset_flags, std::string *err) {
+    if (host_staging && !d_rate_io_) {
+        d_rate_io_ = (int16_t *) dalloc((size_t) B_ * Tmax_ * rs_frame_length(rate_) * 2, false);
+        if (!d_rate_io_) {
+            (void) hipGetLastError();
+            *err = "Failed to allocate the staging buffer of host-memory calls.";
+            return false;
+        }
+    }
+    if (reset_flags && !d_rs_flags_) {
+        uint8_t *d = rsf_ring_.ready((size_t) B_ * Tmax_) ? (uint8_t *) dalloc((size_t) B_ * Tmax_, false) : nullptr;
+        if (!d) {
+            (void) hipGetLastError();
+            *err = "Failed to allocate the buffers of per-frame stream resets.";
+            return false;
+        }
+        d_rs_flags_ = d;
+    }
+    return true;
+}
+
+// A call of a handle at 8, 32 or 48 kHz (third extension): the in-stage kernel takes the caller's samples to 16 kHz
+// (into d_in_), the call runs unchanged as a device-pointer call from d_in_ to d_out_ -- its resets, attenuation limit and frame report
+// with it -- and the out-stage kernel takes the enhanced samples to the caller's rate.  Everything is enqueued on the handle's stream.
+// Host pointers: one copy in, this route, one copy out, then synchronise (no sub-chunks, no one-frame graph).  The in-stage has read all
+// of `pcm` before the out-stage writes `out`, so the two may overlap in any way.  The call's per-frame resets go to the device as they
+// are (uint8 [B][T]): both stages read everything in front of a reset block as zero.
+bool Engine::run_call_rate(const Call &c, std::string *err) {
+    const int T = c.T, FL = rs_frame_length(rate_), R = rs_ratio(rate_);
+    (void) hipSetDevice(device_);
+    const PointerKind kin = pointer_kind(c.pcm), kout = pointer_kind(c.out);
+    if ((kin == kPtrDevice) != (kout == kPtrDevice)) {
+        *err = "`pcm` and `enhanced` must both be host or both be device memory.";
+        return false;
+    }
+    const bool host = kin != kPtrDevice;
+    if (c.report && (pointer_kind(c.report) == kPtrDevice) == host) {
+        *err = "`report` must be memory of the same kind as `enhanced`: host with host, device with device.";
+        return false;
+    }
+    bool any = false, late = false;
+    for (int b = 0; c.resets && b < B_ && !late; ++b)
+        for (int t = 0; t < T; ++t)
+            if (c.resets[(size_t) b * T + t]) any = true, late = late || t > 0;
+    if (late && taps_ > 1) {  // (refused in front of the in-stage: a refused call advances nothing)
+        *err = "per-frame stream resets after frame 0 are not supported for models with a several-frame front-end (front_taps > 1).";
+        return false;
+    }
+    if (!rate_ready(host, any, err)) return false;
+    if (host && c.report && !report_ready(false, err)) return false;
+    const size_t bytes = (size_t) B_ * T * FL * 2, rbytes = (size_t) B_ * T * 16;
+    const int16_t *src = c.pcm;
+    int16_t *dst = c.out;
+    if (host) {
+        if (hipMemcpyAsync(d_rate_io_, c.pcm, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) goto fail;
+        src = dst = d_rate_io_;
+    }
+    {
+        const uint8_t *flags = nullptr;
+        if (any) {
+            const int k = rsf_ring_.acquire();
+            if (k < 0) goto fail;
+            memcpy(rsf_ring_.host[k], c.resets, (size_t) B_ * T);
+            if (hipMemcpyAsync(d_rs_flags_, rsf_ring_.host[k], (size_t) B_ * T, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+                !rsf_ring_.uploaded(k, stream_))
+                goto fail;
+            flags = d_rs_flags_;
+        }
+        ResampleArgs a;
+        a.B = B_, a.T = T, a.R = R, a.resets = flags;
+        a.n_low = rate_ < kRate16k ? FL : kFrame;
+        a.in = src, a.out = d_in_;
+        a.state = d_rs_state_[0][rs_cur_], a.state_next = d_rs_state_[0][rs_cur_ ^ 1];
+        a.interpolate = rate_ < kRate16k;
+        memcpy(a.taps, (a.interpolate ? rs_hi_ : rs_hd_).data(), sizeof(a.taps));
+        launch_resample(a, stream_);
+        if (hipGetLastError() != hipSuccess) goto fail;
+        Call inner{T, d_in_, d_out_, c.resets};
+        inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
+        inner.report = host && c.report ? d_report_ : c.report;
+        if (!run_call(inner, err)) return false;
+        a.in = d_out_, a.out = dst;
+        a.state = d_rs_state_[1][rs_cur_], a.state_next = d_rs_state_[1][rs_cur_ ^ 1];
+        a.interpolate = !a.interpolate;
+        memcpy(a.taps, (a.interpolate ? rs_hi_ : rs_hd_).data(), sizeof(a.taps));
+        launch_resample(a, stream_);
+        if (hipGetLastError() != hipSuccess) goto fail;
+        rs_cur_ ^= 1;
+    }
+    if (host) {
+        if (hipMemcpyAsync(c.out, d_rate_io_, bytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
+        if (c.report && hipMemcpyAsync(c.report, d_report_, rbytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
+        if (hipStreamSynchronize(stream_) != hipSuccess) goto fail;
+    }
+    return true;
+fail:
+    *err = hip_last_error();
+    return false;
+}
+
 // ------------------------------------------------------------------------------------------------ stream records
 
 namespace {
 struct StateHeader {  // the first 32 bytes of a record (kns_kernels.h)
     uint32_t magic, version, front_taps, precision;
     uint64_t model;
-    uint64_t reserved;
+    uint32_t sample_rate;  // version 2 (handles that are not at 16 kHz); version 1: reserved, zero
+    uint32_t reserved;
 };
 static_assert(sizeof(StateHeader) == kStateHeaderBytes, "record header");
 }  // namespace
@@ -2061,8 +2208,11 @@ static_assert(sizeof(StateHeader) == kStateHeaderBytes, "record header");
 bool Engine::state_ready(std::string *err) {
     if (d_state_) return true;
     (void) hipSetDevice(device_);
-    uint8_t *d = (uint8_t *) dalloc((size_t) B_ * state_bytes(), false);
+    // (the records' version-1 part and the sample-rate stages' part are staged apart: the state kernels see the records they always saw)
+    uint8_t *d = (uint8_t *) dalloc((size_t) B_ * state_record_bytes(taps_), false);
     int32_t *t = d ? (int32_t *) dalloc((size_t) Bpad_ * 4, false) : nullptr;
+    if (t && rate_ != kRate16k && !d_state_rs_) d_state_rs_ = (uint8_t *) dalloc((size_t) B_ * rs_record_bytes(rate_), false);
+    if (rate_ != kRate16k && !d_state_rs_) t = nullptr;
     if (!d || !t || !recof_ring_.ready((size_t) Bpad_ * 4)) {
         // (what was allocated stays on the handle's lists and goes with the handle; the next call tries the rest again)
         (void) hipGetLastError();
@@ -2114,10 +2264,11 @@ StateArgs Engine::state_args() const {
     a.fhist = d_fhist_;
     a.rec_of = d_recof_;
     a.records = d_state_;
-    const StateHeader h{kStateMagic, kStateVersion, (uint32_t) taps_, (uint32_t) prec_, model_key_, 0};
+    const StateHeader h{kStateMagic, rate_ == kRate16k ? kStateVersion : kStateVersionRate, (uint32_t) taps_, (uint32_t) prec_, model_key_,
+                        rate_ == kRate16k ? 0u : (uint32_t) rate_, 0};
     memcpy(&a.hdr0, &h, 16);
     memcpy(&a.hdr1, (const char *) &h + 16, 16);
-    a.state_bytes = (uint32_t) state_bytes();
+    a.state_bytes = (uint32_t) state_record_bytes(taps_);
     a.Bpad = Bpad_;
     a.nbf = nbf_;
     a.precision = prec_;
@@ -2125,14 +2276,33 @@ StateArgs Engine::state_args() const {
     return a;
 }
 
+void Engine::launch_states(bool import) {
+    if (import) launch_state_import(state_args(), stream_);
+    else launch_state_export(state_args(), stream_);
+    if (rate_ == kRate16k) return;
+    ResampleStateArgs a;
+    for (int c = 0; c < 2; ++c) a.state_in[c] = d_rs_state_[0][rs_cur_ ^ c], a.state_out[c] = d_rs_state_[1][rs_cur_ ^ c];
+    a.hist_in = rs_in_hist(rate_), a.hist_out = rs_out_hist(rate_);
+    a.rec_of = d_recof_;
+    a.records = d_state_rs_;
+    a.rec_bytes = (uint32_t) rs_record_bytes(rate_);
+    a.Bpad = Bpad_;
+    a.import = import ? 1 : 0;
+    launch_resample_state(a, stream_);
+}
+
 Status Engine::export_state(int count, const int32_t *streams, void *host_records, std::string *err) {
     (void) hipSetDevice(device_);
     if (async_n_ && !drain_async(err)) return Status::kRuntime;
     const Status listed = state_list(count, streams, err);
     if (listed != Status::kOk) return listed;
-    launch_state_export(state_args(), stream_);
+    launch_states(false);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(host_records, d_state_, (size_t) count * state_bytes(), hipMemcpyDeviceToHost, stream_);
+    const size_t S = state_bytes(), S1 = state_record_bytes(taps_);
+    if (e == hipSuccess && S == S1) e = hipMemcpyAsync(host_records, d_state_, (size_t) count * S, hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess && S > S1) e = hipMemcpy2DAsync(host_records, S, d_state_, S1, S1, (size_t) count, hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess && S > S1)
+        e = hipMemcpy2DAsync((char *) host_records + S1, S, d_state_rs_, S - S1, S - S1, (size_t) count, hipMemcpyDeviceToHost, stream_);
     if (e == hipSuccess) e = hipStreamSynchronize(stream_);
     if (e != hipSuccess) {
         (void) hipGetLastError();
@@ -2146,19 +2316,22 @@ Status Engine::import_state(int count, const int32_t *streams, const void *host_
     (void) hipSetDevice(device_);
     if (async_n_ && !drain_async(err)) return Status::kRuntime;
     // every header before anything is written (the list is checked by state_list, which writes only the table)
-    const size_t S = state_bytes();
+    const size_t S = state_bytes(), S1 = state_record_bytes(taps_);
+    const uint32_t want_version = rate_ == kRate16k ? kStateVersion : kStateVersionRate;
     for (int i = 0; i < count && count <= B_; ++i) {
         StateHeader h;
         memcpy(&h, (const char *) host_records + (size_t) i * S, sizeof(h));
         std::string what;
         if (h.magic != kStateMagic) what = "magic is not `KNSS`";
-        else if (h.version != kStateVersion) what = "version " + std::to_string(h.version) + " is not " + std::to_string(kStateVersion);
+        else if (h.version != want_version) what = "version " + std::to_string(h.version) + " is not " + std::to_string(want_version);
         else if (h.front_taps != (uint32_t) taps_)
             what = "front_taps " + std::to_string(h.front_taps) + " does not match the handle's model (" + std::to_string(taps_) + ")";
         else if (h.precision != (uint32_t) prec_)
             what = std::string("precision is ") + (h.precision == kBf16 ? "bf16" : h.precision == kFp32 ? "fp32" : "unknown") +
                    ", the handle's is " + (prec_ == kBf16 ? "bf16" : "fp32") + " (records do not cross precisions)";
         else if (h.model != model_key_) what = "model hash does not match the handle's model";
+        else if (rate_ != kRate16k && h.sample_rate != (uint32_t) rate_)
+            what = "sample_rate " + std::to_string(h.sample_rate) + " is not the handle's (" + std::to_string(rate_) + ")";
         if (!what.empty()) {
             *err = "record " + std::to_string(i) + ": " + what + ".";
             return Status::kBadArgument;
@@ -2166,9 +2339,13 @@ Status Engine::import_state(int count, const int32_t *streams, const void *host_
     }
     const Status listed = state_list(count, streams, err);
     if (listed != Status::kOk) return listed;
-    hipError_t e = hipMemcpyAsync(d_state_, host_records, (size_t) count * S, hipMemcpyHostToDevice, stream_);
+    // (a version-2 record interleaves the two staged parts)
+    hipError_t e = S == S1 ? hipMemcpyAsync(d_state_, host_records, (size_t) count * S, hipMemcpyHostToDevice, stream_)
+                           : hipMemcpy2DAsync(d_state_, S1, host_records, S, S1, (size_t) count, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && S > S1)
+        e = hipMemcpy2DAsync(d_state_rs_, S - S1, (const char *) host_records + S1, S, S - S1, (size_t) count, hipMemcpyHostToDevice, stream_);
     if (e == hipSuccess) {
-        launch_state_import(state_args(), stream_);
+        launch_states(true);
         e = hipGetLastError();
     }
     // (the copy may read pageable records when it runs, not when it is enqueued: the call returns once the stream has passed it)
@@ -2192,19 +2369,19 @@ Status Engine::process(const Call &c, std::string *err) {
     std::vector<int32_t> held;
     for (int b = 0; c.hold && b < B_; ++b)
         if (c.hold[b]) held.push_back(b);
-    if (held.empty()) return run_call(c, err) ? Status::kOk : Status::kRuntime;
+    if (held.empty()) return advance(c, err) ? Status::kOk : Status::kRuntime;
     (void) hipSetDevice(device_);
     if (async_n_ && !drain_async(err)) return Status::kRuntime;
     const Status listed = state_list((int) held.size(), held.data(), err);
     if (listed != Status::kOk) return listed;
-    launch_state_export(state_args(), stream_);
+    launch_states(false);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         *err = hip_error(e);
         return Status::kRuntime;
     }
-    if (!run_call(c, err)) return Status::kRuntime;  // (a refused call has advanced nothing)
-    launch_state_import(state_args(), stream_);
+    if (!advance(c, err)) return Status::kRuntime;  // (a refused call has advanced nothing)
+    launch_states(true);
     e = hipGetLastError();
     if (e != hipSuccess) {
         *err = hip_error(e);

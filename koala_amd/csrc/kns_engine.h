@@ -16,6 +16,9 @@ namespace kns {
 
 // host copy of a KNS1 parameter file (fp32, logical layout; see koala_amd/params.py)
 struct Params {
+    // Not part of the file: the sample rate of the handle to be made (8 000, 16 000, 32 000 or 48 000 Hz; DESIGN.md section 2, third
+    // extension).  load_params leaves 16 000; the batch C ABI sets it.  It is no part of the content hash: all rates share one weight image.
+    int sample_rate = 16000;
     int front_taps = 1;  // feature frames the front-end sees (KNS-v1: 1; KNS-v1.1: up to 5, w_in then has front_taps * 257 rows, oldest frame first)
     int head[kStages];
     std::vector<float> mean, scale, w_in, b_in;
@@ -31,7 +34,8 @@ LoadResult load_params(const char *path, Params *out, std::string *err);
 constexpr int kNumKernelClasses = 5;
 enum KernelClass { kClsAnalysis = 0, kClsGemmIn = 1, kClsGru = 2, kClsGemmHead = 3, kClsSynthesis = 4 };
 
-// One call that advances the streams, with everything it carries.  pcm/out: [B][T*256], host or device pointers (both of the same kind).
+// One call that advances the streams, with everything it carries.  pcm/out: [B][T*frame_length] at the handle's sample rate (256 at
+// 16 kHz), host or device pointers (both of the same kind).
 struct Call {
     int T;
     const int16_t *pcm;
@@ -74,6 +78,7 @@ public:
     int max_frames() const { return Tmax_; }
     int device() const { return device_; }
     int front_taps() const { return taps_; }
+    int sample_rate() const { return rate_; }
 
     // The two entries that advance the streams.  Host pointers: synchronous.  Device pointers: enqueued.
     Status process(const Call &c, std::string *err);
@@ -98,7 +103,7 @@ public:
     // its feature context is the other engine's) and every index (outside [0, num_streams), the same slot twice) BEFORE anything is written,
     // returns when the host records may be reused, and its scatter is ordered on the stream in front of the next call.  A failed call
     // leaves all state as it was.
-    size_t state_bytes() const { return state_record_bytes(taps_); }
+    size_t state_bytes() const { return state_record_bytes(taps_, rate_); }
     Status export_state(int count, const int32_t *streams, void *host_records, std::string *err);
     Status import_state(int count, const int32_t *streams, const void *host_records, std::string *err);
 
@@ -109,7 +114,21 @@ public:
 private:
     Engine() {}
     bool init(const Params &p, int device, int B, int Tmax, int precision, std::string *err, bool *oom);
-    bool run_call(const Call &c, std::string *err);  // process() without the held streams
+    bool run_call(const Call &c, std::string *err);  // process() without the held streams, at 16 kHz
+    // Handles that are not at 16 kHz (kns_engine.cpp, run_call_rate): in-stage kernel, run_call on device buffers, out-stage kernel.
+    // The stages' per-stream state (rs_in, rs_out: kns_kernels.h) is a ping-pong pair each, like the history; it is part of the stream
+    // record (version 2), of reset() and of a call's per-frame resets.
+    bool advance(const Call &c, std::string *err) { return rate_ == kRate16k ? run_call(c, err) : run_call_rate(c, err); }
+    bool run_call_rate(const Call &c, std::string *err);
+    bool rate_ready(bool host_staging, bool reset_flags, std::string *err);
+    void launch_states(bool import);  // the state kernels of export / import / held streams: the engine's and, at such a rate, the stages'
+    int rate_ = kRate16k;
+    int16_t *d_rs_state_[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [in-stage, out-stage][ping-pong copy], [Bpad][hist] each
+    int rs_cur_ = 0;
+    std::vector<float> rs_hd_, rs_hi_;  // the prototype's two tables (decimator, interpolator)
+    int16_t *d_rate_io_ = nullptr;      // host-pointer calls: [B][Tmax * frame_length], the call's input, then its output
+    uint8_t *d_rs_flags_ = nullptr;     // a call's per-frame resets on the device, uint8 [B][T], and their upload ring
+    uint8_t *d_state_rs_ = nullptr;     // the stages' part of the staged stream records [B][rs_record_bytes]
     // what run_device is given: the frames [t0, t0 + T) of a call, their device buffers, and the call's reset table if it has one
     struct ResetTable;
     struct Slice {
@@ -242,7 +261,7 @@ private:
     // Per-frame stream resets (kns_engine.cpp, begin_resets).  A call's packed table -- per (m-tile, frame) the rows that restart, uint32
     // [mtiles][T] -- goes through a slot of rs_ring_ to d_rs_ on the stream that runs the call's kernels, a frame-0 mask to d_rmask_.
     // The table belongs to its call: process*() own it and hand it to run_device with every slice.
-    UploadRing rs_ring_;
+    UploadRing rs_ring_, rsf_ring_;  // (rsf_ring_: the sample-rate stages' copy of a call's reset flags)
     unsigned *d_rs_ = nullptr;
     struct ResetTable {
         int slot = -1, T = 0;        // the call's ring slot (-1: no stream restarts after frame 0, there is no table) and its length

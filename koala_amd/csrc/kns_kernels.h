@@ -266,6 +266,10 @@ void launch_reset(const ResetArgs &a, hipStream_t s);
 // precision: importing into a handle of the other precision is refused (a bf16 handle's feature context is not an fp32 handle's).
 constexpr uint32_t kStateMagic = 0x53534e4bu;  // "KNSS"
 constexpr uint32_t kStateVersion = 1;
+// Version 2, of handles that are not at 16 kHz: the first four reserved header bytes hold uint32 sample_rate, and behind the version-1 parts
+// follow rs_in and rs_out, int16, oldest first (the sample-rate stages' histories, below), zero-padded to whole 16-byte words: 288 bytes at
+// 8 and 32 kHz, 384 at 48 kHz.  A 16 kHz handle writes and accepts version 1 only, a handle at another rate version 2 of its own rate.
+constexpr uint32_t kStateVersionRate = 2;
 constexpr int kStateHeaderBytes = 32, kStateHistOff = 32, kStateTailOff = kStateHistOff + kFrame * 2,
               kStateHOff = kStateTailOff + kFrame * 4, kStateFctxOff = kStateHOff + kGruLayers * kHidden * 4;
 static_assert(kStateFctxOff == 10240 && kStateFctxOff % 16 == 0 && (kBins * 4 * 4) % 16 == 0, "stream record layout");
@@ -285,6 +289,42 @@ struct StateArgs {
 };
 void launch_state_export(const StateArgs &a, hipStream_t s);
 void launch_state_import(const StateArgs &a, hipStream_t s);
+// ---- sample-rate stages of handles that are not at 16 kHz (kns_resample.hip; DESIGN.md section 2, third extension).  R = 2 (8 and
+// 32 kHz) or 3 (48 kHz); the prototype has L = 48 R + 1 taps.  An interpolator keeps its last 48 input samples per stream, a decimator
+// its last L - 1 = 48 R, int16, oldest first.
+constexpr int kRate16k = 16000, kRsHalf = 24, kRsInterpHist = 2 * kRsHalf, kRsMaxTaps = 2 * kRsHalf * 3 + 1;
+KNS_HD bool rs_rate_ok(int rate) { return rate == 8000 || rate == 16000 || rate == 32000 || rate == 48000; }
+KNS_HD int rs_ratio(int rate) { return rate == 48000 ? 3 : rate == kRate16k ? 1 : 2; }
+KNS_HD int rs_frame_length(int rate) { return rate / 1000 * kFrame / 16; }  // 128 / 256 / 512 / 768
+KNS_HD int rs_in_hist(int rate) { return rate == kRate16k ? 0 : rate < kRate16k ? kRsInterpHist : 2 * kRsHalf * rs_ratio(rate); }
+KNS_HD int rs_out_hist(int rate) { return rate == kRate16k ? 0 : rate < kRate16k ? 2 * kRsHalf * rs_ratio(rate) : kRsInterpHist; }
+// what both stages add to a stream's delay, in samples at the handle's rate (each stage: 24 R high-rate samples)
+KNS_HD int rs_delay(int rate) { return rate == kRate16k ? 0 : rate < kRate16k ? 2 * kRsHalf : 2 * kRsHalf * rs_ratio(rate); }
+// the part of a version-2 stream record behind the version-1 parts: rs_in, rs_out, zero-padded to whole 16-byte words
+KNS_HD size_t rs_record_bytes(int rate) { return ((size_t) (rs_in_hist(rate) + rs_out_hist(rate)) * 2 + 15) / 16 * 16; }
+KNS_HD size_t state_record_bytes(int front_taps, int rate) { return state_record_bytes(front_taps) + rs_record_bytes(rate); }
+struct ResampleArgs {
+    const int16_t *in;      // [B][T * n_in] (caller layout), n_in = n_low (interpolate) or R n_low (decimate)
+    int16_t *out;           // [B][T * n_out], n_out = the other of the two
+    const int16_t *state;   // [Bpad][hist]: the stream's last `hist` input samples before the call, oldest first
+    int16_t *state_next;    // the same after the call: the other copy of the ping-pong pair
+    const uint8_t *resets;  // optional, device memory [B][T]: non-zero at [b][t] = everything in front of block t of stream b reads as zero
+    int B, T, R, n_low, interpolate;
+    float taps[kRsMaxTaps];  // hi (interpolate) or hd (decimate): wave-uniform, read from the kernel's argument segment
+};
+void launch_resample(const ResampleArgs &a, hipStream_t s);
+// state rows [Bpad][hist], both copies, of the streams with mask[b] != 0 (null: all) := 0
+void launch_resample_reset(int16_t *state0, int16_t *state1, int hist, const uint8_t *mask, int Bpad, hipStream_t s);
+// the rs part of stream records [count][rec_bytes] (device) <- / -> the two state arrays, for the streams with rec_of[b] >= 0
+struct ResampleStateArgs {
+    int16_t *state_in[2], *state_out[2];  // [Bpad][hist_in], [Bpad][hist_out]; [0] = the current copy (export reads it; import writes both)
+    int hist_in, hist_out;
+    const int32_t *rec_of;          // [Bpad]
+    uint8_t *records;
+    uint32_t rec_bytes;
+    int Bpad, import;               // import != 0: records -> state
+};
+void launch_resample_state(const ResampleStateArgs &a, hipStream_t s);
 // last node of a captured one-frame replay: ++*counter (device memory), published to *host_word (page-locked host memory)
 void launch_frame_done(unsigned *counter, unsigned *host_word, hipStream_t s);
 

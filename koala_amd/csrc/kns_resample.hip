@@ -1,0 +1,152 @@
+// kns_resample.hip -- the sample-rate stages of batch handles that are not at 16 kHz (third extension; section 6).
+// resample_interp_kernel<R>: v[R n + p] = sum_j hi[p + R j] a[n - j];  resample_decim_kernel<R>: v[n] = sum_i hd[i] a[R n - i] -- one fmaf
+// per tap from acc = 0, taps ascending, then the synthesis kernel's rounding to int16.  Plain HIP C++, vector loads and stores only.
+//
+// One workgroup serves 256 low-rate samples (one or two 16 ms blocks) of ONE stream.  They and the `hist` samples in front of them are
+// staged in LDS as floats (a decimator's de-interleaved by input phase, so that the lanes of a wave read consecutive words for every
+// tap); the samples in front of the call come from the stream's state.  The state is a ping-pong pair like the engine's history: the
+// row's first workgroup reads the current copy, its last one writes the other (the call's last `hist` input samples), once per call.
+// The taps are wave-uniform: they arrive in the kernel's argument segment, the tap loop is fully unrolled straight-line code, so each
+// tap is a scalar load used once.  The tap loop holds no vector-memory operation; the staging loads are unconditional (a clamped or
+// selected address), the stores are guarded once per wave (a block is a multiple of 64 samples).
+//
+// Per-frame stream resets (kResets): a stage's history is shorter than a block, so a wave needs its own block's flag only -- where it
+// is set, every staged sample in front of the block's first enters its fmaf as +0.
+#include "kns_kernels.h"
+
+namespace kns {
+
+namespace {
+
+constexpr int kChunk = 256;  // low-rate samples per workgroup
+constexpr int kNoFloor = -0x40000000;
+
+__device__ __forceinline__ int16_t to_pcm(float a) {
+    a = __builtin_fminf(__builtin_fmaxf(__builtin_roundf(a), -32768.0f), 32767.0f);
+    return (int16_t) (int) a;
+}
+
+// the row's samples [g0 - hist, g0 - hist + count) as floats, element i through put(i, value); samples in front of the row come from
+// `state`, indices behind the row's end (a last, half-filled workgroup's) are clamped onto its last sample and never reach a stored output
+template <class Put>
+__device__ __forceinline__ void stage(const int16_t *row, const int16_t *state, int hist, int g0, int count, int n_row, Put put) {
+    for (int i = threadIdx.x; i < count; i += 256) {
+        const int gi = g0 - hist + i;
+        const int16_t *p = gi < 0 ? state + i : row + min(gi, n_row - 1);
+        put(i, (float) *p);
+    }
+}
+
+}  // namespace
+
+template <int R, bool kResets>
+__global__ __launch_bounds__(256) void resample_interp_kernel(ResampleArgs g) {
+    constexpr int H = kRsInterpHist;
+    __shared__ float xs[H + kChunk];
+    const int N = g.T * g.n_low, chunks = (N + kChunk - 1) / kChunk;
+    const int b = blockIdx.x / chunks, c0 = (blockIdx.x - b * chunks) * kChunk, n = threadIdx.x, gn = c0 + n;
+    const int16_t *row = g.in + (size_t) b * N;
+    int16_t *orow = g.out + (size_t) b * N * R;
+    stage(row, g.state + (size_t) b * H, H, c0, H + kChunk, N, [&](int i, float v) { xs[i] = v; });
+    if (c0 + kChunk >= N && n < H) g.state_next[(size_t) b * H + n] = row[N - H + n];  // (a call has at least 128 samples: all this call's)
+    __syncthreads();
+    const bool valid = gn < N;  // (wave-uniform: N is a multiple of 64)
+    int floor_ = kNoFloor;
+    if (kResets) {
+        const int t = min(gn, N - 1) / g.n_low;
+        floor_ = g.resets[(size_t) b * g.T + t] ? t * g.n_low : kNoFloor;
+    }
+    float acc[R];
+#pragma unroll
+    for (int p = 0; p < R; ++p) acc[p] = 0.0f;
+#pragma unroll
+    for (int j = 0; j <= H; ++j) {
+        float x = xs[H + n - j];
+        if (kResets) x = gn - j >= floor_ ? x : 0.0f;
+#pragma unroll
+        for (int p = 0; p < (j < H ? R : 1); ++p) acc[p] = fmaf(g.taps[p + R * j], x, acc[p]);  // (j = 48: phase 0 only)
+    }
+    if (valid) {
+#pragma unroll
+        for (int p = 0; p < R; ++p) orow[(size_t) gn * R + p] = to_pcm(acc[p]);
+    }
+}
+
+template <int R, bool kResets>
+__global__ __launch_bounds__(256) void resample_decim_kernel(ResampleArgs g) {
+    constexpr int H = 2 * kRsHalf * R, L = H + 1, W = kRsInterpHist + kChunk;  // W: words per input phase
+    __shared__ float xs[R * W];  // sample m (counted from the first history sample) at [m % R][m / R]
+    const int N = g.T * g.n_low, n_in = g.n_low * R, chunks = (N + kChunk - 1) / kChunk;
+    const int b = blockIdx.x / chunks, c0 = (blockIdx.x - b * chunks) * kChunk, n = threadIdx.x, gn = c0 + n;
+    const int16_t *row = g.in + (size_t) b * N * R;
+    int16_t *orow = g.out + (size_t) b * N;
+    stage(row, g.state + (size_t) b * H, H, c0 * R, R * W, N * R, [&](int i, float v) { xs[(i % R) * W + i / R] = v; });
+    if (c0 + kChunk >= N && n < H) g.state_next[(size_t) b * H + n] = row[N * R - H + n];  // (a call has at least 256 input samples)
+    __syncthreads();
+    const bool valid = gn < N;
+    int floor_ = kNoFloor;
+    if (kResets) {
+        const int t = min(gn, N - 1) / g.n_low;
+        floor_ = g.resets[(size_t) b * g.T + t] ? t * n_in : kNoFloor;
+    }
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < L; ++i) {
+        // input R gn - i = staged sample R (48 + n) - i: phase (-i) mod R, word 48 + n - ceil(i / R)
+        const int ph = (R - i % R) % R, q = kRsInterpHist + n - (i + R - 1) / R;
+        float x = xs[ph * W + q];
+        if (kResets) x = gn * R - i >= floor_ ? x : 0.0f;
+        acc = fmaf(g.taps[i], x, acc);
+    }
+    if (valid) orow[gn] = to_pcm(acc);
+}
+
+__global__ __launch_bounds__(256) void resample_reset_kernel(int16_t *state0, int16_t *state1, int hist, const uint8_t *mask, int Bpad) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= Bpad * hist) return;
+    if (!mask || mask[i / hist]) state0[i] = 0, state1[i] = 0;
+}
+
+// one workgroup per stream; a listed stream's rs_in and rs_out move as int16, the record's padding is written as zeros
+__global__ __launch_bounds__(256) void resample_state_kernel(ResampleStateArgs g) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int rec = g.rec_of[b];
+    if (rec < 0) return;
+    int16_t *r = (int16_t *) (g.records + (size_t) rec * g.rec_bytes);
+    const int n = g.hist_in + g.hist_out, words = (int) (g.rec_bytes / 2);
+    if (tid >= words) return;
+    const size_t off = tid < g.hist_in ? (size_t) b * g.hist_in + tid : (size_t) b * g.hist_out + (tid - g.hist_in);
+    int16_t *const *s = tid < g.hist_in ? g.state_in : g.state_out;
+    if (g.import) {
+        if (tid < n) s[0][off] = r[tid], s[1][off] = r[tid];
+    } else {
+        r[tid] = tid < n ? s[0][off] : (int16_t) 0;
+    }
+}
+
+void launch_resample(const ResampleArgs &a, hipStream_t s) {
+    const dim3 grid((unsigned) a.B * (unsigned) ((a.T * a.n_low + kChunk - 1) / kChunk)), block(256);
+#define KNS_RS(KERNEL, RR)                                                                    \
+    do {                                                                                      \
+        if (a.resets) hipLaunchKernelGGL((KERNEL<RR, true>), grid, block, 0, s, a);           \
+        else hipLaunchKernelGGL((KERNEL<RR, false>), grid, block, 0, s, a);                   \
+    } while (0)
+    if (a.interpolate) {
+        if (a.R == 2) KNS_RS(resample_interp_kernel, 2);
+        else KNS_RS(resample_interp_kernel, 3);
+    } else {
+        if (a.R == 2) KNS_RS(resample_decim_kernel, 2);
+        else KNS_RS(resample_decim_kernel, 3);
+    }
+#undef KNS_RS
+}
+
+void launch_resample_reset(int16_t *state0, int16_t *state1, int hist, const uint8_t *mask, int Bpad, hipStream_t s) {
+    hipLaunchKernelGGL(resample_reset_kernel, dim3((Bpad * hist + 255) / 256), dim3(256), 0, s, state0, state1, hist, mask, Bpad);
+}
+
+void launch_resample_state(const ResampleStateArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(resample_state_kernel, dim3(a.Bpad), dim3(256), 0, s, a);
+}
+
+}  // namespace kns

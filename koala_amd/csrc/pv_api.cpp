@@ -41,6 +41,7 @@ struct pv_koala {
 struct pv_koala_batch {
     kns::Engine *engine;
     MinGain limit;
+    int32_t sample_rate = kns::kRate16k;  // fixed at creation (pv_koala_batch_init_rate); the engine was made with the same value
 };
 
 namespace {
@@ -102,6 +103,13 @@ pv_status_t check_call(const pv_koala_batch_t *object, int32_t num_frames, const
         return PV_STATUS_INVALID_ARGUMENT;
     }
     return PV_STATUS_SUCCESS;
+}
+
+// handles that are not at 16 kHz have no asynchronous path yet
+pv_status_t check_synchronous(const pv_koala_batch_t *object) {
+    if (object->sample_rate == kns::kRate16k) return PV_STATUS_SUCCESS;
+    push_error(0x66, "Asynchronous calls are not available on a handle whose sample rate is %d, not 16000.", object->sample_rate);
+    return PV_STATUS_INVALID_ARGUMENT;
 }
 
 // the five-frame front-end takes per-frame stream resets at frame 0 only (the reset kernel)
@@ -214,7 +222,7 @@ bool parse_device(const char *text, DeviceSpec *out) {
 
 // shared front half of pv_koala_init / pv_koala_batch_init
 pv_status_t open_engine_unguarded(const char *access_key, const char *model_path, const char *device, void *object,
-                                  int num_streams, int max_frames, int precision, kns::Engine **engine) {
+                                  int num_streams, int max_frames, int precision, int sample_rate, kns::Engine **engine) {
     if (!access_key) {
         push_error(0x64, "Argument `access_key` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
@@ -270,6 +278,7 @@ pv_status_t open_engine_unguarded(const char *access_key, const char *model_path
         push_error(0x12C, "Picovoice Error.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
+    params.sample_rate = sample_rate;
     bool oom = false;
     kns::Engine *e = kns::Engine::create(params, index, num_streams, max_frames, precision, &err, &oom);
     if (!e) {
@@ -282,8 +291,10 @@ pv_status_t open_engine_unguarded(const char *access_key, const char *model_path
 }
 
 pv_status_t open_engine(const char *access_key, const char *model_path, const char *device, void *object, int num_streams,
-                        int max_frames, int precision, kns::Engine **engine) {
-    return guarded([&] { return open_engine_unguarded(access_key, model_path, device, object, num_streams, max_frames, precision, engine); });
+                        int max_frames, int precision, int sample_rate, kns::Engine **engine) {
+    return guarded([&] {
+        return open_engine_unguarded(access_key, model_path, device, object, num_streams, max_frames, precision, sample_rate, engine);
+    });
 }
 
 // the handle around a new engine (takes the engine over: deleted when the handle cannot be made)
@@ -410,7 +421,7 @@ PV_API pv_status_t pv_koala_init(const char *access_key, const char *model_path,
                                  pv_koala_t **object) {
     t_stack.clear();
     kns::Engine *e = nullptr;
-    pv_status_t st = open_engine(access_key, model_path, device, object, 1, 1, default_precision(), &e);
+    pv_status_t st = open_engine(access_key, model_path, device, object, 1, 1, default_precision(), kns::kRate16k, &e);
     if (st != PV_STATUS_SUCCESS) return st;
     return make_handle(e, object);
 }
@@ -501,6 +512,12 @@ PV_API void pv_koala_free_hardware_devices(char **hardware_devices, int32_t num_
 PV_API pv_status_t pv_koala_batch_init(const char *access_key, const char *model_path, const char *device,
                                        int32_t num_streams, int32_t max_frames_per_call,
                                        pv_koala_precision_t precision, pv_koala_batch_t **object) {
+    return pv_koala_batch_init_rate(access_key, model_path, device, num_streams, max_frames_per_call, precision, kns::kRate16k, object);
+}
+
+PV_API pv_status_t pv_koala_batch_init_rate(const char *access_key, const char *model_path, const char *device,
+                                            int32_t num_streams, int32_t max_frames_per_call,
+                                            pv_koala_precision_t precision, int32_t sample_rate, pv_koala_batch_t **object) {
     t_stack.clear();
     if (num_streams <= 0 || max_frames_per_call <= 0) {
         push_error(0x66, "`num_streams` and `max_frames_per_call` must be positive.");
@@ -510,11 +527,17 @@ PV_API pv_status_t pv_koala_batch_init(const char *access_key, const char *model
         push_error(0x66, "`precision` must be PV_KOALA_PRECISION_FP32 or PV_KOALA_PRECISION_BF16.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
+    if (!kns::rs_rate_ok(sample_rate)) {
+        push_error(0x66, "`sample_rate` %d is not one of 8000, 16000, 32000, 48000.", sample_rate);
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
     kns::Engine *e = nullptr;
     pv_status_t st = open_engine(access_key, model_path, device, object, num_streams, max_frames_per_call,
-                                 precision == PV_KOALA_PRECISION_BF16 ? kns::kBf16 : kns::kFp32, &e);
+                                 precision == PV_KOALA_PRECISION_BF16 ? kns::kBf16 : kns::kFp32, sample_rate, &e);
     if (st != PV_STATUS_SUCCESS) return st;
-    return make_handle(e, object);
+    st = make_handle(e, object);
+    if (st == PV_STATUS_SUCCESS) (*object)->sample_rate = sample_rate;
+    return st;
 }
 
 PV_API void pv_koala_batch_delete(pv_koala_batch_t *object) {
@@ -534,7 +557,8 @@ PV_API pv_status_t pv_koala_batch_process_chunk(pv_koala_batch_t *object, int32_
 PV_API pv_status_t pv_koala_batch_process_chunk_async(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
                                                       int16_t *enhanced) {
     t_stack.clear();
-    const pv_status_t st = check_call(object, num_frames, pcm, enhanced);
+    pv_status_t st = check_call(object, num_frames, pcm, enhanced);
+    if (st == PV_STATUS_SUCCESS) st = check_synchronous(object);
     if (st != PV_STATUS_SUCCESS) return st;
     return advance(object->engine, object->limit, {num_frames, pcm, enhanced}, /*async=*/true);
 }
@@ -553,6 +577,7 @@ PV_API pv_status_t pv_koala_batch_process_chunk_resets_async(pv_koala_batch_t *o
     t_stack.clear();
     pv_status_t st = check_call(object, num_frames, pcm, enhanced);
     if (st == PV_STATUS_SUCCESS) st = check_resets(object, num_frames, reset);
+    if (st == PV_STATUS_SUCCESS) st = check_synchronous(object);
     if (st != PV_STATUS_SUCCESS) return st;
     return advance(object->engine, object->limit, {num_frames, pcm, enhanced, reset}, /*async=*/true);
 }
@@ -580,6 +605,7 @@ PV_API pv_status_t pv_koala_batch_process_call(pv_koala_batch_t *object, const p
     }
     pv_status_t st = check_call(object, call->num_frames, call->pcm, call->enhanced);
     if (st == PV_STATUS_SUCCESS) st = check_resets(object, call->num_frames, call->reset);
+    if (st == PV_STATUS_SUCCESS && call->asynchronous != 0) st = check_synchronous(object);
     if (st != PV_STATUS_SUCCESS) return st;
     kns::Call c{call->num_frames, call->pcm, call->enhanced, call->reset, call->hold};
     c.report = call->report;
@@ -629,7 +655,7 @@ PV_API pv_status_t pv_koala_batch_state_size(const pv_koala_batch_t *object, int
         push_error(0x64, "Argument `%s` is NULL.", object ? "num_bytes" : "object");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    *num_bytes = (int32_t) object->engine->state_bytes();
+    *num_bytes = (int32_t) kns::state_record_bytes(object->engine->front_taps(), object->sample_rate);
     return PV_STATUS_SUCCESS;
 }
 
@@ -706,7 +732,27 @@ PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, i
         push_error(0x64, "Argument `%s` is NULL.", object ? "delay_sample" : "object");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    *delay_sample = kns::kFrame;
+    *delay_sample = kns::rs_frame_length(object->sample_rate) + kns::rs_delay(object->sample_rate);
+    return PV_STATUS_SUCCESS;
+}
+
+PV_API pv_status_t pv_koala_batch_sample_rate(const pv_koala_batch_t *object, int32_t *sample_rate) {
+    t_stack.clear();
+    if (!object || !sample_rate) {
+        push_error(0x64, "Argument `%s` is NULL.", object ? "sample_rate" : "object");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    *sample_rate = object->sample_rate;
+    return PV_STATUS_SUCCESS;
+}
+
+PV_API pv_status_t pv_koala_batch_frame_length(const pv_koala_batch_t *object, int32_t *frame_length) {
+    t_stack.clear();
+    if (!object || !frame_length) {
+        push_error(0x64, "Argument `%s` is NULL.", object ? "frame_length" : "object");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    *frame_length = kns::rs_frame_length(object->sample_rate);
     return PV_STATUS_SUCCESS;
 }
 

@@ -1,0 +1,168 @@
+"""
+Batch handles at 8, 32 and 48 kHz (include/pv_koala_batch.h: pv_koala_batch_init_rate; DESIGN.md section 2, third extension) without a GPU:
+the prototype low-pass, the numpy recipe (tests/sample_rate_recipe.py) against itself -- chunkings, level, delay -- the gfx950 build of
+koala_amd/csrc/kns_resample.hip, the new symbols, and the C-ABI shim's new entry points under AddressSanitizer + UndefinedBehaviorSanitizer
+(tests/abi_sample_rate/driver.cpp with the engine double of tests/abi_sanitizer).  tests/test_gpu_sample_rate.py checks the samples on the GPU.
+"""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+import sys
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import koala_amd
+import sample_rate_recipe as srr
+from conftest import ROOT, model_file, synth_streams
+
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+SYMBOLS = ('pv_koala_batch_init_rate', 'pv_koala_batch_sample_rate', 'pv_koala_batch_frame_length')
+
+
+def test_fma32_is_the_single_rounding_for_operands_of_any_sign():
+    rng = np.random.default_rng(0)
+    a = rng.standard_normal(600).astype(np.float32)
+    b = (rng.standard_normal(600) * 3e4).astype(np.float32)
+    c = (rng.standard_normal(600) * 1e4).astype(np.float32)
+    c[:150] = (-a[:150].astype(np.float64) * b[:150]).astype(np.float32)  # (cancellation)
+    got = srr.fma32(a, b, c)
+    for i in range(a.size):
+        v = Fraction(float(a[i])) * Fraction(float(b[i])) + Fraction(float(c[i]))
+        f = np.float32(float(v))
+        cands = [np.nextafter(f, np.float32(-np.inf)), f, np.nextafter(f, np.float32(np.inf))]
+        best = min(cands, key=lambda q: (abs(Fraction(float(q)) - v), int(np.float32(q).view(np.int32)) & 1))
+        assert got[i] == best, (i, a[i], b[i], c[i])
+
+
+@pytest.mark.parametrize('R', [2, 3])
+def test_prototype_passes_the_low_band_and_stops_its_images(R):
+    g, hd, hi = srr.prototype(R)
+    assert len(g) == 48 * R + 1 and abs(g.sum() - 1.0) < 1e-12 and np.allclose(g, g[::-1], rtol=0, atol=1e-15)
+    assert np.array_equal(hd, g.astype(np.float32)) and np.array_equal(hi, (R * g).astype(np.float32))
+    nyq = 0.5 / R  # the low rate's Nyquist frequency, in cycles per high-rate sample
+    i = np.arange(len(g))
+    for name, taps in (('double', g), ('hd', hd.astype(np.float64)), ('hi / R', hi.astype(np.float64) / R)):
+        resp = lambda f: 20 * np.log10(np.abs(np.exp(-2j * np.pi * np.outer(f, i)) @ taps) + 1e-300)
+        pb = resp(np.linspace(0, 0.8 * nyq, 801))
+        sb = resp(np.linspace(1.1 * nyq, 0.5, 1601))
+        print('R = %d %s: pass band %+.4f .. %+.4f dB, stop band max %.1f dB' % (R, name, pb.min(), pb.max(), sb.max()))
+        assert np.abs(pb).max() <= 0.1 and sb.max() <= -80.0
+
+
+@pytest.mark.parametrize('rate', srr.RATES)
+def test_recipe_in_any_chunking_is_the_recipe_in_one_shot(random_model, rate):
+    n, T, fl = 2, 12, srr.frame_length(rate)
+    x16 = synth_streams(n, T * fl // 256 + 1, seed=5)[:, :T * fl]  # (any int16 signal serves: taken as samples at `rate`)
+    x = np.ascontiguousarray(x16)
+    one = srr.Recipe(random_model, n, 'fp32', rate).process(x)
+    for cuts in ([1] * T, [5, 1, 3, 2, 1], [11, 1]):
+        r, out, t0 = srr.Recipe(random_model, n, 'fp32', rate), [], 0
+        for c in cuts:
+            out.append(r.process(np.ascontiguousarray(x[:, t0 * fl:(t0 + c) * fl])))
+            t0 += c
+        assert t0 == T and np.array_equal(np.concatenate(out, axis=1), one), (rate, cuts)
+    # per-frame resets: the call cut at its frames == fresh streams from there
+    reset = np.zeros((n, T), np.uint8)
+    reset[1, 7] = 1
+    got = srr.Recipe(random_model, n, 'fp32', rate).process_resets(x, reset)
+    fresh = srr.Recipe(random_model, n, 'fp32', rate).process(np.ascontiguousarray(x[:, 7 * fl:]))
+    assert np.array_equal(got[0], one[0]) and np.array_equal(got[1, :7 * fl], one[1, :7 * fl]) and np.array_equal(got[1, 7 * fl:], fresh[1])
+
+
+@pytest.mark.parametrize('rate', srr.RATES)
+def test_a_1_khz_tone_keeps_its_level_and_shows_the_stated_delay(rate):
+    fl, N = srr.frame_length(rate), 16 * srr.frame_length(rate)
+    x = np.round(8000.0 * np.sin(2 * np.pi * 1000.0 * np.arange(N) / rate)).astype(np.int16).reshape(1, N)
+    r = srr.Recipe(None, 1, 'fp32', rate)
+    y = r.s_out.run(r.s_in.run(x))[0].astype(np.float64)  # both stages, without the engine's frame
+    want = srr.delay_sample(rate) - fl
+    assert srr.delay_sample(rate) == {8000: 176, 32000: 608, 48000: 912}[rate] and want == {8000: 48, 32000: 96, 48000: 144}[rate]
+    xs = x[0].astype(np.float64)
+    # the distance between y and x delayed by d (zeros in front: the tone starts at sample 0, so one lag fits its onset as well)
+    dist = [float(np.sum((y - np.concatenate([np.zeros(d), xs[:N - d]])) ** 2)) for d in range(2 * want + 1)]
+    assert int(np.argmin(dist)) == want, (rate, int(np.argmin(dist)))
+    steady = slice(want + 2 * fl, N)
+    level = 20 * np.log10(np.sqrt(np.mean(y[steady] ** 2)) / np.sqrt(np.mean(xs[2 * fl:N - want] ** 2)))
+    err = np.abs(y[steady] - xs[2 * fl:N - want]).max()
+    print('%d Hz: delay %d samples, level %+.4f dB, max |y[n] - x[n - delay]| = %.1f of 8000' % (rate, want, level, err))
+    assert abs(level) <= 0.1
+    # and through the whole recipe with the engine as a pure delay: delay_sample
+    z = srr.Recipe(None, 1, 'fp32', rate).process(x)[0].astype(np.float64)
+    d = srr.delay_sample(rate)
+    assert np.array_equal(z[d:], y[want:N - fl]) and not z[:fl].any()
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not available')
+def test_resample_kernels_build_for_gfx950_without_scratch_or_spills(tmp_path):
+    import isa_scan
+    src = 'kns_resample.hip'
+    out = tmp_path / (src + '.s')
+    mk = open(os.path.join(ROOT, 'koala_amd', 'Makefile')).read()
+    assert 'csrc/' + src in mk and 'obj/kns_resample.o' in mk
+    cxx = re.search(r'^CXXFLAGS\s*=\s*(.*)$', mk, re.M).group(1).split()
+    subprocess.check_call([HIPCC, '--offload-arch=gfx950'] + [f for f in cxx if f != '-fPIC'] +
+                          ['-S', '--cuda-device-only', '-x', 'hip', os.path.join(ROOT, 'koala_amd', 'csrc', src), '-o', str(out)],
+                          stderr=subprocess.DEVNULL)
+    text = out.read_text()
+    assert isa_scan.scan(text) == []
+    info = {}
+    for name, body in re.findall(r'\.set (\S+)\.has_indirect_call, \d+\n[^\n]*\n; Kernel info:\n((?:;[^\n]*\n)*)', text):
+        info[name] = {k: int(re.search(r'; %s: (\d+)' % k, body).group(1)) for k in ('ScratchSize', 'NumVgprs', 'Occupancy')}
+    meta = re.findall(r'\.name:\s+(\S+)\n(?:(?!\.name:).*\n)*?\s+\.sgpr_spill_count:\s+(\d+)\n(?:(?!\.name:).*\n)*?\s+\.vgpr_spill_count:\s+(\d+)', text)
+    spills = {name: (int(s), int(v)) for name, s, v in meta}
+    kernels = [k for k in info if 'resample_' in k]
+    # interpolator and decimator, R = 2 and 3, with and without the reset arm; the reset and the record kernels
+    assert len([k for k in kernels if 'resample_interp_kernel' in k]) == 4 and len([k for k in kernels if 'resample_decim_kernel' in k]) == 4
+    assert any('resample_reset_kernel' in k for k in kernels) and any('resample_state_kernel' in k for k in kernels)
+    for k in kernels:
+        print(k, info[k], 'spills (sgpr, vgpr):', spills.get(k))
+        assert info[k]['ScratchSize'] == 0, (k, info[k])
+        assert spills[k] == (0, 0), (k, spills[k])
+    # the tap loops are straight-line code whose taps are scalar loads of the argument segment: no vector-memory load of a tap
+    body = text.split('resample_decim_kernelILi3ELb0EEEvNS_12ResampleArgsE:')[1].split('s_endpgm')[0]
+    assert len(re.findall(r'\bv_fmac?_f32', body)) >= 145 and len(re.findall(r'\bs_load_dword', body)) >= 10
+    assert len(re.findall(r'\b(global|flat|buffer)_load', body)) <= 16, 'vector-memory loads beyond the staging of one chunk'
+
+
+def test_symbols_are_exported_and_declared(native_library):
+    header = open(os.path.join(ROOT, 'include', 'pv_koala_batch.h')).read()
+    for path in (native_library, koala_amd.developer_library_path()):
+        lib = ctypes.CDLL(path)
+        for sym in SYMBOLS:
+            assert hasattr(lib, sym), (path, sym)
+    for sym in SYMBOLS:
+        assert re.search(r'PV_API pv_status_t %s\(' % sym, header), sym
+    # the single-stream header stays the reference's
+    assert 'sample_rate' not in open(os.path.join(ROOT, 'include', 'pv_koala.h')).read()
+
+
+def test_python_refuses_other_rates_before_it_loads_anything(random_model):
+    for bad in (0, 16001, 44100):
+        with pytest.raises(koala_amd.KoalaInvalidArgumentError):
+            koala_amd.create_batch('key', 2, 1, 'fp32', model_path=random_model, sample_rate=bad)
+
+
+def test_sample_rate_entry_points_under_asan_and_ubsan(tmp_path):
+    gxx = shutil.which('g++')
+    if not gxx or not os.path.isdir('/opt/rocm/include/hip'):
+        pytest.skip('needs g++ and the HIP headers')
+    exe = str(tmp_path / 'sample_rate_driver')
+    cmd = [gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-fno-omit-frame-pointer',
+           '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include', '-I' + os.path.join(ROOT, 'include'),
+           '-I' + os.path.join(ROOT, 'koala_amd', 'csrc'), '-Wno-deprecated-declarations', '-Wno-unused-result',
+           os.path.join(ROOT, 'koala_amd', 'csrc', 'pv_api.cpp'), os.path.join(ROOT, 'tests', 'abi_sanitizer', 'engine_stub.cpp'),
+           os.path.join(ROOT, 'tests', 'abi_sample_rate', 'driver.cpp'), '-o', exe, '-lpthread']
+    build = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    if build.returncode != 0 and 'sanitizer' in build.stderr.lower() and 'cannot find' in build.stderr.lower():
+        pytest.skip('sanitizer runtimes not installed: ' + build.stderr[-300:])
+    assert build.returncode == 0, build.stderr[-4000:]
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
+    for k in ('STUB_GPUS', 'STUB_OOM', 'STUB_FAIL_PROCESS', 'STUB_THROW', 'STUB_FRONT_TAPS', 'LD_PRELOAD'):
+        env.pop(k, None)
+    run = subprocess.run([exe, model_file('random', 1234)], capture_output=True, text=True, timeout=300, env=env)
+    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-6000:])
