@@ -224,6 +224,50 @@ PV_API pv_status_t pv_koala_batch_process_call(pv_koala_batch_t *object, const p
  * call).  Calls with and without a report may be mixed freely: the samples are those of a handle that never asked. */
 PV_API pv_status_t pv_koala_process_report(pv_koala_t *object, const int16_t *pcm, int16_t *enhanced_pcm, float report[4]);
 
+/* PACKET HANDLES: streams that deliver ANY NUMBER OF SAMPLES per call.  Live audio arrives in 10 and 20 ms packets (80 / 160 / 320 / 480 /
+ * 960 samples), with jitter and not in phase across callers; a packet handle is a batch handle at any of the four rates whose streams are
+ * sample-in / sample-out filters (fourth extension).  With F the frame length, D the frame handle's delay_sample at
+ * that rate, x everything stream b was given since its last reset and e what a frame handle produces for x cut into frames, the stream's
+ * output is  o = [F - 1 zeros] ++ e,  and every call delivers the next counts[b] samples of it: pv_koala_batch_delay_sample() is D + F - 1
+ * (511 at 16 kHz).  The handle rebuffers on the device in both directions, so device pointers stay device pointers and no host loop
+ * runs per stream.
+ *   - pv_koala_batch_init_packets: `max_samples_per_call` >= 1 bounds `max_samples` of a call; the engine behind the handle is made
+ *     with max_frames_per_call = ceil(max_samples_per_call / F).
+ *   - the frame entry points (process, process_chunk*, process_call, the asynchronous ones) are refused on a packet handle, and
+ *     pv_koala_batch_process_packets on a frame handle, with PV_STATUS_INVALID_ARGUMENT, a message on the error stack and nothing processed.
+ *   - per-stream state on top of the frame handle's: fill = (length of x) mod F and one buffer of F - 1 int16 whose first `fill` entries
+ *     are pending input and whose last F - 1 - fill entries are pending output.  Every reset (pv_koala_batch_reset, full or masked, and
+ *     `restart`) makes it fill = 0 and F - 1 zeros.  It travels in the stream record, which is VERSION 3 then: the header with its version
+ *     and sample_rate fields set, the handle's version 1 or 2 body, uint32 fill, int16[F - 1], zero-padded to whole 16-byte words.  A packet
+ *     handle writes and accepts version 3 of its own rate only; a stream parked or moved mid-frame continues sample for sample.
+ *
+ * pv_koala_batch_process_packets: stream b gives its next counts[b] samples and takes the next counts[b] samples of its output.
+ * counts[b] = 0 is a stalled stream: it is not advanced, bit for bit (this replaces `hold`).  `pcm` and `enhanced` are host memory (the
+ * call is synchronous) or device memory (the call is enqueued on the handle's stream with no host wait) and may overlap in any way: the
+ * input is consumed before the output is written.  `counts`, `restart` and `frames` are always HOST memory; the first two are read and
+ * `frames` is written before the function returns.  Stream b completes k_b = floor((fill_b + counts[b]) / F) frames in the call:
+ * frames[b] = k_b, and report[b][0 .. k_b) are those frames' report rows (rows past k_b are unspecified).  The attenuation limit applies
+ * unchanged.  PV_STATUS_INVALID_ARGUMENT, with a message on the error stack and all state unchanged: a NULL object / call / counts / pcm /
+ * enhanced, a struct_size that is not sizeof(pv_koala_batch_packets_t), max_samples outside [1, max_samples_per_call], a count outside
+ * [0, max_samples], a report with report_frames below the largest k_b of the call, `pcm` in host and `enhanced` in device memory or the
+ * other way round, a `report` that is not memory of enhanced's kind. */
+PV_API pv_status_t pv_koala_batch_init_packets(const char *access_key, const char *model_path, const char *device, int32_t num_streams,
+                                               int32_t max_samples_per_call, pv_koala_precision_t precision, int32_t sample_rate,
+                                               pv_koala_batch_t **object);
+PV_API pv_status_t pv_koala_batch_is_packet_handle(const pv_koala_batch_t *object, int32_t *is_packet_handle);
+typedef struct {
+    int32_t struct_size;      /* sizeof(pv_koala_batch_packets_t): lets the struct grow */
+    int32_t max_samples;      /* row length of pcm / enhanced, 1 .. max_samples_per_call */
+    const int32_t *counts;    /* HOST [num_streams], each in [0, max_samples] */
+    const int16_t *pcm;       /* [num_streams][max_samples], row b's first counts[b] samples count */
+    int16_t *enhanced;        /* [num_streams][max_samples], row b's first counts[b] samples are written */
+    const uint8_t *restart;   /* HOST [num_streams] or NULL: the stream is fresh before this packet (a join) */
+    float *report;            /* [num_streams][report_frames][4] or NULL, memory of enhanced's kind */
+    int32_t report_frames;    /* rows per stream of `report`: at least the most frames any stream completes in the call */
+    int32_t *frames;          /* HOST [num_streams] or NULL, out: the frames stream b completed in this call */
+} pv_koala_batch_packets_t;
+PV_API pv_status_t pv_koala_batch_process_packets(pv_koala_batch_t *object, const pv_koala_batch_packets_t *call);
+
 PV_API pv_status_t pv_koala_batch_num_streams(const pv_koala_batch_t *object, int32_t *num_streams);
 PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, int32_t *delay_sample);
 

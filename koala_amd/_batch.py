@@ -24,12 +24,21 @@ class BatchCall(Structure):
                 ('hold', c_void_p), ('report', c_void_p), ('asynchronous', c_int32)]
 
 
+class BatchPackets(Structure):
+    """pv_koala_batch_packets_t (include/pv_koala_batch.h)"""
+    _fields_ = [('struct_size', c_int32), ('max_samples', c_int32), ('counts', c_void_p), ('pcm', c_void_p), ('enhanced', c_void_p),
+                ('restart', c_void_p), ('report', c_void_p), ('report_frames', c_int32), ('frames', c_void_p)]
+
+
 class KoalaBatch(object):
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
-                 max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000) -> None:
+                 max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0) -> None:
         """`sample_rate`: 8000, 16000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
         array of samples is [num_streams, T * frame_length] with frame_length = sample_rate * 256 / 16000; at a rate other than 16000 the
-        handle converts on the device, `delay_sample` includes both converters, and the asynchronous calls are refused."""
+        handle converts on the device, `delay_sample` includes both converters, and the asynchronous calls are refused.
+        `packet_samples` > 0 makes a PACKET HANDLE (pv_koala_batch_init_packets): its streams take and deliver any number of samples per call,
+        up to `packet_samples`, through `process_packets` / `process_device_packets`; the frame calls are refused on it, `max_frames_per_call`
+        is ceil(packet_samples / frame_length) and `delay_sample` grows by frame_length - 1."""
         if not isinstance(access_key, str) or len(access_key) == 0:
             raise KoalaInvalidArgumentError("`access_key` should be a non-empty string.")
         if not os.path.exists(model_path):
@@ -38,6 +47,8 @@ class KoalaBatch(object):
             raise KoalaInvalidArgumentError("`precision` should be `fp32` or `bf16`.")
         if sample_rate not in (8000, 16000, 32000, 48000):
             raise KoalaInvalidArgumentError("`sample_rate` should be 8000, 16000, 32000 or 48000.")
+        if not isinstance(packet_samples, int) or packet_samples < 0:
+            raise KoalaInvalidArgumentError("`packet_samples` should be a positive number of samples (0: a frame handle).")
         lib = load_library(library_path)
         lib.pv_set_sdk(b'python')
         self._lib = lib
@@ -73,7 +84,15 @@ class KoalaBatch(object):
 
         self._handle = c_void_p()
         prec = PRECISION_BF16 if precision == 'bf16' else PRECISION_FP32
-        if sample_rate == 16000:
+        if packet_samples:
+            lib.pv_koala_batch_init_packets.argtypes = [c_char_p, c_char_p, c_char_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)]
+            lib.pv_koala_batch_init_packets.restype = PicovoiceStatuses
+            lib.pv_koala_batch_process_packets.argtypes = [c_void_p, POINTER(BatchPackets)]
+            lib.pv_koala_batch_process_packets.restype = PicovoiceStatuses
+            status = lib.pv_koala_batch_init_packets(access_key.encode(), model_path.encode(), device.encode(), num_streams, packet_samples,
+                                                     prec, sample_rate, byref(self._handle))
+            max_frames_per_call = -(-packet_samples // (sample_rate * 256 // 16000))
+        elif sample_rate == 16000:
             status = lib.pv_koala_batch_init(access_key.encode(), model_path.encode(), device.encode(), num_streams, max_frames_per_call,
                                              prec, byref(self._handle))
         else:
@@ -85,6 +104,7 @@ class KoalaBatch(object):
             raise_status(lib, status, 'Initialization failed')
         self.num_streams = num_streams
         self.max_frames_per_call = max_frames_per_call
+        self.packet_samples = packet_samples
         self.precision = precision
         self.frame_length = lib.pv_koala_frame_length()
         self.sample_rate = lib.pv_sample_rate()
@@ -317,6 +337,47 @@ class KoalaBatch(object):
         self._check(self._lib.pv_koala_batch_process_chunk_hold(self._handle, num_frames, c_void_p(pcm_ptr), c_void_p(enhanced_ptr), mp),
                     'Processing failed')
 
+    # ---- packet handles (include/pv_koala_batch.h, pv_koala_batch_process_packets)
+
+    def _packets(self, max_samples, counts, pcm_ptr, enhanced_ptr, restart, report_ptr, report_frames):
+        if not self.packet_samples:
+            raise KoalaInvalidArgumentError("not a packet handle: create it with `packet_samples`")
+        n = np.ascontiguousarray(counts, dtype=np.int32)
+        if n.shape != (self.num_streams,):
+            raise KoalaInvalidArgumentError("`counts` must have one entry per stream")
+        r, rp = self._hold_mask(restart) if restart is not None else (None, None)
+        frames = np.zeros(self.num_streams, np.int32)
+        call = BatchPackets(sizeof(BatchPackets), max_samples, n.ctypes.data, pcm_ptr, enhanced_ptr, rp, report_ptr or None, report_frames,
+                            frames.ctypes.data)
+        self._check(self._lib.pv_koala_batch_process_packets(self._handle, byref(call)), 'Processing failed')
+        return frames
+
+    def process_packets(self, pcm: np.ndarray, counts, restart=None, report: bool = False):
+        """One call of a packet handle.  pcm: int16 [num_streams, max_samples] in host memory, of which row b's first counts[b] samples
+        count (0: the stream is stalled and not advanced); `restart`: [num_streams] or None, non-zero = the stream is fresh before this
+        packet.  Returns `enhanced` (same shape; row b's first counts[b] samples are the stream's next output samples, the rest zeros),
+        or `(enhanced, frames, report)` when `report` is true: frames int32 [num_streams] = the frames each stream completed in the call,
+        report float32 [num_streams, max(frames), 4] with stream b's rows [0, frames[b]) filled."""
+        a = np.ascontiguousarray(pcm, dtype=np.int16)
+        if a.ndim != 2 or a.shape[0] != self.num_streams or a.shape[1] < 1:
+            raise KoalaInvalidArgumentError("expected int16 array of shape [%d, max_samples]" % self.num_streams)
+        out = np.zeros_like(a)
+        if not report:
+            self._packets(a.shape[1], counts, a.ctypes.data, out.ctypes.data, restart, None, 0)
+            return out
+        rows = a.shape[1] // self.frame_length + 1
+        rep = np.zeros((self.num_streams, rows, 4), np.float32)
+        frames = self._packets(a.shape[1], counts, a.ctypes.data, out.ctypes.data, restart, rep.ctypes.data, rows)
+        return out, frames, rep[:, :int(frames.max()) if frames.size else 0]
+
+    def process_device_packets(self, max_samples: int, counts, pcm_ptr: int, enhanced_ptr: int, restart=None, report_ptr: int = 0,
+                               report_frames: int = 0) -> np.ndarray:
+        """`process_packets` for device pointers of int16 [num_streams, max_samples] (and float32 [num_streams, report_frames, 4]):
+        `counts` and `restart` are host arrays read before the call returns, the work is enqueued on the handle's stream without a host
+        wait.  Returns frames int32 [num_streams]."""
+        return self._packets(max_samples, counts, c_void_p(pcm_ptr), c_void_p(enhanced_ptr), restart,
+                             c_void_p(report_ptr) if report_ptr else None, report_frames)
+
     def set_min_gain(self, gains, streams=None) -> None:
         """Per-stream attenuation limit as a minimum mask gain in [0, 1] (include/pv_koala_batch.h, pv_koala_batch_set_min_gain): 0 = no
         limit, 1 = bypass with unchanged latency, in between no bin of the stream is attenuated by more than -20 log10(gain) dB.
@@ -393,4 +454,4 @@ class KoalaBatch(object):
             pass
 
 
-__all__ = ['KoalaBatch', 'BatchCall', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']
+__all__ = ['KoalaBatch', 'BatchCall', 'BatchPackets', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']

@@ -35,8 +35,11 @@ def create_batch(
         model_path: Optional[str] = None,
         device: Optional[str] = None,
         library_path: Optional[str] = None,
-        sample_rate: int = 16000) -> KoalaBatch:
-    """`num_streams` independent streams advancing together on one GPU (see KoalaBatch), at 8000, 16000, 32000 or 48000 Hz."""
+        sample_rate: int = 16000,
+        packet_samples: int = 0) -> KoalaBatch:
+    """`num_streams` independent streams advancing together on one GPU (see KoalaBatch), at 8000, 16000, 32000 or 48000 Hz.
+    `packet_samples=N` makes a packet handle: streams that take and deliver any number of samples, up to N, per call
+    (`KoalaBatch.process_packets`; `max_frames_per_call` is then derived from N)."""
     return KoalaBatch(
         access_key=access_key,
         model_path=default_model_path() if model_path is None else model_path,
@@ -45,7 +48,8 @@ def create_batch(
         num_streams=num_streams,
         max_frames_per_call=max_frames_per_call,
         precision=precision,
-        sample_rate=sample_rate)
+        sample_rate=sample_rate,
+        packet_samples=packet_samples)
 
 
 def available_devices(library_path: Optional[str] = None) -> Sequence[str]:

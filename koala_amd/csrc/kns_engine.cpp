@@ -744,6 +744,7 @@ Engine::~Engine() {
     rsf_ring_.release();
     recof_ring_.release();
     mg_ring_.release();
+    pk_ring_.release();
     for (int i = 0; i < 4; ++i)
         if (aev_out_[i]) (void) hipEventDestroy(aev_out_[i]);
     for (int i = 0; i < 2; ++i) {
@@ -868,17 +869,24 @@ bool Engine::reset(const uint8_t *host_mask, std::string *err) {
         }
         r.mask = d_rmask_;
     }
-    launch_reset(r, stream_);
-    if (rate_ != kRate16k) {
-        launch_resample_reset(d_rs_state_[0][0], d_rs_state_[0][1], rs_in_hist(rate_), r.mask, Bpad_, stream_);
-        launch_resample_reset(d_rs_state_[1][0], d_rs_state_[1][1], rs_out_hist(rate_), r.mask, Bpad_, stream_);
-    }
+    launch_resets(r.mask);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         *err = hip_error(e);
         return false;
     }
+    for (int b = 0; pk_max_ && b < B_; ++b)
+        if (!host_mask || host_mask[b]) pk_fill_[b] = 0;
     return true;
+}
+
+void Engine::launch_resets(const uint8_t *d_mask) {
+    launch_reset(reset_args(d_mask), stream_);
+    if (rate_ != kRate16k) {
+        launch_resample_reset(d_rs_state_[0][0], d_rs_state_[0][1], rs_in_hist(rate_), d_mask, Bpad_, stream_);
+        launch_resample_reset(d_rs_state_[1][0], d_rs_state_[1][1], rs_out_hist(rate_), d_mask, Bpad_, stream_);
+    }
+    if (pk_max_) launch_packet_reset(packet_state_args(), d_mask, stream_);
 }
 
 bool Engine::UploadRing::ready(size_t slot_bytes) {
@@ -2213,6 +2221,8 @@ bool Engine::state_ready(std::string *err) {
     int32_t *t = d ? (int32_t *) dalloc((size_t) Bpad_ * 4, false) : nullptr;
     if (t && rate_ != kRate16k && !d_state_rs_) d_state_rs_ = (uint8_t *) dalloc((size_t) B_ * rs_record_bytes(rate_), false);
     if (rate_ != kRate16k && !d_state_rs_) t = nullptr;
+    if (t && pk_max_ && !d_state_pk_) d_state_pk_ = (uint8_t *) dalloc((size_t) B_ * pk_record_bytes(rate_), false);
+    if (pk_max_ && !d_state_pk_) t = nullptr;
     if (!d || !t || !recof_ring_.ready((size_t) Bpad_ * 4)) {
         // (what was allocated stays on the handle's lists and goes with the handle; the next call tries the rest again)
         (void) hipGetLastError();
@@ -2264,8 +2274,8 @@ StateArgs Engine::state_args() const {
     a.fhist = d_fhist_;
     a.rec_of = d_recof_;
     a.records = d_state_;
-    const StateHeader h{kStateMagic, rate_ == kRate16k ? kStateVersion : kStateVersionRate, (uint32_t) taps_, (uint32_t) prec_, model_key_,
-                        rate_ == kRate16k ? 0u : (uint32_t) rate_, 0};
+    const StateHeader h{kStateMagic, pk_max_ ? kStateVersionPacket : rate_ == kRate16k ? kStateVersion : kStateVersionRate, (uint32_t) taps_,
+                        (uint32_t) prec_, model_key_, rate_ == kRate16k && !pk_max_ ? 0u : (uint32_t) rate_, 0};
     memcpy(&a.hdr0, &h, 16);
     memcpy(&a.hdr1, (const char *) &h + 16, 16);
     a.state_bytes = (uint32_t) state_record_bytes(taps_);
@@ -2276,9 +2286,14 @@ StateArgs Engine::state_args() const {
     return a;
 }
 
-void Engine::launch_states(bool import) {
+void Engine::launch_states(bool import, bool packet_part) {
     if (import) launch_state_import(state_args(), stream_);
     else launch_state_export(state_args(), stream_);
+    if (pk_max_ && packet_part) {
+        PacketStateArgs a = packet_state_args();
+        a.import = import ? 1 : 0;
+        launch_packet_state(a, stream_);
+    }
     if (rate_ == kRate16k) return;
     ResampleStateArgs a;
     for (int c = 0; c < 2; ++c) a.state_in[c] = d_rs_state_[0][rs_cur_ ^ c], a.state_out[c] = d_rs_state_[1][rs_cur_ ^ c];
@@ -2296,13 +2311,15 @@ Status Engine::export_state(int count, const int32_t *streams, void *host_record
     if (async_n_ && !drain_async(err)) return Status::kRuntime;
     const Status listed = state_list(count, streams, err);
     if (listed != Status::kOk) return listed;
-    launch_states(false);
+    launch_states(false, true);
     hipError_t e = hipGetLastError();
-    const size_t S = state_bytes(), S1 = state_record_bytes(taps_);
+    const size_t S = state_bytes(), S1 = state_record_bytes(taps_), S2 = rate_ == kRate16k ? 0 : rs_record_bytes(rate_), S3 = S - S1 - S2;
     if (e == hipSuccess && S == S1) e = hipMemcpyAsync(host_records, d_state_, (size_t) count * S, hipMemcpyDeviceToHost, stream_);
     if (e == hipSuccess && S > S1) e = hipMemcpy2DAsync(host_records, S, d_state_, S1, S1, (size_t) count, hipMemcpyDeviceToHost, stream_);
-    if (e == hipSuccess && S > S1)
-        e = hipMemcpy2DAsync((char *) host_records + S1, S, d_state_rs_, S - S1, S - S1, (size_t) count, hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess && S2)
+        e = hipMemcpy2DAsync((char *) host_records + S1, S, d_state_rs_, S2, S2, (size_t) count, hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess && S3)  // (a packet handle's part)
+        e = hipMemcpy2DAsync((char *) host_records + S1 + S2, S, d_state_pk_, S3, S3, (size_t) count, hipMemcpyDeviceToHost, stream_);
     if (e == hipSuccess) e = hipStreamSynchronize(stream_);
     if (e != hipSuccess) {
         (void) hipGetLastError();
@@ -2316,8 +2333,8 @@ Status Engine::import_state(int count, const int32_t *streams, const void *host_
     (void) hipSetDevice(device_);
     if (async_n_ && !drain_async(err)) return Status::kRuntime;
     // every header before anything is written (the list is checked by state_list, which writes only the table)
-    const size_t S = state_bytes(), S1 = state_record_bytes(taps_);
-    const uint32_t want_version = rate_ == kRate16k ? kStateVersion : kStateVersionRate;
+    const size_t S = state_bytes(), S1 = state_record_bytes(taps_), S2 = rate_ == kRate16k ? 0 : rs_record_bytes(rate_), S3 = S - S1 - S2;
+    const uint32_t want_version = pk_max_ ? kStateVersionPacket : rate_ == kRate16k ? kStateVersion : kStateVersionRate;
     for (int i = 0; i < count && count <= B_; ++i) {
         StateHeader h;
         memcpy(&h, (const char *) host_records + (size_t) i * S, sizeof(h));
@@ -2330,8 +2347,14 @@ Status Engine::import_state(int count, const int32_t *streams, const void *host_
             what = std::string("precision is ") + (h.precision == kBf16 ? "bf16" : h.precision == kFp32 ? "fp32" : "unknown") +
                    ", the handle's is " + (prec_ == kBf16 ? "bf16" : "fp32") + " (records do not cross precisions)";
         else if (h.model != model_key_) what = "model hash does not match the handle's model";
-        else if (rate_ != kRate16k && h.sample_rate != (uint32_t) rate_)
+        else if ((rate_ != kRate16k || pk_max_) && h.sample_rate != (uint32_t) rate_)
             what = "sample_rate " + std::to_string(h.sample_rate) + " is not the handle's (" + std::to_string(rate_) + ")";
+        else if (pk_max_) {
+            uint32_t fill;
+            memcpy(&fill, (const char *) host_records + (size_t) i * S + S1 + S2, 4);
+            if (fill >= (uint32_t) rs_frame_length(rate_))
+                what = "fill " + std::to_string(fill) + " is not below the frame length " + std::to_string(rs_frame_length(rate_));
+        }
         if (!what.empty()) {
             *err = "record " + std::to_string(i) + ": " + what + ".";
             return Status::kBadArgument;
@@ -2342,10 +2365,12 @@ Status Engine::import_state(int count, const int32_t *streams, const void *host_
     // (a version-2 record interleaves the two staged parts)
     hipError_t e = S == S1 ? hipMemcpyAsync(d_state_, host_records, (size_t) count * S, hipMemcpyHostToDevice, stream_)
                            : hipMemcpy2DAsync(d_state_, S1, host_records, S, S1, (size_t) count, hipMemcpyHostToDevice, stream_);
-    if (e == hipSuccess && S > S1)
-        e = hipMemcpy2DAsync(d_state_rs_, S - S1, (const char *) host_records + S1, S, S - S1, (size_t) count, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && S2)
+        e = hipMemcpy2DAsync(d_state_rs_, S2, (const char *) host_records + S1, S, S2, (size_t) count, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && S3)
+        e = hipMemcpy2DAsync(d_state_pk_, S3, (const char *) host_records + S1 + S2, S, S3, (size_t) count, hipMemcpyHostToDevice, stream_);
     if (e == hipSuccess) {
-        launch_states(true);
+        launch_states(true, true);
         e = hipGetLastError();
     }
     // (the copy may read pageable records when it runs, not when it is enqueued: the call returns once the stream has passed it)
@@ -2354,6 +2379,11 @@ Status Engine::import_state(int count, const int32_t *streams, const void *host_
         (void) hipGetLastError();
         *err = hip_error(e);
         return Status::kRuntime;
+    }
+    for (int i = 0; pk_max_ && i < count; ++i) {  // the host mirror of fill follows the records
+        uint32_t fill;
+        memcpy(&fill, (const char *) host_records + (size_t) i * S + S1 + S2, 4);
+        pk_fill_[streams ? streams[i] : i] = (int32_t) fill;
     }
     return Status::kOk;
 }
@@ -2374,18 +2404,205 @@ Status Engine::process(const Call &c, std::string *err) {
     if (async_n_ && !drain_async(err)) return Status::kRuntime;
     const Status listed = state_list((int) held.size(), held.data(), err);
     if (listed != Status::kOk) return listed;
-    launch_states(false);
+    launch_states(false, false);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         *err = hip_error(e);
         return Status::kRuntime;
     }
     if (!advance(c, err)) return Status::kRuntime;  // (a refused call has advanced nothing)
-    launch_states(true);
+    launch_states(true, false);
     e = hipGetLastError();
     if (e != hipSuccess) {
         *err = hip_error(e);
         return Status::kRuntime;
+    }
+    return Status::kOk;
+}
+
+// ------------------------------------------------------------------------------------------------ packet handles
+
+bool Engine::enable_packets(int max_samples, std::string *err) {
+    (void) hipSetDevice(device_);
+    const int F = rs_frame_length(rate_);
+    // a stream completes at most floor((F - 1 + max_samples) / F) = ceil(max_samples / F) = Tmax frames in a call
+    const size_t K = (size_t) Tmax_;
+    const size_t tab_bytes = ((size_t) Bpad_ + 2 + K) * 4 + (size_t) Bpad_;  // counts, the number of sub-calls, <= K + 1 cuts; the mask
+    d_pk_pin_ = (int16_t *) dalloc((size_t) Bpad_ * F * 2, true);
+    d_pk_pout_ = (int16_t *) dalloc((size_t) Bpad_ * F * 2, true);
+    d_pk_fill_[0] = (int32_t *) dalloc((size_t) Bpad_ * 4, true);
+    d_pk_fill_[1] = (int32_t *) dalloc((size_t) Bpad_ * 4, true);
+    d_pk_in_ = (int16_t *) dalloc((size_t) B_ * K * F * 2, false);
+    d_pk_out_ = (int16_t *) dalloc((size_t) B_ * K * F * 2, false);
+    d_pk_rep_ = (float *) dalloc((size_t) B_ * K * 16, false);
+    d_pk_tab_ = (int32_t *) dalloc(tab_bytes, false);
+    if (!d_pk_pin_ || !d_pk_pout_ || !d_pk_fill_[0] || !d_pk_fill_[1] || !d_pk_in_ || !d_pk_out_ || !d_pk_rep_ || !d_pk_tab_ ||
+        !pk_ring_.ready(tab_bytes)) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the buffers of a packet handle.";
+        return false;
+    }
+    pk_fill_.assign((size_t) B_, 0);
+    pk_max_ = max_samples;
+    return true;
+}
+
+PacketStateArgs Engine::packet_state_args() const {
+    PacketStateArgs a;
+    a.pin = d_pk_pin_, a.pout = d_pk_pout_;
+    a.fill_in = d_pk_fill_[0], a.fill_out = d_pk_fill_[1];
+    a.rec_of = d_recof_;
+    a.records = d_state_pk_;
+    a.rec_bytes = (uint32_t) pk_record_bytes(rate_);
+    a.Bpad = Bpad_, a.F = rs_frame_length(rate_), a.import = 0;
+    return a;
+}
+
+// One call of a packet handle (fourth extension; section 6).  The plan is made on the host from the mirror of fill:
+// stream b completes k_b = (fill_b + counts[b]) / F frames; the sub-calls are cut at every distinct non-zero k_b (k_b <= max_frames always), and
+// sub-call [c0, c1) holds the streams with k_b < c1 (koala_amd/packets.py restates the plan).  Everything goes onto the handle's stream:
+// the call's table, the masked reset of `restart`, packet_in_kernel, the sub-calls through process() -- routes, held streams, rate
+// stages, attenuation limit and report as they are -- and packet_out_kernel.  Host pointers: one copy in, that, one copy out, a wait.
+Status Engine::run_packets(const PacketCall &c, std::string *err) {
+    const int F = rs_frame_length(rate_);
+    if (c.max_samples < 1 || c.max_samples > pk_max_) {
+        *err = "`max_samples` " + std::to_string(c.max_samples) + " is outside [1, " + std::to_string(pk_max_) + "].";
+        return Status::kBadArgument;
+    }
+    std::vector<int32_t> k((size_t) B_);
+    std::vector<int32_t> cuts{0};
+    bool any_restart = false, any_count = false;
+    int kmax = 0;
+    for (int b = 0; b < B_; ++b) {
+        if (c.counts[b] < 0 || c.counts[b] > c.max_samples) {
+            *err = "`counts[" + std::to_string(b) + "]` = " + std::to_string(c.counts[b]) + " is outside [0, " + std::to_string(c.max_samples) + "].";
+            return Status::kBadArgument;
+        }
+        const bool fresh = c.restart && c.restart[b];
+        any_restart = any_restart || fresh;
+        any_count = any_count || c.counts[b] > 0;
+        k[b] = ((fresh ? 0 : pk_fill_[b]) + c.counts[b]) / F;
+        kmax = std::max(kmax, k[b]);
+    }
+    if (c.report && c.report_frames < kmax) {
+        *err = "`report_frames` " + std::to_string(c.report_frames) + " is below the " + std::to_string(kmax) + " frames a stream completes in this call.";
+        return Status::kBadArgument;
+    }
+    (void) hipSetDevice(device_);
+    const PointerKind kin = pointer_kind(c.pcm), kout = pointer_kind(c.out);
+    if ((kin == kPtrDevice) != (kout == kPtrDevice)) {
+        *err = "`pcm` and `enhanced` must both be host or both be device memory.";
+        return Status::kBadArgument;
+    }
+    const bool host = kin != kPtrDevice;
+    if (c.report && (pointer_kind(c.report) == kPtrDevice) == host) {
+        *err = "`report` must be memory of the same kind as `enhanced`: host with host, device with device.";
+        return Status::kBadArgument;
+    }
+    if (!any_count && !any_restart) {  // every stream stalled: nothing to do
+        for (int b = 0; c.frames && b < B_; ++b) c.frames[b] = 0;
+        return Status::kOk;
+    }
+    {  // the sub-calls: frames [cuts[l], cuts[l + 1])
+        std::vector<int32_t> ks(k);
+        std::sort(ks.begin(), ks.end());
+        for (int32_t v : ks) {
+            if (v > cuts.back()) cuts.push_back(v);  // (v <= Tmax: no sub-call is longer than the inner engine's max_frames)
+        }
+    }
+    const int nsub = (int) cuts.size() - 1;
+    const size_t io_bytes = (size_t) B_ * c.max_samples * 2;
+    if (host && !d_pk_io_) d_pk_io_ = (int16_t *) dalloc((size_t) B_ * pk_max_ * 2, false);
+    if (host && c.report && !d_pk_user_rep_) d_pk_user_rep_ = (float *) dalloc((size_t) B_ * Tmax_ * 16, false);
+    if (host && (!d_pk_io_ || (c.report && !d_pk_user_rep_))) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the staging buffer of host-memory calls.";
+        return Status::kRuntime;
+    }
+    // the call's table, and the restart mask behind it
+    const size_t tab_ints = (size_t) Bpad_ + 2 + (size_t) Tmax_;
+    const int slot = pk_ring_.acquire();
+    if (slot < 0) {
+        *err = hip_last_error();
+        return Status::kRuntime;
+    }
+    int32_t *tab = (int32_t *) pk_ring_.host[slot];
+    uint8_t *mask = (uint8_t *) (tab + tab_ints);
+    memset(tab, 0, tab_ints * 4 + (size_t) Bpad_);
+    memcpy(tab, c.counts, (size_t) B_ * 4);
+    tab[Bpad_] = nsub;
+    memcpy(tab + Bpad_ + 1, cuts.data(), cuts.size() * 4);
+    for (int b = 0; any_restart && b < B_; ++b) mask[b] = c.restart[b] ? 1 : 0;
+    if (hipMemcpyAsync(d_pk_tab_, tab, tab_ints * 4 + (size_t) Bpad_, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+        !pk_ring_.uploaded(slot, stream_)) {
+        *err = hip_last_error();
+        return Status::kRuntime;
+    }
+    if (any_restart) {
+        launch_resets((const uint8_t *) (d_pk_tab_ + tab_ints));
+        for (int b = 0; b < B_; ++b)
+            if (c.restart[b]) pk_fill_[b] = 0;
+    }
+    if (host && hipMemcpyAsync(d_pk_io_, c.pcm, io_bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) {
+        *err = hip_last_error();
+        return Status::kRuntime;
+    }
+    PacketArgs a;
+    a.user_in = host ? d_pk_io_ : c.pcm;
+    a.user_out = host ? d_pk_io_ : c.out;
+    a.tab = d_pk_tab_;
+    a.pin = d_pk_pin_, a.pout = d_pk_pout_;
+    a.fill_in = d_pk_fill_[0], a.fill_out = d_pk_fill_[1];
+    a.frames = d_pk_in_;
+    a.sub_report = d_pk_rep_;
+    a.report = !c.report ? nullptr : host ? d_pk_user_rep_ : c.report;
+    a.report_frames = host ? kmax : c.report_frames;
+    a.max_samples = c.max_samples, a.B = B_, a.Bpad = Bpad_, a.F = F;
+    launch_packet_in(a, stream_);
+    if (hipGetLastError() != hipSuccess) {
+        *err = hip_last_error();
+        return Status::kRuntime;
+    }
+    std::vector<uint8_t> hold((size_t) B_);
+    for (int l = 0; l < nsub; ++l) {
+        const int c0 = cuts[l], c1 = cuts[l + 1];
+        bool held = false;
+        for (int b = 0; b < B_; ++b) held = (hold[b] = k[b] < c1) || held;
+        Call inner{c1 - c0, d_pk_in_ + (size_t) B_ * F * c0, d_pk_out_ + (size_t) B_ * F * c0};
+        inner.hold = held ? hold.data() : nullptr;
+        inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
+        inner.report = c.report ? d_pk_rep_ + (size_t) B_ * c0 * 4 : nullptr;
+        const Status st = process(inner, err);
+        if (st != Status::kOk) return Status::kRuntime;
+    }
+    a.frames = d_pk_out_;
+    launch_packet_out(a, stream_);
+    if (hipGetLastError() != hipSuccess) {
+        *err = hip_last_error();
+        return Status::kRuntime;
+    }
+    for (int b = 0; b < B_; ++b) {
+        pk_fill_[b] = pk_fill_[b] + c.counts[b] - k[b] * F;
+        if (c.frames) c.frames[b] = k[b];
+    }
+    if (host) {
+        pk_host_out_.resize((size_t) B_ * c.max_samples);
+        hipError_t e = hipMemcpyAsync(pk_host_out_.data(), d_pk_io_, io_bytes, hipMemcpyDeviceToHost, stream_);
+        if (e == hipSuccess && c.report && kmax) {
+            pk_host_rep_.resize((size_t) B_ * kmax * 4);
+            e = hipMemcpyAsync(pk_host_rep_.data(), d_pk_user_rep_, (size_t) B_ * kmax * 16, hipMemcpyDeviceToHost, stream_);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+        if (e != hipSuccess) {
+            (void) hipGetLastError();
+            *err = hip_error(e);
+            return Status::kRuntime;
+        }
+        // (only a row's first counts[b] samples, and a stream's first k_b report rows, are the caller's to be written)
+        for (int b = 0; b < B_; ++b) {
+            memcpy(c.out + (size_t) b * c.max_samples, pk_host_out_.data() + (size_t) b * c.max_samples, (size_t) c.counts[b] * 2);
+            if (c.report) memcpy(c.report + (size_t) b * c.report_frames * 4, pk_host_rep_.data() + (size_t) b * kmax * 4, (size_t) k[b] * 16);
+        }
     }
     return Status::kOk;
 }

@@ -67,6 +67,20 @@ struct Call {
 // overlapping buffers).
 enum class Status { kOk, kBadArgument, kRuntime };
 
+// One call of a packet handle (include/pv_koala_batch.h, pv_koala_batch_process_packets): stream b gives and takes counts[b] samples.
+struct PacketCall {
+    int max_samples;                   // row length of pcm / out, 1 .. the handle's
+    const int32_t *counts;             // host [num_streams], each in [0, max_samples]
+    const int16_t *pcm;                // [num_streams][max_samples], host or device
+    int16_t *out;                      // the same kind
+    const uint8_t *restart = nullptr;  // host [num_streams] or nullptr: the stream is fresh before this packet
+    float *report = nullptr;           // [num_streams][report_frames][4], memory of out's kind, or nullptr
+    int report_frames = 0;
+    int32_t *frames = nullptr;         // host [num_streams] or nullptr, out: frames completed by the call
+    const float *min_gain = nullptr;   // as Call's
+    unsigned min_gain_rev = 0;
+};
+
 class Engine {
 public:
     // returns nullptr and fills *err on failure (*oom set when the failure was an allocation)
@@ -103,9 +117,15 @@ public:
     // its feature context is the other engine's) and every index (outside [0, num_streams), the same slot twice) BEFORE anything is written,
     // returns when the host records may be reused, and its scatter is ordered on the stream in front of the next call.  A failed call
     // leaves all state as it was.
-    size_t state_bytes() const { return state_record_bytes(taps_, rate_); }
+    size_t state_bytes() const { return state_record_bytes(taps_, rate_) + (pk_max_ ? pk_record_bytes(rate_) : 0); }
     Status export_state(int count, const int32_t *streams, void *host_records, std::string *err);
     Status import_state(int count, const int32_t *streams, const void *host_records, std::string *err);
+
+    // ---- packet handles (fourth extension).  enable_packets, once, right after create(): the handle's streams take
+    // and deliver up to max_samples samples per call through run_packets; the frame entries above are then the owner's to refuse.
+    bool enable_packets(int max_samples, std::string *err);
+    int packet_samples() const { return pk_max_; }  // 0: a frame handle
+    Status run_packets(const PacketCall &c, std::string *err);
 
     void profile_enable(bool on);
     bool profile_read(double *ms, int64_t *launches, std::string *err);
@@ -121,7 +141,22 @@ private:
     bool advance(const Call &c, std::string *err) { return rate_ == kRate16k ? run_call(c, err) : run_call_rate(c, err); }
     bool run_call_rate(const Call &c, std::string *err);
     bool rate_ready(bool host_staging, bool reset_flags, std::string *err);
-    void launch_states(bool import);  // the state kernels of export / import / held streams: the engine's and, at such a rate, the stages'
+    // the state kernels of export / import / held streams: the engine's and, at such a rate, the stages'; packet_part: and a packet handle's
+    // (not for held streams: a sub-call of a packet call does not touch the packetiser's state, whose two lengths differ inside a call)
+    void launch_states(bool import, bool packet_part);
+    void launch_resets(const uint8_t *d_mask);  // every reset kernel of the handle (d_mask: device [Bpad], null: every stream)
+    // packet handles: the packetiser's state (kns_kernels.h, PacketArgs), the sub-calls' stacked frame matrices and reports
+    // [B][Tmax F] / [B][Tmax][4], the staging of host-pointer calls, the call table and its upload ring, and the HOST MIRROR of
+    // fill, from which a call is planned without a look at the device (updated by calls, resets and import_state)
+    int pk_max_ = 0;
+    int16_t *d_pk_pin_ = nullptr, *d_pk_pout_ = nullptr, *d_pk_in_ = nullptr, *d_pk_out_ = nullptr, *d_pk_io_ = nullptr;
+    int32_t *d_pk_fill_[2] = {nullptr, nullptr}, *d_pk_tab_ = nullptr;
+    float *d_pk_rep_ = nullptr, *d_pk_user_rep_ = nullptr;
+    uint8_t *d_state_pk_ = nullptr;  // the packet part of the staged stream records [B][pk_record_bytes]
+    std::vector<int32_t> pk_fill_;
+    std::vector<int16_t> pk_host_out_;  // host-pointer calls: the whole output matrix, of which the rows' first counts[b] samples go on
+    std::vector<float> pk_host_rep_;
+    PacketStateArgs packet_state_args() const;
     int rate_ = kRate16k;
     int16_t *d_rs_state_[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [in-stage, out-stage][ping-pong copy], [Bpad][hist] each
     int rs_cur_ = 0;
@@ -261,7 +296,7 @@ private:
     // Per-frame stream resets (kns_engine.cpp, begin_resets).  A call's packed table -- per (m-tile, frame) the rows that restart, uint32
     // [mtiles][T] -- goes through a slot of rs_ring_ to d_rs_ on the stream that runs the call's kernels, a frame-0 mask to d_rmask_.
     // The table belongs to its call: process*() own it and hand it to run_device with every slice.
-    UploadRing rs_ring_, rsf_ring_;  // (rsf_ring_: the sample-rate stages' copy of a call's reset flags)
+    UploadRing rs_ring_, rsf_ring_, pk_ring_;  // (rsf_ring_: the sample-rate stages' copy of a call's reset flags; pk_ring_: a packet call's table)
     unsigned *d_rs_ = nullptr;
     struct ResetTable {
         int slot = -1, T = 0;        // the call's ring slot (-1: no stream restarts after frame 0, there is no table) and its length

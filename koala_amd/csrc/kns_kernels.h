@@ -325,6 +325,39 @@ struct ResampleStateArgs {
     int Bpad, import;               // import != 0: records -> state
 };
 void launch_resample_state(const ResampleStateArgs &a, hipStream_t s);
+// ---- packet handles (kns_packet.hip; DESIGN.md section 2, fourth extension): streams that take and deliver any number of samples per call.
+// Per stream on top of everything above: fill = (samples since the last reset) mod F, `fill` pending input samples and F - 1 - fill pending
+// output samples, oldest first.  On the device the two parts are two rows of F int16 (pin, pout: each kernel rewrites its own in place) with
+// a length each (fill_in, fill_out: equal between calls, apart only between a call's two kernels).
+// Version 3, of packet handles: the header's sample_rate field is always set, and behind the version-1 (16 kHz) or version-2 parts follow
+// uint32 fill and int16[F - 1] = [pending input | pending output], zero-padded to whole 16-byte words: 272 / 528 / 1040 / 1552 bytes.
+constexpr uint32_t kStateVersionPacket = 3;
+KNS_HD size_t pk_record_bytes(int rate) { return ((size_t) 4 + (size_t) (rs_frame_length(rate) - 1) * 2 + 15) / 16 * 16; }
+struct PacketArgs {
+    const int16_t *user_in;  // [B][max_samples]: row b's first tab[b] samples count (packet_in_kernel)
+    int16_t *user_out;       // [B][max_samples]: row b's first tab[b] samples are written (packet_out_kernel)
+    // the call's table, device memory: int32 counts[Bpad], nsub, cut[nsub + 1] (sub-call l = frames [cut[l], cut[l + 1]) of the call)
+    const int32_t *tab;
+    int16_t *pin, *pout;          // [Bpad][F]
+    int32_t *fill_in, *fill_out;  // [Bpad]
+    // the sub-calls' dense frame matrices [B][T_l F], stacked: sub-call l starts B F cut[l] samples in (in: their input, out: their output)
+    int16_t *frames;
+    const float *sub_report;  // the sub-calls' reports [B][T_l][4], stacked the same way
+    float *report;            // optional: [B][report_frames][4], stream b's rows [0, k_b) are written
+    int report_frames, max_samples, B, Bpad, F;
+};
+void launch_packet_in(const PacketArgs &a, hipStream_t s);
+void launch_packet_out(const PacketArgs &a, hipStream_t s);
+struct PacketStateArgs {
+    int16_t *pin, *pout;
+    int32_t *fill_in, *fill_out;
+    const int32_t *rec_of;  // [Bpad] (launch_packet_state)
+    uint8_t *records;       // the packet part of stream records [count][rec_bytes] (device)
+    uint32_t rec_bytes;
+    int Bpad, F, import;
+};
+void launch_packet_reset(const PacketStateArgs &a, const uint8_t *mask, hipStream_t s);  // mask: device [Bpad], null: every stream
+void launch_packet_state(const PacketStateArgs &a, hipStream_t s);
 // last node of a captured one-frame replay: ++*counter (device memory), published to *host_word (page-locked host memory)
 void launch_frame_done(unsigned *counter, unsigned *host_word, hipStream_t s);
 

@@ -20,6 +20,7 @@
 #include "../../include/pv_koala.h"
 #include "../../include/pv_koala_batch.h"
 #include "kns_engine.h"
+#include "pv_api_internal.h"
 
 #ifdef KNS_TIMING
 namespace kns {
@@ -27,24 +28,9 @@ void read_timing(unsigned long long *out);
 }
 #endif
 
-// The attenuation limit of a handle (include/pv_koala_batch.h, pv_koala_batch_set_min_gain): configuration that the handle owns and every
-// call carries to the engine (kns::Call::min_gain) -- the engine keeps nothing of it between calls but its device table.
-struct MinGain {
-    std::vector<float> gain;  // [num_streams], every value in [0, 1]
-    unsigned rev = 0;         // counts the accepted changes: the engine uploads the table when it has not seen this one
-    bool any = false;         // some gain is non-zero (none: the calls are the plain calls, no table at all)
-};
-struct pv_koala {
-    kns::Engine *engine;
-    MinGain limit;
-};
-struct pv_koala_batch {
-    kns::Engine *engine;
-    MinGain limit;
-    int32_t sample_rate = kns::kRate16k;  // fixed at creation (pv_koala_batch_init_rate); the engine was made with the same value
-};
-
 namespace {
+
+using kns_api::guarded;
 
 const char kBuildId[] = "a355c0a";  // 7 hex digits, as the reference prints in front of every message
 
@@ -62,27 +48,6 @@ void push_error(unsigned code, const char *fmt, ...) {
     if (t_stack.size() < 8) t_stack.push_back(line);
 }
 
-// No C++ exception may cross the C ABI (the callers are ctypes / dlsym hosts: an escaping exception is std::terminate).  Every
-// entry point that reaches engine code runs it through this: bad_alloc -> OUT_OF_MEMORY, anything else -> RUNTIME_ERROR.
-template <class F>
-pv_status_t guarded(F &&body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        push_error(0x65, "Failed to allocate memory.");
-        return PV_STATUS_OUT_OF_MEMORY;
-    } catch (const std::length_error &) {
-        push_error(0x65, "Failed to allocate memory.");
-        return PV_STATUS_OUT_OF_MEMORY;
-    } catch (const std::exception &e) {
-        push_error(0x339, "Unexpected failure: %s", e.what());
-        return PV_STATUS_RUNTIME_ERROR;
-    } catch (...) {
-        push_error(0x339, "Unexpected failure.");
-        return PV_STATUS_RUNTIME_ERROR;
-    }
-}
-
 // ---- the argument checks that several entry points share: the first failure's message and status, in this order
 pv_status_t check_object(const void *object) {
     if (!object) {
@@ -94,6 +59,10 @@ pv_status_t check_object(const void *object) {
 
 pv_status_t check_call(const pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm, const int16_t *enhanced) {
     if (!object) return check_object(object);
+    if (object->packet_samples) {  // every frame entry point comes through here
+        push_error(0x66, "Frame calls are not available on a packet handle: its streams advance through pv_koala_batch_process_packets.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
     if (!pcm || !enhanced) {
         push_error(0x64, "Argument `%s` is NULL.", pcm ? "enhanced" : "pcm");
         return PV_STATUS_INVALID_ARGUMENT;
@@ -162,6 +131,24 @@ pv_status_t advance(kns::Engine *engine, const MinGain &limit, kns::Call call, b
         return status == kns::Status::kOk ? PV_STATUS_SUCCESS : engine_failure(status, async ? 0x33A : 0x337, err);
     });
 }
+
+}  // namespace
+
+// what the other translation units of the C ABI (pv_api_packets.cpp) share with this one: pv_api_internal.h
+namespace kns_api {
+void clear_errors() { t_stack.clear(); }
+void push_error(unsigned code, const char *fmt, ...) {
+    char text[768];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(text, sizeof(text), fmt, ap);
+    va_end(ap);
+    ::push_error(code, "%s", text);
+}
+pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std::string &err) { return ::engine_failure(status, runtime_code, err); }
+}  // namespace kns_api
+
+namespace {
 
 std::mutex g_sdk_mutex;
 std::string g_sdk = "c";
@@ -655,7 +642,8 @@ PV_API pv_status_t pv_koala_batch_state_size(const pv_koala_batch_t *object, int
         push_error(0x64, "Argument `%s` is NULL.", object ? "num_bytes" : "object");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    *num_bytes = (int32_t) kns::state_record_bytes(object->engine->front_taps(), object->sample_rate);
+    *num_bytes = (int32_t) (kns::state_record_bytes(object->engine->front_taps(), object->sample_rate) +
+                            (object->packet_samples ? kns::pk_record_bytes(object->sample_rate) : 0));
     return PV_STATUS_SUCCESS;
 }
 
@@ -732,7 +720,9 @@ PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, i
         push_error(0x64, "Argument `%s` is NULL.", object ? "delay_sample" : "object");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    *delay_sample = kns::rs_frame_length(object->sample_rate) + kns::rs_delay(object->sample_rate);
+    // (a packet handle: and the F - 1 samples in front of its output stream)
+    *delay_sample = kns::rs_frame_length(object->sample_rate) + kns::rs_delay(object->sample_rate) +
+                    (object->packet_samples ? kns::rs_frame_length(object->sample_rate) - 1 : 0);
     return PV_STATUS_SUCCESS;
 }
 

@@ -1,0 +1,60 @@
+// pv_api_internal.h -- what the translation units of the C ABI share: the handles behind the opaque pointers, the calling thread's error
+// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_packets.cpp (packet handles) uses it.  Nothing here leaves the library.
+#pragma once
+
+#include <new>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/pv_koala.h"
+#include "../../include/pv_koala_batch.h"
+#include "kns_engine.h"
+
+// The attenuation limit of a handle (include/pv_koala_batch.h, pv_koala_batch_set_min_gain): configuration that the handle owns and every
+// call carries to the engine (kns::Call::min_gain) -- the engine keeps nothing of it between calls but its device table.
+struct MinGain {
+    std::vector<float> gain;  // [num_streams], every value in [0, 1]
+    unsigned rev = 0;         // counts the accepted changes: the engine uploads the table when it has not seen this one
+    bool any = false;         // some gain is non-zero (none: the calls are the plain calls, no table at all)
+};
+struct pv_koala {
+    kns::Engine *engine;
+    MinGain limit;
+};
+struct pv_koala_batch {
+    kns::Engine *engine;
+    MinGain limit;
+    int32_t sample_rate = kns::kRate16k;  // fixed at creation (pv_koala_batch_init_rate); the engine was made with the same value
+    int32_t packet_samples = 0;           // a packet handle's max_samples_per_call (pv_koala_batch_init_packets); 0: a frame handle
+};
+
+namespace kns_api {
+
+void clear_errors();                                   // every entry point first: the calling thread's error stack is emptied
+void push_error(unsigned code, const char *fmt, ...);  // one message onto it (at most 8 are kept)
+// what an engine call that did not succeed leaves on the stack: a refused argument, or a failure under the entry point's own code
+pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std::string &err);
+
+// No C++ exception may cross the C ABI (the callers are ctypes / dlsym hosts: an escaping exception is std::terminate).  Every
+// entry point that reaches engine code runs it through this: bad_alloc -> OUT_OF_MEMORY, anything else -> RUNTIME_ERROR.
+template <class F>
+pv_status_t guarded(F &&body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        push_error(0x65, "Failed to allocate memory.");
+        return PV_STATUS_OUT_OF_MEMORY;
+    } catch (const std::length_error &) {
+        push_error(0x65, "Failed to allocate memory.");
+        return PV_STATUS_OUT_OF_MEMORY;
+    } catch (const std::exception &e) {
+        push_error(0x339, "Unexpected failure: %s", e.what());
+        return PV_STATUS_RUNTIME_ERROR;
+    } catch (...) {
+        push_error(0x339, "Unexpected failure.");
+        return PV_STATUS_RUNTIME_ERROR;
+    }
+}
+
+}  // namespace kns_api

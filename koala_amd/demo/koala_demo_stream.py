@@ -53,6 +53,69 @@ def frames_from_wav(path, frame_length, sample_rate):
         yield frame
 
 
+def run_in_packets(args):
+    """--packet-ms: the stream arrives in packets of 10 or 20 ms, not in frames, and goes through a packet handle (one stream of
+    `koala_amd.create_batch(..., packet_samples=N)`): every packet returns as many samples as it brought, `delay_sample` later.
+    --meter and --reference_output_path work as with frames: the report rows are those of the frames a packet completes."""
+    import os
+    from koala_amd import report
+    rate = 16000  # the rate the handle is made at; the packet length follows from it
+    batch = koala_amd.create_batch(args.access_key, 1, precision=args.precision or os.environ.get('KOALA_AMD_PRECISION', 'fp32'),
+                                   model_path=args.model_path, device=args.device, library_path=args.library_path,
+                                   sample_rate=rate, packet_samples=rate * args.packet_ms // 1000)
+    n, lat, packets, samples, frames = batch.packet_samples, [], 0, 0, 0
+    meter = []  # report rows since the last printed line
+    source = frames_from_wav(args.input_path, n, batch.sample_rate) if args.input_path else frames_from_raw(sys.stdin.buffer, n)
+    batch.set_attenuation_limit(args.attenuation_limit_db)
+    t_start = time.perf_counter()
+    try:
+        with contextlib.ExitStack() as stack:
+            def open_wav(path):
+                w = stack.enter_context(wave.open(path, 'wb'))
+                w.setnchannels(1), w.setsampwidth(2), w.setframerate(batch.sample_rate)
+                return w
+            out = open_wav(args.output_path)
+            ref = open_wav(args.reference_output_path) if args.reference_output_path else None
+            print('Listening in packets of %d ms (%d samples; a frame is %d)... (press Ctrl+C to stop)' % (args.packet_ms, n, batch.frame_length))
+            for packet in source:
+                if args.realtime:
+                    due = t_start + samples / batch.sample_rate
+                    if due > time.perf_counter():
+                        time.sleep(due - time.perf_counter())
+                t0 = time.perf_counter()
+                if args.meter > 0:
+                    enhanced, done, rows = batch.process_packets(packet[None], [n], report=True)
+                    enhanced = enhanced[0]
+                else:
+                    enhanced = batch.process_packets(packet[None], [n])[0]
+                lat.append(time.perf_counter() - t0)
+                if args.meter > 0:
+                    for row in rows[0, :int(done[0])]:
+                        frames += 1
+                        meter.append(row)
+                        if len(meter) == args.meter:
+                            total = np.sum(np.array(meter, np.float64), axis=0)  # (energies and mask sums add up over the N frames)
+                            total[2] /= len(meter)
+                            print('frame %6d  in %7.1f dBFS  suppression %6.1f dB  mean gain %.3f' %
+                                  (frames, report.input_dbfs(total / [len(meter), len(meter), 1, 1]), report.suppression_db(total),
+                                   report.mean_gain(total)))
+                            meter = []
+                out.writeframes(enhanced.astype('<i2').tobytes())
+                if ref is not None:
+                    ref.writeframes(packet.astype('<i2').tobytes())
+                packets, samples = packets + 1, samples + n
+    except KeyboardInterrupt:
+        print('Stopping...')
+    finally:
+        delay, rate = batch.delay_sample, batch.sample_rate
+        batch.delete()
+    if packets:
+        a = np.array(lat) * 1e6
+        print('%d packets (%.2f s of audio); process_packets() latency p50 %.0f us, p99 %.0f us; delay %d samples' %
+              (packets, samples / float(rate), np.percentile(a, 50), np.percentile(a, 99), delay))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='frame-by-frame noise suppression of a live PCM stream')
     ap.add_argument('--access_key', default='koala-amd', help='accepted for interface compatibility; not checked')
@@ -69,6 +132,8 @@ def main(argv=None):
                     help='suppress by at most this many dB (0: bypass with unchanged latency; default: unlimited)')
     ap.add_argument('--meter', type=int, default=0, metavar='N',
                     help='every N frames print input level (dBFS), suppression (dB) and mean mask gain, from the frame report')
+    ap.add_argument('--packet-ms', dest='packet_ms', type=int, default=0, choices=[10, 20],
+                    help='feed the stream in packets of this many ms through a packet handle instead of in 16 ms frames')
     ap.add_argument('--show_devices', action='store_true')
     args = ap.parse_args(argv)
 
@@ -81,6 +146,8 @@ def main(argv=None):
         if p is not None and not p.lower().endswith('.wav'):
             raise ValueError('Given output paths must have WAV file extension')
 
+    if args.packet_ms:
+        return run_in_packets(args)
     if args.precision is not None:
         import os
         os.environ['KOALA_AMD_PRECISION'] = args.precision
