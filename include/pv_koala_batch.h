@@ -268,6 +268,56 @@ typedef struct {
 } pv_koala_batch_packets_t;
 PV_API pv_status_t pv_koala_batch_process_packets(pv_koala_batch_t *object, const pv_koala_batch_packets_t *call);
 
+/* SAMPLE FORMATS: batch handles that take and deliver float32 or G.711 samples, converted on the device.  Telephony holds 8 kHz G.711, one
+ * byte per sample; WebRTC and everything that arrives as a tensor holds float32 in [-1, 1).  A batch handle has a sample format, fixed at
+ * creation and orthogonal to its rate and to frame / packet kind (fifth extension):
+ *   PV_KOALA_SAMPLE_S16   int16   the handle as it has always been
+ *   PV_KOALA_SAMPLE_F32   float   in: NaN -> 0, else x * 32768 rounded half away from zero and clipped to [-32768, 32767]; out: s / 32768
+ *   PV_KOALA_SAMPLE_ULAW  uint8   ITU G.711 mu-law on a 16-bit scale (255 levels in +-32124; the encoder truncates; 0x7F decodes to 0 and
+ *                                 0 encodes to 0xFF)
+ *   PV_KOALA_SAMPLE_ALAW  uint8   ITU G.711 A-law on a 16-bit scale (256 levels in +-32256; the encoder truncates)
+ * A call of such a handle is: decode every sample the call reads -> the S16 handle's call, unchanged -> encode every sample the call
+ * writes.  So its output is exactly encode(S16 handle(decode(input))) in both precisions, and everything else a handle does -- rates,
+ * frame report (rows of the decoded stream), attenuation limit, resets of every kind, held streams, packet calls with stalled and
+ * restarting streams -- is the S16 handle's.  The engine's samples stay int16 inside: F32 is an input / output form, not a wider path
+ * (for inputs s / 32768 an F32 handle is the S16 handle value for value).  The format is CONFIGURATION of the handle, not stream state:
+ * delay_sample and frame_length (in samples), state_size and the stream record (version and bytes) are the S16 handle's, and a record
+ * written by a handle of one format imports into a handle of another that matches in model, precision, rate and kind.  A packet handle's
+ * leading F - 1 output zeros are encode(0): 0.0f, 0xFF, 0xD5.
+ *
+ * pv_koala_batch_init_config is the one constructor for every kind of batch handle.  With PV_KOALA_SAMPLE_S16 the handle is exactly what
+ * pv_koala_batch_init / _init_rate / _init_packets returns for the other members.  PV_STATUS_INVALID_ARGUMENT with a message on the
+ * error stack: a NULL config, a struct_size that is not sizeof(pv_koala_batch_config_t), a sample_format outside 0 ... 3, and whatever
+ * the three constructors refuse.
+ *
+ * THE PROCESSING ENTRY POINTS KEEP THEIR SIGNATURES (there are no void* twins).  On a handle with a format, every `pcm` and `enhanced` --
+ * of pv_koala_batch_process, _process_chunk, _resets, _hold, _process_call and _process_packets -- points to elements of the handle's
+ * format behind its int16_t type: float[...] or uint8_t[...] of the documented shape, cast by the caller.  A device pointer need be
+ * aligned to its element only.  Host pointers: one copy in of the format's bytes, the device route, one copy out, then synchronise;
+ * `pcm` and `enhanced` may overlap in any way, with host and with device pointers (every extent is in bytes of the format; the input is
+ * consumed before the output is written).  A packet call writes row b's first counts[b] elements only.  pv_koala_batch_host_alloc takes
+ * bytes: num_streams * samples * (4, 1 or 1).  The asynchronous entry points, and `asynchronous != 0` in pv_koala_batch_process_call, are
+ * refused with PV_STATUS_INVALID_ARGUMENT on a handle whose format is not S16 (nothing processed).  The single-stream ABI (pv_koala.h)
+ * is int16 only. */
+typedef enum {
+    PV_KOALA_SAMPLE_S16 = 0,
+    PV_KOALA_SAMPLE_F32 = 1,
+    PV_KOALA_SAMPLE_ULAW = 2,
+    PV_KOALA_SAMPLE_ALAW = 3
+} pv_koala_sample_format_t;
+typedef struct {
+    int32_t struct_size;           /* sizeof(pv_koala_batch_config_t): lets the struct grow */
+    int32_t num_streams;
+    int32_t max_frames_per_call;   /* frame handles; ignored when max_samples_per_call > 0 */
+    int32_t max_samples_per_call;  /* > 0: a packet handle */
+    int32_t precision;             /* pv_koala_precision_t */
+    int32_t sample_rate;           /* 8000 / 16000 / 32000 / 48000 */
+    int32_t sample_format;         /* pv_koala_sample_format_t */
+} pv_koala_batch_config_t;
+PV_API pv_status_t pv_koala_batch_init_config(const char *access_key, const char *model_path, const char *device,
+                                              const pv_koala_batch_config_t *config, pv_koala_batch_t **object);
+PV_API pv_status_t pv_koala_batch_sample_format(const pv_koala_batch_t *object, int32_t *sample_format);
+
 PV_API pv_status_t pv_koala_batch_num_streams(const pv_koala_batch_t *object, int32_t *num_streams);
 PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, int32_t *delay_sample);
 

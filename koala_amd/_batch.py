@@ -5,13 +5,14 @@ sample-for-sample what its own `Koala` instance would produce.
 """
 
 import os
-from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int16, c_int32, c_int64, c_void_p, sizeof
+from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int32, c_int64, c_uint8, c_void_p, sizeof
 from typing import Optional
 
 import numpy as np
 
 from ._koala import (KoalaError, KoalaInvalidArgumentError, KoalaIOError, PicovoiceStatuses, attenuation_limit_to_gain, load_library,
                      raise_status)
+from .formats import DTYPES, FORMATS
 
 PRECISION_FP32 = 0
 PRECISION_BF16 = 1
@@ -30,15 +31,27 @@ class BatchPackets(Structure):
                 ('restart', c_void_p), ('report', c_void_p), ('report_frames', c_int32), ('frames', c_void_p)]
 
 
+class BatchConfig(Structure):
+    """pv_koala_batch_config_t (include/pv_koala_batch.h)"""
+    _fields_ = [('struct_size', c_int32), ('num_streams', c_int32), ('max_frames_per_call', c_int32), ('max_samples_per_call', c_int32),
+                ('precision', c_int32), ('sample_rate', c_int32), ('sample_format', c_int32)]
+
+
 class KoalaBatch(object):
+    sample_format, _dtype, _dtype_name = 's16', np.int16, 'int16'  # (what a handle is unless it was made with a sample format)
+
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
-                 max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0) -> None:
+                 max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0, sample_format: str = 's16') -> None:
         """`sample_rate`: 8000, 16000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
         array of samples is [num_streams, T * frame_length] with frame_length = sample_rate * 256 / 16000; at a rate other than 16000 the
         handle converts on the device, `delay_sample` includes both converters, and the asynchronous calls are refused.
         `packet_samples` > 0 makes a PACKET HANDLE (pv_koala_batch_init_packets): its streams take and deliver any number of samples per call,
         up to `packet_samples`, through `process_packets` / `process_device_packets`; the frame calls are refused on it, `max_frames_per_call`
-        is ceil(packet_samples / frame_length) and `delay_sample` grows by frame_length - 1."""
+        is ceil(packet_samples / frame_length) and `delay_sample` grows by frame_length - 1.
+        `sample_format`: 's16' (default), 'f32', 'ulaw' or 'alaw' -- what every array of samples that goes in or comes out holds: np.int16,
+        np.float32 in [-1, 1) or np.uint8 G.711 bytes (koala_amd.formats has the codecs).  The handle converts on the device around the
+        unchanged int16 call (pv_koala_batch_init_config): its result is formats.encode(the 's16' handle(formats.decode(x))), delay, frame
+        length and stream records are the 's16' handle's, and the asynchronous calls are refused.  An array of another dtype is refused."""
         if not isinstance(access_key, str) or len(access_key) == 0:
             raise KoalaInvalidArgumentError("`access_key` should be a non-empty string.")
         if not os.path.exists(model_path):
@@ -49,6 +62,11 @@ class KoalaBatch(object):
             raise KoalaInvalidArgumentError("`sample_rate` should be 8000, 16000, 32000 or 48000.")
         if not isinstance(packet_samples, int) or packet_samples < 0:
             raise KoalaInvalidArgumentError("`packet_samples` should be a positive number of samples (0: a frame handle).")
+        if not isinstance(sample_format, str) or sample_format not in FORMATS:
+            raise KoalaInvalidArgumentError("`sample_format` should be `s16`, `f32`, `ulaw` or `alaw`.")
+        self.sample_format = sample_format
+        self._dtype = DTYPES[sample_format]
+        self._dtype_name = np.dtype(self._dtype).name
         lib = load_library(library_path)
         lib.pv_set_sdk(b'python')
         self._lib = lib
@@ -85,10 +103,19 @@ class KoalaBatch(object):
         self._handle = c_void_p()
         prec = PRECISION_BF16 if precision == 'bf16' else PRECISION_FP32
         if packet_samples:
-            lib.pv_koala_batch_init_packets.argtypes = [c_char_p, c_char_p, c_char_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)]
-            lib.pv_koala_batch_init_packets.restype = PicovoiceStatuses
             lib.pv_koala_batch_process_packets.argtypes = [c_void_p, POINTER(BatchPackets)]
             lib.pv_koala_batch_process_packets.restype = PicovoiceStatuses
+        if sample_format != 's16':  # (an 's16' handle is made as it has always been: init_config would return the same handle)
+            lib.pv_koala_batch_init_config.argtypes = [c_char_p, c_char_p, c_char_p, POINTER(BatchConfig), POINTER(c_void_p)]
+            lib.pv_koala_batch_init_config.restype = PicovoiceStatuses
+            config = BatchConfig(sizeof(BatchConfig), num_streams, max_frames_per_call, packet_samples, prec, sample_rate,
+                                 FORMATS.index(sample_format))
+            status = lib.pv_koala_batch_init_config(access_key.encode(), model_path.encode(), device.encode(), byref(config), byref(self._handle))
+            if packet_samples:
+                max_frames_per_call = -(-packet_samples // (sample_rate * 256 // 16000))
+        elif packet_samples:
+            lib.pv_koala_batch_init_packets.argtypes = [c_char_p, c_char_p, c_char_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)]
+            lib.pv_koala_batch_init_packets.restype = PicovoiceStatuses
             status = lib.pv_koala_batch_init_packets(access_key.encode(), model_path.encode(), device.encode(), num_streams, packet_samples,
                                                      prec, sample_rate, byref(self._handle))
             max_frames_per_call = -(-packet_samples // (sample_rate * 256 // 16000))
@@ -125,33 +152,40 @@ class KoalaBatch(object):
         if status is not PicovoiceStatuses.SUCCESS:
             raise_status(self._lib, status, what)
 
+    def _samples(self, pcm):
+        """the caller's samples as a C-contiguous array of the handle's dtype; on a handle with a format a wrong dtype is refused, not converted"""
+        if self.sample_format != 's16' and (not isinstance(pcm, np.ndarray) or pcm.dtype != self._dtype):
+            raise KoalaInvalidArgumentError("expected a %s array: the handle's sample format is `%s`" % (self._dtype_name, self.sample_format))
+        return np.ascontiguousarray(pcm, dtype=self._dtype)
+
     def process(self, pcm: np.ndarray) -> np.ndarray:
         """pcm: int16 [num_streams, T*frame_length] in host memory -> enhanced, same shape (synchronous)."""
-        a = np.ascontiguousarray(pcm, dtype=np.int16)
+        a = self._samples(pcm)
         if a.ndim != 2 or a.shape[0] != self.num_streams or a.shape[1] % self.frame_length:
-            raise KoalaInvalidArgumentError("expected int16 array of shape [%d, T*%d]" % (self.num_streams, self.frame_length))
+            raise KoalaInvalidArgumentError("expected %s array of shape [%d, T*%d]" % (self._dtype_name, self.num_streams, self.frame_length))
         out = np.empty_like(a)
         self._check(self._lib.pv_koala_batch_process_chunk(self._handle, a.shape[1] // self.frame_length,
                                                            a.ctypes.data, out.ctypes.data), 'Processing failed')
         return out
 
     def alloc_host(self, num_frames: int) -> np.ndarray:
-        """int16 [num_streams, num_frames*frame_length] in page-locked host memory (freed by `delete()`): `process()` on such arrays
+        """[num_streams, num_frames*frame_length] of the handle's dtype (int16 unless it has a sample format) in page-locked host memory (freed by `delete()`): `process()` on such arrays
         lets the GPU's copy engines move the audio directly instead of through a staging copy."""
         n = self.num_streams * num_frames * self.frame_length
         p = c_void_p()
-        self._check(self._lib.pv_koala_batch_host_alloc(2 * n, byref(p)), 'Host allocation failed')
+        nbytes = n * np.dtype(self._dtype).itemsize
+        self._check(self._lib.pv_koala_batch_host_alloc(nbytes, byref(p)), 'Host allocation failed')
         self._pinned.append(p)
-        buf = (c_int16 * n).from_address(p.value)
-        return np.frombuffer(buf, dtype=np.int16).reshape(self.num_streams, num_frames * self.frame_length)
+        buf = (c_uint8 * nbytes).from_address(p.value)
+        return np.frombuffer(buf, dtype=self._dtype).reshape(self.num_streams, num_frames * self.frame_length)
 
     def process_into(self, pcm: np.ndarray, enhanced: np.ndarray) -> None:
         """Like `process()`, writing into a caller-provided array (both C-contiguous int16 of the same shape)."""
         for a in (pcm, enhanced):
-            if (not isinstance(a, np.ndarray) or a.dtype != np.int16 or not a.flags['C_CONTIGUOUS'] or a.ndim != 2 or
+            if (not isinstance(a, np.ndarray) or a.dtype != self._dtype or not a.flags['C_CONTIGUOUS'] or a.ndim != 2 or
                     a.shape[0] != self.num_streams or a.shape[1] % self.frame_length or a.shape != pcm.shape):
                 raise KoalaInvalidArgumentError(
-                    "expected C-contiguous int16 arrays of shape [%d, T*%d]" % (self.num_streams, self.frame_length))
+                    "expected C-contiguous %s arrays of shape [%d, T*%d]" % (self._dtype_name, self.num_streams, self.frame_length))
         self._check(self._lib.pv_koala_batch_process_chunk(self._handle, pcm.shape[1] // self.frame_length,
                                                            pcm.ctypes.data, enhanced.ctypes.data), 'Processing failed')
 
@@ -160,10 +194,10 @@ class KoalaBatch(object):
         in flight, so a caller that rotates over three buffer pairs keeps the link and the GPU busy at once.  `enhanced` is valid
         after `synchronize()` or once `wait(k)` says the call is no longer among the k in flight."""
         for a in (pcm, enhanced):
-            if (not isinstance(a, np.ndarray) or a.dtype != np.int16 or not a.flags['C_CONTIGUOUS'] or a.ndim != 2 or
+            if (not isinstance(a, np.ndarray) or a.dtype != self._dtype or not a.flags['C_CONTIGUOUS'] or a.ndim != 2 or
                     a.shape[0] != self.num_streams or a.shape[1] % self.frame_length or a.shape != pcm.shape):
                 raise KoalaInvalidArgumentError(
-                    "expected C-contiguous int16 arrays of shape [%d, T*%d]" % (self.num_streams, self.frame_length))
+                    "expected C-contiguous %s arrays of shape [%d, T*%d]" % (self._dtype_name, self.num_streams, self.frame_length))
         self._check(self._lib.pv_koala_batch_process_chunk_async(self._handle, pcm.shape[1] // self.frame_length,
                                                                  pcm.ctypes.data, enhanced.ctypes.data), 'Processing failed')
 
@@ -189,9 +223,9 @@ class KoalaBatch(object):
     def process_resets(self, pcm: np.ndarray, reset: Optional[np.ndarray]) -> np.ndarray:
         """`process()` with per-frame stream resets: reset[b, t] != 0 restarts stream b from the fresh state right before frame t of this
         call (include/pv_koala_batch.h, pv_koala_batch_process_chunk_resets).  `reset`: [num_streams, T] (None: no resets)."""
-        a = np.ascontiguousarray(pcm, dtype=np.int16)
+        a = self._samples(pcm)
         if a.ndim != 2 or a.shape[0] != self.num_streams or a.shape[1] % self.frame_length:
-            raise KoalaInvalidArgumentError("expected int16 array of shape [%d, T*%d]" % (self.num_streams, self.frame_length))
+            raise KoalaInvalidArgumentError("expected %s array of shape [%d, T*%d]" % (self._dtype_name, self.num_streams, self.frame_length))
         T = a.shape[1] // self.frame_length
         m, mp = self._reset_mask(reset, T)
         out = np.empty_like(a)
@@ -202,10 +236,10 @@ class KoalaBatch(object):
     def process_async_resets(self, pcm: np.ndarray, enhanced: np.ndarray, reset: Optional[np.ndarray]) -> None:
         """`process_async()` with per-frame stream resets ([num_streams, T]); the mask is copied before the call returns."""
         for a in (pcm, enhanced):
-            if (not isinstance(a, np.ndarray) or a.dtype != np.int16 or not a.flags['C_CONTIGUOUS'] or a.ndim != 2 or
+            if (not isinstance(a, np.ndarray) or a.dtype != self._dtype or not a.flags['C_CONTIGUOUS'] or a.ndim != 2 or
                     a.shape[0] != self.num_streams or a.shape[1] % self.frame_length or a.shape != pcm.shape):
                 raise KoalaInvalidArgumentError(
-                    "expected C-contiguous int16 arrays of shape [%d, T*%d]" % (self.num_streams, self.frame_length))
+                    "expected C-contiguous %s arrays of shape [%d, T*%d]" % (self._dtype_name, self.num_streams, self.frame_length))
         T = pcm.shape[1] // self.frame_length
         m, mp = self._reset_mask(reset, T)
         self._check(self._lib.pv_koala_batch_process_chunk_resets_async(self._handle, T, pcm.ctypes.data, enhanced.ctypes.data, mp),
@@ -228,10 +262,10 @@ class KoalaBatch(object):
 
     def _audio(self, *arrays):
         for a in arrays:
-            if (not isinstance(a, np.ndarray) or a.dtype != np.int16 or not a.flags['C_CONTIGUOUS'] or a.ndim != 2 or
+            if (not isinstance(a, np.ndarray) or a.dtype != self._dtype or not a.flags['C_CONTIGUOUS'] or a.ndim != 2 or
                     a.shape[0] != self.num_streams or a.shape[1] == 0 or a.shape[1] % self.frame_length or a.shape != arrays[0].shape):
                 raise KoalaInvalidArgumentError(
-                    "expected C-contiguous int16 arrays of shape [%d, T*%d]" % (self.num_streams, self.frame_length))
+                    "expected C-contiguous %s arrays of shape [%d, T*%d]" % (self._dtype_name, self.num_streams, self.frame_length))
         return arrays[0].shape[1] // self.frame_length
 
     def _report_array(self, report, num_frames):
@@ -245,7 +279,7 @@ class KoalaBatch(object):
         FRAME REPORT.  Returns `enhanced`, or `(enhanced, report)` when `report` is true: float32 [num_streams, T, 4] = e_in, e_out,
         mask_sum, 0 of every stream and frame (include/pv_koala_batch.h; koala_amd.report turns rows into dBFS, dB of suppression and
         mean gain).  The samples do not depend on whether the report is asked for."""
-        a = np.ascontiguousarray(pcm, dtype=np.int16)
+        a = self._samples(pcm)
         T = self._audio(a)
         out = np.empty_like(a)
         rep = np.empty((self.num_streams, T, 4), np.float32) if report else None
@@ -321,9 +355,9 @@ class KoalaBatch(object):
     def process_hold(self, pcm: np.ndarray, hold: Optional[np.ndarray]) -> np.ndarray:
         """`process()` in which the streams with hold[b] != 0 are not advanced (their state stays bit for bit what it was; their rows of
         the result are unspecified).  `hold`: [num_streams] (None: nobody)."""
-        a = np.ascontiguousarray(pcm, dtype=np.int16)
+        a = self._samples(pcm)
         if a.ndim != 2 or a.shape[0] != self.num_streams or a.shape[1] % self.frame_length:
-            raise KoalaInvalidArgumentError("expected int16 array of shape [%d, T*%d]" % (self.num_streams, self.frame_length))
+            raise KoalaInvalidArgumentError("expected %s array of shape [%d, T*%d]" % (self._dtype_name, self.num_streams, self.frame_length))
         m, mp = self._hold_mask(hold)
         out = np.empty_like(a)
         self._check(self._lib.pv_koala_batch_process_chunk_hold(self._handle, a.shape[1] // self.frame_length, a.ctypes.data,
@@ -358,9 +392,9 @@ class KoalaBatch(object):
         packet.  Returns `enhanced` (same shape; row b's first counts[b] samples are the stream's next output samples, the rest zeros),
         or `(enhanced, frames, report)` when `report` is true: frames int32 [num_streams] = the frames each stream completed in the call,
         report float32 [num_streams, max(frames), 4] with stream b's rows [0, frames[b]) filled."""
-        a = np.ascontiguousarray(pcm, dtype=np.int16)
+        a = self._samples(pcm)
         if a.ndim != 2 or a.shape[0] != self.num_streams or a.shape[1] < 1:
-            raise KoalaInvalidArgumentError("expected int16 array of shape [%d, max_samples]" % self.num_streams)
+            raise KoalaInvalidArgumentError("expected %s array of shape [%d, max_samples]" % (self._dtype_name, self.num_streams))
         out = np.zeros_like(a)
         if not report:
             self._packets(a.shape[1], counts, a.ctypes.data, out.ctypes.data, restart, None, 0)
@@ -454,4 +488,4 @@ class KoalaBatch(object):
             pass
 
 
-__all__ = ['KoalaBatch', 'BatchCall', 'BatchPackets', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']
+__all__ = ['KoalaBatch', 'BatchCall', 'BatchPackets', 'BatchConfig', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']

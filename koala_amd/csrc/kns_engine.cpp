@@ -1841,6 +1841,10 @@ bool Engine::async_wait(int max_in_flight, std::string *err) {
 // once call n - 2's copy-out has -- both waited for on the device, by the stream that needs it.  A synchronous call of that size cannot
 // hide its first copy-in and last copy-out and has to cut its kernels into short, less efficient sub-chunks (process_host_pipelined).
 Status Engine::process_host_async(const Call &c, std::string *err) {
+    if (fmt_ != kFmtS16) {
+        *err = "asynchronous calls are not available on a handle whose sample format is not S16.";
+        return Status::kBadArgument;
+    }
     if (rate_ != kRate16k) {
         *err = "asynchronous calls are not available on a handle whose sample rate is not 16000.";
         return Status::kBadArgument;
@@ -2391,7 +2395,9 @@ Status Engine::import_state(int count, const int32_t *streams, const void *host_
 // A call and its held streams: export the held rows' records to the device scratch, run the call unchanged, import them back -- around the
 // WHOLE call (outside the one-frame graph and the sub-chunks of large host calls), all on the handle's stream, so a device-pointer call
 // stays enqueued without a host wait.  The import restores both ping-pong copies, whichever parity the call has left current.
-Status Engine::process(const Call &c, std::string *err) {
+Status Engine::process(const Call &c, std::string *err) { return fmt_ == kFmtS16 ? process_frames(c, err) : process_format(c, err); }
+
+Status Engine::process_frames(const Call &c, std::string *err) {
     if (c.hold && c.resets) {
         *err = "held streams are not combined with per-frame stream resets in one call.";
         return Status::kBadArgument;
@@ -2464,6 +2470,10 @@ PacketStateArgs Engine::packet_state_args() const {
 // the call's table, the masked reset of `restart`, packet_in_kernel, the sub-calls through process() -- routes, held streams, rate
 // stages, attenuation limit and report as they are -- and packet_out_kernel.  Host pointers: one copy in, that, one copy out, a wait.
 Status Engine::run_packets(const PacketCall &c, std::string *err) {
+    return fmt_ == kFmtS16 ? run_packets_s16(c, err) : run_packets_format(c, err);
+}
+
+Status Engine::run_packets_s16(const PacketCall &c, std::string *err) {
     const int F = rs_frame_length(rate_);
     if (c.max_samples < 1 || c.max_samples > pk_max_) {
         *err = "`max_samples` " + std::to_string(c.max_samples) + " is outside [1, " + std::to_string(pk_max_) + "].";
@@ -2572,7 +2582,7 @@ Status Engine::run_packets(const PacketCall &c, std::string *err) {
         inner.hold = held ? hold.data() : nullptr;
         inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
         inner.report = c.report ? d_pk_rep_ + (size_t) B_ * c0 * 4 : nullptr;
-        const Status st = process(inner, err);
+        const Status st = process_frames(inner, err);
         if (st != Status::kOk) return Status::kRuntime;
     }
     a.frames = d_pk_out_;
@@ -2603,6 +2613,165 @@ Status Engine::run_packets(const PacketCall &c, std::string *err) {
             memcpy(c.out + (size_t) b * c.max_samples, pk_host_out_.data() + (size_t) b * c.max_samples, (size_t) c.counts[b] * 2);
             if (c.report) memcpy(c.report + (size_t) b * c.report_frames * 4, pk_host_rep_.data() + (size_t) b * kmax * 4, (size_t) k[b] * 16);
         }
+    }
+    return Status::kOk;
+}
+
+// ------------------------------------------------------------------------------------------------ sample formats
+
+// A handle whose callers hold float32 or G.711 samples (fifth extension; section 6): the outermost stage of a call.
+// format_in_kernel takes every element the call reads to int16 (d_fmt_in_), the S16 handle's call runs unchanged on device pointers
+// from d_fmt_in_ to d_fmt_out_ -- rate stages, packetiser, resets, held streams, attenuation limit and report with it -- and
+// format_out_kernel takes the samples the call writes to the caller's elements.  Everything is enqueued on the handle's stream, with no host
+// wait for device pointers.  Host pointers: one copy in of the FORMAT's bytes, this route, one copy out, a wait (no sub-chunks, no
+// one-frame graph).  The input is consumed before the output is written: `pcm` and `enhanced` may overlap in any way.
+bool Engine::set_format(int fmt, std::string *err) {
+    if (fmt == kFmtS16) return true;
+    (void) hipSetDevice(device_);
+    fmt_row_ = pk_max_ ? (size_t) pk_max_ : (size_t) Tmax_ * rs_frame_length(rate_);
+    d_fmt_in_ = (int16_t *) dalloc((size_t) B_ * fmt_row_ * 2, false);
+    d_fmt_out_ = (int16_t *) dalloc((size_t) B_ * fmt_row_ * 2, false);
+    if (!d_fmt_in_ || !d_fmt_out_) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the staging buffers of a sample format.";
+        return false;
+    }
+    fmt_ = fmt;
+    return true;
+}
+
+bool Engine::format_host_ready(bool report, std::string *err) {
+    if (!d_fmt_io_) d_fmt_io_ = (uint8_t *) dalloc((size_t) B_ * fmt_row_ * sample_bytes(), false);
+    if (report && !d_fmt_rep_) d_fmt_rep_ = (float *) dalloc((size_t) B_ * Tmax_ * 16, false);
+    if (!d_fmt_io_ || (report && !d_fmt_rep_)) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the staging buffer of host-memory calls.";
+        return false;
+    }
+    return true;
+}
+
+Status Engine::process_format(const Call &c, std::string *err) {
+    (void) hipSetDevice(device_);
+    const PointerKind kin = pointer_kind(c.pcm), kout = pointer_kind(c.out);
+    if ((kin == kPtrDevice) != (kout == kPtrDevice)) {
+        *err = "`pcm` and `enhanced` must both be host or both be device memory.";
+        return Status::kRuntime;
+    }
+    const bool host = kin != kPtrDevice;
+    if (c.report && (pointer_kind(c.report) == kPtrDevice) == host) {
+        *err = "`report` must be memory of the same kind as `enhanced`: host with host, device with device.";
+        return Status::kRuntime;
+    }
+    if (host && !format_host_ready(c.report != nullptr, err)) return Status::kRuntime;
+    const size_t n = (size_t) B_ * c.T * rs_frame_length(rate_), bytes = n * sample_bytes();
+    const void *src = c.pcm;  // (Call::pcm / out: elements of the handle's format behind the int16 type)
+    void *dst = c.out;
+    if (host) {
+        if (hipMemcpyAsync(d_fmt_io_, c.pcm, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) goto fail;
+        src = dst = d_fmt_io_;
+    }
+    {
+        launch_format_in(fmt_, FormatArgs{src, d_fmt_in_, nullptr, (long long) n, 1}, stream_);
+        if (hipGetLastError() != hipSuccess) goto fail;
+        Call inner = c;
+        inner.pcm = d_fmt_in_, inner.out = d_fmt_out_;
+        inner.host_contract = false;
+        if (host && c.report) inner.report = d_fmt_rep_;
+        const Status st = process_frames(inner, err);
+        if (st != Status::kOk) return st;  // (a refused call has advanced nothing: the in-stage wrote its staging matrix only)
+        launch_format_out(fmt_, FormatArgs{d_fmt_out_, dst, nullptr, (long long) n, 1}, stream_);
+        if (hipGetLastError() != hipSuccess) goto fail;
+    }
+    if (host) {
+        if (hipMemcpyAsync(c.out, d_fmt_io_, bytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
+        if (c.report && hipMemcpyAsync(c.report, d_fmt_rep_, (size_t) B_ * c.T * 16, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
+        if (hipStreamSynchronize(stream_) != hipSuccess) goto fail;
+    }
+    return Status::kOk;
+fail:
+    *err = hip_last_error();
+    return Status::kRuntime;
+}
+
+// A packet call of such a handle: the whole rows [B][max_samples] are decoded (the caller owns them), the S16 packet call runs on the two
+// staging matrices, and format_out_kernel writes row b's first counts[b] elements only, from the call's device table (d_pk_tab_ starts with
+// the counts) -- the rest of the caller's `enhanced` keeps its bytes.  A call in which every stream is stalled converts nothing.
+Status Engine::run_packets_format(const PacketCall &c, std::string *err) {
+    if (c.max_samples < 1 || c.max_samples > pk_max_) {
+        *err = "`max_samples` " + std::to_string(c.max_samples) + " is outside [1, " + std::to_string(pk_max_) + "].";
+        return Status::kBadArgument;
+    }
+    bool any_count = false;
+    for (int b = 0; b < B_; ++b) {
+        if (c.counts[b] < 0 || c.counts[b] > c.max_samples) {
+            *err = "`counts[" + std::to_string(b) + "]` = " + std::to_string(c.counts[b]) + " is outside [0, " + std::to_string(c.max_samples) + "].";
+            return Status::kBadArgument;
+        }
+        any_count = any_count || c.counts[b] > 0;
+    }
+    (void) hipSetDevice(device_);
+    const PointerKind kin = pointer_kind(c.pcm), kout = pointer_kind(c.out);
+    if ((kin == kPtrDevice) != (kout == kPtrDevice)) {
+        *err = "`pcm` and `enhanced` must both be host or both be device memory.";
+        return Status::kBadArgument;
+    }
+    const bool host = kin != kPtrDevice;
+    if (c.report && (pointer_kind(c.report) == kPtrDevice) == host) {
+        *err = "`report` must be memory of the same kind as `enhanced`: host with host, device with device.";
+        return Status::kBadArgument;
+    }
+    if (host && !format_host_ready(c.report != nullptr, err)) return Status::kRuntime;
+    const size_t eb = (size_t) sample_bytes(), n = (size_t) B_ * c.max_samples;
+    const void *src = c.pcm;
+    void *dst = c.out;
+    hipError_t e = hipSuccess;
+    if (host) src = dst = d_fmt_io_;
+    if (any_count) {
+        if (host) e = hipMemcpyAsync(d_fmt_io_, c.pcm, n * eb, hipMemcpyHostToDevice, stream_);
+        if (e == hipSuccess) {
+            launch_format_in(fmt_, FormatArgs{src, d_fmt_in_, nullptr, (long long) n, 1}, stream_);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) {
+            *err = hip_error(e);
+            return Status::kRuntime;
+        }
+    }
+    std::vector<int32_t> k((size_t) B_, 0);
+    PacketCall inner = c;
+    inner.pcm = d_fmt_in_, inner.out = d_fmt_out_;
+    inner.frames = k.data();
+    if (host && c.report) inner.report = d_fmt_rep_, inner.report_frames = std::min(c.report_frames, Tmax_);
+    const Status st = run_packets_s16(inner, err);
+    if (st != Status::kOk) return st;
+    for (int b = 0; c.frames && b < B_; ++b) c.frames[b] = k[b];
+    if (any_count) {
+        launch_format_out(fmt_, FormatArgs{d_fmt_out_, dst, d_pk_tab_, (long long) c.max_samples, B_}, stream_);
+        e = hipGetLastError();
+    }
+    if (host && e == hipSuccess) {
+        const int rf = inner.report_frames;
+        if (any_count) {
+            fmt_host_out_.resize(n * eb);
+            e = hipMemcpyAsync(fmt_host_out_.data(), d_fmt_io_, n * eb, hipMemcpyDeviceToHost, stream_);
+        }
+        if (e == hipSuccess && c.report && rf > 0) {
+            fmt_host_rep_.resize((size_t) B_ * rf * 4);
+            e = hipMemcpyAsync(fmt_host_rep_.data(), d_fmt_rep_, (size_t) B_ * rf * 16, hipMemcpyDeviceToHost, stream_);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+        // (only a row's first counts[b] elements, and a stream's first k_b report rows, are the caller's to be written)
+        for (int b = 0; e == hipSuccess && b < B_; ++b) {
+            const size_t at = (size_t) b * c.max_samples * eb;
+            if (any_count) memcpy((uint8_t *) c.out + at, fmt_host_out_.data() + at, (size_t) c.counts[b] * eb);
+            if (c.report && k[b]) memcpy(c.report + (size_t) b * c.report_frames * 4, fmt_host_rep_.data() + (size_t) b * rf * 4, (size_t) k[b] * 16);
+        }
+    }
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        *err = hip_error(e);
+        return Status::kRuntime;
     }
     return Status::kOk;
 }

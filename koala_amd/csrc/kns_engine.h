@@ -35,7 +35,8 @@ constexpr int kNumKernelClasses = 5;
 enum KernelClass { kClsAnalysis = 0, kClsGemmIn = 1, kClsGru = 2, kClsGemmHead = 3, kClsSynthesis = 4 };
 
 // One call that advances the streams, with everything it carries.  pcm/out: [B][T*frame_length] at the handle's sample rate (256 at
-// 16 kHz), host or device pointers (both of the same kind).
+// 16 kHz), host or device pointers (both of the same kind).  On a handle with a sample format (Engine::set_format) they point to elements
+// of that format -- float or uint8 -- behind the int16 type: the entry casts, and every size is a count of sample_bytes().
 struct Call {
     int T;
     const int16_t *pcm;
@@ -71,7 +72,7 @@ enum class Status { kOk, kBadArgument, kRuntime };
 struct PacketCall {
     int max_samples;                   // row length of pcm / out, 1 .. the handle's
     const int32_t *counts;             // host [num_streams], each in [0, max_samples]
-    const int16_t *pcm;                // [num_streams][max_samples], host or device
+    const int16_t *pcm;                // [num_streams][max_samples], host or device (elements of the handle's format, as Call's)
     int16_t *out;                      // the same kind
     const uint8_t *restart = nullptr;  // host [num_streams] or nullptr: the stream is fresh before this packet
     float *report = nullptr;           // [num_streams][report_frames][4], memory of out's kind, or nullptr
@@ -127,12 +128,35 @@ public:
     int packet_samples() const { return pk_max_; }  // 0: a frame handle
     Status run_packets(const PacketCall &c, std::string *err);
 
+    // ---- sample formats (fifth extension).  set_format, once, right after create() -- and after enable_packets on a
+    // packet handle: from then on the `pcm` and `out` of process() and run_packets() point to elements of that format (kns_kernels.h,
+    // SampleFormat) behind their int16 types, sample_bytes() each, and are converted on the device around the unchanged call.  The engine's
+    // samples stay int16 inside: F32 is an input / output form, not a wider path.  Configuration, not stream state: records, state_bytes()
+    // and the delay are those of the S16 handle.  The asynchronous host calls are refused.  kFmtS16 allocates and changes nothing.
+    bool set_format(int fmt, std::string *err);
+    int sample_format() const { return fmt_; }
+    int sample_bytes() const { return fmt_bytes(fmt_); }
+
     void profile_enable(bool on);
     bool profile_read(double *ms, int64_t *launches, std::string *err);
     int64_t debug_read(int what, float *out, int64_t capacity, std::string *err);
 
 private:
     Engine() {}
+    // sample formats: the int16 staging matrices [B][fmt_row_] on either side of the inner call, the staging of host-pointer calls (the
+    // format's bytes; a report [B][Tmax][4]) and the host copy of a packet call's output, of which the rows' first counts[b] elements go on
+    int fmt_ = kFmtS16;
+    size_t fmt_row_ = 0;
+    int16_t *d_fmt_in_ = nullptr, *d_fmt_out_ = nullptr;
+    uint8_t *d_fmt_io_ = nullptr;
+    float *d_fmt_rep_ = nullptr;
+    std::vector<uint8_t> fmt_host_out_;
+    std::vector<float> fmt_host_rep_;
+    bool format_host_ready(bool report, std::string *err);
+    Status process_format(const Call &c, std::string *err);
+    Status run_packets_format(const PacketCall &c, std::string *err);
+    Status process_frames(const Call &c, std::string *err);          // process() of an S16 handle
+    Status run_packets_s16(const PacketCall &c, std::string *err);  // run_packets() of an S16 handle
     bool init(const Params &p, int device, int B, int Tmax, int precision, std::string *err, bool *oom);
     bool run_call(const Call &c, std::string *err);  // process() without the held streams, at 16 kHz
     // Handles that are not at 16 kHz (kns_engine.cpp, run_call_rate): in-stage kernel, run_call on device buffers, out-stage kernel.

@@ -358,6 +358,23 @@ struct PacketStateArgs {
 };
 void launch_packet_reset(const PacketStateArgs &a, const uint8_t *mask, hipStream_t s);  // mask: device [Bpad], null: every stream
 void launch_packet_state(const PacketStateArgs &a, hipStream_t s);
+// ---- sample formats of batch handles (kns_format.hip; DESIGN.md section 2, fifth extension): what a caller's `pcm` and `enhanced` hold.
+// Configuration of the handle, not stream state: the engine's samples are int16 whatever the format, which is a conversion on the device in
+// front of and behind the unchanged call.  The values are pv_koala_sample_format_t's.
+enum SampleFormat { kFmtS16 = 0, kFmtF32 = 1, kFmtUlaw = 2, kFmtAlaw = 3 };
+KNS_HD bool fmt_ok(int fmt) { return fmt >= kFmtS16 && fmt <= kFmtAlaw; }
+KNS_HD int fmt_bytes(int fmt) { return fmt == kFmtS16 ? 2 : fmt == kFmtF32 ? 4 : 1; }  // bytes per element
+KNS_HD int fmt_group(int fmt) { return fmt == kFmtF32 ? 8 : 16; }                       // elements one lane converts
+struct FormatArgs {
+    const void *in;         // [rows][n] dense: the format's elements (format_in) or int16 (format_out), aligned to the element only
+    void *out;              // [rows][n] dense: int16 (format_in) or the format's elements (format_out), aligned to the element only
+    const int32_t *counts;  // device [rows] or nullptr: row b's first counts[b] elements are converted and written (nullptr: all n)
+    long long n;
+    int rows;
+};
+// fmt: kFmtF32, kFmtUlaw or kFmtAlaw (an S16 handle launches neither)
+void launch_format_in(int fmt, const FormatArgs &a, hipStream_t s);
+void launch_format_out(int fmt, const FormatArgs &a, hipStream_t s);
 // last node of a captured one-frame replay: ++*counter (device memory), published to *host_word (page-locked host memory)
 void launch_frame_done(unsigned *counter, unsigned *host_word, hipStream_t s);
 

@@ -116,6 +116,41 @@ def run_in_packets(args):
     return 0
 
 
+def run_raw_format(args):
+    """--sample_format: raw samples of that format (s16: little-endian int16; f32: little-endian float32 in [-1, 1); ulaw / alaw: G.711
+    bytes) on stdin at --sample_rate, the enhanced stream in the same format on stdout, through one stream of a packet handle
+    (`koala_amd.create_batch(..., packet_samples=N, sample_format=...)`: the conversion runs on the device).  Telephony, for instance:
+    `... | koala_demo_stream.py --sample_format ulaw --sample_rate 8000 --packet-ms 20 | ...`.  Messages go to stderr."""
+    import os
+    from koala_amd import formats
+    rate, dt = args.sample_rate, np.dtype(formats.dtype(args.sample_format)).newbyteorder('<')
+    n = rate * (args.packet_ms or 20) // 1000
+    batch = koala_amd.create_batch(args.access_key, 1, precision=args.precision or os.environ.get('KOALA_AMD_PRECISION', 'fp32'),
+                                   model_path=args.model_path, device=args.device, library_path=args.library_path,
+                                   sample_rate=rate, packet_samples=n, sample_format=args.sample_format)
+    batch.set_attenuation_limit(args.attenuation_limit_db)
+    samples = 0
+    try:
+        while True:
+            buf = sys.stdin.buffer.read(n * dt.itemsize)
+            got = np.frombuffer(buf[:len(buf) // dt.itemsize * dt.itemsize], dtype=dt)
+            if got.size == 0:
+                break
+            packet = np.zeros((1, n), formats.dtype(args.sample_format))
+            packet[0, :got.size] = got
+            enhanced = batch.process_packets(packet, [got.size])
+            sys.stdout.buffer.write(enhanced[0, :got.size].astype(dt).tobytes())
+            sys.stdout.buffer.flush()
+            samples += got.size
+    except KeyboardInterrupt:
+        pass
+    finally:
+        delay = batch.delay_sample
+        batch.delete()
+    print('%d samples of %s at %d Hz; delay %d samples' % (samples, args.sample_format, rate, delay), file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='frame-by-frame noise suppression of a live PCM stream')
     ap.add_argument('--access_key', default='koala-amd', help='accepted for interface compatibility; not checked')
@@ -134,12 +169,17 @@ def main(argv=None):
                     help='every N frames print input level (dBFS), suppression (dB) and mean mask gain, from the frame report')
     ap.add_argument('--packet-ms', dest='packet_ms', type=int, default=0, choices=[10, 20],
                     help='feed the stream in packets of this many ms through a packet handle instead of in 16 ms frames')
+    ap.add_argument('--sample_format', default=None, choices=['s16', 'f32', 'ulaw', 'alaw'],
+                    help='raw samples of this format on stdin and stdout at --sample_rate, through a packet handle that converts on the device')
+    ap.add_argument('--sample_rate', type=int, default=16000, choices=[8000, 16000, 32000, 48000], help='with --sample_format: the stream\'s rate')
     ap.add_argument('--show_devices', action='store_true')
     args = ap.parse_args(argv)
 
     if args.show_devices:
         print('\n'.join(koala_amd.available_devices(library_path=args.library_path)))
         return 0
+    if args.sample_format is not None:
+        return run_raw_format(args)
     if args.output_path is None:
         raise ValueError('Missing required argument --output_path')
     for p in (args.output_path, args.reference_output_path):
