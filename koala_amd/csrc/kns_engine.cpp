@@ -1348,6 +1348,7 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
         GruArgs g;
         const size_t m0 = (size_t) c_t0 * mtb;
         if (head) {  // this stage's narrow head inside the launch, into the padding of the feature matrix (kns_kernels.h)
+            ++last_head_launches_;
             g.yw = head->w_head;
             g.yb = head->b_head;
             g.yout = feat_now + (size_t) c_t0 * feat_frame_bytes_;
@@ -1361,7 +1362,7 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
         g.bhh = bhh;
         g.hstate_in = d_hstate_[c_hs] + (size_t) layer * mtb * kUnitTiles * 256;
         g.hstate_out = d_hstate_[c_hs ^ 1] + (size_t) layer * mtb * kUnitTiles * 256;
-        g.hseq = (char *) hseq + m0 * nbh_ * 1024;
+        g.hseq = (char *) hseq + m0 * nbh_ * 1024;  // (left untouched by a launch that carries the head: the head was its only reader)
         g.T = c_T;
         g.mtiles = mtb;
         g.precision = prec_;
@@ -1439,6 +1440,7 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
     };
 
     const bool small_steps = T > 1 && mtb <= steps_mt && prec_ != kBf16 && !no_small_ && !wave && !resets;
+    last_head_launches_ = 0;
     last_route_ = resets ? kRouteChunkedResets : small ? kRouteSmall : wave ? kRouteWave : small_steps ? kRouteSmallSteps : quad ? kRouteQuad1 : kRouteChunked;
     // ---- mid-size batches: the layer pipeline over sub-chunks of frames (see the chunk loop below)
     const int pipe_chunk = dev_pipe_chunk_ > 0 ? dev_pipe_chunk_ : (T + 1) / 2;
@@ -1593,7 +1595,8 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
             } else {
                 // multi-frame calls: a narrow head whose values go into the features' padding (stages 0 and 1) is computed by layer
                 // B's recurrent kernel itself, step by step, while the hidden vectors are in LDS: two head launches and two passes
-                // over a hidden sequence (2 x 151 MB at the bench shape) less
+                // over a hidden sequence (2 x 151 MB at the bench shape) less -- and, the head GEMM below being that sequence's only
+                // reader (the next stage's layer B overwrites d_hseq_b_, the last stage never carries its head), no sequence at all
                 head_in_recurrent = T > 1 && s < kStages - 1 && sd_[s + 1].ypad && d.head_tiles == pi_.npb && fuse_head_ && !debug_taps_ &&
                                     !(dev_variant_ & kDevGruStream);
                 gemm(kClsGemmIn, nullptr, 0, d_hseq_a_, nbh_, d.w_ih_b, d.b_ih_b, d_gi_, kGateTiles, 3 * kHidden, kOutGi);
@@ -2901,6 +2904,10 @@ int64_t Engine::debug_read(int what, float *out, int64_t capacity, std::string *
         out[2] = mask_valid_ ? 0.0f : 1.0f;   // mask head inside the synthesis launch
         out[3] = spec_valid_ ? 1.0f : 0.0f;   // spectrum stored (not recomputed)
         return 4;
+    } else if (what == 7) {  // developer build: recurrent launches of the last call that carried their stage's narrow head
+        if (capacity < 1) return -2;
+        out[0] = (float) last_head_launches_;
+        return 1;
 #endif
     } else if (what == 5) {  // developer build: stamps of the last fused layer launch, [8 waves][4 T][8] ticks since the first one
         if (!d_qdbg_) {

@@ -671,7 +671,9 @@ constexpr int kR8HeadLds = PBF16::NBH * 1024;          // (kYHead) the narrow he
                     // spills 20 bytes inside the step
 #endif
 #ifndef R8_APF_Y
-#define R8_APF_Y 0  // gru_resident8_kernel<true>: the head's chain and epilogue leave no registers (a distance of 1 spills inside the step)
+#define R8_APF_Y 0  // gru_resident8_kernel<true> and <true, true>: the head's chain and epilogue leave no registers -- also without the
+                    // hidden-sequence copy (its two fragments and descriptor gone): a distance of 1 spills 20 / 36 bytes, 2 spills 40 / 52
+                    // (profiles/r14_head_launch.txt)
 #endif
 template <int kFirstLds, int kQ, int kNReg, bool kChain = false, int kChainStride = 3, int D = 0>
 __device__ __forceinline__ void r8_tile_mma(f32x4 (&acc)[3], const bf16x8 *ha, const bf16x8 (&wreg)[kNReg], const bf16x8 *wl,
@@ -719,6 +721,10 @@ __device__ __forceinline__ f16x4 buf_load_gi(__amdgpu_buffer_rsrc_t r, unsigned 
 // (profiles/r04_recurrent_stamps.txt) -- carries its nine MFMAs through its first tile's loop as a fourth accumulator, on the same A
 // fragments (the image of h_{t-1} it multiplies anyway), then the sigmoid and sixteen 2-byte stores: y_{t-1} leaves one step late,
 // y_{T-1} after the loop.  The chain is k-ascending from 0 with the bias after, like gemm_head_kernel's: the same bits.
+// A launch that carries the head publishes NO hidden sequence (kPublish below, GruArgs::hseq is not touched): the sequence of a stage's
+// layer B has one reader, the stage's head, and that is this launch -- 160 MB of stores per launch at the bench shape, and two LDS
+// reads per wave and step on a saturated LDS pipe, for nobody.  The operation is absent for every wave at compile time, not branched
+// around (the rule above the step loop).
 // kResets (GruArgs::resets): before step t the rows that restart at t get h_{t-1} = 0 -- hreg, h16 and their rows of the operand image
 // (column 15 of tile 16 stays the bias constant) -- after the image has gone out as frame t - 1's hidden vector.  With kYHead the head's
 // y_{t-1} belongs to frame t - 1, the last frame before the reset: in such a step wave 0 computes it from the image BEFORE the rows are
@@ -729,6 +735,7 @@ __global__ __launch_bounds__(64 * kR8Waves, 2) void gru_resident8_kernel(GruArgs
     typedef P::frag_t frag_t;
     constexpr int NBH = P::NBH;
     constexpr int kApf = kYHead ? R8_APF_Y : kResets ? R8_APF_R : R8_APF;  // A fragments requested this many k-blocks ahead
+    constexpr bool kPublish = !kYHead;  // the hidden sequence goes out (every launch whose sequence a later launch reads)
     __shared__ __attribute__((aligned(16))) char smem[kR8Lds + 3 * 1024 + 16 + (kYHead ? kR8HeadLds : 0)];
     frag_t *wlh = (frag_t *) (smem + kR8Lds + 3 * 1024 + 16);  // (kYHead) [9][64]: the head's n-tile 0
     char *hbuf0 = smem, *hbuf1 = smem + NBH * 1024;
@@ -834,16 +841,16 @@ __global__ __launch_bounds__(64 * kR8Waves, 2) void gru_resident8_kernel(GruArgs
     __syncthreads();
 
     // Every wave issues the same vector-memory operations every step and none of them sits inside a branch (the hidden
-    // sequence copy is unconditional -- at t = 0 it writes h_{-1} into slot 0, which the same lanes overwrite with h_0 one
-    // step later --, block 8 goes out in eighths, and tile 16's pre-activations are requested by all waves although only
-    // waves 0..3 use them): with conditional loads and stores in the loop hipcc's first vmcnt wait of a step also covered
-    // the pre-activations requested last in the previous step.
+    // sequence copy is unconditional where there is one -- kPublish: with kYHead it is absent at compile time --, at t = 0
+    // it writes h_{-1} into slot 0, which the same lanes overwrite with h_0 one step later, block 8 goes out in eighths, and
+    // tile 16's pre-activations are requested by all waves although only waves 0..3 use them): with conditional loads and
+    // stores in the loop hipcc's first vmcnt wait of a step also covered the pre-activations requested last in the previous step.
     const unsigned lane8 = lane * 8u;
     // The bases of the two per-step streams are ADVANCED by their stride instead of being recomputed from t (hipcc does not
     // strength-reduce the 64-bit (t * mtiles + mt) * bytes products: ~40 scalar instructions per step in a loop whose waves issue
     // an instruction every ~5 cycles): the hidden-sequence slot of step t is max(t - 1, 0), the pre-activation slot min(t + 1, T - 1)
     const size_t hs_stride = (size_t) g.mtiles * NBH * 1024, gi_stride = (size_t) g.mtiles * kGateTiles * 512;
-    const char *hs_base = (const char *) g.hseq + (size_t) mt * NBH * 1024;
+    const char *hs_base = kPublish ? (const char *) g.hseq + (size_t) mt * NBH * 1024 : nullptr;
     const char *gn_base = (const char *) g.gi + (size_t) mt * kGateTiles * 512 + (g.T > 1 ? gi_stride : 0);
     auto publish = [&](const frag_t *src, const char *slot_base) {
         const __amdgpu_buffer_rsrc_t hs = make_rsrc(slot_base, NBH * 1024);
@@ -858,6 +865,8 @@ __global__ __launch_bounds__(64 * kR8Waves, 2) void gru_resident8_kernel(GruArgs
     // (in a wave-0 branch, against the rule that no vector-memory operation of the step sits inside one: the unconditional form --
     // every wave issuing the stores through a descriptor that is empty for waves 1..7 -- costs registers the kernel does not have
     // (256 VGPRs + 24 B of scratch) and measured 171.7 us per launch against 156.5)
+    // (the destination as a base ADVANCED by y_frame_bytes per step, like hs_base, with the lane's part hoisted or formed here: 151.7 and
+    // 152.6 us per launch against 152.1 with the product below -- nothing; source of both forms: profiles/r14_head_launch.txt section 6)
     auto emit_y = [&](const f32x4 &ya, int frame) {
         uint16_t *dst = (uint16_t *) ((char *) g.yout + (size_t) frame * y_frame_bytes + ((size_t) mt * g.y_nb + g.y_blk) * 1024);
         if (colq < g.yvalid) {
@@ -872,7 +881,7 @@ __global__ __launch_bounds__(64 * kR8Waves, 2) void gru_resident8_kernel(GruArgs
         char *hc = (t & 1) ? hbuf1 : hbuf0;
         char *hn = (t & 1) ? hbuf0 : hbuf1;
         const frag_t *ha = (const frag_t *) hc;
-        publish(ha, hs_base);  // LDS holds h_{t-1}
+        if (kPublish) publish(ha, hs_base);  // LDS holds h_{t-1}
         bool reset_step = false;
         if (kResets) {
             const unsigned rm = reset_rows(g.resets, g.rs_pitch, mt, g.rs_t0 + t);
@@ -901,7 +910,7 @@ __global__ __launch_bounds__(64 * kR8Waves, 2) void gru_resident8_kernel(GruArgs
             }
         }
         const __amdgpu_buffer_rsrc_t gnext = make_rsrc(gn_base, kGateTiles * 512);
-        hs_base += t > 0 ? hs_stride : 0;
+        if (kPublish) hs_base += t > 0 ? hs_stride : 0;
         gn_base += t + 2 < g.T ? gi_stride : 0;
 
         auto gates = [&](const int q, f32x4 (&acc)[3]) {
@@ -978,10 +987,15 @@ __global__ __launch_bounds__(64 * kR8Waves, 2) void gru_resident8_kernel(GruArgs
         for (int blk = 0; blk < NBH; ++blk) ya = P::mma(hl[blk * 64 + lane], wlh[blk * 64 + lane], ya);
         emit_y(ya, g.T - 1);
     }
-    publish((const frag_t *) ((g.T & 1) ? hbuf1 : hbuf0), (const char *) g.hseq + ((size_t) (g.T - 1) * g.mtiles + mt) * NBH * 1024);
+    if (kPublish)
+        publish((const frag_t *) ((g.T & 1) ? hbuf1 : hbuf0), (const char *) g.hseq + ((size_t) (g.T - 1) * g.mtiles + mt) * NBH * 1024);
     ((f32x4 *) g.hstate_out)[((size_t) mt * kUnitTiles + u0) * 64 + lane] = hreg[0];
     ((f32x4 *) g.hstate_out)[((size_t) mt * kUnitTiles + u1) * 64 + lane] = hreg[1];
-    if (q16) g.hstate_out[(((size_t) mt * kUnitTiles + u2) * 64 + lane) * 4 + e16] = h16;
+    // (kYHead: the index below is formed from an opaque copy of the lane number -- otherwise hipcc keeps the 64-bit index of the
+    // prologue's h16 load through the loop and, without the publish, spills it: 12 bytes of scratch for one store per launch)
+    int lane_o = lane;
+    if (kYHead) asm volatile("" : "+v"(lane_o));
+    if (q16) g.hstate_out[(((size_t) mt * kUnitTiles + u2) * 64 + lane_o) * 4 + e16] = h16;
 }
 
 // (Round 6 measured a form WITHOUT the step's barrier -- per-tile step counters in LDS, the first MFMA loop waiting in front of k-blocks 0

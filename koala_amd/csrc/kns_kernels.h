@@ -148,7 +148,7 @@ struct GruArgs {
     // optional (bf16 resident kernel): the stage's NARROW head (at most kYPadMax values) computed inside this launch, step by step,
     // from the hidden vectors while they are in LDS -- y_t = sigmoid(h_t . W_head + b_head) written into columns y_kk0 ... of block
     // y_blk of an A-packed matrix with y_nb blocks per m-tile and T x mtiles m-tiles (the feature matrix' padding, kns_layout.h): no
-    // head launch, no second pass over the hidden sequence
+    // head launch, no second pass over the hidden sequence -- and no hidden sequence: with yw set, hseq is neither read nor written
     const void *yw = nullptr;    // B-packed head weights, n-tile 0: [nbh] blocks
     const float *yb = nullptr;   // [16]
     void *yout = nullptr;
