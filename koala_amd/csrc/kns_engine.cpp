@@ -2108,78 +2108,45 @@ fail:
 
 // ------------------------------------------------------------------------------------------------ handles that are not at 16 kHz
 
-bool Engine::rate_ready(bool host_staging, bool reset_flags, std::string *err) {
-    if (host_staging && !d_rate_io_) {
-        d_rate_io_ = (int16_t *) dalloc((size_t) B_ * Tmax_ * rs_frame_length(rate_) * 2, false);
-        if (!d_rate_io_) {
-            (void) hipGetLastError();
-            *err = "Failed to allocate the staging buffer of host-memory calls.";
-            return false;
-        }
+bool Engine::rate_ready(std::string *err) {  // the device copy of a call's reset flags and its upload ring, at first use
+    if (d_rs_flags_) return true;
+    uint8_t *d = rsf_ring_.ready((size_t) B_ * Tmax_) ? (uint8_t *) dalloc((size_t) B_ * Tmax_, false) : nullptr;
+    if (!d) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the buffers of per-frame stream resets.";
+        return false;
     }
-    if (reset_flags && !d_rs_flags_) {
-        uint8_t *d = rsf_ring_.ready((size_t) B_ * Tmax_) ? (uint8_t *) dalloc((size_t) B_ * Tmax_, false) : nullptr;
-        if (!d) {
-            (void) hipGetLastError();
-            *err = "Failed to allocate the buffers of per-frame stream resets.";
-            return false;
-        }
-        d_rs_flags_ = d;
-    }
+    d_rs_flags_ = d;
     return true;
 }
 
 // A call of a handle at 8, 32 or 48 kHz (third extension): the in-stage kernel takes the caller's samples to 16 kHz
 // (into d_in_), the call runs unchanged as a device-pointer call from d_in_ to d_out_ -- its resets, attenuation limit and frame report
 // with it -- and the out-stage kernel takes the enhanced samples to the caller's rate.  Everything is enqueued on the handle's stream.
-// Host pointers: one copy in, this route, one copy out, then synchronise (no sub-chunks, no one-frame graph).  The in-stage has read all
-// of `pcm` before the out-stage writes `out`, so the two may overlap in any way.  The call's per-frame resets go to the device as they
-// are (uint8 [B][T]): both stages read everything in front of a reset block as zero.
+// Device pointers only, and no refusal of its own: host memory and every argument check are the entry's (process, run_packets).  The
+// in-stage has read all of `pcm` before the out-stage writes `out`, so the two may overlap in any way.  The call's per-frame resets go to
+// the device as they are (uint8 [B][T]): both stages read everything in front of a reset block as zero.
 bool Engine::run_call_rate(const Call &c, std::string *err) {
     const int T = c.T, FL = rs_frame_length(rate_), R = rs_ratio(rate_);
     (void) hipSetDevice(device_);
-    const PointerKind kin = pointer_kind(c.pcm), kout = pointer_kind(c.out);
-    if ((kin == kPtrDevice) != (kout == kPtrDevice)) {
-        *err = "`pcm` and `enhanced` must both be host or both be device memory.";
-        return false;
-    }
-    const bool host = kin != kPtrDevice;
-    if (c.report && (pointer_kind(c.report) == kPtrDevice) == host) {
-        *err = "`report` must be memory of the same kind as `enhanced`: host with host, device with device.";
-        return false;
-    }
-    bool any = false, late = false;
-    for (int b = 0; c.resets && b < B_ && !late; ++b)
-        for (int t = 0; t < T; ++t)
-            if (c.resets[(size_t) b * T + t]) any = true, late = late || t > 0;
-    if (late && taps_ > 1) {  // (refused in front of the in-stage: a refused call advances nothing)
-        *err = "per-frame stream resets after frame 0 are not supported for models with a several-frame front-end (front_taps > 1).";
-        return false;
-    }
-    if (!rate_ready(host, any, err)) return false;
-    if (host && c.report && !report_ready(false, err)) return false;
-    const size_t bytes = (size_t) B_ * T * FL * 2, rbytes = (size_t) B_ * T * 16;
-    const int16_t *src = c.pcm;
-    int16_t *dst = c.out;
-    if (host) {
-        if (hipMemcpyAsync(d_rate_io_, c.pcm, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) goto fail;
-        src = dst = d_rate_io_;
+    bool any = false;
+    for (size_t i = 0; c.resets && i < (size_t) B_ * T && !any; ++i) any = c.resets[i] != 0;
+    if (any && !rate_ready(err)) return false;
+    const uint8_t *flags = nullptr;
+    if (any) {
+        const int k = rsf_ring_.acquire();
+        if (k < 0) goto fail;
+        memcpy(rsf_ring_.host[k], c.resets, (size_t) B_ * T);
+        if (hipMemcpyAsync(d_rs_flags_, rsf_ring_.host[k], (size_t) B_ * T, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+            !rsf_ring_.uploaded(k, stream_))
+            goto fail;
+        flags = d_rs_flags_;
     }
     {
-        const uint8_t *flags = nullptr;
-        if (any) {
-            const int k = rsf_ring_.acquire();
-            if (k < 0) goto fail;
-            memcpy(rsf_ring_.host[k], c.resets, (size_t) B_ * T);
-            if (hipMemcpyAsync(d_rs_flags_, rsf_ring_.host[k], (size_t) B_ * T, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-                !rsf_ring_.uploaded(k, stream_))
-                goto fail;
-            flags = d_rs_flags_;
-        }
         ResampleArgs a;
         a.B = B_, a.T = T, a.R = R, a.resets = flags;
         a.n_low = rate_ < kRate16k ? FL : kFrame;
-        a.in = src, a.out = d_in_;
+        a.in = c.pcm, a.out = d_in_;
         a.state = d_rs_state_[0][rs_cur_], a.state_next = d_rs_state_[0][rs_cur_ ^ 1];
         a.interpolate = rate_ < kRate16k;
         memcpy(a.taps, (a.interpolate ? rs_hi_ : rs_hd_).data(), sizeof(a.taps));
@@ -2187,20 +2154,15 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
         if (hipGetLastError() != hipSuccess) goto fail;
         Call inner{T, d_in_, d_out_, c.resets};
         inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
-        inner.report = host && c.report ? d_report_ : c.report;
+        inner.report = c.report;
         if (!run_call(inner, err)) return false;
-        a.in = d_out_, a.out = dst;
+        a.in = d_out_, a.out = c.out;
         a.state = d_rs_state_[1][rs_cur_], a.state_next = d_rs_state_[1][rs_cur_ ^ 1];
         a.interpolate = !a.interpolate;
         memcpy(a.taps, (a.interpolate ? rs_hi_ : rs_hd_).data(), sizeof(a.taps));
         launch_resample(a, stream_);
         if (hipGetLastError() != hipSuccess) goto fail;
         rs_cur_ ^= 1;
-    }
-    if (host) {
-        if (hipMemcpyAsync(c.out, d_rate_io_, bytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
-        if (c.report && hipMemcpyAsync(c.report, d_report_, rbytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
-        if (hipStreamSynchronize(stream_) != hipSuccess) goto fail;
     }
     return true;
 fail:
@@ -2395,16 +2357,112 @@ Status Engine::import_state(int count, const int32_t *streams, const void *host_
     return Status::kOk;
 }
 
-// A call and its held streams: export the held rows' records to the device scratch, run the call unchanged, import them back -- around the
-// WHOLE call (outside the one-frame graph and the sub-chunks of large host calls), all on the handle's stream, so a device-pointer call
-// stays enqueued without a host wait.  The import restores both ping-pong copies, whichever parity the call has left current.
-Status Engine::process(const Call &c, std::string *err) { return fmt_ == kFmtS16 ? process_frames(c, err) : process_format(c, err); }
+// ------------------------------------------------------------------------------------------------ the host-pointer boundary
 
-Status Engine::process_frames(const Call &c, std::string *err) {
+// Handles that are not the plain one -- a rate other than 16 kHz, a packet handle, a sample format -- meet host memory HERE and nowhere
+// else: the two public entries (process, run_packets) decide every refusal in pure host code, copy the caller's input into the one staging
+// buffer, run the layers below on device pointers (format stage, packetiser, held streams, rate stages, run_call), copy the result back
+// and wait.  The plain handle's host calls are run_call's own (sub-chunks, one-frame graph).
+
+// Host or device memory of a call's three buffers; false and *err where the kinds are mixed (the entry maps the status).
+static bool call_on_host(const void *pcm, const void *out, const void *report, bool *host, std::string *err) {
+    *host = pointer_kind(pcm) != kPtrDevice;
+    if ((pointer_kind(out) != kPtrDevice) != *host) {
+        *err = "`pcm` and `enhanced` must both be host or both be device memory.";
+        return false;
+    }
+    if (report && (pointer_kind(report) != kPtrDevice) != *host) {
+        *err = "`report` must be memory of the same kind as `enhanced`: host with host, device with device.";
+        return false;
+    }
+    return true;
+}
+
+// The one copy of caller host memory to the device: `bytes` of `pcm` into d_host_io_ [B][io_row()] elements of the handle's format (and
+// d_host_rep_ [B][Tmax][4] for a call with a report), both allocated by the first call that needs them.
+bool Engine::stage_in(const void *pcm, size_t bytes, bool report, std::string *err) {
+    if (!d_host_io_) d_host_io_ = (uint8_t *) dalloc((size_t) B_ * io_row() * sample_bytes(), false);
+    if (report && !d_host_rep_) d_host_rep_ = (float *) dalloc((size_t) B_ * Tmax_ * 16, false);
+    if (!d_host_io_ || (report && !d_host_rep_)) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the staging buffer of host-memory calls.";
+        return false;
+    }
+    if (bytes && hipMemcpyAsync(d_host_io_, pcm, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) {
+        *err = hip_last_error();
+        return false;
+    }
+    return true;
+}
+
+// ... and the one copy back, then the wait: a frame call's straight into the caller's memory, a packet call's into host_out_ / host_rep_.
+bool Engine::stage_out(void *out, size_t bytes, float *report, size_t report_bytes, std::string *err) {
+    hipError_t e = bytes ? hipMemcpyAsync(out, d_host_io_, bytes, hipMemcpyDeviceToHost, stream_) : hipSuccess;
+    if (e == hipSuccess && report_bytes) e = hipMemcpyAsync(report, d_host_rep_, report_bytes, hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        *err = hip_error(e);
+        return false;
+    }
+    return true;
+}
+
+// One frame call.  The refusals stand in front of everything that is enqueued, in the order an S16 handle has always reported them (a
+// format handle used to report the pointer kinds first): held streams with resets, pointer kinds, late resets of a several-frame
+// front-end.  What can fail behind them is HIP.  On a format handle format_in_kernel takes the call's elements to int16 (d_fmt_in_), the
+// S16 call runs from d_fmt_in_ to d_fmt_out_, and format_out_kernel takes the result to the caller's elements (kns_format.hip); the input is
+// consumed before the output is written, so `pcm` and `enhanced` may overlap in any way.
+Status Engine::process(const Call &c, std::string *err) {
     if (c.hold && c.resets) {
         *err = "held streams are not combined with per-frame stream resets in one call.";
         return Status::kBadArgument;
     }
+    if (rate_ == kRate16k && fmt_ == kFmtS16) return process_frames(c, err);  // the plain handle
+    (void) hipSetDevice(device_);
+    bool host, late = false;
+    if (!call_on_host(c.pcm, c.out, c.report, &host, err)) return Status::kRuntime;
+    for (int b = 0; c.resets && taps_ > 1 && b < B_ && !late; ++b)
+        for (int t = 1; t < c.T && !late; ++t) late = c.resets[(size_t) b * c.T + t] != 0;
+    if (late) {
+        *err = "per-frame stream resets after frame 0 are not supported for models with a several-frame front-end (front_taps > 1).";
+        return Status::kRuntime;
+    }
+    const size_t n = (size_t) B_ * c.T * rs_frame_length(rate_), bytes = n * sample_bytes();
+    Call dev = c;  // the call below the boundary (Call::pcm / out: elements of the handle's format behind the int16 type)
+    dev.host_contract = false;
+    if (host) {
+        if (!stage_in(c.pcm, bytes, c.report != nullptr, err)) return Status::kRuntime;
+        dev.pcm = dev.out = (int16_t *) d_host_io_;
+        if (c.report) dev.report = d_host_rep_;
+    }
+    Call inner = dev;
+    hipError_t e = hipSuccess;
+    if (fmt_ != kFmtS16) {
+        inner.pcm = d_fmt_in_, inner.out = d_fmt_out_;
+        launch_format_in(fmt_, FormatArgs{dev.pcm, d_fmt_in_, nullptr, (long long) n, 1}, stream_);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        const Status st = process_frames(inner, err);
+        if (st != Status::kOk) return st;
+    }
+    if (e == hipSuccess && fmt_ != kFmtS16) {
+        launch_format_out(fmt_, FormatArgs{d_fmt_out_, dev.out, nullptr, (long long) n, 1}, stream_);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        *err = hip_error(e);
+        return Status::kRuntime;
+    }
+    if (host && !stage_out(c.out, bytes, c.report, c.report ? (size_t) B_ * c.T * 16 : 0, err)) return Status::kRuntime;
+    return Status::kOk;
+}
+
+// A call and its held streams: export the held rows' records to the device scratch, run the call unchanged, import them back -- around the
+// WHOLE call (outside the one-frame graph and the sub-chunks of large host calls), all on the handle's stream, so a device-pointer call
+// stays enqueued without a host wait.  The import restores both ping-pong copies, whichever parity the call has left current.
+Status Engine::process_frames(const Call &c, std::string *err) {
     std::vector<int32_t> held;
     for (int b = 0; c.hold && b < B_; ++b)
         if (c.hold[b]) held.push_back(b);
@@ -2469,14 +2527,15 @@ PacketStateArgs Engine::packet_state_args() const {
 
 // One call of a packet handle (fourth extension; section 6).  The plan is made on the host from the mirror of fill:
 // stream b completes k_b = (fill_b + counts[b]) / F frames; the sub-calls are cut at every distinct non-zero k_b (k_b <= max_frames always), and
-// sub-call [c0, c1) holds the streams with k_b < c1 (koala_amd/packets.py restates the plan).  Everything goes onto the handle's stream:
-// the call's table, the masked reset of `restart`, packet_in_kernel, the sub-calls through process() -- routes, held streams, rate
-// stages, attenuation limit and report as they are -- and packet_out_kernel.  Host pointers: one copy in, that, one copy out, a wait.
+// sub-call [c0, c1) holds the streams with k_b < c1 (koala_amd/packets.py restates the plan).  Every refusal is decided before anything is
+// touched: max_samples, counts, report_frames, pointer kinds.  Then everything goes onto the handle's stream: on a format handle
+// format_in_kernel over the whole rows [B][max_samples] (the caller owns them), the call's table, the masked reset of `restart`,
+// packet_in_kernel, the sub-calls through process_frames -- routes, held streams, rate stages, attenuation limit and report as they are --
+// packet_out_kernel, and on a format handle format_out_kernel, which writes row b's first counts[b] elements only, from the call's table
+// (d_pk_tab_ starts with the counts).  A call without a sample (restarts only) moves and converts no samples.  Host pointers: the staging
+// stands in for the caller's device memory, and of what comes back only a row's first counts[b] elements and a stream's first k_b report
+// rows are copied on: the rest of the caller's bytes stay.
 Status Engine::run_packets(const PacketCall &c, std::string *err) {
-    return fmt_ == kFmtS16 ? run_packets_s16(c, err) : run_packets_format(c, err);
-}
-
-Status Engine::run_packets_s16(const PacketCall &c, std::string *err) {
     const int F = rs_frame_length(rate_);
     if (c.max_samples < 1 || c.max_samples > pk_max_) {
         *err = "`max_samples` " + std::to_string(c.max_samples) + " is outside [1, " + std::to_string(pk_max_) + "].";
@@ -2502,16 +2561,8 @@ Status Engine::run_packets_s16(const PacketCall &c, std::string *err) {
         return Status::kBadArgument;
     }
     (void) hipSetDevice(device_);
-    const PointerKind kin = pointer_kind(c.pcm), kout = pointer_kind(c.out);
-    if ((kin == kPtrDevice) != (kout == kPtrDevice)) {
-        *err = "`pcm` and `enhanced` must both be host or both be device memory.";
-        return Status::kBadArgument;
-    }
-    const bool host = kin != kPtrDevice;
-    if (c.report && (pointer_kind(c.report) == kPtrDevice) == host) {
-        *err = "`report` must be memory of the same kind as `enhanced`: host with host, device with device.";
-        return Status::kBadArgument;
-    }
+    bool host;
+    if (!call_on_host(c.pcm, c.out, c.report, &host, err)) return Status::kBadArgument;
     if (!any_count && !any_restart) {  // every stream stalled: nothing to do
         for (int b = 0; c.frames && b < B_; ++b) c.frames[b] = 0;
         return Status::kOk;
@@ -2524,13 +2575,24 @@ Status Engine::run_packets_s16(const PacketCall &c, std::string *err) {
         }
     }
     const int nsub = (int) cuts.size() - 1;
-    const size_t io_bytes = (size_t) B_ * c.max_samples * 2;
-    if (host && !d_pk_io_) d_pk_io_ = (int16_t *) dalloc((size_t) B_ * pk_max_ * 2, false);
-    if (host && c.report && !d_pk_user_rep_) d_pk_user_rep_ = (float *) dalloc((size_t) B_ * Tmax_ * 16, false);
-    if (host && (!d_pk_io_ || (c.report && !d_pk_user_rep_))) {
-        (void) hipGetLastError();
-        *err = "Failed to allocate the staging buffer of host-memory calls.";
-        return Status::kRuntime;
+    const bool convert = fmt_ != kFmtS16 && any_count;
+    const size_t n = (size_t) B_ * c.max_samples, eb = (size_t) sample_bytes();
+    // what the call reads and writes on the device: the caller's memory, or the staging (its report rows kmax apart)
+    const void *src = c.pcm;
+    void *dst = c.out;
+    float *report = c.report;
+    int report_frames = c.report_frames;
+    if (host) {
+        if (!stage_in(c.pcm, any_count ? n * eb : 0, c.report != nullptr, err)) return Status::kRuntime;
+        src = dst = d_host_io_;
+        if (c.report) report = d_host_rep_, report_frames = kmax;
+    }
+    if (convert) {
+        launch_format_in(fmt_, FormatArgs{src, d_fmt_in_, nullptr, (long long) n, 1}, stream_);
+        if (hipGetLastError() != hipSuccess) {
+            *err = hip_last_error();
+            return Status::kRuntime;
+        }
     }
     // the call's table, and the restart mask behind it
     const size_t tab_ints = (size_t) Bpad_ + 2 + (size_t) Tmax_;
@@ -2556,20 +2618,16 @@ Status Engine::run_packets_s16(const PacketCall &c, std::string *err) {
         for (int b = 0; b < B_; ++b)
             if (c.restart[b]) pk_fill_[b] = 0;
     }
-    if (host && hipMemcpyAsync(d_pk_io_, c.pcm, io_bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) {
-        *err = hip_last_error();
-        return Status::kRuntime;
-    }
     PacketArgs a;
-    a.user_in = host ? d_pk_io_ : c.pcm;
-    a.user_out = host ? d_pk_io_ : c.out;
+    a.user_in = fmt_ != kFmtS16 ? d_fmt_in_ : (const int16_t *) src;
+    a.user_out = fmt_ != kFmtS16 ? d_fmt_out_ : (int16_t *) dst;
     a.tab = d_pk_tab_;
     a.pin = d_pk_pin_, a.pout = d_pk_pout_;
     a.fill_in = d_pk_fill_[0], a.fill_out = d_pk_fill_[1];
     a.frames = d_pk_in_;
     a.sub_report = d_pk_rep_;
-    a.report = !c.report ? nullptr : host ? d_pk_user_rep_ : c.report;
-    a.report_frames = host ? kmax : c.report_frames;
+    a.report = report;
+    a.report_frames = report_frames;
     a.max_samples = c.max_samples, a.B = B_, a.Bpad = Bpad_, a.F = F;
     launch_packet_in(a, stream_);
     if (hipGetLastError() != hipSuccess) {
@@ -2585,11 +2643,11 @@ Status Engine::run_packets_s16(const PacketCall &c, std::string *err) {
         inner.hold = held ? hold.data() : nullptr;
         inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
         inner.report = c.report ? d_pk_rep_ + (size_t) B_ * c0 * 4 : nullptr;
-        const Status st = process_frames(inner, err);
-        if (st != Status::kOk) return Status::kRuntime;
+        if (process_frames(inner, err) != Status::kOk) return Status::kRuntime;
     }
     a.frames = d_pk_out_;
     launch_packet_out(a, stream_);
+    if (convert) launch_format_out(fmt_, FormatArgs{d_fmt_out_, dst, d_pk_tab_, (long long) c.max_samples, B_}, stream_);
     if (hipGetLastError() != hipSuccess) {
         *err = hip_last_error();
         return Status::kRuntime;
@@ -2599,22 +2657,14 @@ Status Engine::run_packets_s16(const PacketCall &c, std::string *err) {
         if (c.frames) c.frames[b] = k[b];
     }
     if (host) {
-        pk_host_out_.resize((size_t) B_ * c.max_samples);
-        hipError_t e = hipMemcpyAsync(pk_host_out_.data(), d_pk_io_, io_bytes, hipMemcpyDeviceToHost, stream_);
-        if (e == hipSuccess && c.report && kmax) {
-            pk_host_rep_.resize((size_t) B_ * kmax * 4);
-            e = hipMemcpyAsync(pk_host_rep_.data(), d_pk_user_rep_, (size_t) B_ * kmax * 16, hipMemcpyDeviceToHost, stream_);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-        if (e != hipSuccess) {
-            (void) hipGetLastError();
-            *err = hip_error(e);
-            return Status::kRuntime;
-        }
-        // (only a row's first counts[b] samples, and a stream's first k_b report rows, are the caller's to be written)
+        const size_t rep_floats = c.report ? (size_t) B_ * kmax * 4 : 0;
+        host_out_.resize(n * eb);
+        host_rep_.resize(rep_floats);
+        if (!stage_out(host_out_.data(), any_count ? n * eb : 0, host_rep_.data(), rep_floats * 4, err)) return Status::kRuntime;
         for (int b = 0; b < B_; ++b) {
-            memcpy(c.out + (size_t) b * c.max_samples, pk_host_out_.data() + (size_t) b * c.max_samples, (size_t) c.counts[b] * 2);
-            if (c.report) memcpy(c.report + (size_t) b * c.report_frames * 4, pk_host_rep_.data() + (size_t) b * kmax * 4, (size_t) k[b] * 16);
+            const size_t at = (size_t) b * c.max_samples * eb;
+            memcpy((uint8_t *) c.out + at, host_out_.data() + at, (size_t) c.counts[b] * eb);
+            if (c.report) memcpy(c.report + (size_t) b * c.report_frames * 4, host_rep_.data() + (size_t) b * kmax * 4, (size_t) k[b] * 16);
         }
     }
     return Status::kOk;
@@ -2622,18 +2672,14 @@ Status Engine::run_packets_s16(const PacketCall &c, std::string *err) {
 
 // ------------------------------------------------------------------------------------------------ sample formats
 
-// A handle whose callers hold float32 or G.711 samples (fifth extension; section 6): the outermost stage of a call.
-// format_in_kernel takes every element the call reads to int16 (d_fmt_in_), the S16 handle's call runs unchanged on device pointers
-// from d_fmt_in_ to d_fmt_out_ -- rate stages, packetiser, resets, held streams, attenuation limit and report with it -- and
-// format_out_kernel takes the samples the call writes to the caller's elements.  Everything is enqueued on the handle's stream, with no host
-// wait for device pointers.  Host pointers: one copy in of the FORMAT's bytes, this route, one copy out, a wait (no sub-chunks, no
-// one-frame graph).  The input is consumed before the output is written: `pcm` and `enhanced` may overlap in any way.
+// A handle whose callers hold float32 or G.711 samples (fifth extension; section 6): two int16 staging matrices
+// [B][io_row()], between which the S16 handle's call runs unchanged.  The two kernel launches around that call are the entries' (process,
+// run_packets: the host-pointer boundary).
 bool Engine::set_format(int fmt, std::string *err) {
     if (fmt == kFmtS16) return true;
     (void) hipSetDevice(device_);
-    fmt_row_ = pk_max_ ? (size_t) pk_max_ : (size_t) Tmax_ * rs_frame_length(rate_);
-    d_fmt_in_ = (int16_t *) dalloc((size_t) B_ * fmt_row_ * 2, false);
-    d_fmt_out_ = (int16_t *) dalloc((size_t) B_ * fmt_row_ * 2, false);
+    d_fmt_in_ = (int16_t *) dalloc((size_t) B_ * io_row() * 2, false);
+    d_fmt_out_ = (int16_t *) dalloc((size_t) B_ * io_row() * 2, false);
     if (!d_fmt_in_ || !d_fmt_out_) {
         (void) hipGetLastError();
         *err = "Failed to allocate the staging buffers of a sample format.";
@@ -2641,142 +2687,6 @@ bool Engine::set_format(int fmt, std::string *err) {
     }
     fmt_ = fmt;
     return true;
-}
-
-bool Engine::format_host_ready(bool report, std::string *err) {
-    if (!d_fmt_io_) d_fmt_io_ = (uint8_t *) dalloc((size_t) B_ * fmt_row_ * sample_bytes(), false);
-    if (report && !d_fmt_rep_) d_fmt_rep_ = (float *) dalloc((size_t) B_ * Tmax_ * 16, false);
-    if (!d_fmt_io_ || (report && !d_fmt_rep_)) {
-        (void) hipGetLastError();
-        *err = "Failed to allocate the staging buffer of host-memory calls.";
-        return false;
-    }
-    return true;
-}
-
-Status Engine::process_format(const Call &c, std::string *err) {
-    (void) hipSetDevice(device_);
-    const PointerKind kin = pointer_kind(c.pcm), kout = pointer_kind(c.out);
-    if ((kin == kPtrDevice) != (kout == kPtrDevice)) {
-        *err = "`pcm` and `enhanced` must both be host or both be device memory.";
-        return Status::kRuntime;
-    }
-    const bool host = kin != kPtrDevice;
-    if (c.report && (pointer_kind(c.report) == kPtrDevice) == host) {
-        *err = "`report` must be memory of the same kind as `enhanced`: host with host, device with device.";
-        return Status::kRuntime;
-    }
-    if (host && !format_host_ready(c.report != nullptr, err)) return Status::kRuntime;
-    const size_t n = (size_t) B_ * c.T * rs_frame_length(rate_), bytes = n * sample_bytes();
-    const void *src = c.pcm;  // (Call::pcm / out: elements of the handle's format behind the int16 type)
-    void *dst = c.out;
-    if (host) {
-        if (hipMemcpyAsync(d_fmt_io_, c.pcm, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) goto fail;
-        src = dst = d_fmt_io_;
-    }
-    {
-        launch_format_in(fmt_, FormatArgs{src, d_fmt_in_, nullptr, (long long) n, 1}, stream_);
-        if (hipGetLastError() != hipSuccess) goto fail;
-        Call inner = c;
-        inner.pcm = d_fmt_in_, inner.out = d_fmt_out_;
-        inner.host_contract = false;
-        if (host && c.report) inner.report = d_fmt_rep_;
-        const Status st = process_frames(inner, err);
-        if (st != Status::kOk) return st;  // (a refused call has advanced nothing: the in-stage wrote its staging matrix only)
-        launch_format_out(fmt_, FormatArgs{d_fmt_out_, dst, nullptr, (long long) n, 1}, stream_);
-        if (hipGetLastError() != hipSuccess) goto fail;
-    }
-    if (host) {
-        if (hipMemcpyAsync(c.out, d_fmt_io_, bytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
-        if (c.report && hipMemcpyAsync(c.report, d_fmt_rep_, (size_t) B_ * c.T * 16, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
-        if (hipStreamSynchronize(stream_) != hipSuccess) goto fail;
-    }
-    return Status::kOk;
-fail:
-    *err = hip_last_error();
-    return Status::kRuntime;
-}
-
-// A packet call of such a handle: the whole rows [B][max_samples] are decoded (the caller owns them), the S16 packet call runs on the two
-// staging matrices, and format_out_kernel writes row b's first counts[b] elements only, from the call's device table (d_pk_tab_ starts with
-// the counts) -- the rest of the caller's `enhanced` keeps its bytes.  A call in which every stream is stalled converts nothing.
-Status Engine::run_packets_format(const PacketCall &c, std::string *err) {
-    if (c.max_samples < 1 || c.max_samples > pk_max_) {
-        *err = "`max_samples` " + std::to_string(c.max_samples) + " is outside [1, " + std::to_string(pk_max_) + "].";
-        return Status::kBadArgument;
-    }
-    bool any_count = false;
-    for (int b = 0; b < B_; ++b) {
-        if (c.counts[b] < 0 || c.counts[b] > c.max_samples) {
-            *err = "`counts[" + std::to_string(b) + "]` = " + std::to_string(c.counts[b]) + " is outside [0, " + std::to_string(c.max_samples) + "].";
-            return Status::kBadArgument;
-        }
-        any_count = any_count || c.counts[b] > 0;
-    }
-    (void) hipSetDevice(device_);
-    const PointerKind kin = pointer_kind(c.pcm), kout = pointer_kind(c.out);
-    if ((kin == kPtrDevice) != (kout == kPtrDevice)) {
-        *err = "`pcm` and `enhanced` must both be host or both be device memory.";
-        return Status::kBadArgument;
-    }
-    const bool host = kin != kPtrDevice;
-    if (c.report && (pointer_kind(c.report) == kPtrDevice) == host) {
-        *err = "`report` must be memory of the same kind as `enhanced`: host with host, device with device.";
-        return Status::kBadArgument;
-    }
-    if (host && !format_host_ready(c.report != nullptr, err)) return Status::kRuntime;
-    const size_t eb = (size_t) sample_bytes(), n = (size_t) B_ * c.max_samples;
-    const void *src = c.pcm;
-    void *dst = c.out;
-    hipError_t e = hipSuccess;
-    if (host) src = dst = d_fmt_io_;
-    if (any_count) {
-        if (host) e = hipMemcpyAsync(d_fmt_io_, c.pcm, n * eb, hipMemcpyHostToDevice, stream_);
-        if (e == hipSuccess) {
-            launch_format_in(fmt_, FormatArgs{src, d_fmt_in_, nullptr, (long long) n, 1}, stream_);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) {
-            *err = hip_error(e);
-            return Status::kRuntime;
-        }
-    }
-    std::vector<int32_t> k((size_t) B_, 0);
-    PacketCall inner = c;
-    inner.pcm = d_fmt_in_, inner.out = d_fmt_out_;
-    inner.frames = k.data();
-    if (host && c.report) inner.report = d_fmt_rep_, inner.report_frames = std::min(c.report_frames, Tmax_);
-    const Status st = run_packets_s16(inner, err);
-    if (st != Status::kOk) return st;
-    for (int b = 0; c.frames && b < B_; ++b) c.frames[b] = k[b];
-    if (any_count) {
-        launch_format_out(fmt_, FormatArgs{d_fmt_out_, dst, d_pk_tab_, (long long) c.max_samples, B_}, stream_);
-        e = hipGetLastError();
-    }
-    if (host && e == hipSuccess) {
-        const int rf = inner.report_frames;
-        if (any_count) {
-            fmt_host_out_.resize(n * eb);
-            e = hipMemcpyAsync(fmt_host_out_.data(), d_fmt_io_, n * eb, hipMemcpyDeviceToHost, stream_);
-        }
-        if (e == hipSuccess && c.report && rf > 0) {
-            fmt_host_rep_.resize((size_t) B_ * rf * 4);
-            e = hipMemcpyAsync(fmt_host_rep_.data(), d_fmt_rep_, (size_t) B_ * rf * 16, hipMemcpyDeviceToHost, stream_);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-        // (only a row's first counts[b] elements, and a stream's first k_b report rows, are the caller's to be written)
-        for (int b = 0; e == hipSuccess && b < B_; ++b) {
-            const size_t at = (size_t) b * c.max_samples * eb;
-            if (any_count) memcpy((uint8_t *) c.out + at, fmt_host_out_.data() + at, (size_t) c.counts[b] * eb);
-            if (c.report && k[b]) memcpy(c.report + (size_t) b * c.report_frames * 4, fmt_host_rep_.data() + (size_t) b * rf * 4, (size_t) k[b] * 16);
-        }
-    }
-    if (e != hipSuccess) {
-        (void) hipGetLastError();
-        *err = hip_error(e);
-        return Status::kRuntime;
-    }
-    return Status::kOk;
 }
 
 // ------------------------------------------------------------------------------------------------ debug taps

@@ -36,7 +36,8 @@ enum KernelClass { kClsAnalysis = 0, kClsGemmIn = 1, kClsGru = 2, kClsGemmHead =
 
 // One call that advances the streams, with everything it carries.  pcm/out: [B][T*frame_length] at the handle's sample rate (256 at
 // 16 kHz), host or device pointers (both of the same kind).  On a handle with a sample format (Engine::set_format) they point to elements
-// of that format -- float or uint8 -- behind the int16 type: the entry casts, and every size is a count of sample_bytes().
+// of that format -- float or uint8 -- behind the int16 type: the entry casts, and every size is a count of sample_bytes().  Host pointers
+// are the entry's business (Engine::process): below it a call of a handle that is not the plain one carries device pointers only.
 struct Call {
     int T;
     const int16_t *pcm;
@@ -69,6 +70,7 @@ struct Call {
 enum class Status { kOk, kBadArgument, kRuntime };
 
 // One call of a packet handle (include/pv_koala_batch.h, pv_koala_batch_process_packets): stream b gives and takes counts[b] samples.
+// Host pointers end at the entry (Engine::run_packets), which refuses a bad member before anything is enqueued.
 struct PacketCall {
     int max_samples;                   // row length of pcm / out, 1 .. the handle's
     const int32_t *counts;             // host [num_streams], each in [0, max_samples]
@@ -130,7 +132,7 @@ public:
 
     // ---- sample formats (fifth extension).  set_format, once, right after create() -- and after enable_packets on a
     // packet handle: from then on the `pcm` and `out` of process() and run_packets() point to elements of that format (kns_kernels.h,
-    // SampleFormat) behind their int16 types, sample_bytes() each, and are converted on the device around the unchanged call.  The engine's
+    // SampleFormat) behind their int16 types, sample_bytes() each, and are converted on the device around the unchanged S16 call.  The engine's
     // samples stay int16 inside: F32 is an input / output form, not a wider path.  Configuration, not stream state: records, state_bytes()
     // and the delay are those of the S16 handle.  The asynchronous host calls are refused.  kFmtS16 allocates and changes nothing.
     bool set_format(int fmt, std::string *err);
@@ -143,49 +145,48 @@ public:
 
 private:
     Engine() {}
-    // sample formats: the int16 staging matrices [B][fmt_row_] on either side of the inner call, the staging of host-pointer calls (the
-    // format's bytes; a report [B][Tmax][4]) and the host copy of a packet call's output, of which the rows' first counts[b] elements go on
+    // The host-pointer boundary of every handle that is not the plain one (a rate other than 16 kHz, a packet handle, a sample format):
+    // process() and run_packets() stage the caller's host memory in and out (kns_engine.cpp, stage_in / stage_out); everything below them
+    // sees device pointers.  One staging set, allocated by the first host-pointer call: d_host_io_ [B][io_row()] elements of the handle's
+    // format, the call's input and then its output; d_host_rep_ [B][Tmax][4]; and the host copies of a packet call's output and report,
+    // of which only a row's first counts[b] elements and a stream's first k_b report rows go on to the caller.
+    size_t io_row() const { return pk_max_ ? (size_t) pk_max_ : (size_t) Tmax_ * rs_frame_length(rate_); }  // a stream's most elements per call
+    uint8_t *d_host_io_ = nullptr;
+    float *d_host_rep_ = nullptr;
+    std::vector<uint8_t> host_out_;
+    std::vector<float> host_rep_;
+    bool stage_in(const void *pcm, size_t bytes, bool report, std::string *err);
+    bool stage_out(void *out, size_t bytes, float *report, size_t report_bytes, std::string *err);
+    // sample formats: the int16 staging matrices [B][io_row()] on either side of the S16 call
     int fmt_ = kFmtS16;
-    size_t fmt_row_ = 0;
     int16_t *d_fmt_in_ = nullptr, *d_fmt_out_ = nullptr;
-    uint8_t *d_fmt_io_ = nullptr;
-    float *d_fmt_rep_ = nullptr;
-    std::vector<uint8_t> fmt_host_out_;
-    std::vector<float> fmt_host_rep_;
-    bool format_host_ready(bool report, std::string *err);
-    Status process_format(const Call &c, std::string *err);
-    Status run_packets_format(const PacketCall &c, std::string *err);
-    Status process_frames(const Call &c, std::string *err);          // process() of an S16 handle
-    Status run_packets_s16(const PacketCall &c, std::string *err);  // run_packets() of an S16 handle
+    Status process_frames(const Call &c, std::string *err);  // a frame call and its held streams, below the boundary
     bool init(const Params &p, int device, int B, int Tmax, int precision, std::string *err, bool *oom);
     bool run_call(const Call &c, std::string *err);  // process() without the held streams, at 16 kHz
-    // Handles that are not at 16 kHz (kns_engine.cpp, run_call_rate): in-stage kernel, run_call on device buffers, out-stage kernel.
+    // Handles that are not at 16 kHz (kns_engine.cpp, run_call_rate; device pointers): in-stage kernel, run_call on device buffers, out-stage kernel.
     // The stages' per-stream state (rs_in, rs_out: kns_kernels.h) is a ping-pong pair each, like the history; it is part of the stream
     // record (version 2), of reset() and of a call's per-frame resets.
     bool advance(const Call &c, std::string *err) { return rate_ == kRate16k ? run_call(c, err) : run_call_rate(c, err); }
     bool run_call_rate(const Call &c, std::string *err);
-    bool rate_ready(bool host_staging, bool reset_flags, std::string *err);
+    bool rate_ready(std::string *err);  // d_rs_flags_ and its ring
     // the state kernels of export / import / held streams: the engine's and, at such a rate, the stages'; packet_part: and a packet handle's
     // (not for held streams: a sub-call of a packet call does not touch the packetiser's state, whose two lengths differ inside a call)
     void launch_states(bool import, bool packet_part);
     void launch_resets(const uint8_t *d_mask);  // every reset kernel of the handle (d_mask: device [Bpad], null: every stream)
     // packet handles: the packetiser's state (kns_kernels.h, PacketArgs), the sub-calls' stacked frame matrices and reports
-    // [B][Tmax F] / [B][Tmax][4], the staging of host-pointer calls, the call table and its upload ring, and the HOST MIRROR of
+    // [B][Tmax F] / [B][Tmax][4], the call table and its upload ring, and the HOST MIRROR of
     // fill, from which a call is planned without a look at the device (updated by calls, resets and import_state)
     int pk_max_ = 0;
-    int16_t *d_pk_pin_ = nullptr, *d_pk_pout_ = nullptr, *d_pk_in_ = nullptr, *d_pk_out_ = nullptr, *d_pk_io_ = nullptr;
+    int16_t *d_pk_pin_ = nullptr, *d_pk_pout_ = nullptr, *d_pk_in_ = nullptr, *d_pk_out_ = nullptr;
     int32_t *d_pk_fill_[2] = {nullptr, nullptr}, *d_pk_tab_ = nullptr;
-    float *d_pk_rep_ = nullptr, *d_pk_user_rep_ = nullptr;
+    float *d_pk_rep_ = nullptr;
     uint8_t *d_state_pk_ = nullptr;  // the packet part of the staged stream records [B][pk_record_bytes]
     std::vector<int32_t> pk_fill_;
-    std::vector<int16_t> pk_host_out_;  // host-pointer calls: the whole output matrix, of which the rows' first counts[b] samples go on
-    std::vector<float> pk_host_rep_;
     PacketStateArgs packet_state_args() const;
     int rate_ = kRate16k;
     int16_t *d_rs_state_[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [in-stage, out-stage][ping-pong copy], [Bpad][hist] each
     int rs_cur_ = 0;
     std::vector<float> rs_hd_, rs_hi_;  // the prototype's two tables (decimator, interpolator)
-    int16_t *d_rate_io_ = nullptr;      // host-pointer calls: [B][Tmax * frame_length], the call's input, then its output
     uint8_t *d_rs_flags_ = nullptr;     // a call's per-frame resets on the device, uint8 [B][T], and their upload ring
     uint8_t *d_state_rs_ = nullptr;     // the stages' part of the staged stream records [B][rs_record_bytes]
     // what run_device is given: the frames [t0, t0 + T) of a call, their device buffers, and the call's reset table if it has one

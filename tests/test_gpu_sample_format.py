@@ -14,7 +14,7 @@ import pytest
 import koala_amd
 import sample_format_recipe as sf
 from conftest import model_file
-from koala_amd import KoalaInvalidArgumentError
+from koala_amd import KoalaInvalidArgumentError, KoalaRuntimeError
 from koala_amd._batch import BatchConfig
 from koala_amd._koala import PicovoiceStatuses
 
@@ -325,4 +325,152 @@ def test_refusals_leave_the_streams_as_they_were():
     for kwargs in (dict(fmt=1, struct_size=24), dict(fmt=1, struct_size=0), dict(fmt=4), dict(fmt=-1)):
         status, handle = init_config(lib, model, B, TMAX, 0, 'bf16', 16000, **kwargs)
         assert status is PicovoiceStatuses.INVALID_ARGUMENT and not handle.value, kwargs
+    kf.delete(), ks.delete()
+
+
+# ------------------------------------------------------------------------------------------------ the host-pointer boundary
+
+BOUNDARY_B, BOUNDARY_T = 6, 3
+MIXED_KINDS = '`pcm` and `enhanced` must both be host or both be device memory.'
+
+
+def fill_value(fmt):
+    return np.float32(-7.5) if fmt == 'f32' else np.uint8(0x3C)
+
+
+def packet_report_call(kb, pcm, counts, mode, sentinel, rows=BOUNDARY_T):
+    """one packet call with a report, into a sentinel-filled `enhanced` (in place: `pcm` itself) and report -> enhanced, report, frames"""
+    N = pcm.shape[1]
+    if mode == 'host':
+        out, rep = np.full_like(pcm, sentinel), np.full((pcm.shape[0], rows, 4), -1.0, np.float32)
+        frames = kb._packets(N, counts, pcm.ctypes.data, out.ctypes.data, None, rep.ctypes.data, rows)
+        return out, rep, frames
+    import torch
+    xd = torch.from_numpy(pcm).cuda()
+    yd = xd if mode == 'inplace' else torch.from_numpy(np.full_like(pcm, sentinel)).cuda()
+    rd = torch.full((pcm.shape[0], rows, 4), -1.0, dtype=torch.float32, device='cuda')
+    torch.cuda.synchronize()
+    frames = kb.process_device_packets(N, counts, xd.data_ptr(), yd.data_ptr(), None, rd.data_ptr(), rows)
+    kb.synchronize()
+    return yd.cpu().numpy(), rd.cpu().numpy(), frames
+
+
+@pytest.mark.parametrize('packets', [False, True])
+@pytest.mark.parametrize('precision', ['fp32', 'bf16'])
+@pytest.mark.parametrize('fmt,rate', [('f32', 16000), ('ulaw', 8000), ('alaw', 48000)])
+def test_host_device_and_in_place_are_one_call(fmt, rate, precision, packets):
+    B, F = BOUNDARY_B, flen(rate)
+    N = 5 * F // 2 if packets else 0  # 2.5 frames: a stream completes 2 or 3 frames of a full packet
+    x = signal(fmt, B, 3 * max(N, 2 * F), seed=37)
+    sentinel = fill_value(fmt)
+    runs = {}
+    for mode in ('host', 'device', 'inplace'):
+        kb = koala_amd.create_batch('key', B, BOUNDARY_T, precision, model_path=model_file('random'), sample_rate=rate, sample_format=fmt,
+                                    packet_samples=N)
+        kb.set_min_gain(np.linspace(0.1, 0.6, B))
+        outs, reps = [], []
+        if packets:
+            rng = np.random.default_rng(41)
+            pos, fill = np.zeros(B, int), np.zeros(B, int)
+            for i in range(3):
+                counts = rng.integers(0, N + 1, B).astype(np.int32)
+                k = (fill + counts) // F
+                fill = fill + counts - k * F
+                pcm = np.full((B, N), sentinel)  # (beyond counts[b] the sentinel: what an in-place call must leave there too)
+                for b in range(B):
+                    pcm[b, :counts[b]] = x[b, pos[b]:pos[b] + counts[b]]
+                pos += counts
+                out, rep, frames = packet_report_call(kb, pcm, counts, mode, sentinel)
+                assert np.array_equal(frames, k), (mode, i)
+                for b in range(B):  # only the counted elements and the completed frames' rows are written
+                    assert same(out[b, counts[b]:], np.full(N - counts[b], sentinel)), (mode, i, b)
+                    assert same(rep[b, k[b]:], np.full((BOUNDARY_T - k[b], 4), -1.0, np.float32)), (mode, i, b)
+                outs.append(out), reps.append(rep)
+        else:
+            t = 0
+            for T in (1, 3, 2):
+                out, rep = call(kb, np.ascontiguousarray(x[:, t * F:(t + T) * F]), mode, report=True)
+                outs.append(out), reps.append(rep)
+                t += T
+        runs[mode] = (outs, reps, kb.export_state())
+        kb.delete()
+    for mode in ('device', 'inplace'):
+        for i in range(3):
+            assert same(runs[mode][0][i], runs['host'][0][i]), (mode, i)
+            assert same(runs[mode][1][i], runs['host'][1][i]), (mode, i)
+        assert np.array_equal(runs[mode][2], runs['host'][2]), mode
+
+
+@pytest.mark.parametrize('precision', ['fp32', 'bf16'])
+def test_a_refused_host_call_leaves_caller_and_streams_alone(precision):
+    import torch
+    B, T, model = BOUNDARY_B, BOUNDARY_T, model_file('random')
+
+    def refuse(kb, error, words, refused, *untouched):
+        before = kb.export_state()
+        with pytest.raises(error) as e:
+            refused()
+        assert all(w in str(e.value) for w in words), str(e.value)
+        kb.synchronize()
+        for a, value in untouched:
+            assert same(a, np.full_like(a, value)), words
+        assert np.array_equal(kb.export_state(), before), words
+
+    # ---- a format frame handle: A-law at 8 kHz
+    fmt, F = 'alaw', flen(8000)
+    kf, ks = pair(model, B, precision, 8000, fmt, T=T)
+    x = signal(fmt, B, 4 * 2 * F, seed=43)
+    parts = iter([np.ascontiguousarray(x[:, i * 2 * F:(i + 1) * 2 * F]) for i in range(4)])
+
+    def accepted():
+        part = next(parts)
+        assert same(kf.process(part), enc(fmt, ks.process(dec(fmt, part))))
+
+    accepted()
+    pcm, out = signal(fmt, B, 2 * F, seed=47), np.full((B, 2 * F), np.uint8(0x3C))
+    pcm_d = torch.from_numpy(pcm).cuda()
+    torch.cuda.synchronize()
+    resets, hold = np.zeros((B, 2), np.uint8), np.array([0, 1, 0, 0, 0, 0], np.uint8)
+    resets[2, 0] = 1
+    refuse(kf, KoalaInvalidArgumentError, ('held streams', 'resets'),
+           lambda: kf._call(2, pcm.ctypes.data, out.ctypes.data, resets, hold, None, False), (out, 0x3C))
+    accepted()
+    refuse(kf, KoalaRuntimeError, (MIXED_KINDS,),
+           lambda: kf._call(2, ctypes.c_void_p(pcm_d.data_ptr()), out.ctypes.data, None, None, None, False), (out, 0x3C))
+    accepted()
+    kf.delete(), ks.delete()
+
+    # ---- a format packet handle: float32 at 16 kHz
+    fmt, F = 'f32', 256
+    N = 5 * F // 2
+    kf, ks = pair(model, B, precision, 16000, fmt, T=T, packet_samples=N)
+    x = signal(fmt, B, 4 * N, seed=53)
+    parts = iter([np.ascontiguousarray(x[:, i * N:(i + 1) * N]) for i in range(4)])
+    counts = np.array([N, 0, N // 2, N, 1, N], np.int32)
+    fill = np.zeros(B, int)
+
+    def accepted_packets():
+        part = next(parts)
+        got, want = packet_call(kf, part, counts, None, 'host', np.float32(-7.5)), packet_call(ks, dec(fmt, part), counts, None, 'host', np.int16(-7))
+        for b in range(B):
+            assert same(got[b, :counts[b]], enc(fmt, want[b, :counts[b]])), b
+        fill[:] = (fill + counts) % F
+
+    accepted_packets()
+    pcm, out = signal(fmt, B, N, seed=59), np.full((B, N), np.float32(-7.5))
+    pcm_d = torch.from_numpy(pcm).cuda()
+    torch.cuda.synchronize()
+    kmax = int(((fill + counts) // F).max())
+    assert kmax >= 2
+    rep = np.full((B, kmax - 1, 4), -1.0, np.float32)
+    refuse(kf, KoalaInvalidArgumentError, ('report_frames',),
+           lambda: kf._packets(N, counts, pcm.ctypes.data, out.ctypes.data, None, rep.ctypes.data, kmax - 1), (out, -7.5), (rep, -1.0))
+    accepted_packets()
+    bad = counts.copy()
+    bad[4] = N + 1
+    refuse(kf, KoalaInvalidArgumentError, ('counts[4]',), lambda: kf._packets(N, bad, pcm.ctypes.data, out.ctypes.data, None, None, 0), (out, -7.5))
+    accepted_packets()
+    refuse(kf, KoalaInvalidArgumentError, (MIXED_KINDS,),
+           lambda: kf._packets(N, counts, ctypes.c_void_p(pcm_d.data_ptr()), out.ctypes.data, None, None, 0), (out, -7.5))
+    accepted_packets()
     kf.delete(), ks.delete()
