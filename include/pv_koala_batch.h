@@ -32,15 +32,19 @@ PV_API pv_status_t pv_koala_batch_init(const char *access_key, const char *model
                                        pv_koala_precision_t precision, pv_koala_batch_t **object);
 PV_API void pv_koala_batch_delete(pv_koala_batch_t *object);
 
-/* A batch handle at a SAMPLE RATE of 8 000, 16 000, 32 000 or 48 000 Hz, fixed at creation (any other value: PV_STATUS_INVALID_ARGUMENT).
+/* A batch handle at a SAMPLE RATE of 8 000, 12 000, 16 000, 24 000, 32 000 or 48 000 Hz, fixed at creation (any other value:
+ * PV_STATUS_INVALID_ARGUMENT).
  * 16 000 is pv_koala_batch_init's handle: same routes, launches, samples and stream records.  At the other rates a call converts the
  * streams to 16 kHz on the device, runs the 16 kHz call unchanged and converts the enhanced samples back (third
- * extension: a 48 R + 1 tap windowed-sinc low-pass, R = 2 or 3, evaluated in a fixed order; the converters' per-stream state lives in
+ * extension: a 48 R + 1 tap windowed-sinc low-pass, R = 2 or 3, evaluated in a fixed order; 12 000 and 24 000 go through 48 kHz in two
+ * rational stages, 4/3 and 3/4 or 2/3 and 3/2, of the same low-pass with R = 4 or 3; the converters' per-stream state lives in
  * the handle, takes part in every kind of reset and in held streams, and travels in the stream record, which is version 2 then).
- *   - a frame is pv_koala_batch_frame_length() = sample_rate * 256 / 16000 samples (128 / 256 / 512 / 768: 16 ms at every rate), and every
+ *   - a frame is pv_koala_batch_frame_length() = sample_rate * 256 / 16000 samples (128 / 192 / 256 / 384 / 512 / 768 at 8 / 12 / 16 / 24 / 32 / 48 kHz:
+ *     16 ms at every rate), and every
  *     entry point that advances streams takes [num_streams][num_frames * frame_length] (process, process_chunk, _resets, _hold,
  *     process_call with its frame report, whose rows are those of the inner 16 kHz stream, one per frame);
- *   - pv_koala_batch_delay_sample() is 176 / 256 / 608 / 912 samples at the handle's rate: the engine's frame and both converters;
+ *   - pv_koala_batch_delay_sample() is 176 / 240 / 256 / 456 / 608 / 912 samples at the handle's rate: the engine's frame and both
+ *     converters (a packet handle: frame_length - 1 more, 431 at 12 kHz and 839 at 24 kHz);
  *   - host pointers: one copy in, the device route, one copy out, then synchronise; `pcm` and `enhanced` may overlap in any way, with
  *     host and with device pointers (the input is consumed before the output is written);
  *   - the asynchronous entry points, and `asynchronous != 0` in pv_koala_batch_process_call, are refused with PV_STATUS_INVALID_ARGUMENT on
@@ -225,7 +229,7 @@ PV_API pv_status_t pv_koala_batch_process_call(pv_koala_batch_t *object, const p
 PV_API pv_status_t pv_koala_process_report(pv_koala_t *object, const int16_t *pcm, int16_t *enhanced_pcm, float report[4]);
 
 /* PACKET HANDLES: streams that deliver ANY NUMBER OF SAMPLES per call.  Live audio arrives in 10 and 20 ms packets (80 / 160 / 320 / 480 /
- * 960 samples), with jitter and not in phase across callers; a packet handle is a batch handle at any of the four rates whose streams are
+ * 960 samples), with jitter and not in phase across callers; a packet handle is a batch handle at any of the six rates whose streams are
  * sample-in / sample-out filters (fourth extension).  With F the frame length, D the frame handle's delay_sample at
  * that rate, x everything stream b was given since its last reset and e what a frame handle produces for x cut into frames, the stream's
  * output is  o = [F - 1 zeros] ++ e,  and every call delivers the next counts[b] samples of it: pv_koala_batch_delay_sample() is D + F - 1
@@ -311,7 +315,7 @@ typedef struct {
     int32_t max_frames_per_call;   /* frame handles; ignored when max_samples_per_call > 0 */
     int32_t max_samples_per_call;  /* > 0: a packet handle */
     int32_t precision;             /* pv_koala_precision_t */
-    int32_t sample_rate;           /* 8000 / 16000 / 32000 / 48000 */
+    int32_t sample_rate;           /* 8000 / 12000 / 16000 / 24000 / 32000 / 48000 */
     int32_t sample_format;         /* pv_koala_sample_format_t */
 } pv_koala_batch_config_t;
 PV_API pv_status_t pv_koala_batch_init_config(const char *access_key, const char *model_path, const char *device,

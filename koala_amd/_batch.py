@@ -42,7 +42,7 @@ class KoalaBatch(object):
 
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
                  max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0, sample_format: str = 's16') -> None:
-        """`sample_rate`: 8000, 16000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
+        """`sample_rate`: 8000, 12000, 16000, 24000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
         array of samples is [num_streams, T * frame_length] with frame_length = sample_rate * 256 / 16000; at a rate other than 16000 the
         handle converts on the device, `delay_sample` includes both converters, and the asynchronous calls are refused.
         `packet_samples` > 0 makes a PACKET HANDLE (pv_koala_batch_init_packets): its streams take and deliver any number of samples per call,
@@ -58,8 +58,8 @@ class KoalaBatch(object):
             raise KoalaIOError("Could not find model file at `%s`." % model_path)
         if precision not in ('fp32', 'bf16'):
             raise KoalaInvalidArgumentError("`precision` should be `fp32` or `bf16`.")
-        if sample_rate not in (8000, 16000, 32000, 48000):
-            raise KoalaInvalidArgumentError("`sample_rate` should be 8000, 16000, 32000 or 48000.")
+        if sample_rate not in (8000, 12000, 16000, 24000, 32000, 48000):
+            raise KoalaInvalidArgumentError("`sample_rate` should be 8000, 12000, 16000, 24000, 32000 or 48000.")
         if not isinstance(packet_samples, int) or packet_samples < 0:
             raise KoalaInvalidArgumentError("`packet_samples` should be a positive number of samples (0: a frame handle).")
         if not isinstance(sample_format, str) or sample_format not in FORMATS:

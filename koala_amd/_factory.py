@@ -38,7 +38,7 @@ def create_batch(
         sample_rate: int = 16000,
         packet_samples: int = 0,
         sample_format: str = 's16') -> KoalaBatch:
-    """`num_streams` independent streams advancing together on one GPU (see KoalaBatch), at 8000, 16000, 32000 or 48000 Hz.
+    """`num_streams` independent streams advancing together on one GPU (see KoalaBatch), at 8000, 12000, 16000, 24000, 32000 or 48000 Hz.
     `packet_samples=N` makes a packet handle: streams that take and deliver any number of samples, up to N, per call
     (`KoalaBatch.process_packets`; `max_frames_per_call` is then derived from N).
     `sample_format`: 's16' (default), 'f32', 'ulaw' or 'alaw' -- the handle takes and delivers np.float32 or G.711 np.uint8 arrays,

@@ -296,27 +296,40 @@ std::string hip_error(hipError_t e) { return std::string("HIP error: ") + hipGet
 std::string hip_last_error() { return hip_error(hipGetLastError()); }
 }  // namespace
 
-// The prototype low-pass of the sample-rate stages (third extension), in double, rounded once into the two tables.
-static void rs_prototype(int R, std::vector<float> *hd, std::vector<float> *hi) {
-    const int L = 2 * kRsHalf * R + 1, c = kRsHalf * R;
+// The prototype low-pass of the sample-rate stages (third extension), in double: g[0 ... 48 K].
+static std::vector<double> rs_prototype_g(int K) {
+    const int L = 2 * kRsHalf * K + 1, c = kRsHalf * K;
     const double pi = 3.141592653589793;
     std::vector<double> g0((size_t) L);
     double sum = 0.0;
     for (int i = 0; i < L; ++i) {
-        const double x = 0.94 * (i - c) / R, px = pi * x;
+        const double x = 0.94 * (i - c) / K, px = pi * x;
         const double sinc = i == c ? 1.0 : sin(px) / px;
         const double w = 0.35875 - 0.48829 * cos(2.0 * pi * i / (L - 1)) + 0.14128 * cos(4.0 * pi * i / (L - 1)) -
                          0.01168 * cos(6.0 * pi * i / (L - 1));
         g0[i] = sinc * w;
         sum += g0[i];
     }
+    for (int i = 0; i < L; ++i) g0[i] = g0[i] / sum;
+    return g0;
+}
+
+// ... rounded once into the two tables of a whole-number rate
+static void rs_prototype(int R, std::vector<float> *hd, std::vector<float> *hi) {
+    const std::vector<double> g = rs_prototype_g(R);
     hd->assign((size_t) kRsMaxTaps, 0.0f);
     hi->assign((size_t) kRsMaxTaps, 0.0f);
-    for (int i = 0; i < L; ++i) {
-        const double g = g0[i] / sum;
-        (*hd)[i] = (float) g;
-        (*hi)[i] = (float) (R * g);
+    for (size_t i = 0; i < g.size(); ++i) {
+        (*hd)[i] = (float) g[i];
+        (*hi)[i] = (float) (R * g[i]);
     }
+}
+
+// ... and into the table h_U[i] = (float) (U g[i]) of a rational stage "up U"
+static void rs_prototype_rational(int K, int U, std::vector<float> *h) {
+    const std::vector<double> g = rs_prototype_g(K);
+    h->assign((size_t) kRsMaxTapsRational, 0.0f);
+    for (size_t i = 0; i < g.size(); ++i) (*h)[i] = (float) (U * g[i]);
 }
 
 void *Engine::dalloc(size_t bytes, bool zero) {
@@ -521,7 +534,7 @@ bool Engine::init(const Params &p, int device, int B, int Tmax, int precision, s
     nbh_ = ceil_div(kHidden, pi_.kb);
     taps_ = p.front_taps;
     if (!rs_rate_ok(p.sample_rate)) {
-        *err = "sample rate " + std::to_string(p.sample_rate) + " is not one of 8000, 16000, 32000, 48000.";
+        *err = "sample rate " + std::to_string(p.sample_rate) + " is not one of 8000, 12000, 16000, 24000, 32000, 48000.";
         return false;
     }
     rate_ = p.sample_rate;
@@ -637,7 +650,12 @@ bool Engine::init(const Params &p, int device, int B, int Tmax, int precision, s
     d_hprev_ = dalloc((size_t) kGruLayers * mtb * nbh_ * 1024, true);  // the state in operand form (wavefront calls, frame 0)
     d_rmask_ = (uint8_t *) dalloc((size_t) Bpad_, true);
     if (rate_ != kRate16k) {  // the sample-rate stages: their tables and per-stream state (zeros: a fresh stream)
-        rs_prototype(rs_ratio(rate_), &rs_hd_, &rs_hi_);
+        if (rs_rational(rate_)) {
+            rs_prototype_rational(rs_common_k(rate_), rs_stage_in(rate_).U, &rs_tin_);
+            rs_prototype_rational(rs_common_k(rate_), rs_stage_out(rate_).U, &rs_tout_);
+        } else {
+            rs_prototype(rs_ratio(rate_), &rs_hd_, &rs_hi_);
+        }
         for (int c = 0; c < 2; ++c) {
             d_rs_state_[0][c] = (int16_t *) dalloc((size_t) Bpad_ * rs_in_hist(rate_) * 2, true);
             d_rs_state_[1][c] = (int16_t *) dalloc((size_t) Bpad_ * rs_out_hist(rate_) * 2, true);
@@ -2120,12 +2138,13 @@ bool Engine::rate_ready(std::string *err) {  // the device copy of a call's rese
     return true;
 }
 
-// A call of a handle at 8, 32 or 48 kHz (third extension): the in-stage kernel takes the caller's samples to 16 kHz
+// A call of a handle that is not at 16 kHz (third extension): the in-stage kernel takes the caller's samples to 16 kHz
 // (into d_in_), the call runs unchanged as a device-pointer call from d_in_ to d_out_ -- its resets, attenuation limit and frame report
 // with it -- and the out-stage kernel takes the enhanced samples to the caller's rate.  Everything is enqueued on the handle's stream.
 // Device pointers only, and no refusal of its own: host memory and every argument check are the entry's (process, run_packets).  The
 // in-stage has read all of `pcm` before the out-stage writes `out`, so the two may overlap in any way.  The call's per-frame resets go to
-// the device as they are (uint8 [B][T]): both stages read everything in front of a reset block as zero.
+// the device as they are (uint8 [B][T]): both stages read everything in front of a reset block as zero.  12 and 24 kHz differ in the two
+// stage launches only (launch_resample_rational: "up U, down D").
 bool Engine::run_call_rate(const Call &c, std::string *err) {
     const int T = c.T, FL = rs_frame_length(rate_), R = rs_ratio(rate_);
     (void) hipSetDevice(device_);
@@ -2143,6 +2162,29 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
         flags = d_rs_flags_;
     }
     {
+        Call inner{T, d_in_, d_out_, c.resets};
+        inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
+        inner.report = c.report;
+        if (rs_rational(rate_)) {
+            RationalArgs a;
+            const RsStage si = rs_stage_in(rate_), so = rs_stage_out(rate_);
+            a.B = B_, a.T = T, a.resets = flags;
+            a.U = si.U, a.D = si.D, a.q_frame = kFrame / si.U;
+            a.in = c.pcm, a.out = d_in_;
+            a.state = d_rs_state_[0][rs_cur_], a.state_next = d_rs_state_[0][rs_cur_ ^ 1];
+            memcpy(a.taps, rs_tin_.data(), sizeof(a.taps));
+            launch_resample_rational(a, stream_);
+            if (hipGetLastError() != hipSuccess) goto fail;
+            if (!run_call(inner, err)) return false;
+            a.U = so.U, a.D = so.D, a.q_frame = kFrame / so.D;
+            a.in = d_out_, a.out = c.out;
+            a.state = d_rs_state_[1][rs_cur_], a.state_next = d_rs_state_[1][rs_cur_ ^ 1];
+            memcpy(a.taps, rs_tout_.data(), sizeof(a.taps));
+            launch_resample_rational(a, stream_);
+            if (hipGetLastError() != hipSuccess) goto fail;
+            rs_cur_ ^= 1;
+            return true;
+        }
         ResampleArgs a;
         a.B = B_, a.T = T, a.R = R, a.resets = flags;
         a.n_low = rate_ < kRate16k ? FL : kFrame;
@@ -2152,9 +2194,6 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
         memcpy(a.taps, (a.interpolate ? rs_hi_ : rs_hd_).data(), sizeof(a.taps));
         launch_resample(a, stream_);
         if (hipGetLastError() != hipSuccess) goto fail;
-        Call inner{T, d_in_, d_out_, c.resets};
-        inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
-        inner.report = c.report;
         if (!run_call(inner, err)) return false;
         a.in = d_out_, a.out = c.out;
         a.state = d_rs_state_[1][rs_cur_], a.state_next = d_rs_state_[1][rs_cur_ ^ 1];

@@ -268,7 +268,7 @@ constexpr uint32_t kStateMagic = 0x53534e4bu;  // "KNSS"
 constexpr uint32_t kStateVersion = 1;
 // Version 2, of handles that are not at 16 kHz: the first four reserved header bytes hold uint32 sample_rate, and behind the version-1 parts
 // follow rs_in and rs_out, int16, oldest first (the sample-rate stages' histories, below), zero-padded to whole 16-byte words: 288 bytes at
-// 8 and 32 kHz, 384 at 48 kHz.  A 16 kHz handle writes and accepts version 1 only, a handle at another rate version 2 of its own rate.
+// 8 and 32 kHz, 384 at 48 kHz, 224 at 12 kHz, 240 at 24 kHz.  A 16 kHz handle writes and accepts version 1 only, a handle at another rate version 2 of its own rate.
 constexpr uint32_t kStateVersionRate = 2;
 constexpr int kStateHeaderBytes = 32, kStateHistOff = 32, kStateTailOff = kStateHistOff + kFrame * 2,
               kStateHOff = kStateTailOff + kFrame * 4, kStateFctxOff = kStateHOff + kGruLayers * kHidden * 4;
@@ -292,17 +292,44 @@ void launch_state_import(const StateArgs &a, hipStream_t s);
 // ---- sample-rate stages of handles that are not at 16 kHz (kns_resample.hip; DESIGN.md section 2, third extension).  R = 2 (8 and
 // 32 kHz) or 3 (48 kHz); the prototype has L = 48 R + 1 taps.  An interpolator keeps its last 48 input samples per stream, a decimator
 // its last L - 1 = 48 R, int16, oldest first.
+// 12 and 24 kHz run two rational stages "up U, down D" through the common rate 48 kHz: K = 48000 / min(rate, 16000) = 4 / 3, the same
+// prototype with L = 48 K + 1 taps, the in-stage (4, 3) / (2, 3), the out-stage (3, 4) / (3, 2).  A stage keeps its last (L - 1) / U input
+// samples: 48 in, 64 out at 12 kHz; 72 in, 48 out at 24 kHz.  frame_length 192 / 384, delay_sample 192 + 24 + 24 = 240 / 384 + 36 + 36 =
+// 456, version-2 record tail 224 / 240 bytes, state_size 10 464 / 10 480 for a one-frame front-end.
 constexpr int kRate16k = 16000, kRsHalf = 24, kRsInterpHist = 2 * kRsHalf, kRsMaxTaps = 2 * kRsHalf * 3 + 1;
-KNS_HD bool rs_rate_ok(int rate) { return rate == 8000 || rate == 16000 || rate == 32000 || rate == 48000; }
-KNS_HD int rs_ratio(int rate) { return rate == 48000 ? 3 : rate == kRate16k ? 1 : 2; }
-KNS_HD int rs_frame_length(int rate) { return rate / 1000 * kFrame / 16; }  // 128 / 256 / 512 / 768
-KNS_HD int rs_in_hist(int rate) { return rate == kRate16k ? 0 : rate < kRate16k ? kRsInterpHist : 2 * kRsHalf * rs_ratio(rate); }
-KNS_HD int rs_out_hist(int rate) { return rate == kRate16k ? 0 : rate < kRate16k ? 2 * kRsHalf * rs_ratio(rate) : kRsInterpHist; }
-// what both stages add to a stream's delay, in samples at the handle's rate (each stage: 24 R high-rate samples)
-KNS_HD int rs_delay(int rate) { return rate == kRate16k ? 0 : rate < kRate16k ? 2 * kRsHalf : 2 * kRsHalf * rs_ratio(rate); }
+constexpr int kRsCommonRate = 48000, kRsMaxTapsRational = 2 * kRsHalf * 4 + 1;
+struct RsStage {
+    int U, D;  // up U, down D; (R, 1) is the interpolator, (1, R) the decimator
+};
+KNS_HD constexpr bool rs_rational(int rate) { return rate == 12000 || rate == 24000; }
+KNS_HD constexpr bool rs_rate_ok(int rate) { return rate == 8000 || rate == 16000 || rate == 32000 || rate == 48000 || rs_rational(rate); }
+KNS_HD constexpr int rs_ratio(int rate) { return rate == 48000 ? 3 : rate == kRate16k ? 1 : 2; }  // (the whole-number rates' R)
+KNS_HD constexpr int rs_common_k(int rate) { return kRsCommonRate / (rate < kRate16k ? rate : kRate16k); }  // K of a rational rate: 4 / 3
+KNS_HD constexpr RsStage rs_stage_in(int rate) {
+    if (rs_rational(rate)) return RsStage{kRsCommonRate / rate, kRsCommonRate / kRate16k};  // (4, 3) / (2, 3)
+    return rate < kRate16k ? RsStage{rs_ratio(rate), 1} : RsStage{1, rs_ratio(rate)};
+}
+KNS_HD constexpr RsStage rs_stage_out(int rate) { return RsStage{rs_stage_in(rate).D, rs_stage_in(rate).U}; }
+KNS_HD constexpr int rs_frame_length(int rate) { return rate / 1000 * kFrame / 16; }  // 128 / 192 / 256 / 384 / 512 / 768
+KNS_HD constexpr int rs_in_hist(int rate) {
+    if (rs_rational(rate)) return 2 * kRsHalf * rs_common_k(rate) / rs_stage_in(rate).U;
+    return rate == kRate16k ? 0 : rate < kRate16k ? kRsInterpHist : 2 * kRsHalf * rs_ratio(rate);
+}
+KNS_HD constexpr int rs_out_hist(int rate) {
+    if (rs_rational(rate)) return 2 * kRsHalf * rs_common_k(rate) / rs_stage_out(rate).U;
+    return rate == kRate16k ? 0 : rate < kRate16k ? 2 * kRsHalf * rs_ratio(rate) : kRsInterpHist;
+}
+// what both stages add to a stream's delay, in samples at the handle's rate (each stage: 24 R high-rate samples; a rational stage: 24 K
+// samples at 48 kHz)
+KNS_HD constexpr int rs_delay(int rate) {
+    if (rs_rational(rate)) return 2 * kRsHalf * rs_common_k(rate) / (kRsCommonRate / rate);
+    return rate == kRate16k ? 0 : rate < kRate16k ? 2 * kRsHalf : 2 * kRsHalf * rs_ratio(rate);
+}
 // the part of a version-2 stream record behind the version-1 parts: rs_in, rs_out, zero-padded to whole 16-byte words
-KNS_HD size_t rs_record_bytes(int rate) { return ((size_t) (rs_in_hist(rate) + rs_out_hist(rate)) * 2 + 15) / 16 * 16; }
+KNS_HD constexpr size_t rs_record_bytes(int rate) { return ((size_t) (rs_in_hist(rate) + rs_out_hist(rate)) * 2 + 15) / 16 * 16; }
 KNS_HD size_t state_record_bytes(int front_taps, int rate) { return state_record_bytes(front_taps) + rs_record_bytes(rate); }
+static_assert(rs_in_hist(24000) == 72 && rs_out_hist(24000) == 48 && rs_in_hist(12000) == 48 && rs_out_hist(12000) == 64, "rational stage histories");
+static_assert(rs_delay(24000) == 72 && rs_delay(12000) == 48 && rs_record_bytes(24000) == 240 && rs_record_bytes(12000) == 224, "rational stage constants");
 struct ResampleArgs {
     const int16_t *in;      // [B][T * n_in] (caller layout), n_in = n_low (interpolate) or R n_low (decimate)
     int16_t *out;           // [B][T * n_out], n_out = the other of the two
@@ -313,6 +340,18 @@ struct ResampleArgs {
     float taps[kRsMaxTaps];  // hi (interpolate) or hd (decimate): wave-uniform, read from the kernel's argument segment
 };
 void launch_resample(const ResampleArgs &a, hipStream_t s);
+// a rational stage "up U, down D" (12 and 24 kHz): out[n] = sum over i = D n mod U, + U, ... < L of taps[i] a[(D n - i) / U].  A frame
+// is q_frame groups of D input and U output samples.
+struct RationalArgs {
+    const int16_t *in;      // [B][T * D q_frame] (caller layout)
+    int16_t *out;           // [B][T * U q_frame]
+    const int16_t *state;   // [Bpad][(L - 1) / U]: the stream's last input samples before the call, oldest first
+    int16_t *state_next;    // the same after the call: the other copy of the ping-pong pair
+    const uint8_t *resets;  // optional, device memory [B][T], as ResampleArgs::resets
+    int B, T, U, D, q_frame;
+    float taps[kRsMaxTapsRational];  // h_U[i] = (float) (U g[i]), L = 48 max(U, D) + 1 of them: wave-uniform, read from the argument segment
+};
+void launch_resample_rational(const RationalArgs &a, hipStream_t s);
 // state rows [Bpad][hist], both copies, of the streams with mask[b] != 0 (null: all) := 0
 void launch_resample_reset(int16_t *state0, int16_t *state1, int hist, const uint8_t *mask, int Bpad, hipStream_t s);
 // the rs part of stream records [count][rec_bytes] (device) <- / -> the two state arrays, for the streams with rec_of[b] >= 0

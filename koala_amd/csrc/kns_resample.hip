@@ -12,6 +12,11 @@
 //
 // Per-frame stream resets (kResets): a stage's history is shorter than a block, so a wave needs its own block's flag only -- where it
 // is set, every staged sample in front of the block's first enters its fmaf as +0.
+//
+// resample_rational_kernel<U, D>: "up U, down D" (12 and 24 kHz), out[U q + p] = sum_j h[r_p + U j] a[D q + e_p - j] with D p = U e_p + r_p.
+// One workgroup serves 256 groups q (D input, U output samples each) of ONE stream, a lane one group: its U chains share every LDS read,
+// so the phase D n mod U is a compile-time constant of each fmaf and the taps stay scalar operands.  The input is staged by phase mod D
+// (consecutive lanes, consecutive words); the outputs are assembled in LDS and leave as lane-consecutive stores.
 #include "kns_kernels.h"
 
 namespace kns {
@@ -101,6 +106,48 @@ __global__ __launch_bounds__(256) void resample_decim_kernel(ResampleArgs g) {
     if (valid) orow[gn] = to_pcm(acc);
 }
 
+template <int U, int D, bool kResets>
+__global__ __launch_bounds__(256) void resample_rational_kernel(RationalArgs g) {
+    constexpr int K = U > D ? U : D, L = 2 * kRsHalf * K + 1, H = (L - 1) / U;
+    constexpr int E = D * (U - 1) / U;             // the newest input a group's outputs read is a[D q + E]
+    constexpr int W = (H + kChunk * D + D - 1) / D;  // words per input phase
+    __shared__ float xs[D * W];                    // sample m (counted from the first history sample) at [m % D][m / D]
+    __shared__ int16_t ys[kChunk * U];
+    const int NQ = g.T * g.q_frame, n_in = NQ * D, n_out = NQ * U, chunks = (NQ + kChunk - 1) / kChunk;
+    const int b = blockIdx.x / chunks, q0 = (blockIdx.x - b * chunks) * kChunk, n = threadIdx.x, gq = q0 + n;
+    const int16_t *row = g.in + (size_t) b * n_in;
+    int16_t *orow = g.out + (size_t) b * n_out;
+    stage(row, g.state + (size_t) b * H, H, q0 * D, H + kChunk * D, n_in, [&](int i, float v) { xs[(i % D) * W + i / D] = v; });
+    if (q0 + kChunk >= NQ && n < H) g.state_next[(size_t) b * H + n] = row[n_in - H + n];  // (a call has at least 192 input samples)
+    __syncthreads();
+    int floor_ = kNoFloor;
+    if (kResets) {
+        const int t = min(gq, NQ - 1) / g.q_frame;
+        floor_ = g.resets[(size_t) b * g.T + t] ? t * g.q_frame * D : kNoFloor;
+    }
+    float acc[U];
+#pragma unroll
+    for (int p = 0; p < U; ++p) acc[p] = 0.0f;
+#pragma unroll
+    for (int d = 0; d <= E + H; ++d) {
+        // input D gq + E - d = staged sample D n + (H + E - d): phase (H + E - d) mod D, word n + (H + E - d) / D
+        float x = xs[((H + E - d) % D) * W + (H + E - d) / D + n];
+        if (kResets) x = gq * D + E - d >= floor_ ? x : 0.0f;
+#pragma unroll
+        for (int p = 0; p < U; ++p) {
+            const int j = d - (E - D * p / U), i = D * p % U + U * j;  // chain p: tap r_p + U j on a[D q + e_p - j]
+            if (j >= 0 && i < L) acc[p] = fmaf(g.taps[i], x, acc[p]);
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < U; ++p) ys[n * U + p] = to_pcm(acc[p]);
+    __syncthreads();
+#pragma unroll
+    for (int k = n; k < kChunk * U; k += 256) {
+        if (q0 * U + k < n_out) orow[(size_t) q0 * U + k] = ys[k];  // (wave-uniform: a frame's outputs are a multiple of 64)
+    }
+}
+
 __global__ __launch_bounds__(256) void resample_reset_kernel(int16_t *state0, int16_t *state1, int hist, const uint8_t *mask, int Bpad) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Bpad * hist) return;
@@ -139,6 +186,20 @@ void launch_resample(const ResampleArgs &a, hipStream_t s) {
         else KNS_RS(resample_decim_kernel, 3);
     }
 #undef KNS_RS
+}
+
+void launch_resample_rational(const RationalArgs &a, hipStream_t s) {
+    const dim3 grid((unsigned) a.B * (unsigned) ((a.T * a.q_frame + kChunk - 1) / kChunk)), block(256);
+#define KNS_RQ(UU, DD)                                                                                  \
+    do {                                                                                                \
+        if (a.resets) hipLaunchKernelGGL((resample_rational_kernel<UU, DD, true>), grid, block, 0, s, a); \
+        else hipLaunchKernelGGL((resample_rational_kernel<UU, DD, false>), grid, block, 0, s, a);         \
+    } while (0)
+    if (a.U == 2) KNS_RQ(2, 3);
+    else if (a.U == 4) KNS_RQ(4, 3);
+    else if (a.D == 2) KNS_RQ(3, 2);
+    else KNS_RQ(3, 4);
+#undef KNS_RQ
 }
 
 void launch_resample_reset(int16_t *state0, int16_t *state1, int hist, const uint8_t *mask, int Bpad, hipStream_t s) {

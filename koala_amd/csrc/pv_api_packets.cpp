@@ -14,7 +14,7 @@ PV_API pv_status_t pv_koala_batch_init_packets(const char *access_key, const cha
         return PV_STATUS_INVALID_ARGUMENT;
     }
     if (!kns::rs_rate_ok(sample_rate)) {
-        push_error(0x66, "`sample_rate` %d is not one of 8000, 16000, 32000, 48000.", sample_rate);
+        push_error(0x66, "`sample_rate` %d is not one of 8000, 12000, 16000, 24000, 32000, 48000.", sample_rate);
         return PV_STATUS_INVALID_ARGUMENT;
     }
     const int32_t F = kns::rs_frame_length(sample_rate);

@@ -171,7 +171,7 @@ def main(argv=None):
                     help='feed the stream in packets of this many ms through a packet handle instead of in 16 ms frames')
     ap.add_argument('--sample_format', default=None, choices=['s16', 'f32', 'ulaw', 'alaw'],
                     help='raw samples of this format on stdin and stdout at --sample_rate, through a packet handle that converts on the device')
-    ap.add_argument('--sample_rate', type=int, default=16000, choices=[8000, 16000, 32000, 48000], help='with --sample_format: the stream\'s rate')
+    ap.add_argument('--sample_rate', type=int, default=16000, choices=[8000, 12000, 16000, 24000, 32000, 48000], help='with --sample_format: the stream\'s rate')
     ap.add_argument('--show_devices', action='store_true')
     args = ap.parse_args(argv)
 
