@@ -314,22 +314,12 @@ static std::vector<double> rs_prototype_g(int K) {
     return g0;
 }
 
-// ... rounded once into the two tables of a whole-number rate
-static void rs_prototype(int R, std::vector<float> *hd, std::vector<float> *hi) {
-    const std::vector<double> g = rs_prototype_g(R);
-    hd->assign((size_t) kRsMaxTaps, 0.0f);
-    hi->assign((size_t) kRsMaxTaps, 0.0f);
-    for (size_t i = 0; i < g.size(); ++i) {
-        (*hd)[i] = (float) g[i];
-        (*hi)[i] = (float) (R * g[i]);
-    }
-}
-
-// ... and into the table h_U[i] = (float) (U g[i]) of a rational stage "up U"
-static void rs_prototype_rational(int K, int U, std::vector<float> *h) {
-    const std::vector<double> g = rs_prototype_g(K);
-    h->assign((size_t) kRsMaxTapsRational, 0.0f);
-    for (size_t i = 0; i < g.size(); ++i) (*h)[i] = (float) (U * g[i]);
+// ... rounded once into the table h_U[i] = (float) (U g[i]) of a stage "up U, down D", zero-padded
+static std::vector<float> rs_table(RsStage s) {
+    const std::vector<double> g = rs_prototype_g(std::max(s.U, s.D));
+    std::vector<float> h((size_t) kRsMaxTaps, 0.0f);
+    for (size_t i = 0; i < g.size(); ++i) h[i] = (float) (s.U * g[i]);
+    return h;
 }
 
 void *Engine::dalloc(size_t bytes, bool zero) {
@@ -650,12 +640,8 @@ bool Engine::init(const Params &p, int device, int B, int Tmax, int precision, s
     d_hprev_ = dalloc((size_t) kGruLayers * mtb * nbh_ * 1024, true);  // the state in operand form (wavefront calls, frame 0)
     d_rmask_ = (uint8_t *) dalloc((size_t) Bpad_, true);
     if (rate_ != kRate16k) {  // the sample-rate stages: their tables and per-stream state (zeros: a fresh stream)
-        if (rs_rational(rate_)) {
-            rs_prototype_rational(rs_common_k(rate_), rs_stage_in(rate_).U, &rs_tin_);
-            rs_prototype_rational(rs_common_k(rate_), rs_stage_out(rate_).U, &rs_tout_);
-        } else {
-            rs_prototype(rs_ratio(rate_), &rs_hd_, &rs_hi_);
-        }
+        rs_taps_[0] = rs_table(rs_stage_in(rate_));
+        rs_taps_[1] = rs_table(rs_stage_out(rate_));
         for (int c = 0; c < 2; ++c) {
             d_rs_state_[0][c] = (int16_t *) dalloc((size_t) Bpad_ * rs_in_hist(rate_) * 2, true);
             d_rs_state_[1][c] = (int16_t *) dalloc((size_t) Bpad_ * rs_out_hist(rate_) * 2, true);
@@ -2143,10 +2129,10 @@ bool Engine::rate_ready(std::string *err) {  // the device copy of a call's rese
 // with it -- and the out-stage kernel takes the enhanced samples to the caller's rate.  Everything is enqueued on the handle's stream.
 // Device pointers only, and no refusal of its own: host memory and every argument check are the entry's (process, run_packets).  The
 // in-stage has read all of `pcm` before the out-stage writes `out`, so the two may overlap in any way.  The call's per-frame resets go to
-// the device as they are (uint8 [B][T]): both stages read everything in front of a reset block as zero.  12 and 24 kHz differ in the two
-// stage launches only (launch_resample_rational: "up U, down D").
+// the device as they are (uint8 [B][T]): both stages read everything in front of a reset block as zero.  The rates differ in the stages'
+// (U, D) and tables only.
 bool Engine::run_call_rate(const Call &c, std::string *err) {
-    const int T = c.T, FL = rs_frame_length(rate_), R = rs_ratio(rate_);
+    const int T = c.T;
     (void) hipSetDevice(device_);
     bool any = false;
     for (size_t i = 0; c.resets && i < (size_t) B_ * T && !any; ++i) any = c.resets[i] != 0;
@@ -2165,42 +2151,19 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
         Call inner{T, d_in_, d_out_, c.resets};
         inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
         inner.report = c.report;
-        if (rs_rational(rate_)) {
-            RationalArgs a;
-            const RsStage si = rs_stage_in(rate_), so = rs_stage_out(rate_);
-            a.B = B_, a.T = T, a.resets = flags;
-            a.U = si.U, a.D = si.D, a.q_frame = kFrame / si.U;
-            a.in = c.pcm, a.out = d_in_;
-            a.state = d_rs_state_[0][rs_cur_], a.state_next = d_rs_state_[0][rs_cur_ ^ 1];
-            memcpy(a.taps, rs_tin_.data(), sizeof(a.taps));
-            launch_resample_rational(a, stream_);
-            if (hipGetLastError() != hipSuccess) goto fail;
-            if (!run_call(inner, err)) return false;
-            a.U = so.U, a.D = so.D, a.q_frame = kFrame / so.D;
-            a.in = d_out_, a.out = c.out;
-            a.state = d_rs_state_[1][rs_cur_], a.state_next = d_rs_state_[1][rs_cur_ ^ 1];
-            memcpy(a.taps, rs_tout_.data(), sizeof(a.taps));
-            launch_resample_rational(a, stream_);
-            if (hipGetLastError() != hipSuccess) goto fail;
-            rs_cur_ ^= 1;
-            return true;
-        }
+        const RsStage si = rs_stage_in(rate_), so = rs_stage_out(rate_);
         ResampleArgs a;
-        a.B = B_, a.T = T, a.R = R, a.resets = flags;
-        a.n_low = rate_ < kRate16k ? FL : kFrame;
-        a.in = c.pcm, a.out = d_in_;
-        a.state = d_rs_state_[0][rs_cur_], a.state_next = d_rs_state_[0][rs_cur_ ^ 1];
-        a.interpolate = rate_ < kRate16k;
-        memcpy(a.taps, (a.interpolate ? rs_hi_ : rs_hd_).data(), sizeof(a.taps));
-        launch_resample(a, stream_);
-        if (hipGetLastError() != hipSuccess) goto fail;
-        if (!run_call(inner, err)) return false;
-        a.in = d_out_, a.out = c.out;
-        a.state = d_rs_state_[1][rs_cur_], a.state_next = d_rs_state_[1][rs_cur_ ^ 1];
-        a.interpolate = !a.interpolate;
-        memcpy(a.taps, (a.interpolate ? rs_hi_ : rs_hd_).data(), sizeof(a.taps));
-        launch_resample(a, stream_);
-        if (hipGetLastError() != hipSuccess) goto fail;
+        a.B = B_, a.T = T, a.resets = flags;
+        a.q_frame = kFrame / si.U;  // (a group is U_in = D_out samples at 16 kHz)
+        for (int k = 0; k < 2; ++k) {  // the in-stage, the call between the two, the out-stage
+            a.U = k ? so.U : si.U, a.D = k ? so.D : si.D;
+            a.in = k ? d_out_ : c.pcm, a.out = k ? c.out : d_in_;
+            a.state = d_rs_state_[k][rs_cur_], a.state_next = d_rs_state_[k][rs_cur_ ^ 1];
+            memcpy(a.taps, rs_taps_[k].data(), sizeof(a.taps));
+            launch_resample(a, stream_);
+            if (hipGetLastError() != hipSuccess) goto fail;
+            if (k == 0 && !run_call(inner, err)) return false;
+        }
         rs_cur_ ^= 1;
     }
     return true;

@@ -186,8 +186,7 @@ private:
     int rate_ = kRate16k;
     int16_t *d_rs_state_[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [in-stage, out-stage][ping-pong copy], [Bpad][hist] each
     int rs_cur_ = 0;
-    std::vector<float> rs_hd_, rs_hi_;  // the prototype's two tables (decimator, interpolator)
-    std::vector<float> rs_tin_, rs_tout_;  // 12 and 24 kHz: the in-stage's and the out-stage's table h_U
+    std::vector<float> rs_taps_[2];     // the in-stage's and the out-stage's table h_U (kns_kernels.h)
     uint8_t *d_rs_flags_ = nullptr;     // a call's per-frame resets on the device, uint8 [B][T], and their upload ring
     uint8_t *d_state_rs_ = nullptr;     // the stages' part of the staged stream records [B][rs_record_bytes]
     // what run_device is given: the frames [t0, t0 + T) of a call, their device buffers, and the call's reset table if it has one

@@ -289,69 +289,50 @@ struct StateArgs {
 };
 void launch_state_export(const StateArgs &a, hipStream_t s);
 void launch_state_import(const StateArgs &a, hipStream_t s);
-// ---- sample-rate stages of handles that are not at 16 kHz (kns_resample.hip; DESIGN.md section 2, third extension).  R = 2 (8 and
-// 32 kHz) or 3 (48 kHz); the prototype has L = 48 R + 1 taps.  An interpolator keeps its last 48 input samples per stream, a decimator
-// its last L - 1 = 48 R, int16, oldest first.
-// 12 and 24 kHz run two rational stages "up U, down D" through the common rate 48 kHz: K = 48000 / min(rate, 16000) = 4 / 3, the same
-// prototype with L = 48 K + 1 taps, the in-stage (4, 3) / (2, 3), the out-stage (3, 4) / (3, 2).  A stage keeps its last (L - 1) / U input
-// samples: 48 in, 64 out at 12 kHz; 72 in, 48 out at 24 kHz.  frame_length 192 / 384, delay_sample 192 + 24 + 24 = 240 / 384 + 36 + 36 =
-// 456, version-2 record tail 224 / 240 bytes, state_size 10 464 / 10 480 for a one-frame front-end.
-constexpr int kRate16k = 16000, kRsHalf = 24, kRsInterpHist = 2 * kRsHalf, kRsMaxTaps = 2 * kRsHalf * 3 + 1;
-constexpr int kRsCommonRate = 48000, kRsMaxTapsRational = 2 * kRsHalf * 4 + 1;
+// ---- sample-rate stages of handles that are not at 16 kHz (kns_resample.hip; DESIGN.md section 2, third extension).  A handle runs two
+// stages "up U, down D": the in-stage from its rate to 16 kHz and the out-stage, the same pair swapped, back.  (R, 1) is the interpolator,
+// (1, R) the decimator (8, 32 and 48 kHz: R = 2, 2, 3); 12 and 24 kHz go through the common rate 48 kHz with (4, 3) and (2, 3).  A stage's
+// prototype has L = 48 K + 1 taps, K = max(U, D), and the stage keeps its last (L - 1) / U input samples per stream, int16, oldest first.
+// At 12 / 24 kHz: 48 in, 64 out / 72 in, 48 out; frame_length 192 / 384, delay_sample 192 + 24 + 24 = 240 / 384 + 36 + 36 = 456,
+// version-2 record tail 224 / 240 bytes, state_size 10 464 / 10 480 for a one-frame front-end.
+constexpr int kRate16k = 16000, kRsHalf = 24, kRsMaxTaps = 2 * kRsHalf * 4 + 1;
 struct RsStage {
-    int U, D;  // up U, down D; (R, 1) is the interpolator, (1, R) the decimator
+    int U, D;  // up U, down D
 };
-KNS_HD constexpr bool rs_rational(int rate) { return rate == 12000 || rate == 24000; }
-KNS_HD constexpr bool rs_rate_ok(int rate) { return rate == 8000 || rate == 16000 || rate == 32000 || rate == 48000 || rs_rational(rate); }
-KNS_HD constexpr int rs_ratio(int rate) { return rate == 48000 ? 3 : rate == kRate16k ? 1 : 2; }  // (the whole-number rates' R)
-KNS_HD constexpr int rs_common_k(int rate) { return kRsCommonRate / (rate < kRate16k ? rate : kRate16k); }  // K of a rational rate: 4 / 3
 KNS_HD constexpr RsStage rs_stage_in(int rate) {
-    if (rs_rational(rate)) return RsStage{kRsCommonRate / rate, kRsCommonRate / kRate16k};  // (4, 3) / (2, 3)
-    return rate < kRate16k ? RsStage{rs_ratio(rate), 1} : RsStage{1, rs_ratio(rate)};
+    return rate == 8000 ? RsStage{2, 1} : rate == 32000 ? RsStage{1, 2} : rate == 48000 ? RsStage{1, 3} : rate == 12000 ? RsStage{4, 3} :
+           rate == 24000 ? RsStage{2, 3} : rate == kRate16k ? RsStage{1, 1} : RsStage{0, 0};
 }
 KNS_HD constexpr RsStage rs_stage_out(int rate) { return RsStage{rs_stage_in(rate).D, rs_stage_in(rate).U}; }
+KNS_HD constexpr bool rs_rate_ok(int rate) { return rs_stage_in(rate).U != 0; }
 KNS_HD constexpr int rs_frame_length(int rate) { return rate / 1000 * kFrame / 16; }  // 128 / 192 / 256 / 384 / 512 / 768
-KNS_HD constexpr int rs_in_hist(int rate) {
-    if (rs_rational(rate)) return 2 * kRsHalf * rs_common_k(rate) / rs_stage_in(rate).U;
-    return rate == kRate16k ? 0 : rate < kRate16k ? kRsInterpHist : 2 * kRsHalf * rs_ratio(rate);
-}
-KNS_HD constexpr int rs_out_hist(int rate) {
-    if (rs_rational(rate)) return 2 * kRsHalf * rs_common_k(rate) / rs_stage_out(rate).U;
-    return rate == kRate16k ? 0 : rate < kRate16k ? 2 * kRsHalf * rs_ratio(rate) : kRsInterpHist;
-}
-// what both stages add to a stream's delay, in samples at the handle's rate (each stage: 24 R high-rate samples; a rational stage: 24 K
-// samples at 48 kHz)
-KNS_HD constexpr int rs_delay(int rate) {
-    if (rs_rational(rate)) return 2 * kRsHalf * rs_common_k(rate) / (kRsCommonRate / rate);
-    return rate == kRate16k ? 0 : rate < kRate16k ? 2 * kRsHalf : 2 * kRsHalf * rs_ratio(rate);
-}
+KNS_HD constexpr int rs_stage_hist(RsStage s) { return 2 * kRsHalf * (s.U > s.D ? s.U : s.D) / s.U; }  // (L - 1) / U
+KNS_HD constexpr int rs_in_hist(int rate) { return rate == kRate16k ? 0 : rs_stage_hist(rs_stage_in(rate)); }
+KNS_HD constexpr int rs_out_hist(int rate) { return rate == kRate16k ? 0 : rs_stage_hist(rs_stage_out(rate)); }
+// what both stages add to a stream's delay, in samples at the handle's rate: each stage 24 K samples at the stages' common high rate,
+// U_in times the handle's -- together 48 K / U_in, which is the in-stage's history
+KNS_HD constexpr int rs_delay(int rate) { return rs_in_hist(rate); }
 // the part of a version-2 stream record behind the version-1 parts: rs_in, rs_out, zero-padded to whole 16-byte words
 KNS_HD constexpr size_t rs_record_bytes(int rate) { return ((size_t) (rs_in_hist(rate) + rs_out_hist(rate)) * 2 + 15) / 16 * 16; }
 KNS_HD size_t state_record_bytes(int front_taps, int rate) { return state_record_bytes(front_taps) + rs_record_bytes(rate); }
-static_assert(rs_in_hist(24000) == 72 && rs_out_hist(24000) == 48 && rs_in_hist(12000) == 48 && rs_out_hist(12000) == 64, "rational stage histories");
-static_assert(rs_delay(24000) == 72 && rs_delay(12000) == 48 && rs_record_bytes(24000) == 240 && rs_record_bytes(12000) == 224, "rational stage constants");
+static_assert(rs_in_hist(8000) == 48 && rs_out_hist(8000) == 96 && rs_in_hist(32000) == 96 && rs_out_hist(32000) == 48 &&
+              rs_in_hist(48000) == 144 && rs_out_hist(48000) == 48 && rs_in_hist(12000) == 48 && rs_out_hist(12000) == 64 &&
+              rs_in_hist(24000) == 72 && rs_out_hist(24000) == 48 && rs_in_hist(kRate16k) == 0 && rs_out_hist(kRate16k) == 0, "stage histories");
+static_assert(rs_delay(8000) == 48 && rs_delay(32000) == 96 && rs_delay(48000) == 144 && rs_delay(12000) == 48 && rs_delay(24000) == 72 &&
+              rs_delay(kRate16k) == 0 && rs_record_bytes(8000) == 288 && rs_record_bytes(32000) == 288 && rs_record_bytes(48000) == 384 &&
+              rs_record_bytes(12000) == 224 && rs_record_bytes(24000) == 240, "stage constants");
+// a stage "up U, down D": out[n] = sum over i = D n mod U, + U, ... < L of taps[i] a[(D n - i) / U].  A frame is q_frame groups of D input
+// and U output samples.
 struct ResampleArgs {
-    const int16_t *in;      // [B][T * n_in] (caller layout), n_in = n_low (interpolate) or R n_low (decimate)
-    int16_t *out;           // [B][T * n_out], n_out = the other of the two
-    const int16_t *state;   // [Bpad][hist]: the stream's last `hist` input samples before the call, oldest first
-    int16_t *state_next;    // the same after the call: the other copy of the ping-pong pair
-    const uint8_t *resets;  // optional, device memory [B][T]: non-zero at [b][t] = everything in front of block t of stream b reads as zero
-    int B, T, R, n_low, interpolate;
-    float taps[kRsMaxTaps];  // hi (interpolate) or hd (decimate): wave-uniform, read from the kernel's argument segment
-};
-void launch_resample(const ResampleArgs &a, hipStream_t s);
-// a rational stage "up U, down D" (12 and 24 kHz): out[n] = sum over i = D n mod U, + U, ... < L of taps[i] a[(D n - i) / U].  A frame
-// is q_frame groups of D input and U output samples.
-struct RationalArgs {
     const int16_t *in;      // [B][T * D q_frame] (caller layout)
     int16_t *out;           // [B][T * U q_frame]
     const int16_t *state;   // [Bpad][(L - 1) / U]: the stream's last input samples before the call, oldest first
     int16_t *state_next;    // the same after the call: the other copy of the ping-pong pair
-    const uint8_t *resets;  // optional, device memory [B][T], as ResampleArgs::resets
+    const uint8_t *resets;  // optional, device memory [B][T]: non-zero at [b][t] = everything in front of block t of stream b reads as zero
     int B, T, U, D, q_frame;
-    float taps[kRsMaxTapsRational];  // h_U[i] = (float) (U g[i]), L = 48 max(U, D) + 1 of them: wave-uniform, read from the argument segment
+    float taps[kRsMaxTaps];  // h_U[i] = (float) (U g[i]), L = 48 max(U, D) + 1 of them, zero-padded: wave-uniform, read from the argument segment
 };
-void launch_resample_rational(const RationalArgs &a, hipStream_t s);
+void launch_resample(const ResampleArgs &a, hipStream_t s);
 // state rows [Bpad][hist], both copies, of the streams with mask[b] != 0 (null: all) := 0
 void launch_resample_reset(int16_t *state0, int16_t *state1, int hist, const uint8_t *mask, int Bpad, hipStream_t s);
 // the rs part of stream records [count][rec_bytes] (device) <- / -> the two state arrays, for the streams with rec_of[b] >= 0

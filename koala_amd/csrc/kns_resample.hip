@@ -1,29 +1,28 @@
 // kns_resample.hip -- the sample-rate stages of batch handles that are not at 16 kHz (third extension; section 6).
-// resample_interp_kernel<R>: v[R n + p] = sum_j hi[p + R j] a[n - j];  resample_decim_kernel<R>: v[n] = sum_i hd[i] a[R n - i] -- one fmaf
-// per tap from acc = 0, taps ascending, then the synthesis kernel's rounding to int16.  Plain HIP C++, vector loads and stores only.
+// resample_kernel<U, D>: the stage "up U, down D", out[U q + p] = sum_j h[r_p + U j] a[D q + e_p - j] with D p = U e_p + r_p -- one
+// fmaf per tap from acc = 0, taps ascending, then the synthesis kernel's rounding to int16.  (R, 1) is the interpolator of 8 kHz handles
+// and of the out-stages at 32 and 48 kHz, (1, R) the decimator on their other side, (4, 3) (3, 4) and (2, 3) (3, 2) the two stages at 12 and
+// 24 kHz.  Plain HIP C++, vector loads and stores only.
 //
-// One workgroup serves 256 low-rate samples (one or two 16 ms blocks) of ONE stream.  They and the `hist` samples in front of them are
-// staged in LDS as floats (a decimator's de-interleaved by input phase, so that the lanes of a wave read consecutive words for every
-// tap); the samples in front of the call come from the stream's state.  The state is a ping-pong pair like the engine's history: the
-// row's first workgroup reads the current copy, its last one writes the other (the call's last `hist` input samples), once per call.
-// The taps are wave-uniform: they arrive in the kernel's argument segment, the tap loop is fully unrolled straight-line code, so each
-// tap is a scalar load used once.  The tap loop holds no vector-memory operation; the staging loads are unconditional (a clamped or
-// selected address), the stores are guarded once per wave (a block is a multiple of 64 samples).
+// One workgroup serves 256 groups q (D input, U output samples each: one to four 16 ms blocks) of ONE stream, a lane one group:
+// its U chains share every LDS read, so the phase D n mod U is a compile-time constant of each fmaf.  The group's input and the `hist`
+// samples in front of it are staged in LDS as floats, de-interleaved by phase mod D, so that the lanes of a wave read consecutive words
+// for every tap; the samples in front of the call come from the stream's state.  The state is a ping-pong pair like the engine's
+// history: the row's first workgroup reads the current copy, its last one writes the other (the call's last `hist` input samples), once
+// per call.  The taps are wave-uniform: they arrive in the kernel's argument segment, the tap loop is fully unrolled straight-line code,
+// so each tap is a scalar load used once.  The tap loop holds no vector-memory operation; the staging loads are unconditional (a clamped
+// or selected address); the outputs are assembled in LDS and leave as lane-consecutive stores, guarded once per wave (a frame's outputs
+// are a multiple of 64 samples).
 //
 // Per-frame stream resets (kResets): a stage's history is shorter than a block, so a wave needs its own block's flag only -- where it
 // is set, every staged sample in front of the block's first enters its fmaf as +0.
-//
-// resample_rational_kernel<U, D>: "up U, down D" (12 and 24 kHz), out[U q + p] = sum_j h[r_p + U j] a[D q + e_p - j] with D p = U e_p + r_p.
-// One workgroup serves 256 groups q (D input, U output samples each) of ONE stream, a lane one group: its U chains share every LDS read,
-// so the phase D n mod U is a compile-time constant of each fmaf and the taps stay scalar operands.  The input is staged by phase mod D
-// (consecutive lanes, consecutive words); the outputs are assembled in LDS and leave as lane-consecutive stores.
 #include "kns_kernels.h"
 
 namespace kns {
 
 namespace {
 
-constexpr int kChunk = 256;  // low-rate samples per workgroup
+constexpr int kChunk = 256;  // groups per workgroup
 constexpr int kNoFloor = -0x40000000;
 
 __device__ __forceinline__ int16_t to_pcm(float a) {
@@ -44,70 +43,8 @@ __device__ __forceinline__ void stage(const int16_t *row, const int16_t *state, 
 
 }  // namespace
 
-template <int R, bool kResets>
-__global__ __launch_bounds__(256) void resample_interp_kernel(ResampleArgs g) {
-    constexpr int H = kRsInterpHist;
-    __shared__ float xs[H + kChunk];
-    const int N = g.T * g.n_low, chunks = (N + kChunk - 1) / kChunk;
-    const int b = blockIdx.x / chunks, c0 = (blockIdx.x - b * chunks) * kChunk, n = threadIdx.x, gn = c0 + n;
-    const int16_t *row = g.in + (size_t) b * N;
-    int16_t *orow = g.out + (size_t) b * N * R;
-    stage(row, g.state + (size_t) b * H, H, c0, H + kChunk, N, [&](int i, float v) { xs[i] = v; });
-    if (c0 + kChunk >= N && n < H) g.state_next[(size_t) b * H + n] = row[N - H + n];  // (a call has at least 128 samples: all this call's)
-    __syncthreads();
-    const bool valid = gn < N;  // (wave-uniform: N is a multiple of 64)
-    int floor_ = kNoFloor;
-    if (kResets) {
-        const int t = min(gn, N - 1) / g.n_low;
-        floor_ = g.resets[(size_t) b * g.T + t] ? t * g.n_low : kNoFloor;
-    }
-    float acc[R];
-#pragma unroll
-    for (int p = 0; p < R; ++p) acc[p] = 0.0f;
-#pragma unroll
-    for (int j = 0; j <= H; ++j) {
-        float x = xs[H + n - j];
-        if (kResets) x = gn - j >= floor_ ? x : 0.0f;
-#pragma unroll
-        for (int p = 0; p < (j < H ? R : 1); ++p) acc[p] = fmaf(g.taps[p + R * j], x, acc[p]);  // (j = 48: phase 0 only)
-    }
-    if (valid) {
-#pragma unroll
-        for (int p = 0; p < R; ++p) orow[(size_t) gn * R + p] = to_pcm(acc[p]);
-    }
-}
-
-template <int R, bool kResets>
-__global__ __launch_bounds__(256) void resample_decim_kernel(ResampleArgs g) {
-    constexpr int H = 2 * kRsHalf * R, L = H + 1, W = kRsInterpHist + kChunk;  // W: words per input phase
-    __shared__ float xs[R * W];  // sample m (counted from the first history sample) at [m % R][m / R]
-    const int N = g.T * g.n_low, n_in = g.n_low * R, chunks = (N + kChunk - 1) / kChunk;
-    const int b = blockIdx.x / chunks, c0 = (blockIdx.x - b * chunks) * kChunk, n = threadIdx.x, gn = c0 + n;
-    const int16_t *row = g.in + (size_t) b * N * R;
-    int16_t *orow = g.out + (size_t) b * N;
-    stage(row, g.state + (size_t) b * H, H, c0 * R, R * W, N * R, [&](int i, float v) { xs[(i % R) * W + i / R] = v; });
-    if (c0 + kChunk >= N && n < H) g.state_next[(size_t) b * H + n] = row[N * R - H + n];  // (a call has at least 256 input samples)
-    __syncthreads();
-    const bool valid = gn < N;
-    int floor_ = kNoFloor;
-    if (kResets) {
-        const int t = min(gn, N - 1) / g.n_low;
-        floor_ = g.resets[(size_t) b * g.T + t] ? t * n_in : kNoFloor;
-    }
-    float acc = 0.0f;
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-        // input R gn - i = staged sample R (48 + n) - i: phase (-i) mod R, word 48 + n - ceil(i / R)
-        const int ph = (R - i % R) % R, q = kRsInterpHist + n - (i + R - 1) / R;
-        float x = xs[ph * W + q];
-        if (kResets) x = gn * R - i >= floor_ ? x : 0.0f;
-        acc = fmaf(g.taps[i], x, acc);
-    }
-    if (valid) orow[gn] = to_pcm(acc);
-}
-
 template <int U, int D, bool kResets>
-__global__ __launch_bounds__(256) void resample_rational_kernel(RationalArgs g) {
+__global__ __launch_bounds__(256) void resample_kernel(ResampleArgs g) {
     constexpr int K = U > D ? U : D, L = 2 * kRsHalf * K + 1, H = (L - 1) / U;
     constexpr int E = D * (U - 1) / U;             // the newest input a group's outputs read is a[D q + E]
     constexpr int W = (H + kChunk * D + D - 1) / D;  // words per input phase
@@ -118,7 +55,7 @@ __global__ __launch_bounds__(256) void resample_rational_kernel(RationalArgs g) 
     const int16_t *row = g.in + (size_t) b * n_in;
     int16_t *orow = g.out + (size_t) b * n_out;
     stage(row, g.state + (size_t) b * H, H, q0 * D, H + kChunk * D, n_in, [&](int i, float v) { xs[(i % D) * W + i / D] = v; });
-    if (q0 + kChunk >= NQ && n < H) g.state_next[(size_t) b * H + n] = row[n_in - H + n];  // (a call has at least 192 input samples)
+    if (q0 + kChunk >= NQ && n < H) g.state_next[(size_t) b * H + n] = row[n_in - H + n];  // (a call has more than H input samples)
     __syncthreads();
     int floor_ = kNoFloor;
     if (kResets) {
@@ -172,34 +109,23 @@ __global__ __launch_bounds__(256) void resample_state_kernel(ResampleStateArgs g
 }
 
 void launch_resample(const ResampleArgs &a, hipStream_t s) {
-    const dim3 grid((unsigned) a.B * (unsigned) ((a.T * a.n_low + kChunk - 1) / kChunk)), block(256);
-#define KNS_RS(KERNEL, RR)                                                                    \
-    do {                                                                                      \
-        if (a.resets) hipLaunchKernelGGL((KERNEL<RR, true>), grid, block, 0, s, a);           \
-        else hipLaunchKernelGGL((KERNEL<RR, false>), grid, block, 0, s, a);                   \
+    const dim3 grid((unsigned) a.B * (unsigned) ((a.T * a.q_frame + kChunk - 1) / kChunk)), block(256);
+#define KNS_RS(UU, DD)                                                                                  \
+    do {                                                                                                \
+        if (a.resets) hipLaunchKernelGGL((resample_kernel<UU, DD, true>), grid, block, 0, s, a); \
+        else hipLaunchKernelGGL((resample_kernel<UU, DD, false>), grid, block, 0, s, a);         \
     } while (0)
-    if (a.interpolate) {
-        if (a.R == 2) KNS_RS(resample_interp_kernel, 2);
-        else KNS_RS(resample_interp_kernel, 3);
-    } else {
-        if (a.R == 2) KNS_RS(resample_decim_kernel, 2);
-        else KNS_RS(resample_decim_kernel, 3);
+    switch (a.U * 8 + a.D) {
+        case 2 * 8 + 1: KNS_RS(2, 1); break;  // 8 kHz in; 32 kHz out
+        case 3 * 8 + 1: KNS_RS(3, 1); break;  // 48 kHz out
+        case 1 * 8 + 2: KNS_RS(1, 2); break;  // 32 kHz in; 8 kHz out
+        case 1 * 8 + 3: KNS_RS(1, 3); break;  // 48 kHz in
+        case 2 * 8 + 3: KNS_RS(2, 3); break;  // 24 kHz in
+        case 3 * 8 + 2: KNS_RS(3, 2); break;  // 24 kHz out
+        case 4 * 8 + 3: KNS_RS(4, 3); break;  // 12 kHz in
+        default: KNS_RS(3, 4); break;         // 12 kHz out
     }
 #undef KNS_RS
-}
-
-void launch_resample_rational(const RationalArgs &a, hipStream_t s) {
-    const dim3 grid((unsigned) a.B * (unsigned) ((a.T * a.q_frame + kChunk - 1) / kChunk)), block(256);
-#define KNS_RQ(UU, DD)                                                                                  \
-    do {                                                                                                \
-        if (a.resets) hipLaunchKernelGGL((resample_rational_kernel<UU, DD, true>), grid, block, 0, s, a); \
-        else hipLaunchKernelGGL((resample_rational_kernel<UU, DD, false>), grid, block, 0, s, a);         \
-    } while (0)
-    if (a.U == 2) KNS_RQ(2, 3);
-    else if (a.U == 4) KNS_RQ(4, 3);
-    else if (a.D == 2) KNS_RQ(3, 2);
-    else KNS_RQ(3, 4);
-#undef KNS_RQ
 }
 
 void launch_resample_reset(int16_t *state0, int16_t *state1, int hist, const uint8_t *mask, int Bpad, hipStream_t s) {

@@ -139,6 +139,29 @@ def test_min_gain_one_is_both_stages_around_a_pure_delay(random_model, rate, pre
     assert np.array_equal(np.concatenate(got, axis=1), np.concatenate(want, axis=1))
 
 
+@pytest.mark.parametrize('rate,precision', RATE_PREC)
+def test_whole_number_rates_at_workgroup_edges(random_model, rate, precision):
+    """Where the stage kernel's workgroup of 256 groups does not line up with the call: a half-filled last workgroup (8 kHz, T = 1: 128
+    groups), a frame boundary and a reset floor inside a workgroup (8 kHz, T = 3: 384 groups), a chunk boundary inside a frame (32 and
+    48 kHz out-stage: 2 and 3 output samples per group), full-range samples through the LDS output assembly.  min_gain = 1 makes the
+    inner engine the bit-exact 256-sample delay in either precision, so every sample is the recipe's."""
+    B, fl = 3, srr.frame_length(rate)
+    x = np.random.default_rng(rate).integers(-32768, 32768, size=(B, 6 * fl)).astype(np.int16)
+    reset = np.zeros((B, 3), np.uint8)
+    reset[1, 1] = reset[2, 2] = 1
+    rec = srr.Recipe(None, B, precision, rate)
+    kb = batch(random_model, B, 3, precision, rate)
+    try:
+        kb.set_min_gain(1.0)
+        x0, x1, x2 = cut(x, rate, 0, 1), cut(x, rate, 1, 4), cut(x, rate, 4, 6)
+        assert np.array_equal(call(kb, x0, 'device'), rec.process(x0))
+        assert np.array_equal(call(kb, x1, 'device', reset=reset), rec.process_resets(x1, reset))
+        assert np.array_equal(call(kb, x2, 'device'), rec.process(x2))
+        assert np.array_equal(kb.export_state()[:, 10240:], rec.rs_state())
+    finally:
+        kb.delete()
+
+
 @pytest.mark.parametrize('precision', ['fp32', 'bf16'])
 def test_rate_16000_through_init_rate_is_the_plain_handle(random_model, precision):
     x = np.ascontiguousarray(synth_streams(NCLS, 9, seed=3))

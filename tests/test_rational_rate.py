@@ -161,9 +161,9 @@ def test_rational_kernels_build_for_gfx950_without_scratch_or_spills(tmp_path):
         info[name] = {k: int(re.search(r'; %s: (\d+)' % k, body).group(1)) for k in ('ScratchSize', 'NumVgprs', 'Occupancy')}
     meta = re.findall(r'\.name:\s+(\S+)\n(?:(?!\.name:).*\n)*?\s+\.sgpr_spill_count:\s+(\d+)\n(?:(?!\.name:).*\n)*?\s+\.vgpr_spill_count:\s+(\d+)', text)
     spills = {name: (int(s), int(v)) for name, s, v in meta}
-    kernels = sorted(k for k in info if 'resample_rational_kernel' in k)
     # four (U, D) pairs, each with and without the reset arm
-    want = ['resample_rational_kernelILi%dELi%dELb%dEEEvNS_12RationalArgsE' % (U, D, r) for U, D in PAIRS for r in (0, 1)]
+    want = ['resample_kernelILi%dELi%dELb%dEEEvNS_12ResampleArgsE' % (U, D, r) for U, D in PAIRS for r in (0, 1)]
+    kernels = sorted(k for k in info if 'resample_kernel' in k and any(w in k for w in want))
     assert len(kernels) == 8 and all(any(w in k for k in kernels) for w in want), kernels
     for k in kernels:
         print(k, info[k], 'spills (sgpr, vgpr):', spills.get(k))
@@ -172,7 +172,7 @@ def test_rational_kernels_build_for_gfx950_without_scratch_or_spills(tmp_path):
     # the tap loops are straight-line code whose taps are scalar loads of the argument segment: one fma per tap, no vector-memory load
     # beyond the staging of one chunk
     for U, D in PAIRS:
-        body = text.split('resample_rational_kernelILi%dELi%dELb0EEEvNS_12RationalArgsE:' % (U, D))[1].split('s_endpgm')[0]
+        body = text.split('resample_kernelILi%dELi%dELb0EEEvNS_12ResampleArgsE:' % (U, D))[1].split('s_endpgm')[0]
         L = 48 * max(U, D) + 1
         assert len(re.findall(r'\bv_fmac?_f32', body)) >= L and len(re.findall(r'\bs_load_dword', body)) >= 10, (U, D)
         assert len(re.findall(r'\b(global|flat|buffer)_load', body)) <= 16, (U, D)

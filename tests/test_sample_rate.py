@@ -116,15 +116,16 @@ def test_resample_kernels_build_for_gfx950_without_scratch_or_spills(tmp_path):
     meta = re.findall(r'\.name:\s+(\S+)\n(?:(?!\.name:).*\n)*?\s+\.sgpr_spill_count:\s+(\d+)\n(?:(?!\.name:).*\n)*?\s+\.vgpr_spill_count:\s+(\d+)', text)
     spills = {name: (int(s), int(v)) for name, s, v in meta}
     kernels = [k for k in info if 'resample_' in k]
-    # interpolator and decimator, R = 2 and 3, with and without the reset arm; the reset and the record kernels
-    assert len([k for k in kernels if 'resample_interp_kernel' in k]) == 4 and len([k for k in kernels if 'resample_decim_kernel' in k]) == 4
+    # interpolator (R, 1) and decimator (1, R), R = 2 and 3, with and without the reset arm; the reset and the record kernels
+    whole = ['resample_kernelILi%dELi%dELb%dEEEvNS_12ResampleArgsE' % (U, D, r) for U, D in ((2, 1), (3, 1), (1, 2), (1, 3)) for r in (0, 1)]
+    assert all(len([k for k in kernels if w in k]) == 1 for w in whole), kernels
     assert any('resample_reset_kernel' in k for k in kernels) and any('resample_state_kernel' in k for k in kernels)
     for k in kernels:
         print(k, info[k], 'spills (sgpr, vgpr):', spills.get(k))
         assert info[k]['ScratchSize'] == 0, (k, info[k])
         assert spills[k] == (0, 0), (k, spills[k])
     # the tap loops are straight-line code whose taps are scalar loads of the argument segment: no vector-memory load of a tap
-    body = text.split('resample_decim_kernelILi3ELb0EEEvNS_12ResampleArgsE:')[1].split('s_endpgm')[0]
+    body = text.split('resample_kernelILi1ELi3ELb0EEEvNS_12ResampleArgsE:')[1].split('s_endpgm')[0]
     assert len(re.findall(r'\bv_fmac?_f32', body)) >= 145 and len(re.findall(r'\bs_load_dword', body)) >= 10
     assert len(re.findall(r'\b(global|flat|buffer)_load', body)) <= 16, 'vector-memory loads beyond the staging of one chunk'
 
