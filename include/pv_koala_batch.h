@@ -294,6 +294,19 @@ PV_API pv_status_t pv_koala_batch_process_packets(pv_koala_batch_t *object, cons
  * error stack: a NULL config, a struct_size that is not sizeof(pv_koala_batch_config_t), a sample_format outside 0 ... 3, and whatever
  * the three constructors refuse.
  *
+ * PACKET HANDLES AT 44 100 AND 22 050 Hz are reached through this constructor alone, with max_samples_per_call in [1, 4 194 304]
+ * (pv_koala_batch_init_rate and _init_packets keep refusing the two rates; max_samples_per_call == 0 is refused with a message that names
+ * `sample_rate`: 16 ms is not a whole number of samples there, so such a handle must be a packet handle).  16 000 / rate is 160 / 441 or
+ * 320 / 441: the handle converts on the device on either side of the unchanged 16 kHz packet path (sixth extension).
+ * Sample in, sample out like every packet handle: a call delivers row b's next counts[b] samples, pv_koala_batch_delay_sample later --
+ * 1541 at 44 100 Hz, 771 at 22 050 Hz.  Report rows and frames[b] are those of the inner 16 kHz stream (16 ms frames of 256 samples at
+ * 16 kHz: a stream that is given n samples completes about n * 16000 / rate / 256 of them; report_frames follows that).  restart,
+ * pv_koala_batch_reset, the attenuation limit, sample formats, host and device pointers and overlapping pcm / enhanced work as on the
+ * other packet handles; pv_koala_batch_sample_rate, _delay_sample, _is_packet_handle and _sample_format answer as usual.
+ * pv_koala_batch_frame_length returns PV_STATUS_INVALID_ARGUMENT with a message: there is no whole frame.  NOT YET at these rates, each
+ * refused with PV_STATUS_INVALID_ARGUMENT and a message, nothing processed: stream records (pv_koala_batch_state_size, _export_state,
+ * _import_state), the asynchronous entry points (with every frame entry point: the handle is a packet handle), and 11 025 Hz.
+ *
  * THE PROCESSING ENTRY POINTS KEEP THEIR SIGNATURES (there are no void* twins).  On a handle with a format, every `pcm` and `enhanced` --
  * of pv_koala_batch_process, _process_chunk, _resets, _hold, _process_call and _process_packets -- points to elements of the handle's
  * format behind its int16_t type: float[...] or uint8_t[...] of the documented shape, cast by the caller.  A device pointer need be
@@ -315,7 +328,7 @@ typedef struct {
     int32_t max_frames_per_call;   /* frame handles; ignored when max_samples_per_call > 0 */
     int32_t max_samples_per_call;  /* > 0: a packet handle */
     int32_t precision;             /* pv_koala_precision_t */
-    int32_t sample_rate;           /* 8000 / 12000 / 16000 / 24000 / 32000 / 48000 */
+    int32_t sample_rate;           /* 8000 / 12000 / 16000 / 24000 / 32000 / 48000; packet handles also 22050 / 44100 */
     int32_t sample_format;         /* pv_koala_sample_format_t */
 } pv_koala_batch_config_t;
 PV_API pv_status_t pv_koala_batch_init_config(const char *access_key, const char *model_path, const char *device,

@@ -13,6 +13,7 @@ import numpy as np
 from ._koala import (KoalaError, KoalaInvalidArgumentError, KoalaIOError, PicovoiceStatuses, attenuation_limit_to_gain, load_library,
                      raise_status)
 from .formats import DTYPES, FORMATS
+from .packets import FRACTIONAL_UP, inner_samples
 
 PRECISION_FP32 = 0
 PRECISION_BF16 = 1
@@ -42,7 +43,9 @@ class KoalaBatch(object):
 
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
                  max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0, sample_format: str = 's16') -> None:
-        """`sample_rate`: 8000, 12000, 16000, 24000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
+        """`sample_rate`: 44100 or 22050 Hz make a packet handle around fractional converters (`packet_samples` > 0 is required; there is
+        no frame length, `frame_length` is None, and stream records and the asynchronous calls are refused); otherwise
+        8000, 12000, 16000, 24000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
         array of samples is [num_streams, T * frame_length] with frame_length = sample_rate * 256 / 16000; at a rate other than 16000 the
         handle converts on the device, `delay_sample` includes both converters, and the asynchronous calls are refused.
         `packet_samples` > 0 makes a PACKET HANDLE (pv_koala_batch_init_packets): its streams take and deliver any number of samples per call,
@@ -58,10 +61,13 @@ class KoalaBatch(object):
             raise KoalaIOError("Could not find model file at `%s`." % model_path)
         if precision not in ('fp32', 'bf16'):
             raise KoalaInvalidArgumentError("`precision` should be `fp32` or `bf16`.")
-        if sample_rate not in (8000, 12000, 16000, 24000, 32000, 48000):
-            raise KoalaInvalidArgumentError("`sample_rate` should be 8000, 12000, 16000, 24000, 32000 or 48000.")
+        fractional = sample_rate in FRACTIONAL_UP
+        if sample_rate not in (8000, 12000, 16000, 24000, 32000, 48000) and not fractional:
+            raise KoalaInvalidArgumentError("`sample_rate` should be 8000, 12000, 16000, 24000, 32000 or 48000 (22050 and 44100: packet handles only).")
         if not isinstance(packet_samples, int) or packet_samples < 0:
             raise KoalaInvalidArgumentError("`packet_samples` should be a positive number of samples (0: a frame handle).")
+        if fractional and not packet_samples:
+            raise KoalaInvalidArgumentError("`sample_rate` %d needs `packet_samples` > 0: a handle at this rate must be a packet handle." % sample_rate)
         if not isinstance(sample_format, str) or sample_format not in FORMATS:
             raise KoalaInvalidArgumentError("`sample_format` should be `s16`, `f32`, `ulaw` or `alaw`.")
         self.sample_format = sample_format
@@ -105,13 +111,15 @@ class KoalaBatch(object):
         if packet_samples:
             lib.pv_koala_batch_process_packets.argtypes = [c_void_p, POINTER(BatchPackets)]
             lib.pv_koala_batch_process_packets.restype = PicovoiceStatuses
-        if sample_format != 's16':  # (an 's16' handle is made as it has always been: init_config would return the same handle)
+        if sample_format != 's16' or fractional:  # (any other 's16' handle is made as it has always been: init_config would return the same handle)
             lib.pv_koala_batch_init_config.argtypes = [c_char_p, c_char_p, c_char_p, POINTER(BatchConfig), POINTER(c_void_p)]
             lib.pv_koala_batch_init_config.restype = PicovoiceStatuses
             config = BatchConfig(sizeof(BatchConfig), num_streams, max_frames_per_call, packet_samples, prec, sample_rate,
                                  FORMATS.index(sample_format))
             status = lib.pv_koala_batch_init_config(access_key.encode(), model_path.encode(), device.encode(), byref(config), byref(self._handle))
-            if packet_samples:
+            if fractional:  # (the inner 16 kHz packet handle's: it takes the most inner samples a call can yield)
+                max_frames_per_call = -(-inner_samples(packet_samples, sample_rate) // 256)
+            elif packet_samples:
                 max_frames_per_call = -(-packet_samples // (sample_rate * 256 // 16000))
         elif packet_samples:
             lib.pv_koala_batch_init_packets.argtypes = [c_char_p, c_char_p, c_char_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)]
@@ -136,8 +144,10 @@ class KoalaBatch(object):
         self.frame_length = lib.pv_koala_frame_length()
         self.sample_rate = lib.pv_sample_rate()
         d = c_int32()
+        if fractional:  # no whole frame, no stream records yet: the library refuses both queries
+            self.frame_length = None
         if sample_rate != 16000:
-            for name in ('sample_rate', 'frame_length'):
+            for name in ('sample_rate',) if fractional else ('sample_rate', 'frame_length'):
                 fn = getattr(lib, 'pv_koala_batch_' + name)
                 fn.argtypes = [c_void_p, POINTER(c_int32)]
                 fn.restype = PicovoiceStatuses
@@ -145,8 +155,10 @@ class KoalaBatch(object):
                 setattr(self, name, d.value)
         self._check(lib.pv_koala_batch_delay_sample(self._handle, byref(d)), 'Failed to get delay samples')
         self.delay_sample = d.value
-        self._check(lib.pv_koala_batch_state_size(self._handle, byref(d)), 'Failed to get the state size')
-        self.state_size = d.value  # bytes of one stream record (export_state / import_state)
+        self.state_size = 0  # bytes of one stream record (export_state / import_state)
+        if not fractional:
+            self._check(lib.pv_koala_batch_state_size(self._handle, byref(d)), 'Failed to get the state size')
+            self.state_size = d.value
 
     def _check(self, status, what):
         if status is not PicovoiceStatuses.SUCCESS:
@@ -399,7 +411,8 @@ class KoalaBatch(object):
         if not report:
             self._packets(a.shape[1], counts, a.ctypes.data, out.ctypes.data, restart, None, 0)
             return out
-        rows = a.shape[1] // self.frame_length + 1
+        # (a stream completes at most this many frames; at 44 100 / 22 050 Hz the rows are the inner 16 kHz stream's)
+        rows = a.shape[1] // self.frame_length + 1 if self.frame_length else inner_samples(a.shape[1], self.sample_rate) // 256 + 1
         rep = np.zeros((self.num_streams, rows, 4), np.float32)
         frames = self._packets(a.shape[1], counts, a.ctypes.data, out.ctypes.data, restart, rep.ctypes.data, rows)
         return out, frames, rep[:, :int(frames.max()) if frames.size else 0]

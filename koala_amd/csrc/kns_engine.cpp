@@ -749,6 +749,7 @@ Engine::~Engine() {
     recof_ring_.release();
     mg_ring_.release();
     pk_ring_.release();
+    fr_ring_.release();
     for (int i = 0; i < 4; ++i)
         if (aev_out_[i]) (void) hipEventDestroy(aev_out_[i]);
     for (int i = 0; i < 2; ++i) {
@@ -881,6 +882,8 @@ bool Engine::reset(const uint8_t *host_mask, std::string *err) {
     }
     for (int b = 0; pk_max_ && b < B_; ++b)
         if (!host_mask || host_mask[b]) pk_fill_[b] = 0;
+    for (int b = 0; fr_rate_ && b < B_; ++b)
+        if (!host_mask || host_mask[b]) fr_phase_[b] = 0;
     return true;
 }
 
@@ -891,6 +894,7 @@ void Engine::launch_resets(const uint8_t *d_mask) {
         launch_resample_reset(d_rs_state_[1][0], d_rs_state_[1][1], rs_out_hist(rate_), d_mask, Bpad_, stream_);
     }
     if (pk_max_) launch_packet_reset(packet_state_args(), d_mask, stream_);
+    if (fr_rate_) launch_fractional_reset(fractional_state_args(), d_mask, stream_);
 }
 
 bool Engine::UploadRing::ready(size_t slot_bytes) {
@@ -2537,38 +2541,106 @@ PacketStateArgs Engine::packet_state_args() const {
 // (d_pk_tab_ starts with the counts).  A call without a sample (restarts only) moves and converts no samples.  Host pointers: the staging
 // stands in for the caller's device memory, and of what comes back only a row's first counts[b] elements and a stream's first k_b report
 // rows are copied on: the rest of the caller's bytes stay.
-Status Engine::run_packets(const PacketCall &c, std::string *err) {
-    const int F = rs_frame_length(rate_);
-    if (c.max_samples < 1 || c.max_samples > pk_max_) {
-        *err = "`max_samples` " + std::to_string(c.max_samples) + " is outside [1, " + std::to_string(pk_max_) + "].";
+Status Engine::run_packets(const PacketCall &c, std::string *err) { return fr_rate_ ? run_fractional(c, err) : run_packet_call(c, fmt_, err); }
+
+// ---- what the two packet calls (run_packet_call, run_fractional) share: the refusals, and the caller's side of the call
+
+// `max_samples` and `counts`, the first two refusals; what the call holds at all
+Status Engine::packet_check(const PacketCall &c, int most, bool *any_restart, bool *any_count, std::string *err) const {
+    if (c.max_samples < 1 || c.max_samples > most) {
+        *err = "`max_samples` " + std::to_string(c.max_samples) + " is outside [1, " + std::to_string(most) + "].";
         return Status::kBadArgument;
     }
-    std::vector<int32_t> k((size_t) B_);
-    std::vector<int32_t> cuts{0};
-    bool any_restart = false, any_count = false;
-    int kmax = 0;
+    *any_restart = *any_count = false;
     for (int b = 0; b < B_; ++b) {
         if (c.counts[b] < 0 || c.counts[b] > c.max_samples) {
             *err = "`counts[" + std::to_string(b) + "]` = " + std::to_string(c.counts[b]) + " is outside [0, " + std::to_string(c.max_samples) + "].";
             return Status::kBadArgument;
         }
-        const bool fresh = c.restart && c.restart[b];
-        any_restart = any_restart || fresh;
-        any_count = any_count || c.counts[b] > 0;
-        k[b] = ((fresh ? 0 : pk_fill_[b]) + c.counts[b]) / F;
-        kmax = std::max(kmax, k[b]);
+        *any_restart = *any_restart || (c.restart && c.restart[b]);
+        *any_count = *any_count || c.counts[b] > 0;
     }
+    return Status::kOk;
+}
+
+// The other refusals (`report_frames` against the kmax frames a stream completes, pointer kinds), the call without a sample or a restart
+// (*nothing: done, every stream stalled), then the caller's samples onto the device: host pointers are staged, and on a handle with a format
+// (fmt: kFmtS16 for none, and for the inner call of a fractional handle) format_in_kernel runs over the whole rows [B][max_samples] (the
+// caller owns them).  io: what the call's kernels read and write from here on.
+Status Engine::packet_begin(const PacketCall &c, int fmt, int kmax, bool any_restart, bool any_count, PacketIo *io, bool *nothing, std::string *err) {
+    *nothing = false;
     if (c.report && c.report_frames < kmax) {
         *err = "`report_frames` " + std::to_string(c.report_frames) + " is below the " + std::to_string(kmax) + " frames a stream completes in this call.";
         return Status::kBadArgument;
     }
     (void) hipSetDevice(device_);
-    bool host;
-    if (!call_on_host(c.pcm, c.out, c.report, &host, err)) return Status::kBadArgument;
+    if (!call_on_host(c.pcm, c.out, c.report, &io->host, err)) return Status::kBadArgument;
     if (!any_count && !any_restart) {  // every stream stalled: nothing to do
         for (int b = 0; c.frames && b < B_; ++b) c.frames[b] = 0;
+        *nothing = true;
         return Status::kOk;
     }
+    io->convert = fmt != kFmtS16 && any_count;
+    io->bytes = any_count ? (size_t) B_ * c.max_samples * fmt_bytes(fmt) : 0;
+    // what the call reads and writes on the device: the caller's memory, or the staging (its report rows kmax apart)
+    const void *src = c.pcm;
+    io->dst = c.out;
+    io->report = c.report;
+    io->report_frames = c.report_frames;
+    if (io->host) {
+        if (!stage_in(c.pcm, io->bytes, c.report != nullptr, err)) return Status::kRuntime;
+        src = io->dst = d_host_io_;
+        if (c.report) io->report = d_host_rep_, io->report_frames = kmax;
+    }
+    if (io->convert) {
+        launch_format_in(fmt, FormatArgs{src, d_fmt_in_, nullptr, (long long) B_ * c.max_samples, 1}, stream_);
+        if (hipGetLastError() != hipSuccess) {
+            *err = hip_last_error();
+            return Status::kRuntime;
+        }
+    }
+    io->in16 = fmt != kFmtS16 ? d_fmt_in_ : (const int16_t *) src;
+    io->out16 = fmt != kFmtS16 ? d_fmt_out_ : (int16_t *) io->dst;
+    return Status::kOk;
+}
+
+// ... and back: format_out_kernel writes row b's first counts[b] elements only, from the call's device table (d_counts: it starts with the
+// counts); of what a host call's staging brings back only a row's first counts[b] elements and a stream's first k[b] report rows are
+// copied on, the rest of the caller's bytes stay.
+Status Engine::packet_end(const PacketCall &c, int fmt, const PacketIo &io, const int32_t *d_counts, const int32_t *k, int kmax, std::string *err) {
+    if (io.convert) launch_format_out(fmt, FormatArgs{d_fmt_out_, io.dst, d_counts, (long long) c.max_samples, B_}, stream_);
+    if (hipGetLastError() != hipSuccess) {
+        *err = hip_last_error();
+        return Status::kRuntime;
+    }
+    if (!io.host) return Status::kOk;
+    const size_t eb = (size_t) fmt_bytes(fmt), rep_floats = c.report ? (size_t) B_ * kmax * 4 : 0;
+    host_out_.resize((size_t) B_ * c.max_samples * eb);
+    host_rep_.resize(rep_floats);
+    if (!stage_out(host_out_.data(), io.bytes, host_rep_.data(), rep_floats * 4, err)) return Status::kRuntime;
+    for (int b = 0; b < B_; ++b) {
+        const size_t at = (size_t) b * c.max_samples * eb;
+        memcpy((uint8_t *) c.out + at, host_out_.data() + at, (size_t) c.counts[b] * eb);
+        if (c.report) memcpy(c.report + (size_t) b * c.report_frames * 4, host_rep_.data() + (size_t) b * kmax * 4, (size_t) k[b] * 16);
+    }
+    return Status::kOk;
+}
+
+Status Engine::run_packet_call(const PacketCall &c, int fmt, std::string *err) {
+    const int F = rs_frame_length(rate_);
+    bool any_restart, any_count, nothing;
+    Status st = packet_check(c, pk_max_, &any_restart, &any_count, err);
+    if (st != Status::kOk) return st;
+    std::vector<int32_t> k((size_t) B_);
+    std::vector<int32_t> cuts{0};
+    int kmax = 0;
+    for (int b = 0; b < B_; ++b) {
+        k[b] = ((c.restart && c.restart[b] ? 0 : pk_fill_[b]) + c.counts[b]) / F;
+        kmax = std::max(kmax, k[b]);
+    }
+    PacketIo io;
+    st = packet_begin(c, fmt, kmax, any_restart, any_count, &io, &nothing, err);
+    if (st != Status::kOk || nothing) return st;
     {  // the sub-calls: frames [cuts[l], cuts[l + 1])
         std::vector<int32_t> ks(k);
         std::sort(ks.begin(), ks.end());
@@ -2577,25 +2649,6 @@ Status Engine::run_packets(const PacketCall &c, std::string *err) {
         }
     }
     const int nsub = (int) cuts.size() - 1;
-    const bool convert = fmt_ != kFmtS16 && any_count;
-    const size_t n = (size_t) B_ * c.max_samples, eb = (size_t) sample_bytes();
-    // what the call reads and writes on the device: the caller's memory, or the staging (its report rows kmax apart)
-    const void *src = c.pcm;
-    void *dst = c.out;
-    float *report = c.report;
-    int report_frames = c.report_frames;
-    if (host) {
-        if (!stage_in(c.pcm, any_count ? n * eb : 0, c.report != nullptr, err)) return Status::kRuntime;
-        src = dst = d_host_io_;
-        if (c.report) report = d_host_rep_, report_frames = kmax;
-    }
-    if (convert) {
-        launch_format_in(fmt_, FormatArgs{src, d_fmt_in_, nullptr, (long long) n, 1}, stream_);
-        if (hipGetLastError() != hipSuccess) {
-            *err = hip_last_error();
-            return Status::kRuntime;
-        }
-    }
     // the call's table, and the restart mask behind it
     const size_t tab_ints = (size_t) Bpad_ + 2 + (size_t) Tmax_;
     const int slot = pk_ring_.acquire();
@@ -2621,15 +2674,15 @@ Status Engine::run_packets(const PacketCall &c, std::string *err) {
             if (c.restart[b]) pk_fill_[b] = 0;
     }
     PacketArgs a;
-    a.user_in = fmt_ != kFmtS16 ? d_fmt_in_ : (const int16_t *) src;
-    a.user_out = fmt_ != kFmtS16 ? d_fmt_out_ : (int16_t *) dst;
+    a.user_in = io.in16;
+    a.user_out = io.out16;
     a.tab = d_pk_tab_;
     a.pin = d_pk_pin_, a.pout = d_pk_pout_;
     a.fill_in = d_pk_fill_[0], a.fill_out = d_pk_fill_[1];
     a.frames = d_pk_in_;
     a.sub_report = d_pk_rep_;
-    a.report = report;
-    a.report_frames = report_frames;
+    a.report = io.report;
+    a.report_frames = io.report_frames;
     a.max_samples = c.max_samples, a.B = B_, a.Bpad = Bpad_, a.F = F;
     launch_packet_in(a, stream_);
     if (hipGetLastError() != hipSuccess) {
@@ -2649,27 +2702,132 @@ Status Engine::run_packets(const PacketCall &c, std::string *err) {
     }
     a.frames = d_pk_out_;
     launch_packet_out(a, stream_);
-    if (convert) launch_format_out(fmt_, FormatArgs{d_fmt_out_, dst, d_pk_tab_, (long long) c.max_samples, B_}, stream_);
     if (hipGetLastError() != hipSuccess) {
         *err = hip_last_error();
         return Status::kRuntime;
     }
-    for (int b = 0; b < B_; ++b) {
+    for (int b = 0; b < B_; ++b) {  // (the mirror follows what is enqueued)
         pk_fill_[b] = pk_fill_[b] + c.counts[b] - k[b] * F;
         if (c.frames) c.frames[b] = k[b];
     }
-    if (host) {
-        const size_t rep_floats = c.report ? (size_t) B_ * kmax * 4 : 0;
-        host_out_.resize(n * eb);
-        host_rep_.resize(rep_floats);
-        if (!stage_out(host_out_.data(), any_count ? n * eb : 0, host_rep_.data(), rep_floats * 4, err)) return Status::kRuntime;
-        for (int b = 0; b < B_; ++b) {
-            const size_t at = (size_t) b * c.max_samples * eb;
-            memcpy((uint8_t *) c.out + at, host_out_.data() + at, (size_t) c.counts[b] * eb);
-            if (c.report) memcpy(c.report + (size_t) b * c.report_frames * 4, host_rep_.data() + (size_t) b * kmax * 4, (size_t) k[b] * 16);
-        }
+    return packet_end(c, fmt, io, d_pk_tab_, k.data(), kmax, err);
+}
+
+// ------------------------------------------------------------------------------------------------ packet handles at 44 100 and 22 050 Hz
+
+// The polyphase table of a fractional stage (kns_kernels.h, FractionalArgs::taps): [tap j][phase r] = (float) (scale g[r + P j]) over the
+// prototype of K = 441, built in double and rounded once; zero where the prototype has no such tap.
+static std::vector<float> fr_table(int scale, int P, int taps) {
+    const std::vector<double> g = rs_prototype_g(kFrDown);
+    std::vector<float> h((size_t) taps * P, 0.0f);
+    for (int j = 0; j < taps; ++j)
+        for (int r = 0; r < P && r + P * j < kFrTaps; ++r) h[(size_t) j * P + r] = (float) (scale * g[(size_t) r + (size_t) P * j]);
+    return h;
+}
+
+bool Engine::enable_fractional(int rate, int max_samples, std::string *err) {
+    (void) hipSetDevice(device_);
+    const int U = fr_up(rate), T = fr_in_taps(U);
+    const size_t tab_bytes = (size_t) Bpad_ * 5;  // int32 counts[Bpad], uint8 restart[Bpad]
+    d_fr_in_ = (int16_t *) dalloc((size_t) B_ * pk_max_ * 2, false);
+    d_fr_out_ = (int16_t *) dalloc((size_t) B_ * pk_max_ * 2, false);
+    d_fr_hist_[0] = (int16_t *) dalloc((size_t) Bpad_ * T * 2, true);
+    d_fr_hist_[1] = (int16_t *) dalloc((size_t) Bpad_ * kFrOutHist * 2, true);
+    d_fr_phase_[0] = (int32_t *) dalloc((size_t) Bpad_ * 4, true);
+    d_fr_phase_[1] = (int32_t *) dalloc((size_t) Bpad_ * 4, true);
+    d_fr_tab_ = (int32_t *) dalloc(tab_bytes, true);
+    const std::vector<float> h_in = fr_table(U, U, T), h_out = fr_table(kFrDown, kFrDown, kFrOutTaps);
+    d_fr_taps_[0] = (float *) upload(h_in.data(), h_in.size() * 4);
+    d_fr_taps_[1] = (float *) upload(h_out.data(), h_out.size() * 4);
+    if (!d_fr_in_ || !d_fr_out_ || !d_fr_hist_[0] || !d_fr_hist_[1] || !d_fr_phase_[0] || !d_fr_phase_[1] || !d_fr_tab_ || !d_fr_taps_[0] ||
+        !d_fr_taps_[1] || !fr_ring_.ready(tab_bytes)) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the buffers of a handle at " + std::to_string(rate) + " Hz.";
+        return false;
     }
-    return Status::kOk;
+    fr_phase_.assign((size_t) B_, 0);
+    fr_rate_ = rate, fr_max_ = max_samples;
+    return true;
+}
+
+FractionalStateArgs Engine::fractional_state_args() const {
+    return FractionalStateArgs{d_fr_hist_[0], d_fr_hist_[1], d_fr_phase_[0], d_fr_phase_[1], fr_in_taps(fr_up(fr_rate_)), Bpad_};
+}
+
+// One call of a packet handle at 44 100 or 22 050 Hz (sixth extension; section 6): the converter sits OUTSIDE the
+// packetiser.  The plan is made on the host from the mirror of N mod 441: stream b feeds the inner 16 kHz packet path
+// M(N + counts[b]) - M(N) samples (koala_amd/packets.py restates it), and the inner call's own plan follows from its mirror of fill.  Every
+// refusal is decided before anything is touched.  Then, on the handle's stream: [format_in], the call's table, the masked reset of
+// `restart` (every layer's state at once, so the inner call sees none), fractional_in_kernel, the inner packet call on device rows -- its
+// report rows and frame counts are the call's -- fractional_out_kernel, [format_out].  A call in which no stream yields an inner sample
+// still runs both stages: the in-stage's history and N advance, and the out-stage delivers from the inner output it holds.
+Status Engine::run_fractional(const PacketCall &c, std::string *err) {
+    const int U = fr_up(fr_rate_);
+    bool any_restart, any_count, nothing;
+    Status st = packet_check(c, fr_max_, &any_restart, &any_count, err);
+    if (st != Status::kOk) return st;
+    std::vector<int32_t> inner((size_t) B_), k((size_t) B_, 0);
+    int kmax = 0;
+    for (int b = 0; b < B_; ++b) {
+        const bool fresh = c.restart && c.restart[b];
+        const long long ph = fresh ? 0 : fr_phase_[b];
+        inner[b] = (int32_t) (fr_inner(ph + c.counts[b], U) - fr_inner(ph, U));
+        kmax = std::max(kmax, ((fresh ? 0 : pk_fill_[b]) + inner[b]) / kFrame);
+    }
+    PacketIo io;
+    st = packet_begin(c, fmt_, kmax, any_restart, any_count, &io, &nothing, err);
+    if (st != Status::kOk || nothing) return st;
+    const int slot = fr_ring_.acquire();
+    if (slot < 0) {
+        *err = hip_last_error();
+        return Status::kRuntime;
+    }
+    int32_t *tab = (int32_t *) fr_ring_.host[slot];
+    uint8_t *mask = (uint8_t *) (tab + Bpad_);
+    memset(tab, 0, (size_t) Bpad_ * 5);
+    memcpy(tab, c.counts, (size_t) B_ * 4);
+    for (int b = 0; any_restart && b < B_; ++b) mask[b] = c.restart[b] ? 1 : 0;
+    if (hipMemcpyAsync(d_fr_tab_, tab, (size_t) Bpad_ * 5, hipMemcpyHostToDevice, stream_) != hipSuccess || !fr_ring_.uploaded(slot, stream_)) {
+        *err = hip_last_error();
+        return Status::kRuntime;
+    }
+    if (any_restart) {
+        launch_resets((const uint8_t *) (d_fr_tab_ + Bpad_));
+        for (int b = 0; b < B_; ++b)
+            if (c.restart[b]) pk_fill_[b] = 0, fr_phase_[b] = 0;
+    }
+    // From here on only HIP can fail, and a call that fails half-way has advanced some layers of the streams and not the others (the
+    // in-stage's N mod 441 and history are ahead of the out-stage's and of the mirror): the error is reported, and the handle's streams are
+    // defined again only after pv_koala_batch_reset.  The inner call's status travels on as it is.
+    FractionalArgs a;
+    a.in = io.in16;
+    a.out = d_fr_in_;
+    a.counts = d_fr_tab_;
+    a.hist = d_fr_hist_[0], a.phase = d_fr_phase_[0], a.taps = d_fr_taps_[0];
+    a.in_stride = c.max_samples, a.out_stride = pk_max_, a.U = U;
+    launch_fractional_in(a, B_, stream_);
+    if (hipGetLastError() != hipSuccess) {
+        *err = hip_last_error();
+        return Status::kRuntime;
+    }
+    // the inner call: an S16 call on device rows, without restarts (done above); its report rows and frame counts are this call's
+    PacketCall in16{pk_max_, inner.data(), d_fr_in_, d_fr_out_, nullptr, io.report, io.report_frames, k.data(), c.min_gain, c.min_gain_rev};
+    st = run_packet_call(in16, kFmtS16, err);
+    if (st != Status::kOk) return st;
+    a.in = d_fr_out_;
+    a.out = io.out16;
+    a.hist = d_fr_hist_[1], a.phase = d_fr_phase_[1], a.taps = d_fr_taps_[1];
+    a.in_stride = pk_max_, a.out_stride = c.max_samples;
+    launch_fractional_out(a, B_, stream_);
+    if (hipGetLastError() != hipSuccess) {
+        *err = hip_last_error();
+        return Status::kRuntime;
+    }
+    for (int b = 0; b < B_; ++b) {  // (the mirror follows what is enqueued)
+        fr_phase_[b] = (fr_phase_[b] + c.counts[b]) % kFrDown;
+        if (c.frames) c.frames[b] = k[b];
+    }
+    return packet_end(c, fmt_, io, d_fr_tab_, k.data(), kmax, err);
 }
 
 // ------------------------------------------------------------------------------------------------ sample formats

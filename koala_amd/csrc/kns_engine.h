@@ -130,6 +130,14 @@ public:
     int packet_samples() const { return pk_max_; }  // 0: a frame handle
     Status run_packets(const PacketCall &c, std::string *err);
 
+    // ---- packet handles at 44 100 and 22 050 Hz (sixth extension).  enable_fractional, once, on a 16 kHz packet
+    // engine right after enable_packets (whose max_samples is the most INNER samples a call can yield, fr_inner(max_samples) =
+    // ceil(U max_samples / 441)) and before set_format: from then on run_packets takes and delivers up to max_samples samples per call at `rate`,
+    // through the fractional stages (kns_fractional.hip) around the unchanged 16 kHz packet call.  Everything else of the engine stays a
+    // 16 kHz packet engine's: sample_rate(), records (which the owner refuses), reports and frame counts are the inner stream's.
+    bool enable_fractional(int rate, int max_samples, std::string *err);
+    int fractional_rate() const { return fr_rate_; }  // 0: not such a handle
+
     // ---- sample formats (fifth extension).  set_format, once, right after create() -- and after enable_packets on a
     // packet handle: from then on the `pcm` and `out` of process() and run_packets() point to elements of that format (kns_kernels.h,
     // SampleFormat) behind their int16 types, sample_bytes() each, and are converted on the device around the unchanged S16 call.  The engine's
@@ -150,7 +158,7 @@ private:
     // sees device pointers.  One staging set, allocated by the first host-pointer call: d_host_io_ [B][io_row()] elements of the handle's
     // format, the call's input and then its output; d_host_rep_ [B][Tmax][4]; and the host copies of a packet call's output and report,
     // of which only a row's first counts[b] elements and a stream's first k_b report rows go on to the caller.
-    size_t io_row() const { return pk_max_ ? (size_t) pk_max_ : (size_t) Tmax_ * rs_frame_length(rate_); }  // a stream's most elements per call
+    size_t io_row() const { return fr_rate_ ? (size_t) fr_max_ : pk_max_ ? (size_t) pk_max_ : (size_t) Tmax_ * rs_frame_length(rate_); }  // a stream's most elements per call
     uint8_t *d_host_io_ = nullptr;
     float *d_host_rep_ = nullptr;
     std::vector<uint8_t> host_out_;
@@ -183,6 +191,31 @@ private:
     uint8_t *d_state_pk_ = nullptr;  // the packet part of the staged stream records [B][pk_record_bytes]
     std::vector<int32_t> pk_fill_;
     PacketStateArgs packet_state_args() const;
+    // run_packets of every handle that is not a fractional one, and a fractional handle's inner call (fmt: the format of c.pcm / c.out)
+    Status run_packet_call(const PacketCall &c, int fmt, std::string *err);
+    // what the two packet calls share (kns_engine.cpp): the refusals in their order, the caller's samples onto the device and back
+    struct PacketIo {
+        bool host, convert;              // the caller's pointers are host memory; format kernels run (a format, and some sample)
+        size_t bytes;                    // of the caller's rows that travel (0: a call without a sample)
+        void *dst;                       // where the format's elements go on the device: the caller's memory or the staging
+        float *report;                   // ... and the report rows, report_frames apart per stream
+        int report_frames;
+        const int16_t *in16;             // the int16 rows [B][max_samples] the call's first kernel reads
+        int16_t *out16;                  // ... and its last one writes
+    };
+    Status packet_check(const PacketCall &c, int most, bool *any_restart, bool *any_count, std::string *err) const;
+    Status packet_begin(const PacketCall &c, int fmt, int kmax, bool any_restart, bool any_count, PacketIo *io, bool *nothing, std::string *err);
+    Status packet_end(const PacketCall &c, int fmt, const PacketIo &io, const int32_t *d_counts, const int32_t *k, int kmax, std::string *err);
+    // fractional handles: the rate, the caller's max_samples, the inner path's rows [B][pk_max_] on either side of the 16 kHz packet call,
+    // the stages' tables and per-stream state ([0]: in-stage, [1]: out-stage), the call table (int32 counts[Bpad], uint8 restart[Bpad])
+    // with its upload ring, and the HOST MIRROR of N mod 441, from which a call's inner counts are planned without a look at the device
+    int fr_rate_ = 0, fr_max_ = 0;
+    int16_t *d_fr_in_ = nullptr, *d_fr_out_ = nullptr, *d_fr_hist_[2] = {nullptr, nullptr};
+    int32_t *d_fr_phase_[2] = {nullptr, nullptr}, *d_fr_tab_ = nullptr;
+    float *d_fr_taps_[2] = {nullptr, nullptr};
+    std::vector<int32_t> fr_phase_;
+    FractionalStateArgs fractional_state_args() const;
+    Status run_fractional(const PacketCall &c, std::string *err);
     int rate_ = kRate16k;
     int16_t *d_rs_state_[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [in-stage, out-stage][ping-pong copy], [Bpad][hist] each
     int rs_cur_ = 0;
@@ -322,7 +355,7 @@ private:
     // Per-frame stream resets (kns_engine.cpp, begin_resets).  A call's packed table -- per (m-tile, frame) the rows that restart, uint32
     // [mtiles][T] -- goes through a slot of rs_ring_ to d_rs_ on the stream that runs the call's kernels, a frame-0 mask to d_rmask_.
     // The table belongs to its call: process*() own it and hand it to run_device with every slice.
-    UploadRing rs_ring_, rsf_ring_, pk_ring_;  // (rsf_ring_: the sample-rate stages' copy of a call's reset flags; pk_ring_: a packet call's table)
+    UploadRing rs_ring_, rsf_ring_, pk_ring_, fr_ring_;  // (fr_ring_: a fractional call's table; rsf_ring_: the sample-rate stages' copy of a call's reset flags; pk_ring_: a packet call's table)
     unsigned *d_rs_ = nullptr;
     struct ResetTable {
         int slot = -1, T = 0;        // the call's ring slot (-1: no stream restarts after frame 0, there is no table) and its length

@@ -378,6 +378,43 @@ struct PacketStateArgs {
 };
 void launch_packet_reset(const PacketStateArgs &a, const uint8_t *mask, hipStream_t s);  // mask: device [Bpad], null: every stream
 void launch_packet_state(const PacketStateArgs &a, hipStream_t s);
+// ---- fractional sample-rate stages of packet handles at 44 100 and 22 050 Hz (kns_fractional.hip; DESIGN.md section 2, sixth extension).
+// 16 000 / 44 100 = 160 / 441 and 16 000 / 22 050 = 320 / 441: the in-stage is "up U, down 441", the out-stage "up 441, down U", over the
+// prototype of K = 441 (L = 21 169 taps), around the unchanged 16 kHz packet path.  Consecutive outputs sit at different phases, so the
+// taps are per-lane loads from a polyphase table in global memory, [tap j][phase r] = h[r + P j] (P = U in, 441 out; zero where r + P j >= L).
+// Per stream: N mod 441 (one copy per stage: they differ between a call's two launches), the in-stage's last fr_in_taps(U) input samples
+// and the out-stage's last kFrOutHist inner output samples, int16, oldest first.
+constexpr int kFrDown = 441, kFrTaps = 2 * kRsHalf * kFrDown + 1, kFrInnerDelay = 2 * kFrame - 1, kFrOutTaps = 49, kFrOutHist = 49;
+constexpr int kFrMaxSamples = 1 << 22;  // the most samples per call of such a handle: U (441 + n) stays an int
+KNS_HD constexpr int fr_up(int rate) { return rate == 44100 ? 160 : rate == 22050 ? 320 : 0; }
+KNS_HD constexpr bool fr_rate_ok(int rate) { return fr_up(rate) != 0; }
+KNS_HD constexpr int fr_in_taps(int U) { return (kFrTaps + U - 1) / U; }  // 133 / 67: the most taps of an in-stage output, and its history
+// the chain's delay in ticks of 1 / (U rate): both stages' 24 * 441 and the inner packet handle's 511 * 441
+KNS_HD constexpr int fr_ticks() { return (2 * kRsHalf + kFrInnerDelay) * kFrDown; }
+KNS_HD constexpr int fr_shift(int U) { return (U - fr_ticks() % U) % U; }  // c: the out-stage's time base, U n - c
+KNS_HD constexpr int fr_delay(int U) { return (fr_ticks() + fr_shift(U)) / U; }
+// M(N) = ceil(U N / 441): the inner samples that exist once a stream has received N samples
+KNS_HD constexpr long long fr_inner(long long n, int U) { return (U * n + kFrDown - 1) / kFrDown; }
+static_assert(fr_in_taps(160) == 133 && fr_in_taps(320) == 67 && fr_shift(160) == 41 && fr_shift(320) == 201 && fr_delay(160) == 1541 &&
+              fr_delay(320) == 771 && kFrTaps == 21169 && (kFrTaps + kFrDown - 1) / kFrDown == kFrOutTaps, "fractional stage constants");
+struct FractionalArgs {
+    const int16_t *in;      // in-stage: [B][in_stride] at the handle's rate, row b's first counts[b] samples; out-stage: the inner output,
+                            // row b's first M(phase + counts[b]) - M(phase) samples
+    int16_t *out;           // [B][out_stride]: the other of the two
+    const int32_t *counts;  // device [Bpad]: the call's samples per stream at the handle's rate
+    int16_t *hist;          // [Bpad][fr_in_taps(U)] or [Bpad][kFrOutHist], rewritten in place (one workgroup owns a stream)
+    int32_t *phase;         // [Bpad]: N mod 441, this stage's copy
+    const float *taps;      // [fr_in_taps(U)][U] or [kFrOutTaps][441]
+    int in_stride, out_stride, U;
+};
+void launch_fractional_in(const FractionalArgs &a, int B, hipStream_t s);
+void launch_fractional_out(const FractionalArgs &a, int B, hipStream_t s);
+struct FractionalStateArgs {
+    int16_t *hist_in, *hist_out;
+    int32_t *phase_in, *phase_out;
+    int taps_in, Bpad;
+};
+void launch_fractional_reset(const FractionalStateArgs &a, const uint8_t *mask, hipStream_t s);  // mask: device [Bpad], null: every stream
 // ---- sample formats of batch handles (kns_format.hip; DESIGN.md section 2, fifth extension): what a caller's `pcm` and `enhanced` hold.
 // Configuration of the handle, not stream state: the engine's samples are int16 whatever the format, which is a conversion on the device in
 // front of and behind the unchanged call.  The values are pv_koala_sample_format_t's.

@@ -171,13 +171,24 @@ def main(argv=None):
                     help='feed the stream in packets of this many ms through a packet handle instead of in 16 ms frames')
     ap.add_argument('--sample_format', default=None, choices=['s16', 'f32', 'ulaw', 'alaw'],
                     help='raw samples of this format on stdin and stdout at --sample_rate, through a packet handle that converts on the device')
-    ap.add_argument('--sample_rate', type=int, default=16000, choices=[8000, 12000, 16000, 24000, 32000, 48000], help='with --sample_format: the stream\'s rate')
+    ap.add_argument('--sample_rate', type=int, default=16000, choices=[8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000],
+                    help='with --sample_format: the stream\'s rate (22050 and 44100 imply --sample_format s16 when none is given)')
     ap.add_argument('--show_devices', action='store_true')
     args = ap.parse_args(argv)
 
     if args.show_devices:
         print('\n'.join(koala_amd.available_devices(library_path=args.library_path)))
         return 0
+    if args.sample_rate in (22050, 44100):
+        # no frame exists at these rates: the raw packet path (stdin -> stdout) is the only one, and it has no files, meter or pacing
+        given = [name for name, v in (('--input_path', args.input_path), ('--output_path', args.output_path),
+                                      ('--reference_output_path', args.reference_output_path), ('--meter', args.meter),
+                                      ('--realtime', args.realtime)) if v]
+        if given:
+            raise ValueError('%s: not available at --sample_rate %d, where the stream is raw samples on stdin and stdout '
+                             '(--sample_format, s16 by default)' % (', '.join(given), args.sample_rate))
+        if args.sample_format is None:
+            args.sample_format = 's16'
     if args.sample_format is not None:
         return run_raw_format(args)
     if args.output_path is None:

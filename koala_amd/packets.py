@@ -40,6 +40,29 @@ def plan(k, max_frames: int) -> List[Tuple[int, int, Optional[np.ndarray]]]:
     return out
 
 
+# ---- packet handles at 44 100 and 22 050 Hz (sixth extension): 16 000 / rate = U / 441
+FRACTIONAL_UP = {44100: 160, 22050: 320}
+
+
+def inner_samples(n, sample_rate: int):
+    """M(N): the samples of the inner 16 kHz stream that exist once a stream at `sample_rate` has received n samples in total,
+    floor((U n - 1) / 441) + 1 with floor division (M(0) = 0).  An int for an int, else an int64 array."""
+    U = FRACTIONAL_UP[sample_rate]
+    if isinstance(n, (int, np.integer)):
+        return (U * int(n) - 1) // 441 + 1
+    return (U * np.asarray(n, np.int64) - 1) // 441 + 1
+
+
+def inner_due(phase, counts, sample_rate: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(inner, new_phase): stream b, which has received N samples with N mod 441 = phase[b], is given counts[b] more: the call feeds its
+    inner 16 kHz packet path inner[b] = M(N + counts) - M(N) samples (0 is possible) and leaves new_phase[b] = (phase + counts) mod 441.
+    The engine plans from the same mirror (koala_amd/csrc/kns_engine.cpp, run_fractional); the inner path's frames then follow from
+    `frames_due(fill, inner, 256)`."""
+    phase, counts = np.asarray(phase, np.int64), np.asarray(counts, np.int64)
+    inner = inner_samples(phase + counts, sample_rate) - inner_samples(phase, sample_rate)
+    return inner.astype(np.int32), ((phase + counts) % 441).astype(np.int32)
+
+
 class PacketClock(object):
     """Collects arriving packets into the rows of the next packet call.
 
@@ -74,4 +97,4 @@ class PacketClock(object):
         return counts, pcm
 
 
-__all__ = ['frames_due', 'plan', 'PacketClock']
+__all__ = ['frames_due', 'plan', 'PacketClock', 'FRACTIONAL_UP', 'inner_samples', 'inner_due']
