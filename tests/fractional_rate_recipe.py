@@ -48,7 +48,7 @@ _tables = {}
 def tables(rate):
     """(h_in, h_out) float32 [L]: (float) (U g[i]) and (float) (441 g[i])"""
     if rate not in _tables:
-        g = srr.prototype(D)[0]
+        g = srr.prototype(D)
         assert g.shape == (L,)
         _tables[rate] = ((UP[rate] * g).astype(F32), (D * g).astype(F32))
     return _tables[rate]

@@ -1,7 +1,7 @@
 """
 Packet handles at 44 100 and 22 050 Hz on the GPU (include/pv_koala_batch.h: pv_koala_batch_init_config; DESIGN.md section 2, sixth
 extension) against tests/fractional_rate_recipe.py: about 40 calls of up to 1000 samples, per-stream counts from {0, 1, 441, 882, random},
-the streams out of phase.  fp32 is the recipe sample for sample; bf16 is held to the bar of tests/test_gpu_rational_rate.py -- the largest
+the streams out of phase.  fp32 is the recipe sample for sample; bf16 is held to the bar of tests/sample_rate_cases.py -- the largest
 distance is at most ceil(BF16_TOL * S) + 1 LSB, S = the out-stage's largest sum of |tap| over an output phase, and the share of samples
 further than 1 LSB from the recipe is at most 4 x the share by which the jittered oracle misses it -- and, between two cuttings of one
 stream, to the bar of tests/test_gpu_packets.py.  The recipe is pushed once per stream and shared.

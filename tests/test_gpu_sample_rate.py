@@ -1,17 +1,15 @@
 """
 Batch handles at 8, 32 and 48 kHz (include/pv_koala_batch.h: pv_koala_batch_init_rate; DESIGN.md section 2, third extension) on a real MI355X:
-koala_amd/csrc/kns_resample.hip's stages around the unchanged 16 kHz call, through the product library.
+koala_amd/csrc/kns_resample.hip's stages around the unchanged 16 kHz call, through the product library.  The tests that hold at every rate are written
+for all five -- 8, 12, 24, 32 and 48 kHz -- and parametrised here over the three whole-number rates; tests/test_gpu_rational_rate.py runs the
+same functions at 12 and 24 kHz with its own batch sizes and modes.  Where the frames per call differ between the rates, the per-rate
+literal stands in the test: they are part of a case.
 
-Expected samples come from tests/sample_rate_recipe.py: in-stage -> oracle.Oracle.process -> out-stage in numpy float32.  fp32: ==.  bf16: the
-largest distance is at most ceil(BF16_TOL * S) + 1 LSB, S = the out-stage's largest sum of |tap| over an output phase (BF16_TOL LSB of the
-engine spread by the out-stage, one more for its rounding), and the share of samples further than 1 LSB from the recipe is at most 4 x the
-share by which the jittered bf16 oracle (oracle.set_jitter: a second valid bf16 implementation) misses the plain one through the same
-recipe on the same inputs -- the margin tools/frame_report_bars.py established.  Wherever the inner engine is a pure delay (a unity-mask
-model, min_gain = 1) the samples are == in both precisions.
+Expected samples come from tests/sample_rate_recipe.py: in-stage -> oracle.Oracle.process -> out-stage in numpy float32, held to the bar of
+tests/sample_rate_cases.py (fp32: ==; bf16: a bound on the distance and on the share further than 1 LSB).  Wherever the inner engine is a
+pure delay (a unity-mask model, min_gain = 1) the samples are == in both precisions.
 """
 import ctypes
-import functools
-import math
 
 import numpy as np
 import pytest
@@ -19,87 +17,16 @@ import pytest
 import koala_amd
 import sample_rate_recipe as srr
 from conftest import model_file, synth_streams
-from oracle import oracle
+from sample_rate_cases import CALLS, NCLS, TMAX, batch, call, check, classes, cut, expected, signal
 
 pytestmark = pytest.mark.gpu
 
-BF16_TOL = 5  # tests/test_gpu_parity.py
-NCLS = 6      # distinct streams; a batch repeats them (cls[b]) so that the CPU side stays small
-CALLS = (1, 3, 16, 2)
-TMAX = 16
-RATE_PREC = [(r, p) for r in srr.RATES for p in ('fp32', 'bf16')]
-
-
-def batch(model, B, T, precision, rate):
-    return koala_amd.create_batch('key', B, T, precision, model_path=model, sample_rate=rate)
-
-
-def classes(B):
-    return np.arange(B) % NCLS
-
-
-def signal(rate, T, seed):
-    """int16 [NCLS, T * frame_length]: the suite's synthetic streams, taken as samples at `rate`"""
-    fl = srr.frame_length(rate)
-    return np.ascontiguousarray(synth_streams(NCLS, T * fl // 256 + 1, seed=seed)[:, :T * fl])
-
-
-def cut(x, rate, t0, t1):
-    fl = srr.frame_length(rate)
-    return np.ascontiguousarray(x[:, t0 * fl:t1 * fl])
-
-
-def call(kb, x, mode, **kw):
-    """one call -> enhanced (or (enhanced, report)): 'host' (pageable), 'device', 'inplace' (device, enhanced == pcm)"""
-    T = x.shape[1] // kb.frame_length
-    if mode == 'host':
-        return kb.process_call(x, **kw)
-    import torch
-    report = kw.pop('report', False)
-    xd = torch.from_numpy(x).cuda()
-    yd = xd if mode == 'inplace' else torch.zeros_like(xd)
-    rd = torch.full((x.shape[0], T, 4), -1.0, dtype=torch.float32, device='cuda') if report else None
-    torch.cuda.synchronize()
-    kb.process_device_call(T, xd.data_ptr(), yd.data_ptr(), rd.data_ptr() if report else 0, **kw)
-    kb.synchronize()
-    return (yd.cpu().numpy(), rd.cpu().numpy()) if report else yd.cpu().numpy()
-
-
-@functools.lru_cache(maxsize=None)
-def expected(kind, precision, rate, jitter=0):
-    """the recipe over CALLS on the NCLS class streams -> (input, [enhanced per call]); kind 'unity': the inner engine as a pure delay"""
-    x = signal(rate, sum(CALLS), seed=11)
-    oracle.set_jitter(jitter)
-    try:
-        rec = srr.Recipe(None if kind == 'unity' else model_file('random', 1234), NCLS, precision, rate)
-        out, t0 = [], 0
-        for T in CALLS:
-            out.append(rec.process(cut(x, rate, t0, t0 + T)))
-            t0 += T
-    finally:
-        oracle.set_jitter(0)
-    return x, out
-
-
-def out_stage_tap_sum(rate):
-    return srr.Stage(1, srr.ratio(rate), up=rate > 16000).abs_tap_sum()
-
-
-def check(got, want, precision, rate, what, jitter_want=None):
-    """prints the figures before it asserts; returns (max distance, share further than 1 LSB)"""
-    d = np.abs(got.astype(np.int32) - want.astype(np.int32))
-    share = float((d > 1).mean())
-    print('%s %s %d Hz: max distance %d LSB, share > 1 LSB %.3e' % (what, precision, rate, int(d.max()), share), end='')
-    if precision == 'fp32' or jitter_want is None:
-        print()
-        assert np.array_equal(got, want), what
-        return int(d.max()), share
-    bound = math.ceil(BF16_TOL * out_stage_tap_sum(rate)) + 1
-    jshare = float((np.abs(jitter_want.astype(np.int32) - want.astype(np.int32)) > 1).mean())
-    print(', bound %d LSB; jittered oracle misses %.3e -> allowed %.3e' % (bound, jshare, 4 * jshare))
-    assert d.max() <= bound, (what, int(d.max()), bound)
-    assert share <= 4 * jshare, (what, share, jshare)
-    return int(d.max()), share
+RATES = (8000, 32000, 48000)
+RATE_PREC = [(r, p) for r in RATES for p in ('fp32', 'bf16')]
+# koala_amd/csrc/kns_kernels.h's static_asserts, as literals: the recipe's own constants are held to them, not the other way round
+FRAME = {8000: 128, 12000: 192, 24000: 384, 32000: 512, 48000: 768}
+DELAY = {8000: 176, 12000: 240, 24000: 456, 32000: 608, 48000: 912}
+TAIL = {8000: 288, 12000: 224, 24000: 240, 32000: 288, 48000: 384}
 
 
 # ------------------------------------------------------------------------------------------------ the recipe, call after call
@@ -111,11 +38,12 @@ def test_calls_of_mixed_lengths_are_the_recipe(rate, precision, kind, B, mode):
     x, want = expected(kind, precision, rate)
     jit = expected(kind, precision, rate, 1)[1] if precision == 'bf16' and kind == 'random' else None
     cls = classes(B)
-    kb = batch(model_file(kind if kind == 'unity' else 'random', 1234), B, TMAX, precision, rate)
+    kb = batch(model_file(kind if kind == 'unity' else 'random', 1234), B, TMAX[rate], precision, rate)
     try:
-        assert (kb.sample_rate, kb.frame_length, kb.delay_sample) == (rate, srr.frame_length(rate), srr.delay_sample(rate))
+        assert (kb.sample_rate, kb.frame_length, kb.delay_sample) == (rate, FRAME[rate], DELAY[rate])
+        assert kb.state_size == 10240 + TAIL[rate]
         got, t0 = [], 0
-        for T in CALLS:
+        for T in CALLS[rate]:
             got.append(call(kb, np.ascontiguousarray(cut(x, rate, t0, t0 + T)[cls]), mode))
             t0 += T
     finally:
@@ -127,11 +55,11 @@ def test_calls_of_mixed_lengths_are_the_recipe(rate, precision, kind, B, mode):
 @pytest.mark.parametrize('rate,precision', RATE_PREC)
 def test_min_gain_one_is_both_stages_around_a_pure_delay(random_model, rate, precision):
     x, want = expected('unity', precision, rate)
-    kb = batch(random_model, NCLS, TMAX, precision, rate)
+    kb = batch(random_model, NCLS, TMAX[rate], precision, rate)
     try:
         kb.set_min_gain(1.0)
         got, t0 = [], 0
-        for T in CALLS:
+        for T in CALLS[rate]:
             got.append(call(kb, cut(x, rate, t0, t0 + T), 'device'))
             t0 += T
     finally:
@@ -162,22 +90,23 @@ def test_whole_number_rates_at_workgroup_edges(random_model, rate, precision):
         kb.delete()
 
 
+@pytest.mark.parametrize('T', [8, 4])
 @pytest.mark.parametrize('precision', ['fp32', 'bf16'])
-def test_rate_16000_through_init_rate_is_the_plain_handle(random_model, precision):
-    x = np.ascontiguousarray(synth_streams(NCLS, 9, seed=3))
-    plain = koala_amd.create_batch('key', NCLS, 8, precision, model_path=random_model)
-    other = koala_amd.create_batch('key', NCLS, 8, precision, model_path=random_model)
+def test_rate_16000_through_init_rate_is_the_plain_handle(random_model, precision, T):
+    x = np.ascontiguousarray(synth_streams(NCLS, T + 1, seed=3))
+    plain = koala_amd.create_batch('key', NCLS, T, precision, model_path=random_model)
+    other = koala_amd.create_batch('key', NCLS, T, precision, model_path=random_model)
     try:
         lib = other._lib
         lib.pv_koala_batch_init_rate.argtypes = [ctypes.c_char_p] * 3 + [ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_void_p)]
         lib.pv_koala_batch_init_rate.restype = ctypes.c_int
         h = ctypes.c_void_p()
-        assert lib.pv_koala_batch_init_rate(b'key', random_model.encode(), b'best', NCLS, 8, 1 if precision == 'bf16' else 0, 16000,
+        assert lib.pv_koala_batch_init_rate(b'key', random_model.encode(), b'best', NCLS, T, 1 if precision == 'bf16' else 0, 16000,
                                             ctypes.byref(h)) == 0
         lib.pv_koala_batch_delete(other._handle)
         other._handle = h  # (the Python class on the handle pv_koala_batch_init_rate made)
-        assert other.state_size == plain.state_size
-        for a, b in ((0, 8), (8, 9)):
+        assert other.state_size == plain.state_size == 10240 and (other.frame_length, other.delay_sample) == (256, 256)
+        for a, b in ((0, T), (T, T + 1)):
             xa = np.ascontiguousarray(x[:, a * 256:b * 256])
             assert np.array_equal(plain.process(xa), other.process(xa))
         ra, rb = plain.export_state(), other.export_state()
@@ -191,9 +120,9 @@ def test_rate_16000_through_init_rate_is_the_plain_handle(random_model, precisio
 # ------------------------------------------------------------------------------------------------ resets
 
 @pytest.mark.parametrize('B,mode', [(NCLS, 'host'), (832, 'device')])
-@pytest.mark.parametrize('rate', srr.RATES)
+@pytest.mark.parametrize('rate', RATES)
 def test_every_kind_of_reset_is_a_fresh_stream(random_model, rate, B, mode):
-    T = 6
+    T = {8000: 6, 12000: 5, 24000: 5, 32000: 6, 48000: 6}[rate]
     x = signal(rate, 3 * T, seed=21)
     cls = classes(B)
     rec = srr.Recipe(random_model, NCLS, 'fp32', rate)
@@ -203,7 +132,8 @@ def test_every_kind_of_reset_is_a_fresh_stream(random_model, rate, B, mode):
         assert np.array_equal(call(kb, x0[cls], mode), rec.process(x0)[cls])
         # per-frame resets: frame 0, adjacent frames, a frame t > 0, the last frame
         reset = np.zeros((NCLS, T), np.uint8)
-        reset[0, 0] = reset[1, 2] = reset[1, 3] = reset[2, T - 1] = reset[3, 1] = 1
+        for b, t in ((0, 0), (1, 2), (1, 3), (2, 5), (3, 1)) if T == 6 else ((0, 0), (1, 2), (2, 4), (3, 1), (3, 2)):
+            reset[b, t] = 1
         got = call(kb, x1[cls], mode, reset=np.ascontiguousarray(reset[cls]))
         assert np.array_equal(got, rec.process_resets(x1, reset)[cls])
         # a masked reset, then a full one
@@ -213,17 +143,17 @@ def test_every_kind_of_reset_is_a_fresh_stream(random_model, rate, B, mode):
         rec.reset(rows)
         assert np.array_equal(call(kb, x2[cls], mode), rec.process(x2)[cls])
         kb.reset()
-        fresh = srr.Recipe(random_model, NCLS, 'fp32', rate)
-        assert np.array_equal(call(kb, x0[cls], mode), fresh.process(x0)[cls])
-        # frame 0 only (the reset kernel in front of the call) == the same fresh streams again
+        fresh = srr.Recipe(random_model, NCLS, 'fp32', rate).process(x0)[cls]
+        assert np.array_equal(call(kb, x0[cls], mode), fresh)
+        # frame 0 of every stream (the reset kernel in front of the call) == the same fresh streams again
         r0 = np.zeros((B, T), np.uint8)
         r0[:, 0] = 1
-        assert np.array_equal(call(kb, x0[cls], mode, reset=r0), srr.Recipe(random_model, NCLS, 'fp32', rate).process(x0)[cls])
+        assert np.array_equal(call(kb, x0[cls], mode, reset=r0), fresh)
     finally:
         kb.delete()
 
 
-@pytest.mark.parametrize('rate', srr.RATES)
+@pytest.mark.parametrize('rate', RATES)
 def test_per_frame_resets_after_frame_0_stay_refused_for_a_five_frame_front_end(random5_model, rate):
     T = 4
     x = signal(rate, 2 * T, seed=23)
@@ -248,10 +178,10 @@ def test_per_frame_resets_after_frame_0_stay_refused_for_a_five_frame_front_end(
 
 @pytest.mark.parametrize('rate,precision', RATE_PREC)
 def test_a_held_stream_is_not_advanced(random_model, rate, precision):
-    T = 5
+    T = {8000: 5, 12000: 3, 24000: 3, 32000: 5, 48000: 5}[rate]
     x = signal(rate, 3 * T, seed=31)
     x0, x1, x2 = (cut(x, rate, i * T, (i + 1) * T) for i in range(3))
-    a, b = batch(random_model, NCLS, T, precision, rate), batch(random_model, NCLS, T, precision, rate)
+    a, b, c = (batch(random_model, NCLS, T, precision, rate) for _ in range(3))
     try:
         hold = np.zeros(NCLS, np.uint8)
         hold[[1, 3]] = 1
@@ -260,26 +190,25 @@ def test_a_held_stream_is_not_advanced(random_model, rate, precision):
         before = a.export_state()
         got = call(a, x1, 'device', hold=hold)
         after = a.export_state()
-        assert np.array_equal(before[hold != 0], after[hold != 0]) and not np.array_equal(before[hold == 0], after[hold == 0])
+        # bit for bit what it was, converters included (the record's tail); the others moved
+        assert np.array_equal(before[hold != 0], after[hold != 0]) and before[hold != 0][:, 10240:].any()
+        assert not np.array_equal(before[hold == 0], after[hold == 0])
+        assert not np.array_equal(before[hold == 0][:, 10240:], after[hold == 0][:, 10240:])
         full = b.process(x1)
         assert np.array_equal(got[hold == 0], full[hold == 0])
-        # the held streams continue as if the call had not happened: b's streams 1 and 3 see x2 right after x0
-        c = batch(random_model, NCLS, T, precision, rate)
-        try:
-            c.process(x0)
-            want_held = c.process(x2)
-        finally:
-            c.delete()
+        # the held streams continue as if the call had not happened: they see x2 right after x0
+        c.process(x0)
+        want_held = c.process(x2)
         got2, full2 = a.process(x2), b.process(x2)
         assert np.array_equal(got2[hold != 0], want_held[hold != 0]) and np.array_equal(got2[hold == 0], full2[hold == 0])
     finally:
-        a.delete()
-        b.delete()
+        for h in (a, b, c):
+            h.delete()
 
 
 @pytest.mark.parametrize('rate,precision', RATE_PREC)
 def test_records_carry_the_converters_between_handles(random_model, rate, precision):
-    T = 4
+    T = {8000: 4, 12000: 3, 24000: 3, 32000: 4, 48000: 4}[rate]
     x = signal(rate, 2 * T, seed=37)
     x0, x1 = cut(x, rate, 0, T), cut(x, rate, T, 2 * T)
     rec = srr.Recipe(random_model, NCLS, precision, rate)
@@ -290,8 +219,7 @@ def test_records_carry_the_converters_between_handles(random_model, rate, precis
         if precision == 'fp32':
             assert np.array_equal(got0, want0)
         blobs = a.export_state()
-        R = srr.ratio(rate)
-        assert a.state_size == 10240 + (288 if R == 2 else 384) and blobs.shape == (NCLS, a.state_size)
+        assert a.state_size == 10240 + TAIL[rate] and blobs.shape == (NCLS, a.state_size)
         hdr = blobs[:, :32].copy().view(np.uint32)
         assert (hdr[:, 1] == 2).all() and (hdr[:, 6] == rate).all() and not hdr[:, 7].any()
         rs = blobs[:, 10240:]
@@ -341,12 +269,12 @@ def test_records_do_not_cross_rates_or_versions(random_model):
 # ------------------------------------------------------------------------------------------------ the frame report, the asynchronous refusal
 
 @pytest.mark.parametrize('mode', ['host', 'device'])
-@pytest.mark.parametrize('rate', srr.RATES)
-def test_the_frame_report_is_the_inner_16_khz_streams(random_model, rate, mode):
-    T = 6
+@pytest.mark.parametrize('rate,precision', [pytest.param(r, 'fp32', id=str(r)) for r in RATES])
+def test_the_frame_report_is_the_inner_16_khz_streams(random_model, rate, precision, mode):
+    T = {8000: 6, 12000: 3, 24000: 3, 32000: 6, 48000: 6}[rate]
     x = signal(rate, 2 * T, seed=43)
     rec = srr.Recipe(None, NCLS, 'fp32', rate)
-    kb, inner = batch(random_model, NCLS, T, 'fp32', rate), batch(random_model, NCLS, T, 'fp32', 16000)
+    kb, inner = batch(random_model, NCLS, T, precision, rate), batch(random_model, NCLS, T, precision, 16000)
     try:
         gains = np.linspace(0.0, 0.5, NCLS).astype(np.float32)
         kb.set_min_gain(gains)
@@ -362,8 +290,8 @@ def test_the_frame_report_is_the_inner_16_khz_streams(random_model, rate, mode):
         inner.delete()
 
 
-def test_asynchronous_calls_are_refused_and_change_nothing(random_model):
-    T, rate = 2, 8000
+def test_asynchronous_calls_are_refused_and_change_nothing(random_model, rate=8000):
+    T = 2
     x = signal(rate, 2 * T, seed=47)
     a, b = batch(random_model, NCLS, T, 'fp32', rate), batch(random_model, NCLS, T, 'fp32', rate)
     try:
@@ -378,6 +306,7 @@ def test_asynchronous_calls_are_refused_and_change_nothing(random_model):
             a.process_async_call(pin, pout)
         a.synchronize()
         assert (pout == -7).all()
+        assert np.array_equal(a.export_state(), b.export_state())
         assert np.array_equal(a.process(x1), b.process(x1))
     finally:
         a.delete()

@@ -1,9 +1,9 @@
 """
-Batch handles at 12 and 24 kHz (include/pv_koala_batch.h: pv_koala_batch_init_rate; DESIGN.md section 2, third extension, generalised)
-without a GPU: the general stage "up U, down D" of tests/rational_rate_recipe.py against the whole-number stages it generalises and against
-a float64 restatement with no fixed order, the recipe against itself in other cuts and across a record, the refusals, the gfx950 build of
-the new kernels of koala_amd/csrc/kns_resample.hip, and the constants through the C ABI under AddressSanitizer +
-UndefinedBehaviorSanitizer (tests/abi_rational_rate/driver.cpp).  tests/test_gpu_rational_rate.py checks the samples on the GPU.
+The general stage "up U, down D" of the sample-rate handles (third extension, generalised) without a GPU: the stage of
+tests/sample_rate_recipe.py against the interpolator and the decimator it generalises, restated here on their own, and against a float64
+restatement with no fixed order; the gfx950 build of the rational kernels of koala_amd/csrc/kns_resample.hip; and the constants of 12 and
+24 kHz through the C ABI under AddressSanitizer + UndefinedBehaviorSanitizer (tests/abi_rational_rate/driver.cpp).
+tests/test_sample_rate.py holds the recipe's own tests, tests/test_gpu_rational_rate.py checks the samples on the GPU.
 """
 import os
 import re
@@ -14,10 +14,8 @@ import sys
 import numpy as np
 import pytest
 
-import koala_amd
-import rational_rate_recipe as rrr
 import sample_rate_recipe as srr
-from conftest import ROOT, model_file, synth_streams
+from conftest import ROOT, model_file
 
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
@@ -28,26 +26,53 @@ def full_range(rows, n, seed):
     return np.random.default_rng(seed).integers(-32768, 32768, size=(rows, n)).astype(np.int16)
 
 
+def interpolate(hist, a, R, hi):
+    """the interpolator as DESIGN.md states it on its own: hist int16 [n, 48] (the samples in front of a), a int16 [n, N] -> int16 [n, R N]"""
+    n, N = a.shape
+    x = np.concatenate([hist, a], axis=1).astype(np.float32)
+    out = np.empty((n, N * R), np.int16)
+    for p in range(R):
+        acc = np.zeros((n, N), np.float32)
+        j = 0
+        while p + R * j <= 48 * R:
+            acc = srr.fma32(np.full((n, N), hi[p + R * j], np.float32), x[:, 48 - j:48 - j + N], acc)
+            j += 1
+        out[:, p::R] = srr.to_pcm(acc)
+    return out
+
+
+def decimate(hist, a, R, hd):
+    """the decimator as DESIGN.md states it on its own: hist int16 [n, 48 R], a int16 [n, R N] -> int16 [n, N]"""
+    n, M = a.shape
+    N, H = M // R, 48 * R
+    x = np.concatenate([hist, a], axis=1).astype(np.float32)
+    acc = np.zeros((n, N), np.float32)
+    for i in range(H + 1):
+        acc = srr.fma32(np.full((n, N), hd[i], np.float32), x[:, H - i:H - i + M:R], acc)
+    return srr.to_pcm(acc)
+
+
 @pytest.mark.parametrize('R', [2, 3])
 def test_general_stage_is_the_interpolator_and_the_decimator(R):
-    g, hd, hi = srr.prototype(R)
-    assert np.array_equal(rrr.table(R, R), hi) and np.array_equal(rrr.table(R, 1), hd)
+    g = srr.prototype(R)
+    hd, hi = g.astype(np.float32), (R * g).astype(np.float32)
+    assert np.array_equal(srr.table(R, R), hi) and np.array_equal(srr.table(R, 1), hd)
     a = full_range(3, 6 * 37 * R, seed=R)  # (a length both stages take: a multiple of R)
     h_up, h_down = full_range(3, 48, seed=10 + R), full_range(3, 48 * R, seed=20 + R)
-    assert rrr.hist_length(R, R) == 48 and rrr.hist_length(R, 1) == 48 * R
-    assert np.array_equal(rrr.stage(h_up, a, R, 1, hi), srr.interpolate(h_up, a, R, hi))
-    assert np.array_equal(rrr.stage(h_down, a, 1, R, hd), srr.decimate(h_down, a, R, hd))
+    assert srr.hist_length(R, R) == 48 and srr.hist_length(R, 1) == 48 * R
+    assert np.array_equal(srr.stage(h_up, a, R, 1, hi), interpolate(h_up, a, R, hi))
+    assert np.array_equal(srr.stage(h_down, a, 1, R, hd), decimate(h_down, a, R, hd))
 
 
-@pytest.mark.parametrize('U,D', PAIRS)
+@pytest.mark.parametrize('U,D', PAIRS + [(2, 1), (1, 2), (3, 1), (1, 3)])
 def test_stage_is_within_one_lsb_of_a_float64_convolution(U, D):
     """zero-stuff, np.convolve with U g, every D-th sample, in double and in no fixed order.  At most 97 float32 fmas on values up to 2^15
     accumulate well under 0.5 LSB before the single rounding to int16, so the recipe is within 1 LSB of the unrounded double value."""
     K = max(U, D)
-    g = srr.prototype(K)[0]
+    g = srr.prototype(K)
     Q = 200
     a = full_range(2, D * Q, seed=7 * U + D)
-    got = rrr.stage(np.zeros((2, rrr.hist_length(K, U)), np.int16), a, U, D, rrr.table(K, U))
+    got = srr.stage(np.zeros((2, srr.hist_length(K, U)), np.int16), a, U, D, srr.table(K, U))
     assert got.shape == (2, U * Q)
     worst = 0.0
     for r in range(2):
@@ -57,91 +82,6 @@ def test_stage_is_within_one_lsb_of_a_float64_convolution(U, D):
         worst = max(worst, float(np.abs(got[r].astype(np.float64) - ref).max()))
     print('(%d, %d): largest distance from the float64 convolution %.4f LSB' % (U, D, worst))
     assert worst <= 1.0
-
-
-def test_constants_of_the_recipe_are_the_specs():
-    assert [rrr.common_k(r) for r in rrr.RATES] == [4, 3]
-    assert [rrr.frame_length(r) for r in rrr.RATES] == [192, 384] and [rrr.delay_sample(r) for r in rrr.RATES] == [240, 456]
-    for rate, hists, tail in ((12000, (48, 64), 224), (24000, (72, 48), 240)):
-        rec = rrr.Recipe(None, 1, 'fp32', rate)
-        assert (rec.s_in.hist.shape[1], rec.s_out.hist.shape[1]) == hists and rec.rs_state().shape == (1, tail)
-    # at K = 3 the prototype is the 48 kHz handle's, value for value
-    assert np.array_equal(rrr.table(3, 1), srr.prototype(3)[1]) and np.array_equal(rrr.table(3, 3), srr.prototype(3)[2])
-
-
-@pytest.mark.parametrize('rate', rrr.RATES)
-def test_a_1_khz_tone_keeps_its_level_and_shows_the_stated_delay(rate):
-    fl, N = rrr.frame_length(rate), 16 * rrr.frame_length(rate)
-    x = np.round(8000.0 * np.sin(2 * np.pi * 1000.0 * np.arange(N) / rate)).astype(np.int16).reshape(1, N)
-    z = rrr.Recipe(None, 1, 'fp32', rate).process(x)[0].astype(np.float64)
-    d = rrr.delay_sample(rate)
-    xs = x[0].astype(np.float64)
-    dist = [float(np.sum((z - np.concatenate([np.zeros(k), xs[:N - k]])) ** 2)) for k in range(d - 40, d + 41)]
-    assert int(np.argmin(dist)) == 40, (rate, int(np.argmin(dist)) + d - 40)
-    steady = slice(d + 2 * fl, N)
-    level = 20 * np.log10(np.sqrt(np.mean(z[steady] ** 2)) / np.sqrt(np.mean(xs[2 * fl:N - d] ** 2)))
-    print('%d Hz: delay %d samples, level %+.4f dB' % (rate, d, level))
-    assert abs(level) <= 0.1 and not z[:fl].any()
-
-
-def test_python_refuses_other_rates_and_takes_the_two_new_ones(random_model, monkeypatch):
-    for bad in (44100, 96000, 16001, 0):
-        with pytest.raises(koala_amd.KoalaInvalidArgumentError, match='sample_rate'):
-            koala_amd.create_batch('key', 2, 1, 'fp32', model_path=random_model, sample_rate=bad)
-    # create_batch's own check takes 12 000 and 24 000: the refusal, if any, comes from further on (the library: a GPU is needed there)
-    import koala_amd._batch as kb
-
-    class Reached(Exception):
-        pass
-
-    def stop(*a, **k):
-        raise Reached()
-    monkeypatch.setattr(kb, 'load_library', stop)
-    for rate in rrr.RATES:
-        with pytest.raises(Reached):
-            koala_amd.create_batch('key', 2, 1, 'fp32', model_path=random_model, sample_rate=rate)
-    with pytest.raises(koala_amd.KoalaInvalidArgumentError):
-        koala_amd.create_batch('key', 2, 1, 'fp32', model_path=random_model, sample_rate=44100)
-
-
-@pytest.mark.parametrize('rate', rrr.RATES)
-def test_recipe_in_calls_of_1_2_and_5_frames_is_the_recipe_in_one_call(random_model, rate):
-    n, T, fl = 2, 8, rrr.frame_length(rate)
-    x = np.ascontiguousarray(synth_streams(n, T * fl // 256 + 1, seed=5)[:, :T * fl])  # (any int16 signal serves: samples at `rate`)
-    one = rrr.Recipe(random_model, n, 'fp32', rate).process(x)
-    for cuts in ([1, 2, 5], [5, 2, 1], [1] * T):
-        r, out, t0 = rrr.Recipe(random_model, n, 'fp32', rate), [], 0
-        for c in cuts:
-            out.append(r.process(np.ascontiguousarray(x[:, t0 * fl:(t0 + c) * fl])))
-            t0 += c
-        assert t0 == T and np.array_equal(np.concatenate(out, axis=1), one), (rate, cuts)
-    # per-frame resets: the call cut at its frames == fresh streams from there
-    reset = np.zeros((n, T), np.uint8)
-    reset[1, 3] = 1
-    got = rrr.Recipe(random_model, n, 'fp32', rate).process_resets(x, reset)
-    fresh = rrr.Recipe(random_model, n, 'fp32', rate).process(np.ascontiguousarray(x[:, 3 * fl:]))
-    assert np.array_equal(got[0], one[0]) and np.array_equal(got[1, :3 * fl], one[1, :3 * fl]) and np.array_equal(got[1, 3 * fl:], fresh[1])
-
-
-@pytest.mark.parametrize('rate', rrr.RATES)
-def test_a_record_taken_mid_stream_continues_in_a_fresh_recipe(rate):
-    n, T, fl = 3, 6, rrr.frame_length(rate)
-    x = full_range(n, T * fl, seed=rate)
-    a = rrr.Recipe(None, n, 'fp32', rate)
-    one = rrr.Recipe(None, n, 'fp32', rate).process(x)
-    head = a.process(np.ascontiguousarray(x[:, :2 * fl]))
-    blob, inner = a.rs_state(), a.o.prev.copy()  # (the stages' part of the record, and the inner engine's: here one frame of samples)
-    assert blob.shape[1] == {12000: 224, 24000: 240}[rate] and blob.any()
-    b = rrr.Recipe(None, n, 'fp32', rate)
-    b.set_rs_state(blob)
-    b.o.prev = inner
-    assert np.array_equal(b.rs_state(), blob)
-    tail = b.process(np.ascontiguousarray(x[:, 2 * fl:]))
-    assert np.array_equal(np.concatenate([head, tail], axis=1), one)
-    # and without the stages' part it does not
-    c = rrr.Recipe(None, n, 'fp32', rate)
-    c.o.prev = inner
-    assert not np.array_equal(c.process(np.ascontiguousarray(x[:, 2 * fl:])), tail)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not available')
