@@ -335,6 +335,40 @@ PV_API pv_status_t pv_koala_batch_init_config(const char *access_key, const char
                                               const pv_koala_batch_config_t *config, pv_koala_batch_t **object);
 PV_API pv_status_t pv_koala_batch_sample_format(const pv_koala_batch_t *object, int32_t *sample_format);
 
+/* CHANNELS: batch handles whose `pcm` and `enhanced` hold several streams interleaved, split and joined on the device.  Stereo and
+ * multi-microphone audio arrives interleaved (L R L R ...) from WebRTC, Opus and WAV.  `channels` is the MEMORY LAYOUT of `pcm` and
+ * `enhanced` and nothing else; it sits at the same boundary as the sample format, outside it (seventh extension).
+ * A handle with channels = C (2 ... 8) and num_streams = B has G = B / C groups; stream s = g * C + c is channel c of group g -- an
+ * ordinary, independent stream of the engine, with the slot, the state and the record it has in a handle made without channels.
+ *   Layout.  Every `pcm` and `enhanced` is [G][n * C] elements of the handle's sample format, n = a stream's row length in the handle
+ *     without channels (num_frames * frame_length, or max_samples of a packet call): sample i of stream g * C + c is element
+ *     [g][i * C + c].
+ *   Output.  Exactly interleave(the handle without channels(deinterleave(pcm))), given the same per-stream arguments: every rate, frame
+ *     and packet handles, every format, both precisions.
+ *   Per-stream arguments stay per stream, [B], indexed by s: reset[B][T], hold[B], the streams of pv_koala_batch_set_min_gain,
+ *     report[B][T][4], counts[B], restart[B], frames[B], stream lists and records.
+ *   Configuration, not stream state: state_size, the record's version and bytes are unchanged, and a record moves between handles of any
+ *     channel count that match as they must today.  pv_koala_batch_delay_sample and _frame_length are in samples per channel, unchanged;
+ *     pv_koala_batch_num_streams stays B.
+ *   Packet calls.  The streams of a group share a row, so `counts` must be equal within a group: otherwise PV_STATUS_INVALID_ARGUMENT with a
+ *     message that names the group and the two streams, nothing processed, state unchanged.  `restart` may differ within a group.  The call
+ *     writes group row g's first counts[g * C] * C elements and nothing behind them.
+ *   Held streams.  A held stream's elements of `enhanced` are unspecified, as its row is today; its state is untouched, bit for bit.
+ *   Pointers.  `pcm` and `enhanced` may overlap in any way, with host and with device pointers: the input is consumed before the output is
+ *     written.  Host pointers: one copy in, the device route, one copy out, then synchronise.  Device pointers stay device pointers,
+ *     enqueued without a host wait, aligned to the element only.
+ * pv_koala_batch_init_channels is pv_koala_batch_init_config with that one more argument (the struct does not grow).  channels == 1 is
+ * exactly pv_koala_batch_init_config: the same handle, routes and bits.  PV_STATUS_INVALID_ARGUMENT with a message that names `channels`:
+ * channels outside [1, 8], and num_streams that is not a multiple of channels; whatever pv_koala_batch_init_config refuses stays refused
+ * with its own message.  The asynchronous entry points, and `asynchronous != 0` in pv_koala_batch_process_call, are refused with
+ * PV_STATUS_INVALID_ARGUMENT on a handle whose channels is not 1 (nothing processed).
+ * NOT PROVIDED: linked-stereo processing (one mask for all channels of a group: the channels are independent streams), and a planar /
+ * interleaved conversion for the single-stream ABI (pv_koala.h is one channel only). */
+PV_API pv_status_t pv_koala_batch_init_channels(const char *access_key, const char *model_path, const char *device,
+                                                const pv_koala_batch_config_t *config, int32_t channels,
+                                                pv_koala_batch_t **object);
+PV_API pv_status_t pv_koala_batch_channels(const pv_koala_batch_t *object, int32_t *channels);
+
 PV_API pv_status_t pv_koala_batch_num_streams(const pv_koala_batch_t *object, int32_t *num_streams);
 PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, int32_t *delay_sample);
 

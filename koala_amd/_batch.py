@@ -12,6 +12,7 @@ import numpy as np
 
 from ._koala import (KoalaError, KoalaInvalidArgumentError, KoalaIOError, PicovoiceStatuses, attenuation_limit_to_gain, load_library,
                      raise_status)
+from .channels import MAX_CHANNELS
 from .formats import DTYPES, FORMATS
 from .packets import FRACTIONAL_UP, inner_samples
 
@@ -40,9 +41,11 @@ class BatchConfig(Structure):
 
 class KoalaBatch(object):
     sample_format, _dtype, _dtype_name = 's16', np.int16, 'int16'  # (what a handle is unless it was made with a sample format)
+    channels = 1  # (... or with channels)
 
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
-                 max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0, sample_format: str = 's16') -> None:
+                 max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0, sample_format: str = 's16',
+                 channels: int = 1) -> None:
         """`sample_rate`: 44100 or 22050 Hz make a packet handle around fractional converters (`packet_samples` > 0 is required; there is
         no frame length, `frame_length` is None, and stream records and the asynchronous calls are refused); otherwise
         8000, 12000, 16000, 24000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
@@ -54,7 +57,14 @@ class KoalaBatch(object):
         `sample_format`: 's16' (default), 'f32', 'ulaw' or 'alaw' -- what every array of samples that goes in or comes out holds: np.int16,
         np.float32 in [-1, 1) or np.uint8 G.711 bytes (koala_amd.formats has the codecs).  The handle converts on the device around the
         unchanged int16 call (pv_koala_batch_init_config): its result is formats.encode(the 's16' handle(formats.decode(x))), delay, frame
-        length and stream records are the 's16' handle's, and the asynchronous calls are refused.  An array of another dtype is refused."""
+        length and stream records are the 's16' handle's, and the asynchronous calls are refused.  An array of another dtype is refused.
+        `channels`: 1 (default) ... 8 -- the memory layout of every array of samples that goes in or comes out of `process`, `process_resets`,
+        `process_hold`, `process_call` and `process_packets`: [num_streams / channels, n * channels] (or [.., n, channels], the same memory),
+        in which sample i of stream g * channels + c is element [g, i * channels + c] (pv_koala_batch_init_channels; koala_amd.channels has
+        the layout in numpy).  The handle splits and joins on the device around the unchanged call: its result is
+        channels.interleave(the handle without channels(channels.deinterleave(x))).  Everything per stream -- reset, hold, counts, restart,
+        report, gains, records -- stays [num_streams], a packet call's counts must be equal within a group, the device-pointer methods take
+        the same layout, and the asynchronous calls are refused.  Linked-stereo processing (one mask for a group) is not provided."""
         if not isinstance(access_key, str) or len(access_key) == 0:
             raise KoalaInvalidArgumentError("`access_key` should be a non-empty string.")
         if not os.path.exists(model_path):
@@ -70,6 +80,12 @@ class KoalaBatch(object):
             raise KoalaInvalidArgumentError("`sample_rate` %d needs `packet_samples` > 0: a handle at this rate must be a packet handle." % sample_rate)
         if not isinstance(sample_format, str) or sample_format not in FORMATS:
             raise KoalaInvalidArgumentError("`sample_format` should be `s16`, `f32`, `ulaw` or `alaw`.")
+        if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= MAX_CHANNELS:
+            raise KoalaInvalidArgumentError("`channels` should be an integer in [1, %d]." % MAX_CHANNELS)
+        if not isinstance(num_streams, int) or num_streams % channels:
+            raise KoalaInvalidArgumentError("`num_streams` %r is not a multiple of `channels` %d: stream g * channels + c is channel c of group g."
+                                            % (num_streams, channels))
+        self.channels = channels
         self.sample_format = sample_format
         self._dtype = DTYPES[sample_format]
         self._dtype_name = np.dtype(self._dtype).name
@@ -111,12 +127,18 @@ class KoalaBatch(object):
         if packet_samples:
             lib.pv_koala_batch_process_packets.argtypes = [c_void_p, POINTER(BatchPackets)]
             lib.pv_koala_batch_process_packets.restype = PicovoiceStatuses
-        if sample_format != 's16' or fractional:  # (any other 's16' handle is made as it has always been: init_config would return the same handle)
+        if sample_format != 's16' or fractional or channels != 1:  # (any other 's16' handle is made as it has always been: init_config would return the same handle)
             lib.pv_koala_batch_init_config.argtypes = [c_char_p, c_char_p, c_char_p, POINTER(BatchConfig), POINTER(c_void_p)]
             lib.pv_koala_batch_init_config.restype = PicovoiceStatuses
             config = BatchConfig(sizeof(BatchConfig), num_streams, max_frames_per_call, packet_samples, prec, sample_rate,
                                  FORMATS.index(sample_format))
-            status = lib.pv_koala_batch_init_config(access_key.encode(), model_path.encode(), device.encode(), byref(config), byref(self._handle))
+            if channels != 1:
+                lib.pv_koala_batch_init_channels.argtypes = [c_char_p, c_char_p, c_char_p, POINTER(BatchConfig), c_int32, POINTER(c_void_p)]
+                lib.pv_koala_batch_init_channels.restype = PicovoiceStatuses
+                status = lib.pv_koala_batch_init_channels(access_key.encode(), model_path.encode(), device.encode(), byref(config), channels,
+                                                          byref(self._handle))
+            else:
+                status = lib.pv_koala_batch_init_config(access_key.encode(), model_path.encode(), device.encode(), byref(config), byref(self._handle))
             if fractional:  # (the inner 16 kHz packet handle's: it takes the most inner samples a call can yield)
                 max_frames_per_call = -(-inner_samples(packet_samples, sample_rate) // 256)
             elif packet_samples:
@@ -170,15 +192,28 @@ class KoalaBatch(object):
             raise KoalaInvalidArgumentError("expected a %s array: the handle's sample format is `%s`" % (self._dtype_name, self.sample_format))
         return np.ascontiguousarray(pcm, dtype=self._dtype)
 
+    def _rows(self, pcm):
+        """(the caller's samples as [num_streams, n] rows of memory, the caller's shape).  On a handle with channels the array is
+        [G, n * C] or [G, n, C] and the rows are that memory cut into num_streams equal parts -- the library reads it interleaved --
+        so the checks and sizes of every method are those of the handle without channels."""
+        a = self._samples(pcm)
+        if self.channels == 1:
+            return a, a.shape
+        C, G = self.channels, self.num_streams // self.channels
+        if not ((a.ndim == 2 and a.shape[0] == G and a.shape[1] % C == 0) or (a.ndim == 3 and a.shape[0] == G and a.shape[2] == C)):
+            raise KoalaInvalidArgumentError("expected %s array of shape [%d, n*%d] or [%d, n, %d]: the handle's `channels` is %d"
+                                            % (self._dtype_name, G, C, G, C, C))
+        return a.reshape(self.num_streams, -1), a.shape
+
     def process(self, pcm: np.ndarray) -> np.ndarray:
         """pcm: int16 [num_streams, T*frame_length] in host memory -> enhanced, same shape (synchronous)."""
-        a = self._samples(pcm)
+        a, shape = self._rows(pcm)
         if a.ndim != 2 or a.shape[0] != self.num_streams or a.shape[1] % self.frame_length:
             raise KoalaInvalidArgumentError("expected %s array of shape [%d, T*%d]" % (self._dtype_name, self.num_streams, self.frame_length))
         out = np.empty_like(a)
         self._check(self._lib.pv_koala_batch_process_chunk(self._handle, a.shape[1] // self.frame_length,
                                                            a.ctypes.data, out.ctypes.data), 'Processing failed')
-        return out
+        return out.reshape(shape)
 
     def alloc_host(self, num_frames: int) -> np.ndarray:
         """[num_streams, num_frames*frame_length] of the handle's dtype (int16 unless it has a sample format) in page-locked host memory (freed by `delete()`): `process()` on such arrays
@@ -235,7 +270,7 @@ class KoalaBatch(object):
     def process_resets(self, pcm: np.ndarray, reset: Optional[np.ndarray]) -> np.ndarray:
         """`process()` with per-frame stream resets: reset[b, t] != 0 restarts stream b from the fresh state right before frame t of this
         call (include/pv_koala_batch.h, pv_koala_batch_process_chunk_resets).  `reset`: [num_streams, T] (None: no resets)."""
-        a = self._samples(pcm)
+        a, shape = self._rows(pcm)
         if a.ndim != 2 or a.shape[0] != self.num_streams or a.shape[1] % self.frame_length:
             raise KoalaInvalidArgumentError("expected %s array of shape [%d, T*%d]" % (self._dtype_name, self.num_streams, self.frame_length))
         T = a.shape[1] // self.frame_length
@@ -243,7 +278,7 @@ class KoalaBatch(object):
         out = np.empty_like(a)
         self._check(self._lib.pv_koala_batch_process_chunk_resets(self._handle, T, a.ctypes.data, out.ctypes.data, mp),
                     'Processing failed')
-        return out
+        return out.reshape(shape)
 
     def process_async_resets(self, pcm: np.ndarray, enhanced: np.ndarray, reset: Optional[np.ndarray]) -> None:
         """`process_async()` with per-frame stream resets ([num_streams, T]); the mask is copied before the call returns."""
@@ -291,12 +326,12 @@ class KoalaBatch(object):
         FRAME REPORT.  Returns `enhanced`, or `(enhanced, report)` when `report` is true: float32 [num_streams, T, 4] = e_in, e_out,
         mask_sum, 0 of every stream and frame (include/pv_koala_batch.h; koala_amd.report turns rows into dBFS, dB of suppression and
         mean gain).  The samples do not depend on whether the report is asked for."""
-        a = self._samples(pcm)
+        a, shape = self._rows(pcm)
         T = self._audio(a)
         out = np.empty_like(a)
         rep = np.empty((self.num_streams, T, 4), np.float32) if report else None
         self._call(T, a.ctypes.data, out.ctypes.data, reset, hold, rep.ctypes.data if report else None, False)
-        return (out, rep) if report else out
+        return (out.reshape(shape), rep) if report else out.reshape(shape)
 
     def process_device_call(self, num_frames: int, pcm_ptr: int, enhanced_ptr: int, report_ptr: int = 0, reset: Optional[np.ndarray] = None,
                             hold: Optional[np.ndarray] = None) -> None:
@@ -367,14 +402,14 @@ class KoalaBatch(object):
     def process_hold(self, pcm: np.ndarray, hold: Optional[np.ndarray]) -> np.ndarray:
         """`process()` in which the streams with hold[b] != 0 are not advanced (their state stays bit for bit what it was; their rows of
         the result are unspecified).  `hold`: [num_streams] (None: nobody)."""
-        a = self._samples(pcm)
+        a, shape = self._rows(pcm)
         if a.ndim != 2 or a.shape[0] != self.num_streams or a.shape[1] % self.frame_length:
             raise KoalaInvalidArgumentError("expected %s array of shape [%d, T*%d]" % (self._dtype_name, self.num_streams, self.frame_length))
         m, mp = self._hold_mask(hold)
         out = np.empty_like(a)
         self._check(self._lib.pv_koala_batch_process_chunk_hold(self._handle, a.shape[1] // self.frame_length, a.ctypes.data,
                                                                 out.ctypes.data, mp), 'Processing failed')
-        return out
+        return out.reshape(shape)
 
     def process_device_hold(self, num_frames: int, pcm_ptr: int, enhanced_ptr: int, hold: Optional[np.ndarray]) -> None:
         """`process_device()` with held streams: the host mask [num_streams] is read before the call returns, the work is enqueued on
@@ -404,18 +439,18 @@ class KoalaBatch(object):
         packet.  Returns `enhanced` (same shape; row b's first counts[b] samples are the stream's next output samples, the rest zeros),
         or `(enhanced, frames, report)` when `report` is true: frames int32 [num_streams] = the frames each stream completed in the call,
         report float32 [num_streams, max(frames), 4] with stream b's rows [0, frames[b]) filled."""
-        a = self._samples(pcm)
+        a, shape = self._rows(pcm)
         if a.ndim != 2 or a.shape[0] != self.num_streams or a.shape[1] < 1:
             raise KoalaInvalidArgumentError("expected %s array of shape [%d, max_samples]" % (self._dtype_name, self.num_streams))
         out = np.zeros_like(a)
         if not report:
             self._packets(a.shape[1], counts, a.ctypes.data, out.ctypes.data, restart, None, 0)
-            return out
+            return out.reshape(shape)
         # (a stream completes at most this many frames; at 44 100 / 22 050 Hz the rows are the inner 16 kHz stream's)
         rows = a.shape[1] // self.frame_length + 1 if self.frame_length else inner_samples(a.shape[1], self.sample_rate) // 256 + 1
         rep = np.zeros((self.num_streams, rows, 4), np.float32)
         frames = self._packets(a.shape[1], counts, a.ctypes.data, out.ctypes.data, restart, rep.ctypes.data, rows)
-        return out, frames, rep[:, :int(frames.max()) if frames.size else 0]
+        return out.reshape(shape), frames, rep[:, :int(frames.max()) if frames.size else 0]
 
     def process_device_packets(self, max_samples: int, counts, pcm_ptr: int, enhanced_ptr: int, restart=None, report_ptr: int = 0,
                                report_frames: int = 0) -> np.ndarray:

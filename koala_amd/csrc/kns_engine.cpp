@@ -2424,7 +2424,7 @@ Status Engine::process(const Call &c, std::string *err) {
         *err = "held streams are not combined with per-frame stream resets in one call.";
         return Status::kBadArgument;
     }
-    if (rate_ == kRate16k && fmt_ == kFmtS16) return process_frames(c, err);  // the plain handle
+    if (rate_ == kRate16k && fmt_ == kFmtS16 && ch_ == 1) return process_frames(c, err);  // the plain handle
     (void) hipSetDevice(device_);
     bool host, late = false;
     if (!call_on_host(c.pcm, c.out, c.report, &host, err)) return Status::kRuntime;
@@ -2442,9 +2442,18 @@ Status Engine::process(const Call &c, std::string *err) {
         dev.pcm = dev.out = (int16_t *) d_host_io_;
         if (c.report) dev.report = d_host_rep_;
     }
-    Call inner = dev;
     hipError_t e = hipSuccess;
-    if (fmt_ != kFmtS16) {
+    // channels, outermost: the call's interleaved elements are split into the rows d_ch_, on which everything below runs in place, and the
+    // rows are joined into the call's output last
+    const ChannelArgs split{dev.pcm, d_ch_, nullptr, (long long) c.T * rs_frame_length(rate_), B_ / ch_, ch_};
+    const ChannelArgs join{d_ch_, dev.out, nullptr, split.n, split.G, ch_};
+    if (ch_ > 1) {
+        dev.pcm = dev.out = (int16_t *) d_ch_;
+        launch_channels_split(sample_bytes(), split, stream_);
+        e = hipGetLastError();
+    }
+    Call inner = dev;
+    if (e == hipSuccess && fmt_ != kFmtS16) {
         inner.pcm = d_fmt_in_, inner.out = d_fmt_out_;
         launch_format_in(fmt_, FormatArgs{dev.pcm, d_fmt_in_, nullptr, (long long) n, 1}, stream_);
         e = hipGetLastError();
@@ -2455,6 +2464,10 @@ Status Engine::process(const Call &c, std::string *err) {
     }
     if (e == hipSuccess && fmt_ != kFmtS16) {
         launch_format_out(fmt_, FormatArgs{d_fmt_out_, dev.out, nullptr, (long long) n, 1}, stream_);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && ch_ > 1) {
+        launch_channels_join(sample_bytes(), join, stream_);
         e = hipGetLastError();
     }
     if (e != hipSuccess) {
@@ -2541,12 +2554,13 @@ PacketStateArgs Engine::packet_state_args() const {
 // (d_pk_tab_ starts with the counts).  A call without a sample (restarts only) moves and converts no samples.  Host pointers: the staging
 // stands in for the caller's device memory, and of what comes back only a row's first counts[b] elements and a stream's first k_b report
 // rows are copied on: the rest of the caller's bytes stay.
-Status Engine::run_packets(const PacketCall &c, std::string *err) { return fr_rate_ ? run_fractional(c, err) : run_packet_call(c, fmt_, err); }
+Status Engine::run_packets(const PacketCall &c, std::string *err) { return fr_rate_ ? run_fractional(c, err) : run_packet_call(c, fmt_, ch_, err); }
 
 // ---- what the two packet calls (run_packet_call, run_fractional) share: the refusals, and the caller's side of the call
 
-// `max_samples` and `counts`, the first two refusals; what the call holds at all
-Status Engine::packet_check(const PacketCall &c, int most, bool *any_restart, bool *any_count, std::string *err) const {
+// `max_samples` and `counts`, the first two refusals -- on a handle with channels (ch > 1) the streams of a group share a row, so their
+// counts must be equal; what the call holds at all
+Status Engine::packet_check(const PacketCall &c, int most, int ch, bool *any_restart, bool *any_count, std::string *err) const {
     if (c.max_samples < 1 || c.max_samples > most) {
         *err = "`max_samples` " + std::to_string(c.max_samples) + " is outside [1, " + std::to_string(most) + "].";
         return Status::kBadArgument;
@@ -2560,14 +2574,24 @@ Status Engine::packet_check(const PacketCall &c, int most, bool *any_restart, bo
         *any_restart = *any_restart || (c.restart && c.restart[b]);
         *any_count = *any_count || c.counts[b] > 0;
     }
+    for (int b = 0; ch > 1 && b < B_; ++b) {
+        const int first = b - b % ch;
+        if (c.counts[b] != c.counts[first]) {
+            *err = "`counts[" + std::to_string(b) + "]` = " + std::to_string(c.counts[b]) + " differs from `counts[" + std::to_string(first) + "]` = " +
+                   std::to_string(c.counts[first]) + ": streams " + std::to_string(first) + " and " + std::to_string(b) + " are channels of group " +
+                   std::to_string(b / ch) + ", whose samples share a row (`channels` = " + std::to_string(ch) + ").";
+            return Status::kBadArgument;
+        }
+    }
     return Status::kOk;
 }
 
 // The other refusals (`report_frames` against the kmax frames a stream completes, pointer kinds), the call without a sample or a restart
 // (*nothing: done, every stream stalled), then the caller's samples onto the device: host pointers are staged, and on a handle with a format
 // (fmt: kFmtS16 for none, and for the inner call of a fractional handle) format_in_kernel runs over the whole rows [B][max_samples] (the
-// caller owns them).  io: what the call's kernels read and write from here on.
-Status Engine::packet_begin(const PacketCall &c, int fmt, int kmax, bool any_restart, bool any_count, PacketIo *io, bool *nothing, std::string *err) {
+// caller owns them).  Channels (ch > 1), outermost: the whole group rows [B / ch][max_samples ch] are split into d_ch_ first, which then
+// stands in for both of the caller's buffers.  io: what the call's kernels read and write from here on.
+Status Engine::packet_begin(const PacketCall &c, int fmt, int ch, int kmax, bool any_restart, bool any_count, PacketIo *io, bool *nothing, std::string *err) {
     *nothing = false;
     if (c.report && c.report_frames < kmax) {
         *err = "`report_frames` " + std::to_string(c.report_frames) + " is below the " + std::to_string(kmax) + " frames a stream completes in this call.";
@@ -2592,6 +2616,16 @@ Status Engine::packet_begin(const PacketCall &c, int fmt, int kmax, bool any_res
         src = io->dst = d_host_io_;
         if (c.report) io->report = d_host_rep_, io->report_frames = kmax;
     }
+    io->joined = nullptr;
+    if (ch > 1 && any_count) {
+        launch_channels_split(fmt_bytes(fmt), ChannelArgs{src, d_ch_, nullptr, (long long) c.max_samples, B_ / ch, ch}, stream_);
+        if (hipGetLastError() != hipSuccess) {
+            *err = hip_last_error();
+            return Status::kRuntime;
+        }
+        io->joined = io->dst;
+        src = io->dst = d_ch_;
+    }
     if (io->convert) {
         launch_format_in(fmt, FormatArgs{src, d_fmt_in_, nullptr, (long long) B_ * c.max_samples, 1}, stream_);
         if (hipGetLastError() != hipSuccess) {
@@ -2606,9 +2640,11 @@ Status Engine::packet_begin(const PacketCall &c, int fmt, int kmax, bool any_res
 
 // ... and back: format_out_kernel writes row b's first counts[b] elements only, from the call's device table (d_counts: it starts with the
 // counts); of what a host call's staging brings back only a row's first counts[b] elements and a stream's first k[b] report rows are
-// copied on, the rest of the caller's bytes stay.
-Status Engine::packet_end(const PacketCall &c, int fmt, const PacketIo &io, const int32_t *d_counts, const int32_t *k, int kmax, std::string *err) {
+// copied on, the rest of the caller's bytes stay.  Channels: the join writes group g's first counts[g ch] ch elements from the same table,
+// and that much of a group's row is what a host call copies on.
+Status Engine::packet_end(const PacketCall &c, int fmt, int ch, const PacketIo &io, const int32_t *d_counts, const int32_t *k, int kmax, std::string *err) {
     if (io.convert) launch_format_out(fmt, FormatArgs{d_fmt_out_, io.dst, d_counts, (long long) c.max_samples, B_}, stream_);
+    if (io.joined) launch_channels_join(fmt_bytes(fmt), ChannelArgs{io.dst, io.joined, d_counts, (long long) c.max_samples, B_ / ch, ch}, stream_);
     if (hipGetLastError() != hipSuccess) {
         *err = hip_last_error();
         return Status::kRuntime;
@@ -2620,16 +2656,16 @@ Status Engine::packet_end(const PacketCall &c, int fmt, const PacketIo &io, cons
     if (!stage_out(host_out_.data(), io.bytes, host_rep_.data(), rep_floats * 4, err)) return Status::kRuntime;
     for (int b = 0; b < B_; ++b) {
         const size_t at = (size_t) b * c.max_samples * eb;
-        memcpy((uint8_t *) c.out + at, host_out_.data() + at, (size_t) c.counts[b] * eb);
+        if (b % ch == 0) memcpy((uint8_t *) c.out + at, host_out_.data() + at, (size_t) c.counts[b] * ch * eb);  // (ch == 1: every row)
         if (c.report) memcpy(c.report + (size_t) b * c.report_frames * 4, host_rep_.data() + (size_t) b * kmax * 4, (size_t) k[b] * 16);
     }
     return Status::kOk;
 }
 
-Status Engine::run_packet_call(const PacketCall &c, int fmt, std::string *err) {
+Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string *err) {
     const int F = rs_frame_length(rate_);
     bool any_restart, any_count, nothing;
-    Status st = packet_check(c, pk_max_, &any_restart, &any_count, err);
+    Status st = packet_check(c, pk_max_, ch, &any_restart, &any_count, err);
     if (st != Status::kOk) return st;
     std::vector<int32_t> k((size_t) B_);
     std::vector<int32_t> cuts{0};
@@ -2639,7 +2675,7 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, std::string *err) {
         kmax = std::max(kmax, k[b]);
     }
     PacketIo io;
-    st = packet_begin(c, fmt, kmax, any_restart, any_count, &io, &nothing, err);
+    st = packet_begin(c, fmt, ch, kmax, any_restart, any_count, &io, &nothing, err);
     if (st != Status::kOk || nothing) return st;
     {  // the sub-calls: frames [cuts[l], cuts[l + 1])
         std::vector<int32_t> ks(k);
@@ -2710,7 +2746,7 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, std::string *err) {
         pk_fill_[b] = pk_fill_[b] + c.counts[b] - k[b] * F;
         if (c.frames) c.frames[b] = k[b];
     }
-    return packet_end(c, fmt, io, d_pk_tab_, k.data(), kmax, err);
+    return packet_end(c, fmt, ch, io, d_pk_tab_, k.data(), kmax, err);
 }
 
 // ------------------------------------------------------------------------------------------------ packet handles at 44 100 and 22 050 Hz
@@ -2764,7 +2800,7 @@ FractionalStateArgs Engine::fractional_state_args() const {
 Status Engine::run_fractional(const PacketCall &c, std::string *err) {
     const int U = fr_up(fr_rate_);
     bool any_restart, any_count, nothing;
-    Status st = packet_check(c, fr_max_, &any_restart, &any_count, err);
+    Status st = packet_check(c, fr_max_, ch_, &any_restart, &any_count, err);
     if (st != Status::kOk) return st;
     std::vector<int32_t> inner((size_t) B_), k((size_t) B_, 0);
     int kmax = 0;
@@ -2775,7 +2811,7 @@ Status Engine::run_fractional(const PacketCall &c, std::string *err) {
         kmax = std::max(kmax, ((fresh ? 0 : pk_fill_[b]) + inner[b]) / kFrame);
     }
     PacketIo io;
-    st = packet_begin(c, fmt_, kmax, any_restart, any_count, &io, &nothing, err);
+    st = packet_begin(c, fmt_, ch_, kmax, any_restart, any_count, &io, &nothing, err);
     if (st != Status::kOk || nothing) return st;
     const int slot = fr_ring_.acquire();
     if (slot < 0) {
@@ -2812,7 +2848,7 @@ Status Engine::run_fractional(const PacketCall &c, std::string *err) {
     }
     // the inner call: an S16 call on device rows, without restarts (done above); its report rows and frame counts are this call's
     PacketCall in16{pk_max_, inner.data(), d_fr_in_, d_fr_out_, nullptr, io.report, io.report_frames, k.data(), c.min_gain, c.min_gain_rev};
-    st = run_packet_call(in16, kFmtS16, err);
+    st = run_packet_call(in16, kFmtS16, 1, err);
     if (st != Status::kOk) return st;
     a.in = d_fr_out_;
     a.out = io.out16;
@@ -2827,7 +2863,7 @@ Status Engine::run_fractional(const PacketCall &c, std::string *err) {
         fr_phase_[b] = (fr_phase_[b] + c.counts[b]) % kFrDown;
         if (c.frames) c.frames[b] = k[b];
     }
-    return packet_end(c, fmt_, io, d_fr_tab_, k.data(), kmax, err);
+    return packet_end(c, fmt_, ch_, io, d_fr_tab_, k.data(), kmax, err);
 }
 
 // ------------------------------------------------------------------------------------------------ sample formats
@@ -2846,6 +2882,24 @@ bool Engine::set_format(int fmt, std::string *err) {
         return false;
     }
     fmt_ = fmt;
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ channels
+
+// A handle whose callers hold the streams of a group interleaved (seventh extension; section 6): one matrix of rows
+// [B][io_row()] of the handle's format elements, into which the call is split, on which it runs in place and from which it is joined.  The
+// two kernel launches are the entries' (process, run_packets: the host-pointer boundary), outside the format stage.
+bool Engine::enable_channels(int C, std::string *err) {
+    if (C == 1) return true;
+    (void) hipSetDevice(device_);
+    d_ch_ = (uint8_t *) dalloc((size_t) B_ * io_row() * sample_bytes(), false);
+    if (!d_ch_) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the rows of a handle with channels.";
+        return false;
+    }
+    ch_ = C;
     return true;
 }
 

@@ -147,6 +147,15 @@ public:
     int sample_format() const { return fmt_; }
     int sample_bytes() const { return fmt_bytes(fmt_); }
 
+    // ---- multi-channel handles (seventh extension).  enable_channels, once, last of the enable_* / set_format calls:
+    // from then on the `pcm` and `out` of process() and run_packets() are [num_streams / C][n C] elements of the handle's format -- sample i of
+    // stream g C + c is element [g][i C + c] -- split into the engine's rows in front of the unchanged call and joined behind it
+    // (kns_channels.hip).  Configuration, not stream state: the streams, their slots, records and every per-stream argument are those of the
+    // handle without channels.  A packet call's counts must be equal within a group.  The asynchronous host calls are the owner's to refuse.
+    // C == 1 allocates and changes nothing.
+    bool enable_channels(int C, std::string *err);
+    int channels() const { return ch_; }
+
     void profile_enable(bool on);
     bool profile_read(double *ms, int64_t *launches, std::string *err);
     int64_t debug_read(int what, float *out, int64_t capacity, std::string *err);
@@ -168,6 +177,9 @@ private:
     // sample formats: the int16 staging matrices [B][io_row()] on either side of the S16 call
     int fmt_ = kFmtS16;
     int16_t *d_fmt_in_ = nullptr, *d_fmt_out_ = nullptr;
+    // channels: the rows [B][io_row()] of format elements between split and join; the call below them runs on it in place
+    int ch_ = 1;
+    uint8_t *d_ch_ = nullptr;
     Status process_frames(const Call &c, std::string *err);  // a frame call and its held streams, below the boundary
     bool init(const Params &p, int device, int B, int Tmax, int precision, std::string *err, bool *oom);
     bool run_call(const Call &c, std::string *err);  // process() without the held streams, at 16 kHz
@@ -191,21 +203,23 @@ private:
     uint8_t *d_state_pk_ = nullptr;  // the packet part of the staged stream records [B][pk_record_bytes]
     std::vector<int32_t> pk_fill_;
     PacketStateArgs packet_state_args() const;
-    // run_packets of every handle that is not a fractional one, and a fractional handle's inner call (fmt: the format of c.pcm / c.out)
-    Status run_packet_call(const PacketCall &c, int fmt, std::string *err);
+    // run_packets of every handle that is not a fractional one, and a fractional handle's inner call (fmt, ch: the format and the channels of
+    // c.pcm / c.out -- kFmtS16 and 1 for the inner call, whose rows are the engine's)
+    Status run_packet_call(const PacketCall &c, int fmt, int ch, std::string *err);
     // what the two packet calls share (kns_engine.cpp): the refusals in their order, the caller's samples onto the device and back
     struct PacketIo {
         bool host, convert;              // the caller's pointers are host memory; format kernels run (a format, and some sample)
         size_t bytes;                    // of the caller's rows that travel (0: a call without a sample)
         void *dst;                       // where the format's elements go on the device: the caller's memory or the staging
+        void *joined;                    // channels: where the join writes (that memory), while dst is the rows between split and join; else nullptr
         float *report;                   // ... and the report rows, report_frames apart per stream
         int report_frames;
         const int16_t *in16;             // the int16 rows [B][max_samples] the call's first kernel reads
         int16_t *out16;                  // ... and its last one writes
     };
-    Status packet_check(const PacketCall &c, int most, bool *any_restart, bool *any_count, std::string *err) const;
-    Status packet_begin(const PacketCall &c, int fmt, int kmax, bool any_restart, bool any_count, PacketIo *io, bool *nothing, std::string *err);
-    Status packet_end(const PacketCall &c, int fmt, const PacketIo &io, const int32_t *d_counts, const int32_t *k, int kmax, std::string *err);
+    Status packet_check(const PacketCall &c, int most, int ch, bool *any_restart, bool *any_count, std::string *err) const;
+    Status packet_begin(const PacketCall &c, int fmt, int ch, int kmax, bool any_restart, bool any_count, PacketIo *io, bool *nothing, std::string *err);
+    Status packet_end(const PacketCall &c, int fmt, int ch, const PacketIo &io, const int32_t *d_counts, const int32_t *k, int kmax, std::string *err);
     // fractional handles: the rate, the caller's max_samples, the inner path's rows [B][pk_max_] on either side of the 16 kHz packet call,
     // the stages' tables and per-stream state ([0]: in-stage, [1]: out-stage), the call table (int32 counts[Bpad], uint8 restart[Bpad])
     // with its upload ring, and the HOST MIRROR of N mod 441, from which a call's inner counts are planned without a look at the device

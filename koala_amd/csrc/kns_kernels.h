@@ -432,6 +432,21 @@ struct FormatArgs {
 // fmt: kFmtF32, kFmtUlaw or kFmtAlaw (an S16 handle launches neither)
 void launch_format_in(int fmt, const FormatArgs &a, hipStream_t s);
 void launch_format_out(int fmt, const FormatArgs &a, hipStream_t s);
+// ---- multi-channel batch handles (kns_channels.hip; DESIGN.md section 2, seventh extension): the caller's `pcm` and `enhanced` hold the C
+// streams of a group interleaved.  Configuration of the handle, not stream state: the layout of two buffers and nothing else -- a split in
+// front of and a join behind the unchanged call, on elements of `width` = 1, 2 or 4 bytes (the handle's format).
+constexpr int kChannelsMax = 8;
+constexpr int kChSpanBytes = 8192;  // a workgroup's span of one group, all channels
+KNS_HD int ch_span(int C, int width) { return (kChSpanBytes / (C * width)) & ~15; }  // ... in samples per channel: whole 16-byte words of a row
+struct ChannelArgs {
+    const void *in;         // split: [G][n C] interleaved; join: [G C][n] rows -- dense, aligned to the element only
+    void *out;              // split: [G C][n] rows; join: [G][n C] interleaved
+    const int32_t *counts;  // join: device [G C] or nullptr: group g's first counts[g C] C elements are written (nullptr: all n C)
+    long long n;            // samples per stream
+    int G, C;               // groups, channels (2 .. kChannelsMax)
+};
+void launch_channels_split(int width, const ChannelArgs &a, hipStream_t s);
+void launch_channels_join(int width, const ChannelArgs &a, hipStream_t s);
 // last node of a captured one-frame replay: ++*counter (device memory), published to *host_word (page-locked host memory)
 void launch_frame_done(unsigned *counter, unsigned *host_word, hipStream_t s);
 

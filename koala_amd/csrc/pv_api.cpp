@@ -74,8 +74,12 @@ pv_status_t check_call(const pv_koala_batch_t *object, int32_t num_frames, const
     return PV_STATUS_SUCCESS;
 }
 
-// handles that are not at 16 kHz, and handles with a sample format, have no asynchronous path yet
+// handles that are not at 16 kHz, handles with a sample format and handles with channels have no asynchronous path yet
 pv_status_t check_synchronous(const pv_koala_batch_t *object) {
+    if (object->channels != 1) {
+        push_error(0x66, "Asynchronous calls are not available on a handle whose `channels` is %d, not 1.", object->channels);
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
     if (object->sample_rate != kns::kRate16k) {
         push_error(0x66, "Asynchronous calls are not available on a handle whose sample rate is %d, not 16000.", object->sample_rate);
         return PV_STATUS_INVALID_ARGUMENT;

@@ -1,5 +1,5 @@
 // pv_api_internal.h -- what the translation units of the C ABI share: the handles behind the opaque pointers, the calling thread's error
-// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_packets.cpp (packet handles) and pv_api_format.cpp (sample formats) use it.  Nothing here leaves the library.
+// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_packets.cpp (packet handles) and pv_api_format.cpp (sample formats) and pv_api_channels.cpp (channels) use it.  Nothing here leaves the library.
 #pragma once
 
 #include <new>
@@ -28,6 +28,7 @@ struct pv_koala_batch {
     int32_t sample_rate = kns::kRate16k;  // fixed at creation (pv_koala_batch_init_rate); the engine was made with the same value
     int32_t packet_samples = 0;           // a packet handle's max_samples_per_call (pv_koala_batch_init_packets); 0: a frame handle
     int32_t sample_format = 0;            // pv_koala_sample_format_t, fixed at creation (pv_koala_batch_init_config); the engine holds the same
+    int32_t channels = 1;                 // fixed at creation (pv_koala_batch_init_channels); the engine holds the same
 };
 
 namespace kns_api {

@@ -151,6 +151,60 @@ def run_raw_format(args):
     return 0
 
 
+def run_channels(args):
+    """--channels C: C interleaved channels (L R L R ...) through the C streams of one group of a packet handle
+    (`koala_amd.create_batch(..., packet_samples=N, channels=C)`: split and joined on the device), at --sample_rate, for instance
+    `--sample_rate 44100 --channels 2`.  With --input_path / --output_path: a C-channel 16-bit WAV of that rate in, one out.  Otherwise raw
+    interleaved samples of --sample_format (s16 by default) on stdin, the enhanced stream in the same form on stdout.  Every channel is
+    enhanced on its own: there is no linked-stereo processing.  Messages go to stderr."""
+    import os
+    from koala_amd import formats
+    C, rate, fmt = args.channels, args.sample_rate, args.sample_format or 's16'
+    for name, v in (('--meter', args.meter), ('--realtime', args.realtime), ('--reference_output_path', args.reference_output_path)):
+        if v:
+            raise ValueError('%s: not available with --channels' % name)
+    if (args.input_path is None) != (args.output_path is None):
+        raise ValueError('--channels: give both --input_path and --output_path (WAV files) or neither (raw samples on stdin and stdout)')
+    if args.input_path and fmt != 's16':
+        raise ValueError('--channels: WAV files are 16-bit PCM; --sample_format %s is for raw samples on stdin and stdout' % fmt)
+    dt = np.dtype(formats.dtype(fmt)).newbyteorder('<')
+    n = rate * (args.packet_ms or 20) // 1000
+    with contextlib.ExitStack() as stack:
+        if args.input_path:
+            src = stack.enter_context(wave.open(args.input_path, 'rb'))
+            if (src.getnchannels(), src.getsampwidth(), src.getframerate()) != (C, 2, rate):
+                raise ValueError('%s: expected a %d-channel 16-bit WAV at %d Hz' % (args.input_path, C, rate))
+            dst = stack.enter_context(wave.open(args.output_path, 'wb'))
+            dst.setnchannels(C), dst.setsampwidth(2), dst.setframerate(rate)
+            read, write = (lambda: src.readframes(n)), dst.writeframes
+        else:
+            read = lambda: sys.stdin.buffer.read(n * C * dt.itemsize)
+            write = lambda b: (sys.stdout.buffer.write(b), sys.stdout.buffer.flush())
+        batch = koala_amd.create_batch(args.access_key, C, precision=args.precision or os.environ.get('KOALA_AMD_PRECISION', 'fp32'),
+                                       model_path=args.model_path, device=args.device, library_path=args.library_path,
+                                       sample_rate=rate, packet_samples=n, sample_format=fmt, channels=C)
+        batch.set_attenuation_limit(args.attenuation_limit_db)
+        samples = 0
+        try:
+            while True:
+                buf = read()
+                got = np.frombuffer(buf[:len(buf) // (C * dt.itemsize) * (C * dt.itemsize)], dtype=dt)  # whole samples of all channels
+                if got.size == 0:
+                    break
+                packet = np.zeros((1, n * C), formats.dtype(fmt))
+                packet[0, :got.size] = got
+                enhanced = batch.process_packets(packet, [got.size // C] * C)
+                write(enhanced[0, :got.size].astype(dt).tobytes())
+                samples += got.size // C
+        except KeyboardInterrupt:
+            pass
+        finally:
+            delay = batch.delay_sample
+            batch.delete()
+    print('%d samples of %d channels of %s at %d Hz; delay %d samples' % (samples, C, fmt, rate, delay), file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='frame-by-frame noise suppression of a live PCM stream')
     ap.add_argument('--access_key', default='koala-amd', help='accepted for interface compatibility; not checked')
@@ -173,12 +227,17 @@ def main(argv=None):
                     help='raw samples of this format on stdin and stdout at --sample_rate, through a packet handle that converts on the device')
     ap.add_argument('--sample_rate', type=int, default=16000, choices=[8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000],
                     help='with --sample_format: the stream\'s rate (22050 and 44100 imply --sample_format s16 when none is given)')
+    ap.add_argument('--channels', type=int, default=1, choices=range(1, 9), metavar='C',
+                    help='C interleaved channels (raw on stdin and stdout, or C-channel WAV files) at --sample_rate through a packet '
+                         'handle that splits and joins on the device; every channel is enhanced on its own')
     ap.add_argument('--show_devices', action='store_true')
     args = ap.parse_args(argv)
 
     if args.show_devices:
         print('\n'.join(koala_amd.available_devices(library_path=args.library_path)))
         return 0
+    if args.channels != 1:
+        return run_channels(args)
     if args.sample_rate in (22050, 44100):
         # no frame exists at these rates: the raw packet path (stdin -> stdout) is the only one, and it has no files, meter or pacing
         given = [name for name, v in (('--input_path', args.input_path), ('--output_path', args.output_path),
