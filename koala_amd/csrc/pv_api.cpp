@@ -76,16 +76,17 @@ pv_status_t check_call(const pv_koala_batch_t *object, int32_t num_frames, const
 
 // handles that are not at 16 kHz, handles with a sample format and handles with channels have no asynchronous path yet
 pv_status_t check_synchronous(const pv_koala_batch_t *object) {
-    if (object->channels != 1) {
-        push_error(0x66, "Asynchronous calls are not available on a handle whose `channels` is %d, not 1.", object->channels);
+    if (object->engine->channels() != 1) {
+        push_error(0x66, "Asynchronous calls are not available on a handle whose `channels` is %d, not 1.", object->engine->channels());
         return PV_STATUS_INVALID_ARGUMENT;
     }
     if (object->sample_rate != kns::kRate16k) {
         push_error(0x66, "Asynchronous calls are not available on a handle whose sample rate is %d, not 16000.", object->sample_rate);
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    if (object->sample_format != kns::kFmtS16) {
-        push_error(0x66, "Asynchronous calls are not available on a handle whose sample format is %d, not PV_KOALA_SAMPLE_S16.", object->sample_format);
+    if (object->engine->sample_format() != kns::kFmtS16) {
+        push_error(0x66, "Asynchronous calls are not available on a handle whose sample format is %d, not PV_KOALA_SAMPLE_S16.",
+                   object->engine->sample_format());
         return PV_STATUS_INVALID_ARGUMENT;
     }
     return PV_STATUS_SUCCESS;
@@ -105,7 +106,7 @@ pv_status_t check_resets(const pv_koala_batch_t *object, int32_t num_frames, con
     return PV_STATUS_SUCCESS;
 }
 
-// a handle at 44 100 or 22 050 Hz (pv_api_format.cpp) has no stream records yet, and no whole frame
+// a handle at 44 100 or 22 050 Hz (pv_api_extensions.cpp) has no stream records yet, and no whole frame
 pv_status_t check_records(const pv_koala_batch_t *object) {
     if (kns::fr_rate_ok(object->sample_rate)) {
         push_error(0x66, "Stream records (state_size, export_state, import_state) are not available yet on a handle whose sample rate is %d.",
@@ -155,7 +156,7 @@ pv_status_t advance(kns::Engine *engine, const MinGain &limit, kns::Call call, b
 
 }  // namespace
 
-// what the other translation units of the C ABI (pv_api_packets.cpp, pv_api_format.cpp) share with this one: pv_api_internal.h
+// what the other translation unit of the C ABI (pv_api_extensions.cpp) shares with this one: pv_api_internal.h
 namespace kns_api {
 void clear_errors() { t_stack.clear(); }
 void push_error(unsigned code, const char *fmt, ...) {

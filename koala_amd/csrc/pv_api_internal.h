@@ -1,5 +1,6 @@
 // pv_api_internal.h -- what the translation units of the C ABI share: the handles behind the opaque pointers, the calling thread's error
-// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_packets.cpp (packet handles) and pv_api_format.cpp (sample formats) and pv_api_channels.cpp (channels) use it.  Nothing here leaves the library.
+// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_extensions.cpp (packet handles, sample formats, channels) uses it.
+// Nothing here leaves the library.
 #pragma once
 
 #include <new>
@@ -27,8 +28,8 @@ struct pv_koala_batch {
     MinGain limit;
     int32_t sample_rate = kns::kRate16k;  // fixed at creation (pv_koala_batch_init_rate); the engine was made with the same value
     int32_t packet_samples = 0;           // a packet handle's max_samples_per_call (pv_koala_batch_init_packets); 0: a frame handle
-    int32_t sample_format = 0;            // pv_koala_sample_format_t, fixed at creation (pv_koala_batch_init_config); the engine holds the same
-    int32_t channels = 1;                 // fixed at creation (pv_koala_batch_init_channels); the engine holds the same
+    // (both are the CALLER's values: on a handle at 44 100 or 22 050 Hz the engine's are those of the 16 kHz packet engine inside.  The
+    // sample format and the channels are the engine's alone: engine->sample_format(), engine->channels())
 };
 
 namespace kns_api {

@@ -2,55 +2,12 @@
 // AddressSanitizer + UndefinedBehaviorSanitizer: the one constructor that reaches the two rates and the ones that keep refusing them, the
 // queries (sample_rate, delay_sample 1541 / 771, is_packet_handle, sample_format; frame_length refused), and every refusal -- frame and
 // asynchronous entry points, stream records, 11 025 Hz -- with exactly one message and nothing processed.  Linked with
-// koala_amd/csrc/pv_api.cpp, pv_api_packets.cpp, pv_api_format.cpp, the host-only engine double of tests/abi_sanitizer (engine_stub.cpp)
-// and fractional_stub.cpp: no GPU, no HIP runtime.  Exit status 0 = every expectation held and the sanitizers stayed silent.
+// koala_amd/csrc/pv_api*.cpp and the host-only engine double of tests/abi_sanitizer (engine_stub.cpp, whose g_packet_calls counts the
+// packet calls that reached it): no GPU, no HIP runtime.  Exit status 0 = every expectation held and the sanitizers stayed silent.
 // usage: driver <model.kns>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include "../abi_sanitizer/expect.h"
 
-#include <string>
-#include <vector>
-
-#include "pv_koala.h"
-#include "pv_koala_batch.h"
-
-extern int g_packet_calls;
-
-static int g_fail = 0;
-#define EXPECT(cond)                                              \
-    do {                                                          \
-        if (!(cond)) {                                            \
-            fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); \
-            ++g_fail;                                             \
-        }                                                         \
-    } while (0)
-
-// drains the thread's stack; returns its depth and the first message
-static int drain(std::string *first = nullptr) {
-    char **stack = nullptr;
-    int32_t depth = -1;
-    const pv_status_t st = pv_get_error_stack(&stack, &depth);
-    if (depth > 0) {
-        EXPECT(st == PV_STATUS_SUCCESS && stack != nullptr);
-        if (first) *first = stack[0];
-        pv_free_error_stack(stack);
-    } else {
-        EXPECT(st == PV_STATUS_INVALID_STATE && depth == 0 && stack == nullptr);
-    }
-    return depth;
-}
-
-static bool has(const std::string &s, const char *what) { return s.find(what) != std::string::npos; }
-
-static pv_koala_batch_config_t config(int32_t B, int32_t frames, int32_t samples, int32_t rate, pv_koala_sample_format_t fmt) {
-    pv_koala_batch_config_t c;
-    memset(&c, 0, sizeof(c));
-    c.struct_size = (int32_t) sizeof(c);
-    c.num_streams = B, c.max_frames_per_call = frames, c.max_samples_per_call = samples;
-    c.precision = PV_KOALA_PRECISION_FP32, c.sample_rate = rate, c.sample_format = fmt;
-    return c;
-}
+extern int g_packet_calls;  // engine_stub.cpp
 
 int main(int argc, char **argv) {
     if (argc < 2) {

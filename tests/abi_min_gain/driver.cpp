@@ -4,42 +4,10 @@
 // koala_amd/csrc/pv_api.cpp and the host-only engine double of tests/abi_sanitizer (engine_stub.cpp): no GPU, no HIP runtime.
 // Exit status 0 = every expectation held and the sanitizers stayed silent.  usage: driver <model.kns>
 #include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <limits>
-#include <string>
-#include <vector>
 
-#include "pv_koala.h"
-#include "pv_koala_batch.h"
-
-static int g_fail = 0;
-#define EXPECT(cond)                                              \
-    do {                                                          \
-        if (!(cond)) {                                            \
-            fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); \
-            ++g_fail;                                             \
-        }                                                         \
-    } while (0)
-
-// drains the thread's stack; returns its depth and the first message
-static int drain(std::string *first = nullptr) {
-    char **stack = nullptr;
-    int32_t depth = -1;
-    const pv_status_t st = pv_get_error_stack(&stack, &depth);
-    if (depth > 0) {
-        EXPECT(st == PV_STATUS_SUCCESS && stack != nullptr);
-        if (first) *first = stack[0];
-        pv_free_error_stack(stack);
-    } else {
-        EXPECT(st == PV_STATUS_INVALID_STATE && depth == 0 && stack == nullptr);
-    }
-    return depth;
-}
-
-static bool has(const std::string &s, const char *what) { return s.find(what) != std::string::npos; }
+#include "../abi_sanitizer/expect.h"
 
 static void batch(const char *model) {
     const int B = 6, T = 4;

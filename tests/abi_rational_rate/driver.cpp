@@ -1,44 +1,10 @@
 // Drives the C ABI at the two rational rates, 12 000 and 24 000 Hz (include/pv_koala_batch.h: pv_koala_batch_init_rate,
 // pv_koala_batch_init_packets, and what pv_koala_batch_frame_length / _delay_sample / _state_size answer there) under AddressSanitizer +
 // UndefinedBehaviorSanitizer: the constants of DESIGN.md section 2 (third extension, generalised), the refusal text with its six rates,
-// the rates that stay refused, and the refusal of asynchronous calls.  Linked with koala_amd/csrc/pv_api.cpp, pv_api_packets.cpp, the
-// host-only engine double of tests/abi_sanitizer (engine_stub.cpp) and packets_stub.cpp: no GPU, no HIP runtime.  Exit status 0 = every
-// expectation held and the sanitizers stayed silent.  usage: driver <model.kns>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <string>
-#include <vector>
-
-#include "pv_koala.h"
-#include "pv_koala_batch.h"
-
-static int g_fail = 0;
-#define EXPECT(cond)                                              \
-    do {                                                          \
-        if (!(cond)) {                                            \
-            fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); \
-            ++g_fail;                                             \
-        }                                                         \
-    } while (0)
-
-// drains the thread's stack; returns its depth and the first message
-static int drain(std::string *first = nullptr) {
-    char **stack = nullptr;
-    int32_t depth = -1;
-    const pv_status_t st = pv_get_error_stack(&stack, &depth);
-    if (depth > 0) {
-        EXPECT(st == PV_STATUS_SUCCESS && stack != nullptr);
-        if (first) *first = stack[0];
-        pv_free_error_stack(stack);
-    } else {
-        EXPECT(st == PV_STATUS_INVALID_STATE && depth == 0 && stack == nullptr);
-    }
-    return depth;
-}
-
-static bool has(const std::string &s, const char *what) { return s.find(what) != std::string::npos; }
+// the rates that stay refused, and the refusal of asynchronous calls.  Linked with koala_amd/csrc/pv_api*.cpp and the
+// host-only engine double of tests/abi_sanitizer (engine_stub.cpp): no GPU, no HIP runtime.  Exit status 0 = every expectation held and
+// the sanitizers stayed silent.  usage: driver <model.kns>
+#include "../abi_sanitizer/expect.h"
 
 int main(int argc, char **argv) {
     if (argc < 2) {

@@ -1,17 +1,15 @@
 // Drives every entry point of the C ABI (include/pv_koala.h, include/picovoice.h, include/pv_koala_batch.h) through its argument
 // checks, error-stack and ownership paths under AddressSanitizer + UndefinedBehaviorSanitizer, with the engine stubbed out
-// (engine_stub.cpp).  Exit status 0 = every expectation held and the sanitizers stayed silent.  usage: driver <model.kns> <not-a-model>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+// (engine_stub.cpp).  The packet, format and 44.1 kHz entry points have drivers of their own (tests/abi_rational_rate,
+// tests/abi_fractional_rate); their constructors' failure paths are here, with the channel entry points.  Exit status 0 = every expectation
+// held and the sanitizers stayed silent, in this process and in the two it starts.  usage: driver <model.kns> <not-a-model>
+#include <spawn.h>
+#include <sys/wait.h>
 
 #include <algorithm>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "pv_koala.h"
-#include "pv_koala_batch.h"
+#include "expect.h"
 
 extern "C" {
 void pv_set_sdk(const char *);
@@ -19,31 +17,7 @@ const char *pv_get_sdk(void);
 void pv_free(void *);
 void pv_log_enable(void);
 void pv_log_disable(void);
-}
-
-static int g_fail = 0;
-#define EXPECT(cond)                                              \
-    do {                                                          \
-        if (!(cond)) {                                            \
-            fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); \
-            ++g_fail;                                             \
-        }                                                         \
-    } while (0)
-
-// drains the thread's stack; returns its depth and the first message
-static int drain(std::string *first = nullptr) {
-    char **stack = nullptr;
-    int32_t depth = -1;
-    const pv_status_t st = pv_get_error_stack(&stack, &depth);
-    if (depth > 0) {
-        EXPECT(st == PV_STATUS_SUCCESS && stack != nullptr);
-        for (int i = 0; i < depth; ++i) EXPECT(stack[i] != nullptr && strlen(stack[i]) > 17);  // "<7 hex> <8 hex>: text"
-        if (first) *first = stack[0];
-        pv_free_error_stack(stack);
-    } else {
-        EXPECT(st == PV_STATUS_INVALID_STATE && depth == 0 && stack == nullptr);  // nothing pending: nothing to free
-    }
-    return depth;
+extern char **environ;
 }
 
 static void single_stream(const char *model, const char *garbage) {
@@ -257,11 +231,96 @@ static void batch_calls_with_arguments(const char *model) {
     pv_koala_batch_delete(b);
 }
 
+// pv_koala_batch_init_channels and pv_koala_batch_channels: every refusal with its message, and what a finished handle reports and refuses
+static void channels(const char *model) {
+    const int T = 2;
+    std::string msg;
+    pv_koala_batch_t *h = nullptr;
+    pv_koala_batch_config_t c = config(4, T, 0, 16000, PV_KOALA_SAMPLE_S16);
+    for (int32_t bad : {0, 9}) {
+        EXPECT(pv_koala_batch_init_channels("k", model, "best", &c, bad, &h) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 &&
+               has(msg, ("`channels` " + std::to_string(bad) + " is outside [1, 8].").c_str()) && h == nullptr);
+    }
+    c.num_streams = 6;
+    EXPECT(pv_koala_batch_init_channels("k", model, "best", &c, 4, &h) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 &&
+           has(msg, "`num_streams` 6 is not a multiple of `channels` 4") && h == nullptr);
+    EXPECT(pv_koala_batch_init_channels("k", model, "best", nullptr, 2, &h) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 &&
+           has(msg, "Argument `config` is NULL.") && h == nullptr);
+    int32_t v = -1;
+    EXPECT(pv_koala_batch_init_channels("k", model, "best", &c, 1, &h) == PV_STATUS_SUCCESS && h != nullptr && drain() == 0);
+    EXPECT(pv_koala_batch_channels(h, &v) == PV_STATUS_SUCCESS && v == 1);
+    pv_koala_batch_delete(h);
+
+    c.num_streams = 4;
+    h = nullptr;
+    EXPECT(pv_koala_batch_init_channels("k", model, "best", &c, 2, &h) == PV_STATUS_SUCCESS && h != nullptr && drain() == 0);
+    if (!h) return;
+    EXPECT(pv_koala_batch_channels(h, &v) == PV_STATUS_SUCCESS && v == 2);
+    EXPECT(pv_koala_batch_num_streams(h, &v) == PV_STATUS_SUCCESS && v == 4);
+    EXPECT(pv_koala_batch_channels(nullptr, &v) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && has(msg, "Argument `object` is NULL."));
+    EXPECT(pv_koala_batch_channels(h, nullptr) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && has(msg, "Argument `channels` is NULL."));
+    // the asynchronous entry points refuse the handle, with one message and nothing written
+    std::vector<int16_t> in(4 * T * 256, 3), out(4 * T * 256, (int16_t) -7);
+    std::vector<uint8_t> reset(4 * T, 0);
+    pv_koala_batch_call_t call;
+    memset(&call, 0, sizeof(call));
+    call.struct_size = (int32_t) sizeof(call);
+    call.num_frames = T, call.pcm = in.data(), call.enhanced = out.data(), call.asynchronous = 1;
+    const char *refusal = "Asynchronous calls are not available on a handle whose `channels` is 2, not 1.";
+    EXPECT(pv_koala_batch_process_chunk_async(h, T, in.data(), out.data()) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && has(msg, refusal));
+    EXPECT(pv_koala_batch_process_chunk_resets_async(h, T, in.data(), out.data(), reset.data()) == PV_STATUS_INVALID_ARGUMENT &&
+           drain(&msg) == 1 && has(msg, refusal));
+    EXPECT(pv_koala_batch_process_call(h, &call) == PV_STATUS_INVALID_ARGUMENT && drain(&msg) == 1 && has(msg, refusal));
+    for (int16_t o : out) EXPECT(o == -7);
+    EXPECT(pv_koala_batch_process_chunk(h, T, in.data(), out.data()) == PV_STATUS_SUCCESS && out == in && drain() == 0);
+    pv_koala_batch_delete(h);
+}
+
+// A constructor whose enable step fails (the child process of enable_failures below: STUB_FAIL_ENABLE is set, to 1 or to throw): the
+// handle it had finished is deleted and *object is NULL, whether the step returned false or threw -- a handle left behind is the leak
+// report that fails this process at its exit.  (At 44 100 Hz the first step to fail is the inner packet handle's.)
+static void enable_failure_cases(const char *model) {
+    const bool throws = !strcmp(getenv("STUB_FAIL_ENABLE"), "throw");
+    int sentinel = 0;
+    std::string msg;
+    const pv_koala_batch_config_t with_format = config(3, 2, 0, 16000, PV_KOALA_SAMPLE_ULAW), at_44100 = config(3, 0, 1000, 44100, PV_KOALA_SAMPLE_S16),
+                                  planar = config(4, 2, 0, 16000, PV_KOALA_SAMPLE_S16);
+    for (int which = 0; which < 4; ++which) {
+        pv_koala_batch_t *h = (pv_koala_batch_t *) &sentinel;
+        const pv_status_t st = which == 0 ? pv_koala_batch_init_packets("k", model, "best", 3, 480, PV_KOALA_PRECISION_FP32, 16000, &h) :
+                               which == 1 ? pv_koala_batch_init_config("k", model, "best", &with_format, &h) :
+                               which == 2 ? pv_koala_batch_init_config("k", model, "best", &at_44100, &h) :
+                                            pv_koala_batch_init_channels("k", model, "best", &planar, 2, &h);
+        EXPECT(st == PV_STATUS_OUT_OF_MEMORY && h == nullptr);
+        EXPECT(drain(&msg) == 1 && has(msg, "00000065") && has(msg, throws ? "Failed to allocate memory." : "(stub)"));
+    }
+}
+
+// the cases above in a fresh child process each way, so that a handle that leaks there is reported at that process's exit
+static void enable_failures(const char *self, const char *model) {
+    for (const char *mode : {"1", "throw"}) {
+        setenv("STUB_FAIL_ENABLE", mode, 1);
+        char *const child[] = {(char *) self, (char *) model, (char *) "enable-failures", nullptr};
+        pid_t pid = -1;
+        int status = -1;
+        EXPECT(posix_spawn(&pid, self, nullptr, nullptr, child, environ) == 0 && waitpid(pid, &status, 0) == pid);
+        EXPECT(WIFEXITED(status) && WEXITSTATUS(status) == 0);
+        unsetenv("STUB_FAIL_ENABLE");
+    }
+}
+
 int main(int argc, char **argv) {
     if (argc < 3) return 2;
+    if (!strcmp(argv[2], "enable-failures")) {
+        enable_failure_cases(argv[1]);
+        if (g_fail) fprintf(stderr, "%d expectation(s) failed with STUB_FAIL_ENABLE=%s\n", g_fail, getenv("STUB_FAIL_ENABLE"));
+        return g_fail ? 1 : 0;
+    }
     single_stream(argv[1], argv[2]);
     batch(argv[1]);
     batch_calls_with_arguments(argv[1]);
+    channels(argv[1]);
+    enable_failures(argv[0], argv[1]);
     // the error stack is per thread: failures on other threads leave this one's untouched, and eight threads hammering the
     // argument checks must not race (the stack is thread_local, the SDK string is behind a mutex)
     EXPECT(pv_koala_process(nullptr, nullptr, nullptr) == PV_STATUS_INVALID_ARGUMENT);

@@ -1,12 +1,15 @@
-// Stand-in for kns_engine.cpp in the sanitizer build of the C-ABI shim (tests/test_abi_sanitized.py; SURVEY.md section 5: "ASan/UBSan
-// build of the shim").  Only koala_amd/csrc/pv_api.cpp is under test here -- argument checks, the thread-local error stack, string
-// and list ownership -- so the engine behind it is a host-only double: parameters "load" when the file exists, a handle is a plain
-// object, process() copies its input, and no HIP call reaches a GPU.  It defines every out-of-line public member of kns::Engine: a new
-// one gets a trivial body here, the engine's interface is not shaped around this file.  TEST INFRASTRUCTURE: never linked into the product.
+// Stand-in for kns_engine.cpp in the sanitizer builds of the C-ABI shim (tests/sanitized_build.py, build_abi_driver; SURVEY.md section 5:
+// "ASan/UBSan build of the shim").  Only koala_amd/csrc/pv_api*.cpp is under test here -- argument checks, the thread-local error stack,
+// string and list ownership -- so the engine behind it is a host-only double: parameters "load" when the file exists, a handle is a plain
+// object, process() and run_packets() copy their input, an enable_* call remembers its argument where the inline getters look for it, and no
+// HIP call reaches a GPU.  It defines every out-of-line public member of kns::Engine: a new one gets a trivial body here, the engine's
+// interface and the product's source files are not shaped around this file.  TEST INFRASTRUCTURE: never linked into the product.
 #include <stdio.h>
 #include <string.h>
 
 #include "kns_engine.h"
+
+int g_packet_calls = 0;  // run_packets calls that reached the engine
 
 namespace kns {
 
@@ -89,6 +92,41 @@ Status Engine::import_state(int count, const int32_t *streams, const void *host_
     unsigned sum = 0;
     for (size_t i = 0; i < (size_t) count * state_bytes(); ++i) sum += ((const uint8_t *) host_records)[i];
     (void) sum;
+    return Status::kOk;
+}
+// STUB_FAIL_ENABLE=1: the four enable members below fail with a message; STUB_FAIL_ENABLE=throw: they throw as a host allocation would
+static bool stub_enables(std::string *err) {
+    const char *e = getenv("STUB_FAIL_ENABLE");
+    if (e && !strcmp(e, "throw")) throw std::bad_alloc();
+    if (e) *err = "Failed to allocate device memory (stub).";
+    return !e;
+}
+bool Engine::enable_packets(int max_samples, std::string *err) {
+    if (!stub_enables(err)) return false;
+    pk_max_ = max_samples;
+    return true;
+}
+bool Engine::enable_fractional(int rate, int max_samples, std::string *err) {
+    if (!stub_enables(err)) return false;
+    fr_rate_ = rate, fr_max_ = max_samples;
+    return true;
+}
+bool Engine::set_format(int fmt, std::string *err) {
+    if (!stub_enables(err)) return false;
+    fmt_ = fmt;
+    return true;
+}
+bool Engine::enable_channels(int C, std::string *err) {
+    if (!stub_enables(err)) return false;
+    ch_ = C;
+    return true;
+}
+// every stream's counted samples, in elements of the handle's format
+Status Engine::run_packets(const PacketCall &c, std::string *) {
+    ++g_packet_calls;
+    const size_t eb = (size_t) sample_bytes();
+    for (int b = 0; b < B_; ++b)
+        memmove((uint8_t *) c.out + (size_t) b * c.max_samples * eb, (const uint8_t *) c.pcm + (size_t) b * c.max_samples * eb, (size_t) c.counts[b] * eb);
     return Status::kOk;
 }
 bool Engine::drain_async(std::string *) { return true; }

@@ -51,7 +51,7 @@ HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
 def test_channel_kernels_build_for_gfx950_without_scratch_or_spills(tmp_path):
     out = tmp_path / 'kns_channels.s'
     mk = open(os.path.join(ROOT, 'koala_amd', 'Makefile')).read()
-    assert 'csrc/kns_channels.hip' in mk and 'obj/kns_channels.o' in mk and 'csrc/pv_api_channels.cpp' in mk and 'obj/pv_api_channels.o' in mk
+    assert 'csrc/kns_channels.hip' in mk and 'obj/kns_channels.o' in mk and 'csrc/pv_api_extensions.cpp' in mk and 'obj/pv_api_extensions.o' in mk
     cxx = re.search(r'^CXXFLAGS\s*=\s*(.*)$', mk, re.M).group(1).split()
     subprocess.check_call([HIPCC, '--offload-arch=gfx950'] + [f for f in cxx if f != '-fPIC'] +
                           ['-S', '--cuda-device-only', '-x', 'hip', os.path.join(ROOT, 'koala_amd', 'csrc', 'kns_channels.hip'), '-o', str(out)],

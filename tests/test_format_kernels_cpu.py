@@ -6,11 +6,10 @@ cases (frame matrices B = 3, T F in {128, 256, 768}; packet matrices of max_samp
 ones in between; base pointers 1 and 15 bytes, 2 bytes, 4 and 12 bytes in) and the codecs restated.
 """
 import os
-import shutil
-import subprocess
 
 import pytest
 
+import sanitized_build
 from conftest import ROOT
 
 SRC = os.path.join(ROOT, 'tests', 'format_emulation')
@@ -27,27 +26,11 @@ def translation_unit():
 
 @pytest.fixture(scope='module')
 def emulator(tmp_path_factory):
-    gxx = shutil.which('g++')
-    if not gxx:
-        pytest.skip('needs g++')
-    # the sanitizer runtimes are looked for BEFORE the build, so that every failure of the build itself is a failure of the test
-    for runtime in ('libasan.so', 'libubsan.so'):
-        found = subprocess.run([gxx, '-print-file-name=' + runtime], capture_output=True, text=True, timeout=60).stdout.strip()
-        if not os.path.isabs(found):  # (g++ echoes the bare name back when it has no such file)
-            pytest.skip('g++ has no %s' % runtime)
-    d = tmp_path_factory.mktemp('format_emulation')
-    (d / 'emu.cpp').write_text(translation_unit())
-    exe = str(d / 'emu')
-    build = subprocess.run([gxx, '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', str(d / 'emu.cpp'),
-                            '-o', exe], capture_output=True, text=True, timeout=600)
-    assert build.returncode == 0, build.stderr[-4000:]
-    return exe
+    return sanitized_build.build_translation_unit(translation_unit(), tmp_path_factory.mktemp('format_emulation'))
 
 
 def test_kernels_convert_exactly_and_touch_nothing_else(emulator):
-    # the environment stays as it is; a library preloaded into it may come before the sanitizer runtime, which is all the order check is about
-    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0:verify_asan_link_order=0', UBSAN_OPTIONS='print_stacktrace=1')
-    run = subprocess.run([emulator], capture_output=True, text=True, timeout=600, env=env)
+    run = sanitized_build.run(emulator)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-4000:])
     # 3 formats x 2 directions x 3 x 2 base offsets x (3 frame matrices + 3 packet matrices)
     assert 'format kernels ok: 216 cases' in run.stdout, run.stdout[-2000:]

@@ -16,6 +16,7 @@ import pytest
 
 import fractional_rate_recipe as frr
 import koala_amd
+import sanitized_build
 from conftest import ROOT, model_file
 from koala_amd import packets
 
@@ -177,25 +178,6 @@ def test_fractional_kernels_build_for_gfx950_without_scratch_or_spills(tmp_path)
         assert not [x for x in lines[loads[0]:fma[-1] + 1] if re.search(r'\b(global|flat|buffer|scratch)_(store|atomic)|\bds_write|\bs_barrier', x)], name
 
 
-def sanitizer_gxx():
-    """g++, once it is known to have the STATIC sanitizer runtimes: looked for BEFORE any build, so that every failure of a build is a
-    failure of the test.  Static, because the programs below are stand-alone and run in the environment as it is: a runtime inside the
-    program does not care what else the loader brings in, or in which order."""
-    gxx = shutil.which('g++')
-    if not gxx:
-        pytest.skip('needs g++')
-    for runtime in ('libasan.a', 'libubsan.a'):
-        found = subprocess.run([gxx, '-print-file-name=' + runtime], capture_output=True, text=True, timeout=60).stdout.strip()
-        if not os.path.isabs(found):  # (g++ echoes the bare name back when it has no such file)
-            pytest.skip('g++ has no %s' % runtime)
-    return gxx
-
-
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-static-libasan', '-static-libubsan']
-# (what the programs' own sanitizers are told; nothing else of the environment is touched)
-SANITIZER_OPTIONS = dict(ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
-
-
 def translation_unit():
     src = os.path.join(ROOT, 'tests', 'fractional_emulation')
     header = open(os.path.join(ROOT, 'koala_amd', 'csrc', 'kns_kernels.h')).read()
@@ -209,38 +191,18 @@ def translation_unit():
 
 @pytest.fixture(scope='module')
 def emulator(tmp_path_factory):
-    gxx = sanitizer_gxx()
-    d = tmp_path_factory.mktemp('fractional_emulation')
-    (d / 'emu.cpp').write_text(translation_unit())
-    exe = str(d / 'emu')
-    build = subprocess.run([gxx, '-O1', '-g', '-std=c++17', '-ffp-contract=off'] + SANITIZE + [str(d / 'emu.cpp'), '-o', exe, '-lpthread'],
-                           capture_output=True, text=True, timeout=600)
-    assert build.returncode == 0, build.stderr[-4000:]
-    return exe
+    return sanitized_build.build_translation_unit(translation_unit(), tmp_path_factory.mktemp('fractional_emulation'), ['-ffp-contract=off'])
 
 
 @pytest.mark.parametrize('U', [160, 320])
 def test_kernels_are_the_definition_and_touch_nothing_else(emulator, U):
     """the kernels' own source, 256 threads a workgroup, against a plain C++ loop of the definition: B = 3 streams out of phase, counts from
     {0, 1, 2, 3, 440, 441, 442, 882, 1000}, max_samples 1000, a masked reset mid-run"""
-    run = subprocess.run([emulator, str(U)], capture_output=True, text=True, timeout=600, env=dict(os.environ, **SANITIZER_OPTIONS))
+    run = sanitized_build.run(emulator, U)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-4000:])
     assert run.stdout.count('samples ok') == 3
 
 
 def test_constructor_queries_and_refusals_through_the_c_abi_under_asan_and_ubsan(tmp_path):
-    gxx = sanitizer_gxx()
-    if not os.path.isdir('/opt/rocm/include/hip'):
-        pytest.skip('needs the HIP headers')
-    exe = str(tmp_path / 'fractional_rate_driver')
-    csrc = os.path.join(ROOT, 'koala_amd', 'csrc')
-    cmd = [gxx, '-std=c++17', '-O1', '-g', '-fno-omit-frame-pointer'] + SANITIZE + [
-           '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include', '-I' + os.path.join(ROOT, 'include'), '-I' + csrc,
-           '-Wno-deprecated-declarations', '-Wno-unused-result',
-           os.path.join(csrc, 'pv_api.cpp'), os.path.join(csrc, 'pv_api_packets.cpp'), os.path.join(csrc, 'pv_api_format.cpp'),
-           os.path.join(ROOT, 'tests', 'abi_sanitizer', 'engine_stub.cpp'), os.path.join(ROOT, 'tests', 'abi_fractional_rate', 'fractional_stub.cpp'),
-           os.path.join(ROOT, 'tests', 'abi_fractional_rate', 'driver.cpp'), '-o', exe, '-lpthread']
-    build = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert build.returncode == 0, build.stderr[-4000:]
-    run = subprocess.run([exe, model_file('random', 1234)], capture_output=True, text=True, timeout=300, env=dict(os.environ, **SANITIZER_OPTIONS))
+    run = sanitized_build.run(sanitized_build.build_abi_driver('abi_fractional_rate', tmp_path), model_file('random', 1234), timeout=300)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-6000:])

@@ -4,11 +4,10 @@ index, every 16-byte store's alignment and the whole rebuffering logic, without 
 (256 threads and a barrier per workgroup), driver.inc for the engine's call sequence around a delay-only frame call.
 """
 import os
-import shutil
-import subprocess
 
 import pytest
 
+import sanitized_build
 from conftest import ROOT
 
 SRC = os.path.join(ROOT, 'tests', 'packet_emulation')
@@ -26,29 +25,13 @@ def translation_unit():
 
 @pytest.fixture(scope='module')
 def emulator(tmp_path_factory):
-    gxx = shutil.which('g++')
-    if not gxx:
-        pytest.skip('needs g++')
-    # the sanitizer runtimes are looked for BEFORE the build, so that every failure of the build itself is a failure of the test
-    for runtime in ('libasan.so', 'libubsan.so'):
-        found = subprocess.run([gxx, '-print-file-name=' + runtime], capture_output=True, text=True, timeout=60).stdout.strip()
-        if not os.path.isabs(found):  # (g++ echoes the bare name back when it has no such file)
-            pytest.skip('g++ has no %s' % runtime)
-    d = tmp_path_factory.mktemp('packet_emulation')
-    (d / 'emu.cpp').write_text(translation_unit())
-    exe = str(d / 'emu')
-    build = subprocess.run([gxx, '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', str(d / 'emu.cpp'),
-                            '-o', exe, '-lpthread'], capture_output=True, text=True, timeout=600)
-    assert build.returncode == 0, build.stderr[-4000:]
-    return exe
+    return sanitized_build.build_translation_unit(translation_unit(), tmp_path_factory.mktemp('packet_emulation'))
 
 
 # frame length, the inner engine's max_frames = ceil(max_samples / F), max_samples
 @pytest.mark.parametrize('F,max_frames,max_samples', [(256, 2, 320), (768, 2, 960), (128, 1, 80), (512, 2, 640), (256, 1, 1),
                                                       (256, 3, 701)])
 def test_kernels_rebuffer_exactly_and_touch_nothing_else(emulator, F, max_frames, max_samples):
-    # the environment stays as it is; a library preloaded into it may come before the sanitizer runtime, which is all the order check is about
-    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0:verify_asan_link_order=0', UBSAN_OPTIONS='print_stacktrace=1')
-    run = subprocess.run([emulator, str(F), str(max_frames), str(max_samples)], capture_output=True, text=True, timeout=600, env=env)
+    run = sanitized_build.run(emulator, F, max_frames, max_samples)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-4000:])
     assert run.stdout.count('samples ok') == 5

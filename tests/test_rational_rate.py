@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import sample_rate_recipe as srr
+import sanitized_build
 from conftest import ROOT, model_file
 
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
@@ -119,23 +120,5 @@ def test_rational_kernels_build_for_gfx950_without_scratch_or_spills(tmp_path):
 
 
 def test_constants_through_the_c_abi_under_asan_and_ubsan(tmp_path):
-    gxx = shutil.which('g++')
-    if not gxx or not os.path.isdir('/opt/rocm/include/hip'):
-        pytest.skip('needs g++ and the HIP headers')
-    exe = str(tmp_path / 'rational_rate_driver')
-    csrc = os.path.join(ROOT, 'koala_amd', 'csrc')
-    cmd = [gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-fno-omit-frame-pointer',
-           '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include', '-I' + os.path.join(ROOT, 'include'), '-I' + csrc,
-           '-Wno-deprecated-declarations', '-Wno-unused-result',
-           os.path.join(csrc, 'pv_api.cpp'), os.path.join(csrc, 'pv_api_packets.cpp'),
-           os.path.join(ROOT, 'tests', 'abi_sanitizer', 'engine_stub.cpp'), os.path.join(ROOT, 'tests', 'abi_rational_rate', 'packets_stub.cpp'),
-           os.path.join(ROOT, 'tests', 'abi_rational_rate', 'driver.cpp'), '-o', exe, '-lpthread']
-    build = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    if build.returncode != 0 and 'sanitizer' in build.stderr.lower() and 'cannot find' in build.stderr.lower():
-        pytest.skip('sanitizer runtimes not installed: ' + build.stderr[-300:])
-    assert build.returncode == 0, build.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
-    for k in ('STUB_GPUS', 'STUB_OOM', 'STUB_FAIL_PROCESS', 'STUB_THROW', 'STUB_FRONT_TAPS', 'LD_PRELOAD'):
-        env.pop(k, None)
-    run = subprocess.run([exe, model_file('random', 1234)], capture_output=True, text=True, timeout=300, env=env)
+    run = sanitized_build.run(sanitized_build.build_abi_driver('abi_rational_rate', tmp_path), model_file('random', 1234), timeout=300)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-6000:])

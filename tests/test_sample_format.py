@@ -86,7 +86,7 @@ HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
 def test_format_kernels_build_for_gfx950_without_scratch_or_spills(tmp_path):
     out = tmp_path / 'kns_format.s'
     mk = open(os.path.join(ROOT, 'koala_amd', 'Makefile')).read()
-    assert 'csrc/kns_format.hip' in mk and 'obj/kns_format.o' in mk and 'csrc/pv_api_format.cpp' in mk and 'obj/pv_api_format.o' in mk
+    assert 'csrc/kns_format.hip' in mk and 'obj/kns_format.o' in mk and 'csrc/pv_api_extensions.cpp' in mk and 'obj/pv_api_extensions.o' in mk
     cxx = re.search(r'^CXXFLAGS\s*=\s*(.*)$', mk, re.M).group(1).split()
     subprocess.check_call([HIPCC, '--offload-arch=gfx950'] + [f for f in cxx if f != '-fPIC'] +
                           ['-S', '--cuda-device-only', '-x', 'hip', os.path.join(ROOT, 'koala_amd', 'csrc', 'kns_format.hip'), '-o', str(out)],

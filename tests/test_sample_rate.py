@@ -19,6 +19,7 @@ import pytest
 
 import koala_amd
 import sample_rate_recipe as srr
+import sanitized_build
 from conftest import ROOT, model_file, synth_streams
 
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
@@ -212,21 +213,5 @@ def test_python_refuses_other_rates_and_takes_the_five(random_model, monkeypatch
 
 
 def test_sample_rate_entry_points_under_asan_and_ubsan(tmp_path):
-    gxx = shutil.which('g++')
-    if not gxx or not os.path.isdir('/opt/rocm/include/hip'):
-        pytest.skip('needs g++ and the HIP headers')
-    exe = str(tmp_path / 'sample_rate_driver')
-    cmd = [gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-fno-omit-frame-pointer',
-           '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include', '-I' + os.path.join(ROOT, 'include'),
-           '-I' + os.path.join(ROOT, 'koala_amd', 'csrc'), '-Wno-deprecated-declarations', '-Wno-unused-result',
-           os.path.join(ROOT, 'koala_amd', 'csrc', 'pv_api.cpp'), os.path.join(ROOT, 'tests', 'abi_sanitizer', 'engine_stub.cpp'),
-           os.path.join(ROOT, 'tests', 'abi_sample_rate', 'driver.cpp'), '-o', exe, '-lpthread']
-    build = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    if build.returncode != 0 and 'sanitizer' in build.stderr.lower() and 'cannot find' in build.stderr.lower():
-        pytest.skip('sanitizer runtimes not installed: ' + build.stderr[-300:])
-    assert build.returncode == 0, build.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
-    for k in ('STUB_GPUS', 'STUB_OOM', 'STUB_FAIL_PROCESS', 'STUB_THROW', 'STUB_FRONT_TAPS', 'LD_PRELOAD'):
-        env.pop(k, None)
-    run = subprocess.run([exe, model_file('random', 1234)], capture_output=True, text=True, timeout=300, env=env)
+    run = sanitized_build.run(sanitized_build.build_abi_driver('abi_sample_rate', tmp_path), model_file('random', 1234), timeout=300)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-6000:])
