@@ -362,12 +362,42 @@ PV_API pv_status_t pv_koala_batch_sample_format(const pv_koala_batch_t *object, 
  * channels outside [1, 8], and num_streams that is not a multiple of channels; whatever pv_koala_batch_init_config refuses stays refused
  * with its own message.  The asynchronous entry points, and `asynchronous != 0` in pv_koala_batch_process_call, are refused with
  * PV_STATUS_INVALID_ARGUMENT on a handle whose channels is not 1 (nothing processed).
- * NOT PROVIDED: linked-stereo processing (one mask for all channels of a group: the channels are independent streams), and a planar /
- * interleaved conversion for the single-stream ABI (pv_koala.h is one channel only). */
+ * NOT PROVIDED: a planar / interleaved conversion for the single-stream ABI (pv_koala.h is one channel only). */
 PV_API pv_status_t pv_koala_batch_init_channels(const char *access_key, const char *model_path, const char *device,
                                                 const pv_koala_batch_config_t *config, int32_t channels,
                                                 pv_koala_batch_t **object);
 PV_API pv_status_t pv_koala_batch_channels(const pv_koala_batch_t *object, int32_t *channels);
+
+/* LINKED CHANNELS: one mask per group (eighth extension).  The channels of a group are independent streams: each gets
+ * its own mask, so one spectral bin is attenuated by different amounts in L and R, frame by frame, which moves the stereo image.  With the
+ * link on, the mask applied to bin k of stream g * C + c in a frame is
+ *     m_link[k] = max over c' in 0 .. C - 1 of m[g * C + c'][k],
+ * m the network's raw mask of that frame, all 257 bins: a bin is kept in every channel if any channel holds speech there.  A max of finite
+ * values: exact in both precisions, whatever the order.  Everything behind it is unchanged: the attenuation limit is applied per stream to
+ * m_link (m' = g_s + (1 - g_s) m_link) and Y = m' X is synthesised as ever.
+ *   State.  The network never sees its own output: a linked handle's hidden states, history, feature context and stream records evolve bit
+ *     for bit as the unlinked handle's; only the overlap-add tail and the samples differ.  The link is configuration, not state: no reset,
+ *     held call or record carries it, and state_size is unchanged.
+ *   Frame report.  mask_sum stays the stream's own raw mask (the speech cue is per channel) and e_in is unchanged: both equal the unlinked
+ *     handle's bit for bit; e_out is of the linked m'.
+ *   Identical channels.  A group whose channels carry the same samples and equal state gives exactly the unlinked output.
+ *   Every rate, frame and packet handles, every sample format, both precisions: interleave(linked(deinterleave(pcm))) as above.
+ * pv_koala_batch_set_channel_link: per handle; may change between any two calls and takes effect with the next call, like
+ * pv_koala_batch_set_min_gain; no device work and no wait.  With PV_KOALA_CHANNEL_LINK_NONE the handle is exactly the handle it was: same
+ * routes, kernels and bits.  PV_STATUS_INVALID_ARGUMENT with a message, everything unchanged: a NULL object or out-pointer; a link outside
+ * 0 ... 1; PV_KOALA_CHANNEL_LINK_MAX on a handle whose `channels` is not 2, 4 or 8 (the message names `channels`: a group must lie inside
+ * one 16-row mask tile, so 1, 3, 5, 6 and 7 are refused).  LINK_NONE is accepted on every handle.
+ * A LINKED CALL is refused with PV_STATUS_INVALID_ARGUMENT, nothing processed and state unchanged, with a message that names the group and
+ * the two streams, when
+ *   `hold` differs within a group (a held stream is computed on meaningless input: its mask must not reach its partner);
+ *   `restart` differs within a group, in a packet call;
+ *   a group is out of phase in a packet call: its streams hold different numbers of samples of an unfinished frame (at 44 100 / 22 050 Hz
+ *     their positions in the 441-sample period count too).  That can follow a masked pv_koala_batch_reset or an import_state of one channel,
+ *     which stay legal per stream; a reset or import of the whole group cures it.
+ * Per-frame `reset` may differ within a group: the fresh stream's mask is simply what it is. */
+typedef enum { PV_KOALA_CHANNEL_LINK_NONE = 0, PV_KOALA_CHANNEL_LINK_MAX = 1 } pv_koala_channel_link_t;
+PV_API pv_status_t pv_koala_batch_set_channel_link(pv_koala_batch_t *object, int32_t link);
+PV_API pv_status_t pv_koala_batch_get_channel_link(const pv_koala_batch_t *object, int32_t *link);
 
 PV_API pv_status_t pv_koala_batch_num_streams(const pv_koala_batch_t *object, int32_t *num_streams);
 PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, int32_t *delay_sample);

@@ -12,7 +12,7 @@ import numpy as np
 
 from ._koala import (KoalaError, KoalaInvalidArgumentError, KoalaIOError, PicovoiceStatuses, attenuation_limit_to_gain, load_library,
                      raise_status)
-from .channels import MAX_CHANNELS
+from .channels import LINK_CHANNELS, MAX_CHANNELS
 from .formats import DTYPES, FORMATS
 from .packets import FRACTIONAL_UP, inner_samples
 
@@ -45,7 +45,7 @@ class KoalaBatch(object):
 
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
                  max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0, sample_format: str = 's16',
-                 channels: int = 1) -> None:
+                 channels: int = 1, channel_link: Optional[str] = None) -> None:
         """`sample_rate`: 44100 or 22050 Hz make a packet handle around fractional converters (`packet_samples` > 0 is required; there is
         no frame length, `frame_length` is None, and stream records and the asynchronous calls are refused); otherwise
         8000, 12000, 16000, 24000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
@@ -64,7 +64,9 @@ class KoalaBatch(object):
         the layout in numpy).  The handle splits and joins on the device around the unchanged call: its result is
         channels.interleave(the handle without channels(channels.deinterleave(x))).  Everything per stream -- reset, hold, counts, restart,
         report, gains, records -- stays [num_streams], a packet call's counts must be equal within a group, the device-pointer methods take
-        the same layout, and the asynchronous calls are refused.  Linked-stereo processing (one mask for a group) is not provided."""
+        the same layout, and the asynchronous calls are refused.
+        `channel_link`: None (default) or 'max' -- with 'max' (`channels` 2, 4 or 8) the channels of a group share one mask, the max of their
+        own masks bin by bin, so the stereo image does not move (`set_channel_link`; koala_amd.channels.link_masks states the rule)."""
         if not isinstance(access_key, str) or len(access_key) == 0:
             raise KoalaInvalidArgumentError("`access_key` should be a non-empty string.")
         if not os.path.exists(model_path):
@@ -86,6 +88,7 @@ class KoalaBatch(object):
             raise KoalaInvalidArgumentError("`num_streams` %r is not a multiple of `channels` %d: stream g * channels + c is channel c of group g."
                                             % (num_streams, channels))
         self.channels = channels
+        link = self._link_value(channel_link)  # (checked before the handle is made)
         self.sample_format = sample_format
         self._dtype = DTYPES[sample_format]
         self._dtype_name = np.dtype(self._dtype).name
@@ -108,6 +111,8 @@ class KoalaBatch(object):
                            ('process_chunk_hold', [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
                            ('set_min_gain', [c_void_p, c_int32, c_void_p, c_void_p]),
                            ('get_min_gain', [c_void_p, c_void_p]),
+                           ('set_channel_link', [c_void_p, c_int32]),
+                           ('get_channel_link', [c_void_p, POINTER(c_int32)]),
                            ('process_call', [c_void_p, POINTER(BatchCall)])):
             fn = getattr(lib, 'pv_koala_batch_' + name)
             fn.argtypes = args
@@ -181,6 +186,33 @@ class KoalaBatch(object):
         if not fractional:
             self._check(lib.pv_koala_batch_state_size(self._handle, byref(d)), 'Failed to get the state size')
             self.state_size = d.value
+        if link:
+            try:
+                self.set_channel_link(channel_link)
+            except Exception:
+                self.delete()
+                raise
+
+    def _link_value(self, link):
+        if link is not None and link != 'max':
+            raise KoalaInvalidArgumentError("`channel_link` should be 'max' or None.")
+        if link and self.channels not in LINK_CHANNELS:
+            raise KoalaInvalidArgumentError("`channel_link` 'max' needs a handle whose `channels` is 2, 4 or 8: this handle's `channels` is %d."
+                                            % self.channels)
+        return 1 if link else 0
+
+    def set_channel_link(self, link: Optional[str]) -> None:
+        """'max': from the next call on, the mask applied to every stream of a group is the max of the group's masks, bin by bin
+        (include/pv_koala_batch.h, pv_koala_batch_set_channel_link; `channels` must be 2, 4 or 8).  None: the channels are independent
+        again -- exactly the handle it was.  Configuration, not state: the streams evolve the same either way, only the samples differ.
+        A linked call refuses `hold` (and a packet call `restart`, or a phase) that differs within a group."""
+        self._check(self._lib.pv_koala_batch_set_channel_link(self._handle, self._link_value(link)), 'set_channel_link failed')
+
+    @property
+    def channel_link(self) -> Optional[str]:
+        v = c_int32()
+        self._check(self._lib.pv_koala_batch_get_channel_link(self._handle, byref(v)), 'channel_link failed')
+        return 'max' if v.value else None
 
     def _check(self, status, what):
         if status is not PicovoiceStatuses.SUCCESS:

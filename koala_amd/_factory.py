@@ -38,14 +38,17 @@ def create_batch(
         sample_rate: int = 16000,
         packet_samples: int = 0,
         sample_format: str = 's16',
-        channels: int = 1) -> KoalaBatch:
+        channels: int = 1,
+        channel_link: Optional[str] = None) -> KoalaBatch:
     """`num_streams` independent streams advancing together on one GPU (see KoalaBatch), at 8000, 12000, 16000, 24000, 32000 or 48000 Hz.
     `packet_samples=N` makes a packet handle: streams that take and deliver any number of samples, up to N, per call
     (`KoalaBatch.process_packets`; `max_frames_per_call` is then derived from N).
     `sample_format`: 's16' (default), 'f32', 'ulaw' or 'alaw' -- the handle takes and delivers np.float32 or G.711 np.uint8 arrays,
     converted on the device (`koala_amd.formats` has the codecs).
     `channels=C` (2 ... 8): every array of samples is [num_streams / C, n * C], the C streams of a group interleaved (L R L R ...), split
-    and joined on the device (`koala_amd.channels` has the layout); the streams stay independent, everything per stream stays [num_streams]."""
+    and joined on the device (`koala_amd.channels` has the layout); the streams stay independent, everything per stream stays [num_streams].
+    `channel_link='max'` (`channels` 2, 4 or 8): the channels of a group share one mask, the max of their own, bin by bin
+    (`KoalaBatch.set_channel_link`)."""
     return KoalaBatch(
         access_key=access_key,
         model_path=default_model_path() if model_path is None else model_path,
@@ -57,7 +60,8 @@ def create_batch(
         sample_rate=sample_rate,
         packet_samples=packet_samples,
         sample_format=sample_format,
-        channels=channels)
+        channels=channels,
+        channel_link=channel_link)
 
 
 def available_devices(library_path: Optional[str] = None) -> Sequence[str]:

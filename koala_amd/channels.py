@@ -10,6 +10,7 @@ where the planar handle is the same configuration without channels.  Pure memory
 import numpy as np
 
 MAX_CHANNELS = 8
+LINK_CHANNELS = (2, 4, 8)  # a linked group lies inside one 16-row mask tile
 
 
 def _check(channels):
@@ -40,4 +41,18 @@ def interleave(planar, channels):
     return np.ascontiguousarray(p.reshape(G, C, n).transpose(0, 2, 1)).reshape(G, n * C)
 
 
-__all__ = ['MAX_CHANNELS', 'deinterleave', 'interleave']
+def link_masks(mask, channels):
+    """The rule of linked channels (include/pv_koala_batch.h, LINKED CHANNELS; DESIGN.md section 2, eighth extension): mask [G*C, ...] ->
+    the same shape, row g*C + c = the max over rows g*C .. g*C + C - 1, element by element.  A max of finite values: exact in any float
+    dtype, whatever the order.  C must be 2, 4 or 8."""
+    C = _check(channels)
+    if C not in LINK_CHANNELS:
+        raise ValueError("linked channels need `channels` 2, 4 or 8, not %d" % C)
+    m = np.asarray(mask)
+    if m.ndim < 1 or m.shape[0] % C:
+        raise ValueError("expected an array of shape [G*%d, ...]" % C)
+    grouped = m.reshape((m.shape[0] // C, C) + m.shape[1:])
+    return np.ascontiguousarray(np.broadcast_to(grouped.max(axis=1, keepdims=True), grouped.shape)).reshape(m.shape)
+
+
+__all__ = ['MAX_CHANNELS', 'LINK_CHANNELS', 'deinterleave', 'interleave', 'link_masks']

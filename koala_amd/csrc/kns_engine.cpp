@@ -1559,6 +1559,7 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
         sy.rs_pitch = rs_pitch;
         sy.rs_t0 = rs_t0 + t0c;
         sy.min_gain = slice.min_gain;
+        sy.link = slice.link;
         sy.report = slice.d_report ? slice.d_report + (size_t) t0c * 4 : nullptr;  // (like `out`: the slice's first frame, rows T frames apart)
         launch_synthesis(sy, st);
     };
@@ -1852,6 +1853,10 @@ bool Engine::async_wait(int max_in_flight, std::string *err) {
 // once call n - 2's copy-out has -- both waited for on the device, by the stream that needs it.  A synchronous call of that size cannot
 // hide its first copy-in and last copy-out and has to cut its kernels into short, less efficient sub-chunks (process_host_pipelined).
 Status Engine::process_host_async(const Call &c, std::string *err) {
+    if (c.channel_link) {  // (its slices carry no link; the owner refuses the asynchronous calls on a handle with channels anyway)
+        *err = "linked channels are not available in asynchronous calls.";
+        return Status::kBadArgument;
+    }
     if (fmt_ != kFmtS16) {
         *err = "asynchronous calls are not available on a handle whose sample format is not S16.";
         return Status::kBadArgument;
@@ -1975,10 +1980,17 @@ bool Engine::run_call(const Call &c, std::string *err) {
     const size_t rbytes = (size_t) B_ * T * 16;
     const float *min_gain = nullptr;  // (this call's attenuation limit on the device, on the handle's stream in front of everything below)
     if (!begin_min_gain(c, &min_gain, err)) return false;
+    // (linked channels: such a handle's calls arrive here with device pointers -- process() has split the channels into device rows -- so
+    // the host routes below, the one-frame graph among them, never see a linked call: no graph is captured with the linked kernel)
+    const int link = c.channel_link ? ch_ : 0;
+    if (link && (!min_gain || kin != kPtrDevice)) {  // (never quietly unlinked: the host routes below build their slices without the link)
+        *err = !min_gain ? "a linked call carries the handle's minimum gains." : "a linked call runs on device rows only.";
+        return false;
+    }
     if (kin == kPtrDevice) {
         const size_t n = (size_t) B_ * T * kFrame;
         const bool overlap = pcm < out + n && out < pcm + n;
-        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table, min_gain, report}, err);
+        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table, min_gain, report, link}, err);
     }
     if (T > host_chunk_ && bytes >= host_pipeline_min_bytes_) {
         const char *pa = (const char *) pcm, *pb = (const char *) out;
@@ -2010,7 +2022,7 @@ bool Engine::run_call(const Call &c, std::string *err) {
     }
     if (!begin_resets(T, c.resets, &table, err)) return false;
     memcpy(h_in_, pcm, bytes);
-    if (T == 1 && use_graph_ && stream_ == own_stream_ && !profiling_) {
+    if (T == 1 && use_graph_ && stream_ == own_stream_ && !profiling_ && !link) {
         // frame-by-frame streaming: (copy-in,) the kernels of one frame (and copy-out) replayed as one hipGraph
         // A captured frame has the state buffers it reads and writes baked in: one graph per combination of the three
         // ping-pong indices.  (A single-frame call leaves history and tail in place and flips the hidden state only, but
@@ -2102,7 +2114,7 @@ bool Engine::run_call(const Call &c, std::string *err) {
         }
     }
     if (hipMemcpyAsync(d_in_, h_in_, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) goto fail;
-    if (!run_device({0, T, d_in_, d_out_, true, &table, min_gain, report ? d_report_ : nullptr}, err)) return false;
+    if (!run_device({0, T, d_in_, d_out_, true, &table, min_gain, report ? d_report_ : nullptr, link}, err)) return false;
     if (hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
     if (report && hipMemcpyAsync(h_report_, d_report_, rbytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
     if (hipStreamSynchronize(stream_) != hipSuccess) goto fail;
@@ -2154,6 +2166,7 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
     {
         Call inner{T, d_in_, d_out_, c.resets};
         inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
+        inner.channel_link = c.channel_link;
         inner.report = c.report;
         const RsStage si = rs_stage_in(rate_), so = rs_stage_out(rate_);
         ResampleArgs a;
@@ -2424,6 +2437,25 @@ Status Engine::process(const Call &c, std::string *err) {
         *err = "held streams are not combined with per-frame stream resets in one call.";
         return Status::kBadArgument;
     }
+    if (c.channel_link) {  // linked channels: the handle, the table the linked kernels read, and a group that is held as a whole or not at all
+        if (!channel_link_ok(ch_)) {
+            *err = "linked channels need a handle whose `channels` is 2, 4 or 8 (this handle's `channels` = " + std::to_string(ch_) + ").";
+            return Status::kBadArgument;
+        }
+        if (!c.min_gain) {
+            *err = "a linked call carries the handle's minimum gains (all zero where no limit is in force).";
+            return Status::kBadArgument;
+        }
+        for (int b = 0; c.hold && b < B_; ++b) {
+            const int first = b - b % ch_;
+            if ((c.hold[b] != 0) != (c.hold[first] != 0)) {
+                *err = "`hold[" + std::to_string(b) + "]` = " + std::to_string((int) c.hold[b]) + " differs from `hold[" + std::to_string(first) + "]` = " +
+                       std::to_string((int) c.hold[first]) + ": streams " + std::to_string(first) + " and " + std::to_string(b) + " are channels of group " +
+                       std::to_string(b / ch_) + ", whose masks are linked (`channels` = " + std::to_string(ch_) + "): a group is held as a whole.";
+                return Status::kBadArgument;
+            }
+        }
+    }
     if (rate_ == kRate16k && fmt_ == kFmtS16 && ch_ == 1) return process_frames(c, err);  // the plain handle
     (void) hipSetDevice(device_);
     bool host, late = false;
@@ -2583,6 +2615,32 @@ Status Engine::packet_check(const PacketCall &c, int most, int ch, bool *any_res
             return Status::kBadArgument;
         }
     }
+    // linked channels (ch_: the handle's, also in a fractional handle's inner call): the sub-calls hold the streams by their frame count, so a
+    // group's streams must complete the same frames -- equal `restart`, equal phase (the mirrors of fill and, at 44.1 / 22.05 kHz, N mod 441)
+    if (c.channel_link && (!channel_link_ok(ch_) || !c.min_gain)) {
+        *err = !c.min_gain ? "a linked call carries the handle's minimum gains (all zero where no limit is in force)."
+                           : "linked channels need a handle whose `channels` is 2, 4 or 8 (this handle's `channels` = " + std::to_string(ch_) + ").";
+        return Status::kBadArgument;
+    }
+    for (int b = 0; c.channel_link && b < B_; ++b) {
+        const int first = b - b % ch_;
+        const std::string who = ": streams " + std::to_string(first) + " and " + std::to_string(b) + " are channels of group " + std::to_string(b / ch_) +
+                                ", whose masks are linked (`channels` = " + std::to_string(ch_) + ")";
+        const int rb = c.restart && c.restart[b] ? 1 : 0, rf = c.restart && c.restart[first] ? 1 : 0;
+        if (rb != rf) {
+            *err = "`restart[" + std::to_string(b) + "]` = " + std::to_string(rb) + " differs from `restart[" + std::to_string(first) + "]` = " +
+                   std::to_string(rf) + who + ": a group restarts as a whole.";
+            return Status::kBadArgument;
+        }
+        if (rb) continue;  // (fresh before this packet: phase 0, both)
+        if (pk_fill_[b] != pk_fill_[first] || (fr_rate_ && fr_phase_[b] != fr_phase_[first])) {
+            *err = "group " + std::to_string(b / ch_) + " is out of phase" + who + ", and stream " + std::to_string(b) + " holds " +
+                   std::to_string(pk_fill_[b]) + " samples of an unfinished frame where stream " + std::to_string(first) + " holds " +
+                   std::to_string(pk_fill_[first]) + (fr_rate_ ? " (or their positions in the 441-sample period differ)" : "") +
+                   ": reset or import the whole group.";
+            return Status::kBadArgument;
+        }
+    }
     return Status::kOk;
 }
 
@@ -2733,6 +2791,7 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string
         Call inner{c1 - c0, d_pk_in_ + (size_t) B_ * F * c0, d_pk_out_ + (size_t) B_ * F * c0};
         inner.hold = held ? hold.data() : nullptr;
         inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
+        inner.channel_link = c.channel_link;  // (packet_check: a group's streams share k_b, so a sub-call holds a group as a whole)
         inner.report = c.report ? d_pk_rep_ + (size_t) B_ * c0 * 4 : nullptr;
         if (process_frames(inner, err) != Status::kOk) return Status::kRuntime;
     }
@@ -2848,6 +2907,7 @@ Status Engine::run_fractional(const PacketCall &c, std::string *err) {
     }
     // the inner call: an S16 call on device rows, without restarts (done above); its report rows and frame counts are this call's
     PacketCall in16{pk_max_, inner.data(), d_fr_in_, d_fr_out_, nullptr, io.report, io.report_frames, k.data(), c.min_gain, c.min_gain_rev};
+    in16.channel_link = c.channel_link;  // (the inner call's rows are the engine's: its `ch` is 1, the link is the handle's)
     st = run_packet_call(in16, kFmtS16, 1, err);
     if (st != Status::kOk) return st;
     a.in = d_fr_out_;

@@ -62,6 +62,11 @@ struct Call {
     // forms in a fixed order); complete when `out` is.  An output only: the streams' evolution and `out` do not depend on whether it was asked
     // for.  Held streams' rows are unspecified.  nullptr: the plain call -- same route, same kernels, same bits.
     float *report = nullptr;
+    // Linked channels (eighth extension; a handle with channels() == 2, 4 or 8 only): non-zero, and the mask applied to
+    // a stream in every frame of the call is the max over the masks of its group's streams, bin by bin.  The call then carries `min_gain`
+    // (all zero where no limit is in force: the linked kernels read the table), and `hold` must be equal within a group.  The owner's
+    // setting, like the limit: the engine keeps nothing of it between calls.  0: the plain call -- same route, same kernels, same bits.
+    int channel_link = 0;
 };
 
 // kBadArgument: a stream list, a record or a combination of Call members that the engine refused before it touched anything (the C ABI
@@ -82,6 +87,7 @@ struct PacketCall {
     int32_t *frames = nullptr;         // host [num_streams] or nullptr, out: frames completed by the call
     const float *min_gain = nullptr;   // as Call's
     unsigned min_gain_rev = 0;
+    int channel_link = 0;              // as Call's; `restart`, and the streams' phase (the mirrors of fill and of N mod 441), must be equal within a group
 };
 
 class Engine {
@@ -155,6 +161,8 @@ public:
     // C == 1 allocates and changes nothing.
     bool enable_channels(int C, std::string *err);
     int channels() const { return ch_; }
+    // (linked channels, Call::channel_link: a group must lie inside one 16-row mask tile)
+    static bool channel_link_ok(int C) { return C == 2 || C == 4 || C == 8; }
 
     void profile_enable(bool on);
     bool profile_read(double *ms, int64_t *launches, std::string *err);
@@ -246,6 +254,7 @@ private:
         ResetTable *resets;
         const float *min_gain;  // the call's per-stream minimum gains on the device [Bpad] (begin_min_gain), nullptr: no limit in force
         float *d_report = nullptr;  // the slice's frame report [B][T][4] (device-visible memory, rows T frames apart), nullptr: not asked for
+        int link = 0;  // the call's linked channels: channels() when Call::channel_link is set (then min_gain is not null), else 0
     };
     bool run_device(const Slice &s, std::string *err);
     void *dalloc(size_t bytes, bool zero);

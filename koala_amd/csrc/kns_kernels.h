@@ -99,6 +99,10 @@ struct SynthesisArgs {
     // frame).  Points at the slice's first frame like `out`, rows `pitch` frames apart (0: T).  Selects the kernels' kReport arm (a null
     // pointer: today's instantiations)
     float *report = nullptr;
+    // optional: linked channels (eighth extension): C = 2, 4 or 8, the rows of a group g C .. g C + C - 1 lie in one mask
+    // tile, and every row's mask value becomes the max over its group's, in all 257 bins, behind the report's mask_sum and in front of the
+    // minimum gain.  Selects the kernels' kLink arm, which reads `min_gain` (not null then); 0: today's instantiations
+    int link = 0;
 };
 void launch_synthesis(const SynthesisArgs &a, hipStream_t s);
 

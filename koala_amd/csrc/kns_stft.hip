@@ -287,6 +287,13 @@ __device__ __forceinline__ float min_gain_mask(float g, float u, float m) {
     return g + p;
 }
 
+// kLink (SynthesisArgs::link; the linked kernels below): the max of two mask values.  They are sigmoids: finite and not below +0, where the order of the bit patterns is the order of the values -- one
+// v_max_i32, exact; fmaxf on values that come straight from memory is three v_max_f32 in IEEE mode (it quiets each operand first)
+__device__ __forceinline__ float link_max(float a, float b) {
+    const int x = __builtin_bit_cast(int, a), y = __builtin_bit_cast(int, b);
+    return __builtin_bit_cast(float, __builtin_elementwise_max(x, y));
+}
+
 // kReport (calls that ask for the frame report, SynthesisArgs::report; DESIGN.md section 2, step 4, second extension): three sums over the
 // row's 257 bins per emitted frame -- |X|^2, |Y|^2 and the raw mask -- formed where x[], y[] and mk[] are live, in the one order the spec
 // fixes: every lane its column's chain, then a butterfly over the row's lanes.
@@ -328,48 +335,62 @@ __device__ __forceinline__ float report_mask_sum(const float (&m)[17], int c) {
 // kMaskH: the mask travels as fp16 C fragments (bf16 configuration), else fp32
 template <bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets = false, bool kMinGain = false>
 __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_kernel(SynthesisArgs g) {
-    constexpr bool kReport = false;
+    constexpr bool kReport = false, kLink = false;
 #include "kns_stft_synthesis.inc"
 }
 // the same forms with the frame report: kernels of their own name, the same text (kns_stft_synthesis.inc) -- a call that asks for no report
 // runs what it always ran
 template <bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets, bool kMinGain>
 __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_report_kernel(SynthesisArgs g) {
-    constexpr bool kReport = true;
+    constexpr bool kReport = true, kLink = false;
+#include "kns_stft_synthesis.inc"
+}
+// kLink (handles with channels whose link is on, SynthesisArgs::link = C; DESIGN.md section 2, eighth extension): the mask of every bin
+// becomes the max over the C rows of the row's group, between the raw mask's sum and m'.  A kernel of its own name again, so the forms
+// above stay the instructions they were.  The arm implies kMinGain (an all-zero gain table is exact: 0 + 1 m == m), and C is a
+// wave-uniform argument, not a template parameter.  The recomputing forms exist as report forms only: without the report hipcc's
+// allocation of them spilled in every variant tried, so a recomputing call that asks for no report gives the
+// report's descriptor no range and the hardware drops the stores.  9 report forms + 5 plain stored-spectrum forms = 14 instantiations.
+template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets>
+__global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_link_kernel(SynthesisArgs g) {
+    static_assert(kReport || !kRecompute, "linked, recomputed: report forms only");
+    constexpr bool kMinGain = true, kLink = true;
 #include "kns_stft_synthesis.inc"
 }
 
-template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets, bool kMinGain>
+template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets, bool kMinGain, bool kLink>
 static void launch_synthesis_form(const SynthesisArgs &a, const dim3 grid, int threads, size_t lds, hipStream_t s) {
-    if constexpr (kReport)
+    if constexpr (kLink)
+        hipLaunchKernelGGL((synthesis_link_kernel<kReport || kRecompute, kRecompute, kMaskH, kMaskIn, kResets>), grid, dim3(threads), lds, s, a);
+    else if constexpr (kReport)
         hipLaunchKernelGGL((synthesis_report_kernel<kRecompute, kMaskH, kMaskIn, kResets, kMinGain>), grid, dim3(threads), lds, s, a);
     else
         hipLaunchKernelGGL((synthesis_kernel<kRecompute, kMaskH, kMaskIn, kResets, kMinGain>), grid, dim3(threads), lds, s, a);
 }
 
 // the forms of one arm (kMinGain: with or without the per-stream minimum gain; kReport: with or without the frame report); the plain arm's
-// are the kernels of a handle without a limit in a call that asks for no report
-template <bool kMinGain, bool kReport>
+// are the kernels of a handle without a limit in a call that asks for no report; kLink: the linked kernels, which carry the gain
+template <bool kMinGain, bool kReport, bool kLink = false>
 static void launch_synthesis_arm(const SynthesisArgs &a, const dim3 grid, size_t lds, hipStream_t s) {
     if (a.resets) {  // (calls with per-frame stream resets: the reset arm; the engine does not put the mask head inside then)
         if (a.recompute && a.mask_fp16)
-            launch_synthesis_form<kReport, true, true, false, true, kMinGain>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, true, true, false, true, kMinGain, kLink>(a, grid, 256, lds, s);
         else if (a.recompute)
-            launch_synthesis_form<kReport, true, false, false, true, kMinGain>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, true, false, false, true, kMinGain, kLink>(a, grid, 256, lds, s);
         else if (a.mask_fp16)
-            launch_synthesis_form<kReport, false, true, false, true, kMinGain>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, false, true, false, true, kMinGain, kLink>(a, grid, 256, lds, s);
         else
-            launch_synthesis_form<kReport, false, false, false, true, kMinGain>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, false, false, false, true, kMinGain, kLink>(a, grid, 256, lds, s);
     } else if (a.mask_w && !a.recompute && a.mask_fp16 && a.T == 1)
-        launch_synthesis_form<kReport, false, true, true, false, kMinGain>(a, grid, 512, lds + kMaskTiles * 512, s);
+        launch_synthesis_form<kReport, false, true, true, false, kMinGain, kLink>(a, grid, 512, lds + kMaskTiles * 512, s);
     else if (a.recompute && a.mask_fp16)
-        launch_synthesis_form<kReport, true, true, false, false, kMinGain>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, true, true, false, false, kMinGain, kLink>(a, grid, 256, lds, s);
     else if (a.recompute)
-        launch_synthesis_form<kReport, true, false, false, false, kMinGain>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, true, false, false, false, kMinGain, kLink>(a, grid, 256, lds, s);
     else if (a.mask_fp16)
-        launch_synthesis_form<kReport, false, true, false, false, kMinGain>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, false, true, false, false, kMinGain, kLink>(a, grid, 256, lds, s);
     else
-        launch_synthesis_form<kReport, false, false, false, false, kMinGain>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, false, false, false, false, kMinGain, kLink>(a, grid, 256, lds, s);
 }
 
 void launch_synthesis(const SynthesisArgs &a, hipStream_t s) {
@@ -379,7 +400,9 @@ void launch_synthesis(const SynthesisArgs &a, hipStream_t s) {
     (void) hipFuncSetAttribute((const void *) synthesis_kernel<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
     (void) hipFuncSetAttribute((const void *) synthesis_report_kernel<true, true, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
 #endif
-    if (a.report)
+    if (a.link)  // (the engine hands a linked launch the gain table, all zero where no limit is in force)
+        a.report ? launch_synthesis_arm<true, true, true>(a, grid, lds, s) : launch_synthesis_arm<true, false, true>(a, grid, lds, s);
+    else if (a.report)
         a.min_gain ? launch_synthesis_arm<true, true>(a, grid, lds, s) : launch_synthesis_arm<false, true>(a, grid, lds, s);
     else if (a.min_gain)
         launch_synthesis_arm<true, false>(a, grid, lds, s);

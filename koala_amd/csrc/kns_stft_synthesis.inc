@@ -1,7 +1,8 @@
 // kns_stft_synthesis.inc -- the body of the synthesis kernels of kns_stft.hip, included once per kernel template: synthesis_kernel
 // (kReport = false) and synthesis_report_kernel (kReport = true).  Text, not a function: the kernels of a call without a report must be the
 // instructions they were before the report existed (tools/asm_same.py), and a body inlined into two kernels through a function call was
-// not -- hipcc ordered and allocated it differently.  In scope: g (SynthesisArgs), kRecompute, kMaskH, kMaskIn, kResets, kMinGain, kReport.
+// not -- hipcc ordered and allocated it differently.  In scope: g (SynthesisArgs), kRecompute, kMaskH, kMaskIn, kResets, kMinGain, kReport,
+// kLink.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!kMaskIn || (kMaskH && !kRecompute), "mask head inside: bf16, stored spectrum");
     static_assert(!kMaskIn || !kResets, "resets: multi-frame form only");
@@ -96,6 +97,31 @@
             m[k2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mr, mlane, k2 * 1024u, 0));
         m[16] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mr, ((unsigned) (wave * 16) * 4u + (unsigned) q) * 4u, 16 * 1024u, 0));
     };
+    // kLink: the 17 mask values of a partner row of this lane's group, frame t -- the fetch above for another row of the tile (elem: the
+    // partner's element of tiles 0..15, (row' >> 2) * 64 + c * 4 + (row' & 3); elem_n: of tile 16's column 0).  The words are the ones the
+    // wave pair's lanes read their own values from
+    auto mask_partner = [&](float (&m)[17], int t, unsigned elem, unsigned elem_n) {
+        if (kMaskIn) {
+            const _Float16 *ml = (const _Float16 *) (smem + kOffStftEnd);
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2) m[k2] = (float) ml[k2 * 256 + elem];
+            m[16] = (float) ml[16 * 256 + elem_n];
+            return;
+        }
+        if (kMaskH) {
+            const __amdgpu_buffer_rsrc_t mr =
+                make_rsrc((const char *) g.mask + ((size_t) t * mtiles + mt) * kMaskTiles * 512, kMaskTiles * 512);
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2)
+                m[k2] = (float) __builtin_bit_cast(_Float16, __builtin_amdgcn_raw_buffer_load_b16(mr, elem * 2u, k2 * 512u, 0));
+            m[16] = (float) __builtin_bit_cast(_Float16, __builtin_amdgcn_raw_buffer_load_b16(mr, elem_n * 2u, 16 * 512u, 0));
+            return;
+        }
+        const __amdgpu_buffer_rsrc_t mr = make_rsrc(g.mask + ((size_t) t * mtiles + mt) * kMaskTiles * 256, kMaskTiles * 1024);
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) m[k2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mr, elem * 4u, k2 * 1024u, 0));
+        m[16] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mr, elem_n * 4u, 16 * 1024u, 0));
+    };
     cpx xs[16], xsn[16];
     auto spec_fetch = [&](cpx (&dst)[16], int t) {
         const f32x4 *spec = (const f32x4 *) g.spec + ((size_t) t * g.Bpad + b) * 128;
@@ -168,7 +194,8 @@
             const int row0 = mt * 16 + wave * 4;
             const int rows_ok = row0 < g.B ? min(4, g.B - row0) : 0;
             const unsigned rep_row = (unsigned) (g.pitch ? g.pitch : g.T) * 16u;  // (bytes between two streams' rows: at most 2^20 frames)
-            const unsigned rspan = emit && rows_ok ? (unsigned) (rows_ok - 1) * rep_row + 16u : 0u;
+            // (kLink: the recomputing linked kernels are report forms only; a call that asks for no report has no rows in range)
+            const unsigned rspan = emit && rows_ok && (!kLink || g.report) ? (unsigned) (rows_ok - 1) * rep_row + 16u : 0u;
             // (wave-uniform by construction; said explicitly, since hipcc otherwise keeps the loop-invariant product in a vector register)
             return make_rsrc((const char *) g.report + (size_t) row0 * rep_row + (size_t) t * 16, (unsigned) __builtin_amdgcn_readfirstlane((int) rspan));
         };
@@ -178,6 +205,19 @@
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, report_energy(x, x[0].x, x[0].y, c)), ro, roff, 0u, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, report_mask_sum(mk, c)), ro, roff, 8u, 0);
             __builtin_amdgcn_raw_buffer_store_b32(0, ro, roff, 12u, 0);
+        }
+        // (kLink: m becomes the max over the rows of the lane's group, rows (row & -C) .. + C - 1 of the tile = row ^ j, j = 1 .. C - 1.  Here,
+        // behind the raw mask's sum and in front of m', for the reason given at kMinGain.  C is wave-uniform: a scalar loop over the partners,
+        // one partner's 17 values at a time, so the arm costs 17 registers whatever C is.  An element index is wave * 64 + c * 4 + q: the
+        // partner's differs from the lane's own in the wave bit j >> 2 and the value bits j & 3)
+        if (kLink) {
+            for (int j = 1; j < g.link; ++j) {
+                const unsigned flip = (unsigned) (((j >> 2) << 6) | (j & 3));
+                float pm[17];
+                mask_partner(pm, t, (mlane >> 2) ^ flip, ((unsigned) (wave * 16) * 4u + (unsigned) q) ^ flip);
+#pragma unroll
+                for (int k2 = 0; k2 < 17; ++k2) mk[k2] = link_max(mk[k2], pm[k2]);
+            }
         }
         if (kMinGain) {
 #pragma unroll

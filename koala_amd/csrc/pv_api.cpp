@@ -143,10 +143,11 @@ pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std:
 
 // one call that advances the streams (arguments already checked), under the handle's attenuation limit
 pv_status_t advance(kns::Engine *engine, const MinGain &limit, kns::Call call, bool async = false) {
-    if (limit.any) {
+    if (limit.any || limit.link) {
         call.min_gain = limit.gain.data();
         call.min_gain_rev = limit.rev;
     }
+    call.channel_link = limit.link;
     return guarded([&] {
         std::string err;
         const kns::Status status = async ? engine->process_host_async(call, &err) : engine->process(call, &err);

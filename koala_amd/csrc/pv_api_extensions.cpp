@@ -1,7 +1,7 @@
 // pv_api_extensions.cpp -- the C ABI of the batch handles that are made above pv_koala_batch_init_rate (include/pv_koala_batch.h; DESIGN.md
 // section 2, fourth to seventh extension): packet handles (pv_koala_batch_init_packets, _is_packet_handle, _process_packets), sample formats
 // and the handles at 44 100 and 22 050 Hz (pv_koala_batch_init_config, _sample_format) and channels (pv_koala_batch_init_channels,
-// _channels).  Each constructor calls the one below it and then enables its feature on the engine behind the finished handle; the
+// _channels, _set_channel_link, _get_channel_link).  Each constructor calls the one below it and then enables its feature on the engine behind the finished handle; the
 // processing entry points (pv_api.cpp, and _process_packets here) read the engine and the handle's two own values, sample_rate and
 // packet_samples.
 #include "pv_api_internal.h"
@@ -91,10 +91,11 @@ PV_API pv_status_t pv_koala_batch_process_packets(pv_koala_batch_t *object, cons
         return PV_STATUS_INVALID_ARGUMENT;
     }
     kns::PacketCall c{call->max_samples, call->counts, call->pcm, call->enhanced, call->restart, call->report, call->report_frames, call->frames};
-    if (object->limit.any) {
+    if (object->limit.any || object->limit.link) {
         c.min_gain = object->limit.gain.data();
         c.min_gain_rev = object->limit.rev;
     }
+    c.channel_link = object->limit.link;
     return kns_api::guarded([&] {
         std::string err;
         const kns::Status status = object->engine->run_packets(c, &err);
@@ -208,5 +209,37 @@ PV_API pv_status_t pv_koala_batch_channels(const pv_koala_batch_t *object, int32
         return PV_STATUS_INVALID_ARGUMENT;
     }
     *channels = object->engine->channels();
+    return PV_STATUS_SUCCESS;
+}
+
+// The link of a handle's channels (eighth extension): a value of the handle that every call carries to the engine, like
+// the attenuation limit -- no device work, no wait; the next call is the first to see it.
+PV_API pv_status_t pv_koala_batch_set_channel_link(pv_koala_batch_t *object, int32_t link) {
+    kns_api::clear_errors();
+    if (!object) {
+        push_error(0x64, "Argument `object` is NULL.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (link != PV_KOALA_CHANNEL_LINK_NONE && link != PV_KOALA_CHANNEL_LINK_MAX) {
+        push_error(0x66, "`link` %d is not one of PV_KOALA_CHANNEL_LINK_NONE, _MAX (0 ... 1).", link);
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    const int channels = object->engine->channels();
+    if (link == PV_KOALA_CHANNEL_LINK_MAX && !kns::Engine::channel_link_ok(channels)) {
+        push_error(0x66, "PV_KOALA_CHANNEL_LINK_MAX needs a handle whose `channels` is 2, 4 or 8: this handle's `channels` is %d, and a group must "
+                         "lie inside one 16-row mask tile.", channels);
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    object->limit.link = link;
+    return PV_STATUS_SUCCESS;
+}
+
+PV_API pv_status_t pv_koala_batch_get_channel_link(const pv_koala_batch_t *object, int32_t *link) {
+    kns_api::clear_errors();
+    if (!object || !link) {
+        push_error(0x64, "Argument `%s` is NULL.", object ? "link" : "object");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    *link = object->limit.link;
     return PV_STATUS_SUCCESS;
 }

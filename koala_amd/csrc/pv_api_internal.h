@@ -1,5 +1,5 @@
 // pv_api_internal.h -- what the translation units of the C ABI share: the handles behind the opaque pointers, the calling thread's error
-// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_extensions.cpp (packet handles, sample formats, channels) uses it.
+// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_extensions.cpp (packet handles, sample formats, channels and their link) uses it.
 // Nothing here leaves the library.
 #pragma once
 
@@ -18,6 +18,9 @@ struct MinGain {
     std::vector<float> gain;  // [num_streams], every value in [0, 1]
     unsigned rev = 0;         // counts the accepted changes: the engine uploads the table when it has not seen this one
     bool any = false;         // some gain is non-zero (none: the calls are the plain calls, no table at all)
+    // Linked channels (pv_koala_batch_set_channel_link; batch handles only): travels with the limit because a linked call carries the gains
+    // whether or not any is non-zero -- the linked kernels read the table (kns::Call::channel_link)
+    int link = 0;
 };
 struct pv_koala {
     kns::Engine *engine;

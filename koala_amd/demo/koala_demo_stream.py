@@ -156,7 +156,7 @@ def run_channels(args):
     (`koala_amd.create_batch(..., packet_samples=N, channels=C)`: split and joined on the device), at --sample_rate, for instance
     `--sample_rate 44100 --channels 2`.  With --input_path / --output_path: a C-channel 16-bit WAV of that rate in, one out.  Otherwise raw
     interleaved samples of --sample_format (s16 by default) on stdin, the enhanced stream in the same form on stdout.  Every channel is
-    enhanced on its own: there is no linked-stereo processing.  Messages go to stderr."""
+    enhanced on its own unless --link is given (`channel_link='max'`: one mask per group, C = 2, 4 or 8).  Messages go to stderr."""
     import os
     from koala_amd import formats
     C, rate, fmt = args.channels, args.sample_rate, args.sample_format or 's16'
@@ -182,7 +182,8 @@ def run_channels(args):
             write = lambda b: (sys.stdout.buffer.write(b), sys.stdout.buffer.flush())
         batch = koala_amd.create_batch(args.access_key, C, precision=args.precision or os.environ.get('KOALA_AMD_PRECISION', 'fp32'),
                                        model_path=args.model_path, device=args.device, library_path=args.library_path,
-                                       sample_rate=rate, packet_samples=n, sample_format=fmt, channels=C)
+                                       sample_rate=rate, packet_samples=n, sample_format=fmt, channels=C,
+                                       channel_link='max' if args.link else None)
         batch.set_attenuation_limit(args.attenuation_limit_db)
         samples = 0
         try:
@@ -230,6 +231,8 @@ def main(argv=None):
     ap.add_argument('--channels', type=int, default=1, choices=range(1, 9), metavar='C',
                     help='C interleaved channels (raw on stdin and stdout, or C-channel WAV files) at --sample_rate through a packet '
                          'handle that splits and joins on the device; every channel is enhanced on its own')
+    ap.add_argument('--link', action='store_true',
+                    help="with --channels 2, 4 or 8: one mask per group, the max of the channels' own (the stereo image does not move)")
     ap.add_argument('--show_devices', action='store_true')
     args = ap.parse_args(argv)
 
