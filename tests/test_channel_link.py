@@ -66,6 +66,33 @@ def test_recipe_identical_channels_give_the_unlinked_oracle_output_and_one_chann
             LinkRecipe(model, 6, C1)
 
 
+def test_recipe_groups_are_independent_of_each_other():
+    """the rule never looks outside a group: the recipe on G groups gives, group by group, what the recipe on that group alone gives --
+    samples and report rows, with gains and per-frame resets that differ within the groups.  What the lone-group references of
+    tests/test_gpu_channel_link_routes.py (packet handles whose groups are out of phase) rest on."""
+    model, T = model_file('random'), 3
+    for C, G in ((2, 4), (8, 2)):
+        B = G * C
+        x = [synth_streams(B, T, 7 + k) for k in range(2)]
+        gains = np.resize(np.array([0.0, 0.5, 1.0, 0.25, 0.0], np.float32), B)
+        rs = np.zeros((B, T), np.uint8)
+        rs[1, 1] = rs[B - 1, 2] = rs[C, 0] = 1
+        args = [(None, None), (gains, rs)]
+        whole = LinkRecipe(model, B, C)
+        got = [whole.process(x[k], *args[k]) for k in range(2)]
+        for g in range(G):
+            rows = slice(g * C, (g + 1) * C)
+            alone = LinkRecipe(model, C, C)
+            for k in range(2):
+                gk, rk = args[k]
+                y, rep = alone.process(x[k][rows], None if gk is None else gk[rows], None if rk is None else rk[rows])
+                assert np.array_equal(got[k][0][rows], y), (C, g, k)
+                assert np.array_equal(got[k][1][rows].view(np.uint32), rep.view(np.uint32)), (C, g, k)
+        # (not vacuous: another group's samples would have changed these rows had they been linked across the boundary)
+        other = LinkRecipe(model, B, 2 * C if C == 2 else 4).process(x[0])[0]
+        assert not np.array_equal(other, got[0][0])
+
+
 def test_symbols_are_exported_and_declared_and_the_config_struct_did_not_grow(native_library):
     header = open(os.path.join(ROOT, 'include', 'pv_koala_batch.h')).read()
     for path in (native_library, koala_amd.developer_library_path()):

@@ -7,8 +7,9 @@ B = 24 streams are two mask tiles, the second ragged (8 rows); C = 8 makes group
 tests/channel_link_recipe.LinkRecipe (the oracle's stages and the rule in numpy).  In bf16 the GPU's raw masks are not the oracle's, so
 the linked handle L is compared with == against oracle.synthesis(spectrum, link_masks(the mask tap of an unlinked twin U), tail) per stream
 from a reset: the synthesis stage is fp32 and exact in both precisions.  The one-frame bf16 route forms its mask inside the synthesis launch
-(kMaskIn), where it never leaves LDS and no tap serves it: that route is covered by the identical-channels test, in which a wrong LDS index
-or wave flip picks up another group's mask.  A handle with channels runs on device rows whatever the caller's pointers are, so its one-frame
+(kMaskIn), where it never leaves LDS and no tap serves it: that route is covered with distinct channels by
+tests/test_gpu_channel_link_routes.py (one-frame calls == one long call that is held to the tapped-mask reference, on the small and the quad
+route), which also walks the other routes, segment lengths and packet phases this module's one size does not reach.  A handle with channels runs on device rows whatever the caller's pointers are, so its one-frame
 calls never take the host route's graph.
 """
 import numpy as np
