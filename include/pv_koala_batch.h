@@ -399,6 +399,33 @@ typedef enum { PV_KOALA_CHANNEL_LINK_NONE = 0, PV_KOALA_CHANNEL_LINK_MAX = 1 } p
 PV_API pv_status_t pv_koala_batch_set_channel_link(pv_koala_batch_t *object, int32_t link);
 PV_API pv_status_t pv_koala_batch_get_channel_link(const pv_koala_batch_t *object, int32_t *link);
 
+/* HIGH-BAND CARRY (ninth extension).  A frame handle at 32 000 or 48 000 Hz decimates to 16 kHz, enhances there and
+ * interpolates back; both converters are the same low-pass, so nothing above about 7.5 kHz comes out of it.  With
+ * PV_KOALA_HIGH_BAND_CARRY the handle adds that band back, as band-split suppressors do: with R = sample_rate / 16000 and
+ * D = delay_sample (608 / 912),
+ *     hb[n]  = x[n - D] - Lf[n]                      Lf: the handle's result with the engine replaced by a pure delay of one frame, kept as float
+ *     out[n] = to_pcm(fmaf(G[n], hb[n], E[n]))       E: what the handle delivers without the feature
+ *     G[n]   = s'[t-1] + w (s'[t] - s'[t-1])         j = floor((n - 24 R) / R), t = floor(j / 256), w = (j - 256 t) / 256
+ *     s'[t]  = g + (1 - g) mask_sum[t] / 257         the frame report's mask_sum, the stream's attenuation limit g; 0 in front of the stream
+ * (linked channels: the max of mask_sum over the group).  The ramp G is the overlap-add's own cross-fade.  With min_gain = 1 the whole handle
+ * is a pure delay to within 1 LSB (from its third frame on, wherever Lf does not clip); a stream with no energy above the converters' pass
+ * band is practically unchanged.  The mask network, E, the streams' state, the records' content and the frame report are bit for bit the
+ * handle's without the feature.  koala_amd/highband.py states the rule in numpy.
+ *   State: the feature keeps the last D input samples, 304 converter samples and two gains per stream, only while it is on; cleared by
+ *     pv_koala_batch_reset (all or masked), by a `reset` at frame 0, and by turning the feature on: the high band is then that of streams
+ *     that began with the next call.
+ * pv_koala_batch_set_high_band: per handle; may change between any two calls and takes effect with the next call; no device work and no
+ * wait.  With PV_KOALA_HIGH_BAND_NONE the handle is exactly the handle it was: same launches, same bits; NONE is accepted on every handle.
+ * PV_STATUS_INVALID_ARGUMENT with a message, everything unchanged: a NULL object or out-pointer; a mode outside 0 ... 1; CARRY on a handle
+ * whose `sample_rate` is not 32000 or 48000 (the message names `sample_rate`: 16 kHz and below have no band to carry; 24 kHz and
+ * 44 100 / 22 050 Hz are not available yet); CARRY on a packet handle (not yet).
+ * WHILE CARRY IS ON these are refused with PV_STATUS_INVALID_ARGUMENT, by name, nothing processed and state unchanged (not yet): a per-frame
+ * `reset` at a frame behind frame 0; `hold`; pv_koala_batch_state_size, _export_state and _import_state (a record would need the feature's
+ * state).  The asynchronous entry points are refused at these rates anyway. */
+typedef enum { PV_KOALA_HIGH_BAND_NONE = 0, PV_KOALA_HIGH_BAND_CARRY = 1 } pv_koala_high_band_t;
+PV_API pv_status_t pv_koala_batch_set_high_band(pv_koala_batch_t *object, int32_t mode);
+PV_API pv_status_t pv_koala_batch_get_high_band(const pv_koala_batch_t *object, int32_t *mode);
+
 PV_API pv_status_t pv_koala_batch_num_streams(const pv_koala_batch_t *object, int32_t *num_streams);
 PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, int32_t *delay_sample);
 

@@ -45,7 +45,7 @@ class KoalaBatch(object):
 
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
                  max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0, sample_format: str = 's16',
-                 channels: int = 1, channel_link: Optional[str] = None) -> None:
+                 channels: int = 1, channel_link: Optional[str] = None, high_band: Optional[str] = None) -> None:
         """`sample_rate`: 44100 or 22050 Hz make a packet handle around fractional converters (`packet_samples` > 0 is required; there is
         no frame length, `frame_length` is None, and stream records and the asynchronous calls are refused); otherwise
         8000, 12000, 16000, 24000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
@@ -66,7 +66,9 @@ class KoalaBatch(object):
         report, gains, records -- stays [num_streams], a packet call's counts must be equal within a group, the device-pointer methods take
         the same layout, and the asynchronous calls are refused.
         `channel_link`: None (default) or 'max' -- with 'max' (`channels` 2, 4 or 8) the channels of a group share one mask, the max of their
-        own masks bin by bin, so the stereo image does not move (`set_channel_link`; koala_amd.channels.link_masks states the rule)."""
+        own masks bin by bin, so the stereo image does not move (`set_channel_link`; koala_amd.channels.link_masks states the rule).
+        `high_band`: None (default) or 'carry' -- a frame handle at 32000 or 48000 Hz adds the band above the 16 kHz call's, delayed like
+        the call and scaled by a broadband gain from the call's masks (`set_high_band`; koala_amd.highband states the rule)."""
         if not isinstance(access_key, str) or len(access_key) == 0:
             raise KoalaInvalidArgumentError("`access_key` should be a non-empty string.")
         if not os.path.exists(model_path):
@@ -89,6 +91,9 @@ class KoalaBatch(object):
                                             % (num_streams, channels))
         self.channels = channels
         link = self._link_value(channel_link)  # (checked before the handle is made)
+        carry = self._high_band_value(high_band)
+        if carry and (sample_rate not in (32000, 48000) or packet_samples):
+            raise KoalaInvalidArgumentError("`high_band` 'carry' needs a frame handle whose `sample_rate` is 32000 or 48000.")
         self.sample_format = sample_format
         self._dtype = DTYPES[sample_format]
         self._dtype_name = np.dtype(self._dtype).name
@@ -186,12 +191,40 @@ class KoalaBatch(object):
         if not fractional:
             self._check(lib.pv_koala_batch_state_size(self._handle, byref(d)), 'Failed to get the state size')
             self.state_size = d.value
-        if link:
+        if link or carry:
             try:
-                self.set_channel_link(channel_link)
+                if link:
+                    self.set_channel_link(channel_link)
+                if carry:
+                    self.set_high_band(high_band)
             except Exception:
                 self.delete()
                 raise
+
+    @staticmethod
+    def _high_band_value(mode):
+        if mode is not None and mode != 'carry':
+            raise KoalaInvalidArgumentError("`high_band` should be 'carry' or None.")
+        return 1 if mode else 0
+
+    def _high_band_fn(self, which, arg):
+        # (bound at first use, not with the others in __init__: developer A/B runs load libraries built before the entry points existed)
+        fn = getattr(self._lib, 'pv_koala_batch_%s_high_band' % which)
+        fn.argtypes, fn.restype = [c_void_p, arg], PicovoiceStatuses
+        return fn
+
+    def set_high_band(self, mode: Optional[str]) -> None:
+        """'carry': from the next call on, the handle (a frame handle at 32000 or 48000 Hz) adds the band the 16 kHz call never saw to its
+        output, delayed by `delay_sample` and scaled by a smooth broadband gain from the call's own masks (include/pv_koala_batch.h,
+        pv_koala_batch_set_high_band; koala_amd.highband states the rule).  The high band is that of streams that begin with that call.
+        None: exactly the handle it was.  While it is on, `hold`, per-frame resets behind frame 0 and stream records are refused."""
+        self._check(self._high_band_fn('set', c_int32)(self._handle, self._high_band_value(mode)), 'set_high_band failed')
+
+    @property
+    def high_band(self) -> Optional[str]:
+        v = c_int32()
+        self._check(self._high_band_fn('get', POINTER(c_int32))(self._handle, byref(v)), 'high_band failed')
+        return 'carry' if v.value else None
 
     def _link_value(self, link):
         if link is not None and link != 'max':

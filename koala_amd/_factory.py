@@ -39,7 +39,8 @@ def create_batch(
         packet_samples: int = 0,
         sample_format: str = 's16',
         channels: int = 1,
-        channel_link: Optional[str] = None) -> KoalaBatch:
+        channel_link: Optional[str] = None,
+        high_band: Optional[str] = None) -> KoalaBatch:
     """`num_streams` independent streams advancing together on one GPU (see KoalaBatch), at 8000, 12000, 16000, 24000, 32000 or 48000 Hz.
     `packet_samples=N` makes a packet handle: streams that take and deliver any number of samples, up to N, per call
     (`KoalaBatch.process_packets`; `max_frames_per_call` is then derived from N).
@@ -48,7 +49,9 @@ def create_batch(
     `channels=C` (2 ... 8): every array of samples is [num_streams / C, n * C], the C streams of a group interleaved (L R L R ...), split
     and joined on the device (`koala_amd.channels` has the layout); the streams stay independent, everything per stream stays [num_streams].
     `channel_link='max'` (`channels` 2, 4 or 8): the channels of a group share one mask, the max of their own, bin by bin
-    (`KoalaBatch.set_channel_link`)."""
+    (`KoalaBatch.set_channel_link`).
+    `high_band='carry'` (a frame handle at 32000 or 48000 Hz): the band above the 16 kHz call's is carried around it and added back
+    (`KoalaBatch.set_high_band`; `koala_amd.highband` has the rule)."""
     return KoalaBatch(
         access_key=access_key,
         model_path=default_model_path() if model_path is None else model_path,
@@ -61,7 +64,8 @@ def create_batch(
         packet_samples=packet_samples,
         sample_format=sample_format,
         channels=channels,
-        channel_link=channel_link)
+        channel_link=channel_link,
+        high_band=high_band)
 
 
 def available_devices(library_path: Optional[str] = None) -> Sequence[str]:

@@ -892,6 +892,7 @@ void Engine::launch_resets(const uint8_t *d_mask) {
     if (rate_ != kRate16k) {
         launch_resample_reset(d_rs_state_[0][0], d_rs_state_[0][1], rs_in_hist(rate_), d_mask, Bpad_, stream_);
         launch_resample_reset(d_rs_state_[1][0], d_rs_state_[1][1], rs_out_hist(rate_), d_mask, Bpad_, stream_);
+        if (d_hb_rep_) launch_high_band_reset(d_hb_x_, d_hb_y_, d_hb_s_, rs_stage_out(rate_).U, d_mask, Bpad_, stream_);  // (the high-band carry's, once it exists)
     }
     if (pk_max_) launch_packet_reset(packet_state_args(), d_mask, stream_);
     if (fr_rate_) launch_fractional_reset(fractional_state_args(), d_mask, stream_);
@@ -2140,6 +2141,38 @@ bool Engine::rate_ready(std::string *err) {  // the device copy of a call's rese
     return true;
 }
 
+// High-band carry (Call::high_band): at the first such call the state's three ping-pong pairs and the engine's own report buffer; at that call and at
+// a call whose epoch is not the last one seen -- the owner turned the feature on again -- the state is cleared on the handle's stream, so the
+// high band is that of streams that begin with this call.
+bool Engine::high_band_ready(const Call &c, std::string *err) {
+    const int R = rs_stage_out(rate_).U;
+    if (!d_hb_rep_) {
+        for (int k = 0; k < 2; ++k) {
+            if (!d_hb_x_[k]) d_hb_x_[k] = (int16_t *) dalloc((size_t) Bpad_ * hb_x_hist(R) * 2, false);
+            if (!d_hb_y_[k]) d_hb_y_[k] = (int16_t *) dalloc((size_t) Bpad_ * kHbYHist * 2, false);
+            if (!d_hb_s_[k]) d_hb_s_[k] = (float *) dalloc((size_t) Bpad_ * 2 * 4, false);
+        }
+        float *rep = d_hb_x_[0] && d_hb_x_[1] && d_hb_y_[0] && d_hb_y_[1] && d_hb_s_[0] && d_hb_s_[1] ? (float *) dalloc((size_t) B_ * Tmax_ * 16, false) : nullptr;
+        if (!rep) {
+            (void) hipGetLastError();
+            *err = "Failed to allocate the buffers of the high-band carry.";
+            return false;
+        }
+        d_hb_rep_ = rep;
+        hb_epoch_ = c.high_band_epoch - 1;  // (cleared below, on the stream the call runs on)
+    }
+    if (hb_epoch_ != c.high_band_epoch) {
+        launch_high_band_reset(d_hb_x_, d_hb_y_, d_hb_s_, R, nullptr, Bpad_, stream_);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            *err = hip_error(e);
+            return false;
+        }
+        hb_epoch_ = c.high_band_epoch;
+    }
+    return true;
+}
+
 // A call of a handle that is not at 16 kHz (third extension): the in-stage kernel takes the caller's samples to 16 kHz
 // (into d_in_), the call runs unchanged as a device-pointer call from d_in_ to d_out_ -- its resets, attenuation limit and frame report
 // with it -- and the out-stage kernel takes the enhanced samples to the caller's rate.  Everything is enqueued on the handle's stream.
@@ -2163,11 +2196,30 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
             goto fail;
         flags = d_rs_flags_;
     }
+    if (c.high_band && !high_band_ready(c, err)) return false;
     {
         Call inner{T, d_in_, d_out_, c.resets};
         inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
         inner.channel_link = c.channel_link;
         inner.report = c.report;
+        // High-band carry: the kernel behind the out-stage reads the call's masks from its report -- an output only, so asking for it into a
+        // buffer of the engine's changes no bit -- the in-stage's rows, which the device-pointer call leaves in d_in_ as they are, and the
+        // call's input, of which a copy is kept where the out-stage writes over it.
+        const size_t n_io = (size_t) B_ * T * rs_frame_length(rate_);
+        const int16_t *hb_x = c.pcm;
+        if (c.high_band) {
+            if (!inner.report) inner.report = d_hb_rep_;
+            if (c.pcm < c.out + n_io && c.out < c.pcm + n_io) {
+                if (!d_hb_in_) d_hb_in_ = (int16_t *) dalloc((size_t) B_ * Tmax_ * rs_frame_length(rate_) * 2, false);
+                if (!d_hb_in_) {
+                    (void) hipGetLastError();
+                    *err = "Failed to allocate the buffers of the high-band carry.";
+                    return false;
+                }
+                if (hipMemcpyAsync(d_hb_in_, c.pcm, n_io * 2, hipMemcpyDeviceToDevice, stream_) != hipSuccess) goto fail;
+                hb_x = d_hb_in_;
+            }
+        }
         const RsStage si = rs_stage_in(rate_), so = rs_stage_out(rate_);
         ResampleArgs a;
         a.B = B_, a.T = T, a.resets = flags;
@@ -2182,6 +2234,19 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
             if (k == 0 && !run_call(inner, err)) return false;
         }
         rs_cur_ ^= 1;
+        if (c.high_band) {
+            HighBandArgs h;
+            h.x = hb_x, h.y = d_in_, h.out = c.out, h.report = inner.report;
+            h.min_gain = c.min_gain ? d_min_gain_ : nullptr;  // (begin_min_gain has put the call's table on the stream)
+            h.resets = flags;
+            h.xs = d_hb_x_[hb_cur_], h.ys = d_hb_y_[hb_cur_], h.ss = d_hb_s_[hb_cur_];
+            h.xs_next = d_hb_x_[hb_cur_ ^ 1], h.ys_next = d_hb_y_[hb_cur_ ^ 1], h.ss_next = d_hb_s_[hb_cur_ ^ 1];
+            h.B = B_, h.T = T, h.R = so.U, h.link = c.channel_link ? ch_ : 0;
+            memcpy(h.taps, rs_taps_[1].data(), sizeof(h.taps));
+            launch_high_band(h, stream_);
+            if (hipGetLastError() != hipSuccess) goto fail;
+            hb_cur_ ^= 1;
+        }
     }
     return true;
 fail:
@@ -2454,6 +2519,20 @@ Status Engine::process(const Call &c, std::string *err) {
                        std::to_string(b / ch_) + ", whose masks are linked (`channels` = " + std::to_string(ch_) + "): a group is held as a whole.";
                 return Status::kBadArgument;
             }
+        }
+    }
+    if (c.high_band) {  // high-band carry: the handle, and what the feature does not take yet (the owner refuses all of it by name first)
+        if (!hb_rate_ok(rate_) || pk_max_) {
+            *err = "the high-band carry needs a frame handle whose `sample_rate` is 32000 or 48000.";
+            return Status::kBadArgument;
+        }
+        bool held = false, late = false;
+        for (int b = 0; c.hold && b < B_ && !held; ++b) held = c.hold[b] != 0;
+        for (size_t i = 0; c.resets && i < (size_t) B_ * c.T && !late; ++i) late = c.resets[i] != 0 && i % (size_t) c.T != 0;
+        if (held || late) {
+            *err = held ? "`hold` is not available yet while the high-band carry is on." :
+                          "per-frame stream resets after frame 0 are not available yet while the high-band carry is on.";
+            return Status::kBadArgument;
         }
     }
     if (rate_ == kRate16k && fmt_ == kFmtS16 && ch_ == 1) return process_frames(c, err);  // the plain handle

@@ -67,6 +67,13 @@ struct Call {
     // (all zero where no limit is in force: the linked kernels read the table), and `hold` must be equal within a group.  The owner's
     // setting, like the limit: the engine keeps nothing of it between calls.  0: the plain call -- same route, same kernels, same bits.
     int channel_link = 0;
+    // High-band carry (ninth extension; a frame handle at 32 or 48 kHz only): non-zero, and the band above the stages'
+    // pass band is added to `out`, delayed like the call and scaled by a broadband gain from the call's masks (kns_highband.hip).  The
+    // owner's setting, like the link; `high_band_epoch` counts the times the owner turned it on: the engine allocates the feature's
+    // per-stream state at the first such call and clears it when the epoch is not the one it saw last.  Not combined with `hold`, nor with
+    // `resets` behind frame 0.  0: the plain call -- same launches, same bits.
+    int high_band = 0;
+    unsigned high_band_epoch = 0;
 };
 
 // kBadArgument: a stream list, a record or a combination of Call members that the engine refused before it touched anything (the C ABI
@@ -244,6 +251,14 @@ private:
     std::vector<float> rs_taps_[2];     // the in-stage's and the out-stage's table h_U (kns_kernels.h)
     uint8_t *d_rs_flags_ = nullptr;     // a call's per-frame resets on the device, uint8 [B][T], and their upload ring
     uint8_t *d_state_rs_ = nullptr;     // the stages' part of the staged stream records [B][rs_record_bytes]
+    // high-band carry (Call::high_band; kns_kernels.h, HighBandArgs): the per-stream state as ping-pong pairs -- x [Bpad][hb_x_hist],
+    // y [Bpad][kHbYHist], s' [Bpad][2] -- allocated (zeroed) by the first such call and part of reset(); the report [B][Tmax][4] of a call
+    // whose caller asked for none; and the copy [B][Tmax F] of a call's input where its output overwrites it
+    int16_t *d_hb_x_[2] = {nullptr, nullptr}, *d_hb_y_[2] = {nullptr, nullptr}, *d_hb_in_ = nullptr;
+    float *d_hb_s_[2] = {nullptr, nullptr}, *d_hb_rep_ = nullptr;
+    int hb_cur_ = 0;
+    unsigned hb_epoch_ = 0;
+    bool high_band_ready(const Call &c, std::string *err);  // the buffers, and the state cleared when the call's epoch is new
     // what run_device is given: the frames [t0, t0 + T) of a call, their device buffers, and the call's reset table if it has one
     struct ResetTable;
     struct Slice {

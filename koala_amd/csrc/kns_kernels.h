@@ -451,6 +451,31 @@ struct ChannelArgs {
 };
 void launch_channels_split(int width, const ChannelArgs &a, hipStream_t s);
 void launch_channels_join(int width, const ChannelArgs &a, hipStream_t s);
+// ---- high-band carry (kns_highband.hip; DESIGN.md section 2, ninth extension): frame handles at 32 and 48 kHz add the band the 16 kHz
+// call never saw, delayed like the call and scaled by a broadband gain from the call's own masks, to the out-stage's result -- one launch
+// behind the out-stage.  R = rate / 16000.  Per stream, held only while the feature is on: the last hb_x_hist(R) input samples, the last
+// kHbYHist in-stage outputs (one engine frame and the out-stage's history) and the broadband gains s' of the last two frames.
+constexpr int kHbYHist = kFrame + 2 * kRsHalf;  // 304
+KNS_HD constexpr bool hb_rate_ok(int rate) { return rate == 32000 || rate == 48000; }
+KNS_HD constexpr int hb_x_hist(int R) { return kHbYHist * R; }  // = delay_sample: 608 / 912
+struct HighBandArgs {
+    const int16_t *x;       // [B][T 256 R]: the call's input at the handle's rate
+    const int16_t *y;       // [B][T 256]: the in-stage's output of the call
+    int16_t *out;           // [B][T 256 R]: the out-stage's result E, rewritten in place
+    const float *report;    // [B][T][4]: the call's frame report (row [b][t][2] = mask_sum)
+    const float *min_gain;  // [Bpad] or nullptr (every gain 0): the call's attenuation limit
+    const uint8_t *resets;  // [B][T] or nullptr: a stream with resets[b T] != 0 is fresh in front of the call (later frames: refused above)
+    const int16_t *xs, *ys;  // the state in front of the call: [Bpad][hb_x_hist(R)], [Bpad][kHbYHist], oldest first
+    const float *ss;         // [Bpad][2]: s' of the frame before the call, and of the one before that
+    int16_t *xs_next, *ys_next;  // ... behind it (the other copy of the ping-pong pair)
+    float *ss_next;
+    int B, T, R;
+    int link;  // channels of a linked group (the gain's s is the max over the group's), 0 or 1: none
+    float taps[kRsMaxTaps];  // the out-stage's table h_R, as ResampleArgs'
+};
+void launch_high_band(const HighBandArgs &a, hipStream_t s);
+// both copies of the three state arrays of the streams with mask[b] != 0 (null: all) := 0
+void launch_high_band_reset(int16_t *const xs[2], int16_t *const ys[2], float *const ss[2], int R, const uint8_t *mask, int Bpad, hipStream_t s);
 // last node of a captured one-frame replay: ++*counter (device memory), published to *host_word (page-locked host memory)
 void launch_frame_done(unsigned *counter, unsigned *host_word, hipStream_t s);
 

@@ -113,6 +113,11 @@ pv_status_t check_records(const pv_koala_batch_t *object) {
                    object->sample_rate);
         return PV_STATUS_INVALID_ARGUMENT;
     }
+    if (object->limit.high_band) {  // (a record would need the feature's per-stream state)
+        push_error(0x66, "Stream records (state_size, export_state, import_state) are not available yet while the high-band carry is on "
+                         "(pv_koala_batch_set_high_band).");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
     return PV_STATUS_SUCCESS;
 }
 
@@ -148,6 +153,22 @@ pv_status_t advance(kns::Engine *engine, const MinGain &limit, kns::Call call, b
         call.min_gain_rev = limit.rev;
     }
     call.channel_link = limit.link;
+    if (limit.high_band) {  // what the high-band carry does not take yet: refused here, before the engine is reached
+        const int32_t B = engine->num_streams();
+        for (int32_t b = 0; call.hold && b < B; ++b)
+            if (call.hold[b]) {
+                push_error(0x66, "`hold[%d]` is set: `hold` is not available yet while the high-band carry is on (pv_koala_batch_set_high_band).", b);
+                return PV_STATUS_INVALID_ARGUMENT;
+            }
+        for (int32_t b = 0; call.resets && b < B; ++b)
+            for (int32_t t = 1; t < call.T; ++t)
+                if (call.resets[(size_t) b * call.T + t]) {
+                    push_error(0x66, "`reset[%d][%d]` is set: while the high-band carry is on (pv_koala_batch_set_high_band) a handle takes "
+                                     "per-frame stream resets at frame 0 only (not yet).", b, t);
+                    return PV_STATUS_INVALID_ARGUMENT;
+                }
+        call.high_band = limit.high_band, call.high_band_epoch = limit.high_band_epoch;
+    }
     return guarded([&] {
         std::string err;
         const kns::Status status = async ? engine->process_host_async(call, &err) : engine->process(call, &err);

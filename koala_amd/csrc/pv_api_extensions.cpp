@@ -1,7 +1,7 @@
 // pv_api_extensions.cpp -- the C ABI of the batch handles that are made above pv_koala_batch_init_rate (include/pv_koala_batch.h; DESIGN.md
 // section 2, fourth to seventh extension): packet handles (pv_koala_batch_init_packets, _is_packet_handle, _process_packets), sample formats
 // and the handles at 44 100 and 22 050 Hz (pv_koala_batch_init_config, _sample_format) and channels (pv_koala_batch_init_channels,
-// _channels, _set_channel_link, _get_channel_link).  Each constructor calls the one below it and then enables its feature on the engine behind the finished handle; the
+// _channels, _set_channel_link, _get_channel_link) and the high-band carry (_set_high_band, _get_high_band).  Each constructor calls the one below it and then enables its feature on the engine behind the finished handle; the
 // processing entry points (pv_api.cpp, and _process_packets here) read the engine and the handle's two own values, sample_rate and
 // packet_samples.
 #include "pv_api_internal.h"
@@ -241,5 +241,43 @@ PV_API pv_status_t pv_koala_batch_get_channel_link(const pv_koala_batch_t *objec
         return PV_STATUS_INVALID_ARGUMENT;
     }
     *link = object->limit.link;
+    return PV_STATUS_SUCCESS;
+}
+
+// ------------------------------------------------------------------------------------------------ high-band carry
+// The mode of a handle (ninth extension): a value of the handle that every call carries to the engine, like the link --
+// no device work, no wait; the next call is the first to see it.  Turning it on counts an epoch: the engine clears the feature's state when
+// it sees a new one, so the high band is that of streams that began with the next call.  Not yet: 24 kHz and 44 100 / 22 050 Hz, packet handles.
+PV_API pv_status_t pv_koala_batch_set_high_band(pv_koala_batch_t *object, int32_t mode) {
+    kns_api::clear_errors();
+    if (!object) {
+        push_error(0x64, "Argument `object` is NULL.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (mode != PV_KOALA_HIGH_BAND_NONE && mode != PV_KOALA_HIGH_BAND_CARRY) {
+        push_error(0x66, "`mode` %d is not one of PV_KOALA_HIGH_BAND_NONE, _CARRY (0 ... 1).", mode);
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (mode == PV_KOALA_HIGH_BAND_CARRY && !kns::hb_rate_ok(object->sample_rate)) {
+        push_error(0x66, "PV_KOALA_HIGH_BAND_CARRY needs a handle whose `sample_rate` is 32000 or 48000: this handle's `sample_rate` is %d (16000 and "
+                         "below have no band to carry; 24000, 44100 and 22050 are not available yet).", object->sample_rate);
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (mode == PV_KOALA_HIGH_BAND_CARRY && object->packet_samples) {
+        push_error(0x66, "PV_KOALA_HIGH_BAND_CARRY is not available yet on a packet handle.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (mode == PV_KOALA_HIGH_BAND_CARRY && !object->limit.high_band) ++object->limit.high_band_epoch;
+    object->limit.high_band = mode;
+    return PV_STATUS_SUCCESS;
+}
+
+PV_API pv_status_t pv_koala_batch_get_high_band(const pv_koala_batch_t *object, int32_t *mode) {
+    kns_api::clear_errors();
+    if (!object || !mode) {
+        push_error(0x64, "Argument `%s` is NULL.", object ? "mode" : "object");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    *mode = object->limit.high_band;
     return PV_STATUS_SUCCESS;
 }

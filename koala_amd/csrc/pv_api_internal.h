@@ -21,6 +21,11 @@ struct MinGain {
     // Linked channels (pv_koala_batch_set_channel_link; batch handles only): travels with the limit because a linked call carries the gains
     // whether or not any is non-zero -- the linked kernels read the table (kns::Call::channel_link)
     int link = 0;
+    // High-band carry (pv_koala_batch_set_high_band; frame handles at 32 and 48 kHz only): the mode, and the number of times it was turned
+    // on -- the engine clears the feature's state when it sees a new one (kns::Call::high_band, high_band_epoch).  Travels with the limit
+    // because every call that advances the streams passes through it.
+    int high_band = 0;
+    unsigned high_band_epoch = 0;
 };
 struct pv_koala {
     kns::Engine *engine;

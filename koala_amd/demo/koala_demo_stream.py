@@ -206,6 +206,38 @@ def run_channels(args):
     return 0
 
 
+def run_high_band(args):
+    """--high_band: a mono 16-bit WAV at --sample_rate 32000 or 48000 through one stream of a frame handle with the high-band carry
+    (`koala_amd.create_batch(..., sample_rate=rate, high_band='carry')`): the band above the 16 kHz call's is delayed like the call, scaled
+    by a broadband gain from the call's masks and added back, so full-band audio stays full-band.  Frame by frame, --input_path to
+    --output_path; the output is `delay_sample` samples late."""
+    import os
+    rate = args.sample_rate
+    if rate not in (32000, 48000):
+        raise ValueError('--high_band: --sample_rate must be 32000 or 48000 (lower rates have no band to carry; the others are not available yet)')
+    for name, v in (('--meter', args.meter), ('--packet-ms', args.packet_ms), ('--sample_format', args.sample_format)):
+        if v:
+            raise ValueError('%s: not available with --high_band' % name)
+    if args.input_path is None or args.output_path is None:
+        raise ValueError('--high_band: give --input_path and --output_path (mono 16-bit WAV files at --sample_rate)')
+    batch = koala_amd.create_batch(args.access_key, 1, precision=args.precision or os.environ.get('KOALA_AMD_PRECISION', 'fp32'),
+                                   model_path=args.model_path, device=args.device, library_path=args.library_path,
+                                   sample_rate=rate, high_band='carry')
+    batch.set_attenuation_limit(args.attenuation_limit_db)
+    frames = 0
+    try:
+        with wave.open(args.output_path, 'wb') as out:
+            out.setnchannels(1), out.setsampwidth(2), out.setframerate(rate)
+            for frame in frames_from_wav(args.input_path, batch.frame_length, rate):
+                out.writeframes(batch.process(frame[None])[0].astype('<i2').tobytes())
+                frames += 1
+    finally:
+        delay = batch.delay_sample
+        batch.delete()
+    print('%d frames at %d Hz with the high-band carry; delay %d samples' % (frames, rate, delay), file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='frame-by-frame noise suppression of a live PCM stream')
     ap.add_argument('--access_key', default='koala-amd', help='accepted for interface compatibility; not checked')
@@ -233,12 +265,18 @@ def main(argv=None):
                          'handle that splits and joins on the device; every channel is enhanced on its own')
     ap.add_argument('--link', action='store_true',
                     help="with --channels 2, 4 or 8: one mask per group, the max of the channels' own (the stereo image does not move)")
+    ap.add_argument('--high_band', action='store_true',
+                    help='with --sample_rate 32000 or 48000 and WAV files: carry the band above 8 kHz around the 16 kHz call (a frame handle)')
     ap.add_argument('--show_devices', action='store_true')
     args = ap.parse_args(argv)
 
     if args.show_devices:
         print('\n'.join(koala_amd.available_devices(library_path=args.library_path)))
         return 0
+    if args.high_band:
+        if args.channels != 1:
+            raise ValueError('--high_band: not available with --channels in this demo')
+        return run_high_band(args)
     if args.channels != 1:
         return run_channels(args)
     if args.sample_rate in (22050, 44100):

@@ -1,0 +1,170 @@
+"""
+The high-band carry without a GPU (ninth extension): the streaming recipe (tests/high_band_recipe.py) against
+tests/sample_rate_recipe.py's stages, a float64 restatement and koala_amd.highband's whole-stream statement; the properties the text
+derives (w exact, G = 1 under the bypass gain, the pure-delay bound); the exported symbols; and kns_highband.hip's build for gfx950
+(three kernels, no scratch, no spills).
+"""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import koala_amd
+import sample_rate_recipe as srr
+from conftest import ROOT
+from high_band_recipe import RATES, Y_HIST, HighBand
+from koala_amd import highband
+
+F32 = np.float32
+SEQ = (1, 1, 1, 3, 2, 1)
+
+
+def noise(n, rate, frames, seed, peak):
+    return np.random.default_rng(seed).integers(-peak, peak + 1, size=(n, frames * srr.frame_length(rate))).astype(np.int16)
+
+
+def cut(x, rate, seq=SEQ):
+    F, out, t0 = srr.frame_length(rate), [], 0
+    for T in seq:
+        out.append(np.ascontiguousarray(x[:, t0 * F:(t0 + T) * F]))
+        t0 += T
+    return out
+
+
+@pytest.mark.parametrize('rate', RATES)
+def test_lf_is_the_out_stage_over_the_delayed_in_stage_before_rounding(rate):
+    """y, yd and Lf against sample_rate_recipe: to_pcm(Lf) is the handle whose engine is the pure delay, call by call; Lf against the same
+    sums in float64 (49 roundings of at most half an ulp of 2^16 each: 49 * 2^-8 < 0.2)"""
+    n, R = 3, rate // 16000
+    x = noise(n, rate, sum(SEQ), 1, 30000)
+    hb, plain = HighBand(n, rate), srr.Recipe(None, n, 'fp32', rate)
+    lf = []
+    for p in cut(x, rate):
+        xd, Lf, G = hb.parts(p, np.zeros((n, p.shape[1] // (256 * R)), F32), np.zeros(n, F32))
+        assert np.array_equal(srr.to_pcm(Lf), plain.process(p))
+        lf.append(Lf)
+    lf = np.concatenate(lf, axis=1)
+    D = srr.delay_sample(rate)
+    assert D == highband.delay_sample(rate) == Y_HIST * R
+    y = srr.Stage(n, R, 1, R).run(x).astype(np.float64)
+    yd = np.concatenate([np.zeros((n, 256 + 48)), y], axis=1)
+    h = (R * srr.prototype(R)).astype(F32).astype(np.float64)
+    ref = np.zeros(lf.shape)
+    for q in range(y.shape[1]):
+        for p in range(R):
+            taps = h[p::R]
+            ref[:, R * q + p] = sum(taps[j] * yd[:, 48 + q - j] for j in range(len(taps)))
+    assert np.abs(lf - ref).max() < 0.2
+    assert np.array_equal(lf, highband.low_band(highband.in_stage(x, rate), rate))  # the whole-stream statement, written independently
+
+
+@pytest.mark.parametrize('channels', [1, 2])
+@pytest.mark.parametrize('rate', RATES)
+def test_streaming_recipe_equals_the_whole_stream_statement(rate, channels):
+    n = 4
+    rng = np.random.default_rng(3)
+    x = noise(n, rate, sum(SEQ), 2, 20000)
+    e = noise(n, rate, sum(SEQ), 4, 20000)
+    ms = (rng.random((n, sum(SEQ))) * 257).astype(F32)
+    g = np.array([0.0, 0.25, 1.0, 0.5], F32)
+    hb, out, t0 = HighBand(n, rate, channels), [], 0
+    for p, q, T in zip(cut(x, rate), cut(e, rate), SEQ):
+        out.append(hb.process(p, q, ms[:, t0:t0 + T], g))
+        t0 += T
+    assert np.array_equal(np.concatenate(out, axis=1), highband.carry(x, e, ms, rate, g, channels))
+    # a reset stream is a fresh stream
+    hb.reset([1, 0, 1, 0])
+    fresh = HighBand(n, rate, channels)
+    a, b = hb.process(x[:, :256 * 3 * (rate // 16000)], e[:, :256 * 3 * (rate // 16000)], ms[:, :3], g), \
+        fresh.process(x[:, :256 * 3 * (rate // 16000)], e[:, :256 * 3 * (rate // 16000)], ms[:, :3], g)
+    assert np.array_equal(a[[0, 2]], b[[0, 2]]) and not np.array_equal(a[[1, 3]], b[[1, 3]])
+
+
+@pytest.mark.parametrize('rate', RATES)
+def test_w_is_exact_and_g_is_exactly_one_under_the_bypass_gain(rate):
+    n, T, R = 2, 4, rate // 16000
+    ms = (np.random.default_rng(5).random((n, T)) * 257).astype(F32)
+    hb = HighBand(n, rate)
+    _, _, G = hb.parts(np.zeros((n, T * 256 * R), np.int16), ms, np.ones(n, F32))  # (parts asserts that 256 w is the integer it came from)
+    first = (256 + 24) * R  # frames t >= 1 ramp between s'[t-1] = s'[t] = 1; in front of them s' = 0 enters
+    assert (G[:, first:] == F32(1.0)).all() and (G[:, :24 * R] == 0).all() and (np.diff(G[:, :first].astype(np.float64), axis=1) >= 0).all()
+    assert np.array_equal(hb.sp, np.ones((n, 2), F32))
+    G2 = highband.ramp(highband.gains(ms, np.ones(n, F32)), rate)
+    assert np.array_equal(G, G2)
+    j = np.arange(T * 256 * R) // R - 24
+    w = ((j - 256 * (j // 256)).astype(F32) / F32(256.0))
+    assert np.array_equal(w.astype(np.float64) * 256, (j % 256).astype(np.float64))
+
+
+@pytest.mark.parametrize('rate', RATES)
+def test_with_the_bypass_gain_the_handle_is_a_pure_delay_to_one_lsb(rate):
+    """g = 1: the engine is a pure delay, E = to_pcm(Lf), G = 1 from frame 2 on, and out = to_pcm(fmaf(1, x - Lf, to_pcm(Lf))): within one
+    LSB of x delayed wherever Lf does not clip -- which noise at a quarter of full scale cannot make it do (checked here)"""
+    n, R, F = 4, rate // 16000, srr.frame_length(rate)
+    x = noise(n, rate, sum(SEQ), 7, 8192)
+    x[n - 1] = 0
+    hb, plain, out, es = HighBand(n, rate), srr.Recipe(None, n, 'fp32', rate), [], []
+    for p in cut(x, rate):
+        e = plain.process(p)
+        out.append(hb.process(p, e, np.full((n, p.shape[1] // F), 100.0, F32), 1.0))
+        es.append(e)
+    peak = float(np.abs(highband.low_band(highband.in_stage(x, rate), rate)).max())
+    out, es = np.concatenate(out, axis=1), np.concatenate(es, axis=1)
+    assert peak < 32767.0, peak  # Lf does not clip
+    D = srr.delay_sample(rate)
+    xd = np.concatenate([np.zeros((n, D), np.int16), x], axis=1)[:, :x.shape[1]].astype(int)
+    assert np.abs(out.astype(int) - xd)[:, 2 * F:].max() <= 1
+    assert np.abs(es.astype(int) - xd)[:n - 1, 2 * F:].max() > 1000  # the plain handle is a low-pass
+    assert not out[n - 1].any()
+
+
+SYMBOLS = ('pv_koala_batch_set_high_band', 'pv_koala_batch_get_high_band')
+
+
+def test_high_band_symbols_are_exported_and_declared(native_library):
+    header = open(os.path.join(ROOT, 'include', 'pv_koala_batch.h')).read()
+    assert re.search(r'typedef enum \{ PV_KOALA_HIGH_BAND_NONE = 0, PV_KOALA_HIGH_BAND_CARRY = 1 \} pv_koala_high_band_t;', header)
+    for path in (native_library, koala_amd.developer_library_path()):
+        lib = ctypes.CDLL(path)
+        for sym in SYMBOLS:
+            assert hasattr(lib, sym), (path, sym)
+            assert re.search(r'PV_API pv_status_t %s\(' % sym, header), sym
+    lib = ctypes.CDLL(native_library)
+    assert lib.pv_koala_batch_set_high_band(None, 1) == 3 and lib.pv_koala_batch_get_high_band(None, None) == 3  # INVALID_ARGUMENT, no GPU needed
+
+
+def test_python_checks_high_band_before_it_loads_anything(random_model):
+    for bad in ('max', 1, True):
+        with pytest.raises(koala_amd.KoalaInvalidArgumentError, match='high_band'):
+            koala_amd.create_batch('key', 4, 1, model_path=random_model, sample_rate=48000, high_band=bad, library_path='/nonexistent.so')
+    for kw in (dict(sample_rate=16000), dict(sample_rate=24000), dict(sample_rate=48000, packet_samples=960)):
+        with pytest.raises(koala_amd.KoalaInvalidArgumentError, match='high_band'):
+            koala_amd.create_batch('key', 4, 1, model_path=random_model, high_band='carry', library_path='/nonexistent.so', **kw)
+
+
+HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not available')
+def test_high_band_kernels_build_for_gfx950_without_scratch_or_spills(tmp_path):
+    out = tmp_path / 'kns_highband.s'
+    mk = open(os.path.join(ROOT, 'koala_amd', 'Makefile')).read()
+    assert 'csrc/kns_highband.hip' in mk and 'obj/kns_highband.o' in mk
+    cxx = re.search(r'^CXXFLAGS\s*=\s*(.*)$', mk, re.M).group(1).split()
+    subprocess.check_call([HIPCC, '--offload-arch=gfx950'] + [f for f in cxx if f != '-fPIC'] +
+                          ['-S', '--cuda-device-only', '-x', 'hip', os.path.join(ROOT, 'koala_amd', 'csrc', 'kns_highband.hip'), '-o', str(out)],
+                          stderr=subprocess.DEVNULL)
+    text = out.read_text()
+    meta = re.findall(r'\.name:\s+(\S+)\n(?:(?!\.name:).*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:(?!\.name:).*\n)*?\s+\.sgpr_spill_count:\s+(\d+)\n'
+                      r'(?:(?!\.name:).*\n)*?\s+\.vgpr_spill_count:\s+(\d+)', text)
+    facts = {name: (int(p), int(s), int(v)) for name, p, s, v in meta}
+    assert len(facts) == 3, sorted(facts)  # the kernel at 32 and at 48 kHz, and the reset
+    for want in ('high_band_kernelILi2E', 'high_band_kernelILi3E', 'high_band_reset_kernel'):
+        name = [k for k in facts if want in k]
+        assert len(name) == 1, (want, sorted(facts))
+        print(name[0], '(scratch, sgpr spills, vgpr spills) =', facts[name[0]])
+        assert facts[name[0]] == (0, 0, 0), (name[0], facts[name[0]])
