@@ -1,8 +1,8 @@
 """
 The high-band carry of DESIGN.md section 2 (ninth extension) restated in numpy float32 on top of tests/sample_rate_recipe.py (prototype /
 table, fma32, to_pcm, the in-stage), STREAMING: call by call, with exactly the per-stream state the text lists -- the last D input samples
-(int16), the last 256 + 48 in-stage outputs (int16) and s' of the last two frames (float32).  Shared by tests/test_high_band.py (CPU) and
-tests/test_gpu_high_band.py; not a test module.  koala_amd/highband.py states the same rule for whole streams, independently.
+(int16), the last 256 + 48 in-stage outputs (int16) and s' of the last two frames (float32).  Shared by tests/test_high_band.py (CPU),
+tests/test_gpu_high_band.py and tests/test_gpu_high_band_routes.py; not a test module.  koala_amd/highband.py states the same rule for whole streams, independently.
 """
 import numpy as np
 
@@ -85,3 +85,37 @@ class HighBand:
         xd, Lf, G = self.parts(x, mask_sum, np.broadcast_to(np.asarray(g, F32), (self.n,)))
         hb = (xd - Lf).astype(F32)
         return to_pcm(fma32(G, hb, np.ascontiguousarray(enhanced, np.int16).astype(F32)))
+
+
+# ------------------------------------------------------------------------------------------------ inputs at and near full scale
+
+EDGE_SEQ = (1, 1, 1, 3, 2, 1)  # frames per call
+EDGE_GAINS = np.tile(np.array([0.0, 1.0], F32), 8)
+EDGE_DITHER = (14, 15)
+
+
+def edge_streams(rate, seed=1):
+    """int16 [16, 9 frames]: eight inputs, each on two streams (the even one with g = 0, the odd one with g = 1): DC at +32767, DC at -32768,
+    the rails alternating at the handle's Nyquist in either phase, uniform noise over the whole int16 range, one full-scale impulse on the
+    last sample of frame 5 (the last of EDGE_SEQ's 3-frame call), two frames of silence and then a full-scale step, +-1 LSB dither"""
+    F = rate * 256 // 16000
+    N, rng = sum(EDGE_SEQ) * F, np.random.default_rng(seed)
+    n = np.arange(N)
+    alt = np.where(n % 2 == 0, 32767, -32768)
+    impulse, step = np.zeros(N, int), np.zeros(N, int)
+    impulse[6 * F - 1] = 32767
+    step[2 * F:] = 32767
+    rows = [np.full(N, 32767), np.full(N, -32768), alt, alt[::-1] if N % 2 == 0 else -alt - 1, rng.integers(-32768, 32768, N), impulse, step,
+            rng.choice([-1, 1], N)]
+    assert rows[3][0] == -32768 and rows[3][1] == 32767
+    return np.ascontiguousarray(np.repeat(np.array(rows), 2, axis=0).astype(np.int16))
+
+
+def edge_conditions(Lf, e, want):
+    """what keeps a run over edge_streams from being vacuous, from the recipe's Lf (HighBand.parts), the plain handle's samples and the
+    expected output of the whole run -- never from the carrying handle's own output"""
+    d = list(EDGE_DITHER)
+    return {'Lf leaves the int16 range': bool((Lf > 32767).any() and (Lf < -32768).any()),
+            'E reaches a rail': bool((e == 32767).any() or (e == -32768).any()),
+            'the output reaches +32767': bool((want == 32767).any()), 'the output reaches -32768': bool((want == -32768).any()),
+            'the dither streams leave E': bool((want[d] != e[d]).any(axis=1).all())}

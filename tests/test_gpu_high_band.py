@@ -7,6 +7,9 @@ precisions, the `random` model, seeded noise with energy up to Nyquist and one s
 The carry is a function of what the plain handle delivers: handle A is plain and asked for its report, handle B carries; B's samples must
 equal tests/high_band_recipe.HighBand(x, A's samples, A's mask_sum, the limit) with array_equal -- in both precisions, since the kernel
 sees int16 samples and the float report only.
+
+Every size beyond B = 4 -- the routes of Engine::run_device other than the low-latency layer kernel and the wavefront, ragged m-tiles,
+calls longer than 3 frames -- and inputs at the rails: tests/test_gpu_high_band_routes.py.
 """
 import ctypes
 

@@ -2,7 +2,8 @@
 The high-band carry without a GPU (ninth extension): the streaming recipe (tests/high_band_recipe.py) against
 tests/sample_rate_recipe.py's stages, a float64 restatement and koala_amd.highband's whole-stream statement; the properties the text
 derives (w exact, G = 1 under the bypass gain, the pure-delay bound); the exported symbols; and kns_highband.hip's build for gfx950
-(three kernels, no scratch, no spills).
+(three kernels, no scratch, no spills); and the kernel's own source on the CPU, 256 OS threads a workgroup, as a stand-alone program under
+AddressSanitizer + UndefinedBehaviorSanitizer (tests/highband_emulation, tests/high_band_emulator.py).
 """
 import ctypes
 import os
@@ -13,10 +14,11 @@ import subprocess
 import numpy as np
 import pytest
 
+import high_band_emulator
 import koala_amd
 import sample_rate_recipe as srr
 from conftest import ROOT
-from high_band_recipe import RATES, Y_HIST, HighBand
+from high_band_recipe import EDGE_GAINS, EDGE_SEQ, RATES, Y_HIST, HighBand, edge_conditions, edge_streams
 from koala_amd import highband
 
 F32 = np.float32
@@ -122,6 +124,23 @@ def test_with_the_bypass_gain_the_handle_is_a_pure_delay_to_one_lsb(rate):
     assert not out[n - 1].any()
 
 
+@pytest.mark.parametrize('rate', RATES)
+def test_edge_streams_reach_the_rails_over_a_pure_delay_engine(rate):
+    """the inputs of tests/test_gpu_high_band_routes.py's edge cases with the seed they use there, the inner engine a pure delay (mask_sum 257
+    on every frame): Lf leaves the int16 range on both sides, E and the expected output sit on rails, the dither streams are moved"""
+    x = edge_streams(rate)
+    assert x.shape == (16, sum(EDGE_SEQ) * srr.frame_length(rate)) and x.min() == -32768 and x.max() == 32767
+    hb, probe, plain = HighBand(16, rate), HighBand(16, rate), srr.Recipe(None, 16, 'fp32', rate)
+    lf, es, out = [], [], []
+    for p in cut(x, rate, EDGE_SEQ):
+        ms = np.full((16, p.shape[1] // srr.frame_length(rate)), 257.0, F32)
+        e = plain.process(p)
+        lf.append(probe.parts(p, ms, EDGE_GAINS)[1]), es.append(e), out.append(hb.process(p, e, ms, EDGE_GAINS))
+    got = edge_conditions(np.concatenate(lf, axis=1), np.concatenate(es, axis=1), np.concatenate(out, axis=1))
+    print(got)
+    assert all(got.values()), got
+
+
 SYMBOLS = ('pv_koala_batch_set_high_band', 'pv_koala_batch_get_high_band')
 
 
@@ -168,3 +187,16 @@ def test_high_band_kernels_build_for_gfx950_without_scratch_or_spills(tmp_path):
         assert len(name) == 1, (want, sorted(facts))
         print(name[0], '(scratch, sgpr spills, vgpr spills) =', facts[name[0]])
         assert facts[name[0]] == (0, 0, 0), (name[0], facts[name[0]])
+
+
+@pytest.mark.parametrize('rate', RATES)
+def test_the_kernels_own_source_on_the_cpu_equals_the_recipe_under_asan_and_ubsan(rate, tmp_path_factory, tmp_path):
+    """high_band_kernel<R> behind the in-stage kernel that makes its y, B = 4, calls of 1, 1, 1, 3, 2, 1, 4 frames, every array (rows, both
+    copies of the three state arrays, report, gains, flags) a heap allocation of exactly its size: samples and state == HighBand's after
+    every call.  E lies in `out` before the launch; min_gain null, then two tables; link 0, then 2; frame-0 flags on two streams in
+    mid-sequence; the reset kernel with null and with a mask; stream 0 full-range in x and E; report rows any floats in [0, 257]."""
+    seen = high_band_emulator.check_carry(high_band_emulator.program(tmp_path_factory), tmp_path, rate)
+    assert [c['T'] for c in seen] == [1, 1, 1, 3, 2, 1, 4]
+    assert [c['link'] for c in seen] == [0, 0, 0, 2, 2, 2, 2] and [c['gains'] for c in seen] == [False, False, True, True, True, True, True]
+    assert [c['flags'] for c in seen] == [False] * 4 + [True, False, False] and [c['mask'] for c in seen] == [False] * 5 + [True, False]
+    assert all(c['full'] for c in seen) and all(c['moved'] > 1000 for c in seen[1:])  # (the launch rewrote E; call 0 reads zeros: D > a frame)

@@ -2,7 +2,8 @@
 Batch handles at 8, 12, 24, 32 and 48 kHz (include/pv_koala_batch.h: pv_koala_batch_init_rate; DESIGN.md section 2, third extension) without a
 GPU: the prototype low-pass, the numpy recipe (tests/sample_rate_recipe.py) against its pinned constants and against itself -- chunkings,
 level, delay, a record -- the gfx950 build of koala_amd/csrc/kns_resample.hip, the new symbols, and the C-ABI shim's new entry points under
-AddressSanitizer + UndefinedBehaviorSanitizer (tests/abi_sample_rate/driver.cpp with the engine double of tests/abi_sanitizer).
+AddressSanitizer + UndefinedBehaviorSanitizer (tests/abi_sample_rate/driver.cpp with the engine double of tests/abi_sanitizer), and the
+stage kernel's own source on the CPU under the same two sanitizers (tests/highband_emulation, tests/high_band_emulator.py).
 tests/test_rational_rate.py holds the general stage against the interpolator, the decimator and a float64 convolution;
 tests/test_gpu_sample_rate.py and tests/test_gpu_rational_rate.py check the samples on the GPU.
 """
@@ -17,6 +18,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import high_band_emulator
 import koala_amd
 import sample_rate_recipe as srr
 import sanitized_build
@@ -215,3 +217,16 @@ def test_python_refuses_other_rates_and_takes_the_five(random_model, monkeypatch
 def test_sample_rate_entry_points_under_asan_and_ubsan(tmp_path):
     run = sanitized_build.run(sanitized_build.build_abi_driver('abi_sample_rate', tmp_path), model_file('random', 1234), timeout=300)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-6000:])
+
+
+@pytest.mark.parametrize('rate,k', high_band_emulator.STAGE_CASES)
+def test_the_stage_kernels_own_source_on_the_cpu_equals_the_recipe_under_asan_and_ubsan(rate, k, tmp_path_factory, tmp_path):
+    """resample_kernel<U, D, kResets> of both stages of all five rates, 256 OS threads a workgroup, B = 3, calls of 1, 1, 3, 2, 16 frames,
+    rows, flags and both copies of the state heap allocations of exactly their size: samples and state == sample_rate_recipe.Stage's after
+    every call.  Per-frame flags in the 3-frame call (frame 0 and the last) and in the 16-frame call (frame 0; adjacent frames; the last);
+    the reset kernel with null and with a mask; stream 0 full-range, stream 2 on the rails."""
+    seen = high_band_emulator.check_stage(high_band_emulator.program(tmp_path_factory), tmp_path, rate, k)
+    assert [T for T, _, _ in seen] == [1, 1, 3, 2, 16] and [m for _, m, _ in seen] == [False, False, False, True, False]
+    assert seen[2][2].tolist() == [[0, 0, 0], [0, 0, 0], [1, 0, 1]] and not seen[3][2].size
+    f = seen[4][2]
+    assert f[0, 0] and f[1, 15] and f[1, 5] and f[1, 6] and f.sum() == 4
