@@ -4,13 +4,20 @@ every add of the spec is one explicit float32 operation here, in the spec's orde
 tests/test_gpu_frame_report.py; not a test module.
 
 Inputs are the oracle's stages: `Oracle.analysis(hist, frame)` for the spectrum X, `Oracle.process_with_mask` for the network's mask m (bf16:
-the fp16 value widened), and m' = g + (1 - g) m as in tests/test_gpu_min_gain.py's Recipe.
+the fp16 value widened), and m' = g + (1 - g) m as in tests/min_gain_recipe.py's Recipe.
 """
 import numpy as np
 
 from oracle import oracle
 
 F32 = np.float32
+
+# The bf16 bars of the report rows on the GPU.  profiles/r10_frame_report.txt (tools/frame_report_bars.py, CPU): the largest distance between
+# the plain and the jittered bf16 recipe over every bf16 input of tests/test_gpu_frame_report.py was 1.449e-3 relative in e_out and 5.320e-5
+# absolute in mask_sum / 257; the bars are 4 x those (the jitter probe has under-predicted the device by about 2 x before, DESIGN.md
+# section 5: one factor of 2 on top of that).
+BF16_E_OUT_REL = 4 * 1.449e-3
+BF16_MEAN_GAIN_ABS = 4 * 5.320e-5
 
 
 def fma32(a, b, c):

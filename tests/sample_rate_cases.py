@@ -1,7 +1,7 @@
 """
 What the GPU cases of batch handles at 8, 12, 24, 32 and 48 kHz share (tests/test_gpu_sample_rate.py for 8, 32 and 48 kHz,
-tests/test_gpu_rational_rate.py for 12 and 24 kHz; tools/sample_rate_figures.py reads the same inputs): handles, inputs, one call in each
-mode, the recipe's expected samples and the bar they are held to.  Not a test module.
+tests/test_gpu_rational_rate.py for 12 and 24 kHz; tools/sample_rate_figures.py reads the same inputs): handles, inputs, the recipe's expected
+samples and the bar they are held to.  Not a test module.
 
 The bar.  fp32: ==.  bf16: the largest distance is at most ceil(BF16_TOL * S) + 1 LSB, S = the out-stage's largest sum of |tap| over an
 output phase (BF16_TOL LSB of the engine spread by the out-stage, one more for its rounding), and the share of samples further than 1 LSB
@@ -13,13 +13,13 @@ import math
 
 import numpy as np
 
-import koala_amd
+import gpu_kit
 import sample_rate_recipe as srr
 from conftest import model_file, synth_streams
+from gpu_kit import BF16_TOL, frames
 from oracle import oracle
 
-BF16_TOL = 5  # tests/test_gpu_parity.py
-NCLS = 6      # distinct streams; a batch repeats them (cls[b]) so that the CPU side stays small
+NCLS = 6  # distinct streams; a batch repeats them (cls[b]) so that the CPU side stays small
 
 # The call schedule and the handle's max_frames are part of a case, so every rate keeps the ones its cases were written with: 8, 32 and
 # 48 kHz a 16-frame call among the mixed lengths, 12 and 24 kHz calls of 1, 2 and 5 frames.  max_frames is the longest call.
@@ -28,7 +28,7 @@ TMAX = {rate: max(calls) for rate, calls in CALLS.items()}
 
 
 def batch(model, B, T, precision, rate, **kw):
-    return koala_amd.create_batch('key', B, T, precision, model_path=model, sample_rate=rate, **kw)
+    return gpu_kit.batch(model, B, T, precision, sample_rate=rate, **kw)
 
 
 def classes(B):
@@ -42,24 +42,7 @@ def signal(rate, T, seed):
 
 
 def cut(x, rate, t0, t1):
-    fl = srr.frame_length(rate)
-    return np.ascontiguousarray(x[:, t0 * fl:t1 * fl])
-
-
-def call(kb, x, mode, **kw):
-    """one call -> enhanced (or (enhanced, report)): 'host' (pageable), 'device', 'inplace' (device, enhanced == pcm)"""
-    T = x.shape[1] // kb.frame_length
-    if mode == 'host':
-        return kb.process_call(x, **kw)
-    import torch
-    report = kw.pop('report', False)
-    xd = torch.from_numpy(x).cuda()
-    yd = xd if mode == 'inplace' else torch.zeros_like(xd)
-    rd = torch.full((x.shape[0], T, 4), -1.0, dtype=torch.float32, device='cuda') if report else None
-    torch.cuda.synchronize()
-    kb.process_device_call(T, xd.data_ptr(), yd.data_ptr(), rd.data_ptr() if report else 0, **kw)
-    kb.synchronize()
-    return (yd.cpu().numpy(), rd.cpu().numpy()) if report else yd.cpu().numpy()
+    return frames(x, t0, t1, srr.frame_length(rate))
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,7 +1,7 @@
 """
 Linked channels (include/pv_koala_batch.h: LINKED CHANNELS; DESIGN.md section 2, eighth extension) on a real MI355X: the kLink arm of the
 synthesis kernels (koala_amd/csrc/kns_stft_synthesis.inc) through the product library, with device pointers between guard zones
-(tests/test_gpu_channels.device_call), every channel its own signal, the `random` model.
+(tests/gpu_kit.call), every channel its own signal, the `random` model.
 
 B = 24 streams are two mask tiles, the second ragged (8 rows); C = 8 makes groups that span a wave pair.  fp32 is compared with == against
 tests/channel_link_recipe.LinkRecipe (the oracle's stages and the rule in numpy).  In bf16 the GPU's raw masks are not the oracle's, so
@@ -19,10 +19,10 @@ import koala_amd
 from channel_link_recipe import LinkRecipe
 from conftest import model_file, synth_streams
 from frame_report_recipe import applied_mask
+from gpu_kit import call, frames, same
 from koala_amd import KoalaError, KoalaInvalidArgumentError
 from koala_amd.channels import deinterleave, interleave, link_masks
 from oracle import oracle
-from test_gpu_channels import device_call, same
 
 pytestmark = pytest.mark.gpu
 
@@ -34,26 +34,22 @@ def make(B, C, precision, link, **kw):
     return koala_amd.create_batch('key', B, T, precision, model_path=model_file('random'), channels=C, channel_link='max' if link else None, **kw)
 
 
-def frames(x, t0, n):
-    return np.ascontiguousarray(x[:, t0 * 256:(t0 + n) * 256])
-
-
 def calls(B, C, seed):
     """the call list of tests 1 and 2: (planar samples, mode, per-frame resets, gains)"""
     x = synth_streams(B, 4 * T + 2, seed)
     rs = np.zeros((B, T), np.uint8)
     rs[0, 1] = rs[C - 1, 2] = rs[B - 1, 0] = rs[17, 1] = 1  # (differing within their groups)
     g = np.tile(np.array([0.0, 0.25, 1.0, 0.0, 1.0, 0.25, 0.0, 0.0], np.float32), B // 8 + 1)[:B]
-    return [(frames(x, 0, T), 'device', None, None), (frames(x, T, T), 'inplace', None, None),
-            (frames(x, 2 * T, 1), 'device', None, None), (frames(x, 2 * T + 1, 1), 'inplace', None, None),
-            (frames(x, 2 * T + 2, T), 'device', rs, None), (frames(x, 3 * T + 2, T), 'device', None, g)]
+    return [(frames(x, 0, T), 'device', None, None), (frames(x, T, 2 * T), 'inplace', None, None),
+            (frames(x, 2 * T, 2 * T + 1), 'device', None, None), (frames(x, 2 * T + 1, 2 * T + 2), 'inplace', None, None),
+            (frames(x, 2 * T + 2, 3 * T + 2), 'device', rs, None), (frames(x, 3 * T + 2, 4 * T + 2), 'device', None, g)]
 
 
 def run(kb, C, x, mode, rs, g):
     if g is not None:
         kb.set_min_gain(g)
     kw = {} if rs is None else {'reset': rs}
-    return device_call(kb, interleave(x, C), mode, report=True, **kw)
+    return call(kb, interleave(x, C), mode, report=True, **kw)
 
 
 @pytest.mark.parametrize('C,B', SHAPES)
@@ -163,10 +159,10 @@ def test_toggling_the_link_between_calls(n, precision):
     x = synth_streams(B, len(seq) * n, 15)
     prev = None
     for i, link in enumerate(seq):
-        xi = interleave(frames(x, i * n, n), C)
+        xi = interleave(frames(x, i * n, (i + 1) * n), C)
         k.set_channel_link(link)
         assert k.channel_link == link and off.channel_link is None and on.channel_link == 'max'
-        got, a, b = device_call(k, xi, 'device'), device_call(off, xi, 'device'), device_call(on, xi, 'device')
+        got, a, b = call(k, xi, 'device'), call(off, xi, 'device'), call(on, xi, 'device')
         want, other = (b, a) if link else (a, b)
         assert not np.array_equal(a, b), i
         if link == prev:
@@ -189,12 +185,12 @@ def test_unequal_hold_is_refused_and_changes_nothing():
     hold[5] = 1  # (stream 5 is channel 1 of group 2; its partner, stream 4, is not held)
     before = kl.export_state()
     with pytest.raises(KoalaInvalidArgumentError) as e:
-        kl.process_hold(interleave(frames(x, T, T), C), hold)
+        kl.process_hold(interleave(frames(x, T, 2 * T), C), hold)
     text = str(e.value) + ' '.join(getattr(e.value, 'message_stack', []) or [])
     assert 'group 2' in text and 'streams 4 and 5' in text and 'hold' in text, text
     assert np.array_equal(kl.export_state(), before)
     hold[4] = 1  # the group as a whole: legal
-    second = interleave(frames(x, T, T), C)
+    second = interleave(frames(x, T, 2 * T), C)
     a, b = kl.process_hold(second, hold), twin.process_hold(second, hold)
     keep = np.ones(B // C, bool)
     keep[2] = False  # (a held group's elements are unspecified)
@@ -223,7 +219,7 @@ def test_a_48_khz_f32_handle_is_the_composition_around_the_linked_16_khz_call():
     x = (synth_streams(B, 2 * T * 3, 17)[:, :2 * T * F].astype(np.float32) / np.float32(32768)).astype(np.float32)
     for k in range(2):
         part = np.ascontiguousarray(x[:, k * T * F:(k + 1) * T * F])
-        got = device_call(kl, interleave(part, C), 'device' if k == 0 else 'inplace')
+        got = call(kl, interleave(part, C), 'device' if k == 0 else 'inplace')
         want = sf.encode(sf.F32, rec.process(sf.decode(sf.F32, part)))
         assert same(got, interleave(want, C)), k
     kl.delete()

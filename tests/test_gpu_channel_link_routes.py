@@ -29,14 +29,13 @@ import functools
 import numpy as np
 import pytest
 
-import koala_amd
 from channel_link_recipe import LinkRecipe
 from conftest import model_file, synth_streams
 from frame_report_recipe import applied_mask, report_rows, row_sum
+from gpu_kit import (DEV_LIB, ROUTE_CHUNKED, ROUTE_PIPELINED, ROUTE_QUAD1, ROUTE_RESETS, ROUTE_SMALL, ROUTE_WAVE, batch, call, frames, replicas,
+                     route_info, route_of, same, streams, tiled)
 from koala_amd.channels import deinterleave, interleave, link_masks
 from oracle import oracle
-from test_gpu_channels import device_call, same, streams
-from test_gpu_min_gain import DEV_LIB, ROUTE_CHUNKED, ROUTE_PIPELINED, ROUTE_QUAD1, ROUTE_RESETS, ROUTE_SMALL, ROUTE_WAVE, route_of
 
 pytestmark = pytest.mark.gpu
 
@@ -46,22 +45,7 @@ SEG_ENV = 'KOALA_AMD_SYNTH_SEG'
 
 
 def make(B, C, T, precision, link=True, **kw):
-    return koala_amd.create_batch('key', B, T, precision, model_path=model_file('random'), library_path=DEV_LIB, channels=C,
-                                  channel_link='max' if link else None, **kw)
-
-
-def frames(x, t0, n):
-    return np.ascontiguousarray(x[:, t0 * 256:(t0 + n) * 256])
-
-
-def tiled(a, B):
-    """the first replica's rows [R, ...] over B slots (B a multiple of C: the last replica ends at a group boundary)"""
-    return np.ascontiguousarray(np.concatenate([a] * -(-B // a.shape[0]))[:B])
-
-
-def replicas(a):
-    """every replica == the first"""
-    return same(a, tiled(a[:R], a.shape[0]))
+    return batch(model_file('random'), B, T, precision, DEV_LIB, channels=C, channel_link='max' if link else None, **kw)
 
 
 def as_f32(s):
@@ -134,14 +118,14 @@ def test_fp32_routes_equal_the_recipe(precision, C, B, Tmax, calls, routes):
         if n == 1:
             gain = np.roll(GAINS, 3)
             kl.set_min_gain(tiled(gain, B))
-        xn = frames(x1, t0, T)
-        y, rep = device_call(kl, interleave(tiled(xn, B), C), mode, report=True)
+        xn = frames(x1, t0, t0 + T)
+        y, rep = call(kl, interleave(tiled(xn, B), C), mode, report=True)
         taken.append(route_of(kl))
         yp = deinterleave(y, C)
         want, wrep = ref.process(xn, gain)
         assert np.array_equal(yp[:R], want), (n, mode, where(yp[:R], want, C))
         assert same(rep[:R], wrep), (n, mode)
-        assert replicas(yp) and replicas(rep), (n, mode)
+        assert replicas(yp, R) and replicas(rep, R), (n, mode)
         t0 += T
     kl.delete()
     for r in routes:
@@ -162,12 +146,12 @@ def test_bf16_routes_equal_the_synthesis_of_the_twins_tapped_masks(precision, C,
         gain = tables[n]
         for h in (kl, ku):
             h.set_min_gain(tiled(gain, B))
-        xn = frames(x1, t0, T)
+        xn = frames(x1, t0, t0 + T)
         xi = interleave(tiled(xn, B), C)
-        yl, rl = device_call(kl, xi, mode, report=True)
+        yl, rl = call(kl, xi, mode, report=True)
         taken.append(route_of(kl))
-        yu, ru = device_call(ku, xi, mode, report=True)
-        info = ku.debug_read('route', 1)
+        yu, ru = call(ku, xi, mode, report=True)
+        info = route_info(ku)
         assert int(info[0]) == taken[-1] and info[2] == 0, (n, info)  # the twin took the same route, its masks are in memory
         m = ku.debug_read('mask', T)[:, :R]
         stored = ku.debug_read('spectrum', T)[:, :R] if info[3] else None
@@ -177,7 +161,7 @@ def test_bf16_routes_equal_the_synthesis_of_the_twins_tapped_masks(precision, C,
         assert np.array_equal(yp[:R], want), (n, mode, where(yp[:R], want, C))
         assert same(rl[:R], wrep), (n, mode)
         assert same(rl[..., [0, 2, 3]], ru[..., [0, 2, 3]]), (n, mode)
-        assert replicas(yp) and replicas(rl), (n, mode)
+        assert replicas(yp, R) and replicas(rl, R), (n, mode)
         assert not np.array_equal(yl, yu), n
         t0 += T
     kl.delete(), ku.delete()
@@ -197,10 +181,10 @@ def test_bf16_pipeline_slices_recompute_linked_with_and_without_a_report():
     for h in (kf, ks):
         h.set_min_gain(tiled(GAINS, B))
     for n in range(2):
-        xi = interleave(tiled(frames(x1, n * T, T), B), C)
-        ys, rs = device_call(ks, xi, 'device', report=True)
-        got = device_call(kf, as_f32(xi), 'device', report=n == 1)
-        info = kf.debug_read('route', 1)
+        xi = interleave(tiled(frames(x1, n * T, (n + 1) * T), B), C)
+        ys, rs = call(ks, xi, 'device', report=True)
+        got = call(kf, as_f32(xi), 'device', report=n == 1)
+        info = route_info(kf)
         assert int(info[0]) == ROUTE_PIPELINED and info[3] == 0, info  # pipelined, no spectrum stored
         assert route_of(ks) == ROUTE_PIPELINED
         yf, rf = got if n == 1 else (got, None)
@@ -226,13 +210,13 @@ def test_bf16_one_frame_calls_equal_one_long_call_linked_and_distinct(C, B, rout
             h.set_min_gain(tiled(GAINS, B))
         ys, reps = [], []
         for t in range(K):
-            y, rep = device_call(k1, interleave(frames(x, t, 1), C), 'inplace' if t % 2 else 'device', report=True)
-            got = k1.debug_read('route', 1)
+            y, rep = call(k1, interleave(frames(x, t, t + 1), C), 'inplace' if t % 2 else 'device', report=True)
+            got = route_info(k1)
             assert int(got[0]) == route and got[2] == 1, (link, t, got)  # the route, and the mask head rode in the synthesis launch
             ys.append(deinterleave(y, C))
             reps.append(rep)
         y1, r1 = np.concatenate(ys, axis=1), np.concatenate(reps, axis=1)
-        yt, rt = device_call(kt, interleave(x, C), 'device', report=True)
+        yt, rt = call(kt, interleave(x, C), 'device', report=True)
         yt = deinterleave(yt, C)
         assert np.array_equal(y1, yt), (link, where(y1, yt, C))
         assert same(r1, rt), link
@@ -242,7 +226,7 @@ def test_bf16_one_frame_calls_equal_one_long_call_linked_and_distinct(C, B, rout
     want, wrep = Tapped(R, C).process(x1, m, GAINS)
     assert np.array_equal(yl[:R], want), where(yl[:R], want, C)
     assert same(rl[:R], wrep)
-    assert replicas(yl) and replicas(rl) and not np.array_equal(yl, yu)
+    assert replicas(yl, R) and replicas(rl, R) and not np.array_equal(yl, yu)
 
 
 # ------------------------------------------------------------------------------------------------ 4. segment length, every arm
@@ -276,9 +260,9 @@ def run_arms(precision, B, C):
             kb.set_min_gain(gains)
         got = []
         for n, (mode, reset) in enumerate(seq):
-            x = tiled(frames(x1, n * SEG_T, SEG_T), B)
+            x = tiled(frames(x1, n * SEG_T, (n + 1) * SEG_T), B)
             x = interleave(x, C) if linked else x
-            r = device_call(kb, as_f32(x) if f32 else x, mode, report='report' in arm, **({} if reset is None else {'reset': reset}))
+            r = call(kb, as_f32(x) if f32 else x, mode, report='report' in arm, **({} if reset is None else {'reset': reset}))
             if reset is not None:
                 assert route_of(kb) == ROUTE_RESETS, arm
             got.append(r if 'report' in arm else (r, None))
@@ -312,12 +296,12 @@ def test_segment_length_unset_arms_agree_and_fp32_is_the_recipe(B, C, precision,
         assert not np.array_equal(calls('linked')[n][0], interleave(calls('plain')[n][0], C)), n
         for arm in ARMS:
             y = calls(arm)[n][0]
-            assert replicas(deinterleave(y, C) if arm.startswith('linked') else y), (arm, n)
+            assert replicas(deinterleave(y, C) if arm.startswith('linked') else y, R), (arm, n)
     if precision == 'fp32':
         x1, rs = synth_streams(R, 3 * SEG_T, 35), seg_resets(C)
         ref = LinkRecipe(model_file('random'), R, C)
         for n in range(3):
-            want, wrep = ref.process(frames(x1, n * SEG_T, SEG_T), GAINS, rs if n == 2 else None)
+            want, wrep = ref.process(frames(x1, n * SEG_T, (n + 1) * SEG_T), GAINS, rs if n == 2 else None)
             y, rep = calls('linked_gains_report')[n]
             assert np.array_equal(deinterleave(y, C)[:R], want), (n, where(deinterleave(y, C)[:R], want, C))
             assert same(rep[:R], wrep), n
@@ -370,8 +354,7 @@ def test_the_schedule_has_the_phases_it_claims():
 
 
 def packet_handle(B, C, rate=16000):
-    return koala_amd.create_batch('key', B, 1, 'fp32', model_path=model_file('random'), library_path=DEV_LIB, sample_rate=rate,
-                                  packet_samples=PACKET, channels=C, channel_link='max')
+    return batch(model_file('random'), B, 1, 'fp32', DEV_LIB, sample_rate=rate, packet_samples=PACKET, channels=C, channel_link='max')
 
 
 def run_schedule(C, G, rate, seed):
@@ -438,7 +421,7 @@ def test_an_8_khz_ulaw_handle_is_the_composition_around_the_linked_16_khz_call()
     x = sf.encode(sf.ULAW, streams(B, 2 * T * F, seed=36))
     for k in range(2):
         part = np.ascontiguousarray(x[:, k * T * F:(k + 1) * T * F])
-        got = device_call(kl, interleave(part, C), 'device' if k == 0 else 'inplace')
+        got = call(kl, interleave(part, C), 'device' if k == 0 else 'inplace')
         want = sf.encode(sf.ULAW, rec.process(sf.decode(sf.ULAW, part)))
         assert same(got, interleave(want, C)), k
     kl.delete()

@@ -17,33 +17,14 @@ import pytest
 
 import koala_amd
 import sample_format_recipe as sf
-from conftest import model_file, synth_streams
+from conftest import model_file
+from gpu_kit import MARK, call, flen, packet_call, same, streams
 from koala_amd import KoalaInvalidArgumentError
 from koala_amd._batch import BatchConfig
 from koala_amd._koala import PicovoiceStatuses
 from koala_amd.channels import deinterleave, interleave
 
 pytestmark = pytest.mark.gpu
-
-MARK = 0x5A5A  # what device `enhanced` is prefilled with around and behind what a call may write
-
-
-def flen(rate):
-    return rate * 256 // 16000
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    if a.dtype == np.float32:
-        return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    return np.array_equal(a, b)
-
-
-def streams(B, n, seed=0):
-    """[B, n] int16, every row its own signal"""
-    return np.ascontiguousarray(synth_streams(B, -(-n // 256), seed)[:, :n])
 
 
 def pair(B, C, precision='fp32', rate=16000, T=3, packet_samples=0, sample_format='s16', model='random'):
@@ -52,48 +33,10 @@ def pair(B, C, precision='fp32', rate=16000, T=3, packet_samples=0, sample_forma
     return koala_amd.create_batch('key', B, T, precision, channels=C, **kw), koala_amd.create_batch('key', B, T, precision, **kw)
 
 
-def device_call(kb, x, mode='device', report=False, offset=0, **kw):
-    """one frame call through device pointers: out of place, in place ('inplace'), or with both pointers `offset` elements behind an aligned
-    address.  `enhanced` lies between two guard zones of MARK, which must come back untouched.  -> enhanced (, report), shaped like x"""
-    import torch
-    flat = torch.from_numpy(np.ascontiguousarray(x).reshape(-1))
-    n, guard = flat.numel(), 64
-    src = torch.zeros(n + offset + 8, dtype=flat.dtype, device='cuda')
-    src[offset:offset + n] = flat.cuda()
-    if mode == 'inplace':
-        big = torch.full((guard + offset + n + guard,), 0, dtype=flat.dtype, device='cuda')
-        big.view(torch.uint8)[:] = MARK & 0xFF
-        big[guard + offset:guard + offset + n] = flat.cuda()
-        xin = big[guard + offset:]
-    else:
-        big = torch.zeros(guard + offset + n + guard, dtype=flat.dtype, device='cuda')
-        big.view(torch.uint8)[:] = MARK & 0xFF
-        xin = src[offset:]
-    out = big[guard + offset:]
-    T = x.size // (kb.num_streams * kb.frame_length)
-    rd = torch.full((kb.num_streams, T, 4), -1.0, dtype=torch.float32, device='cuda') if report else None
-    torch.cuda.synchronize()
-    kb.process_device_call(T, xin.data_ptr(), out.data_ptr(), rd.data_ptr() if report else 0, **kw)
-    kb.synchronize()
-    got = big.cpu().numpy()
-    marks = np.concatenate([got[:guard + offset], got[guard + offset + n:]]).view(np.uint8)
-    assert (marks == (MARK & 0xFF)).all(), 'the call wrote outside [G][n C]'
-    y = got[guard + offset:guard + offset + n].reshape(x.shape)
-    return (y, rd.cpu().numpy()) if report else y
-
-
 def planar_call(kp, x, C, report=False, **kw):
     """the reference: deinterleave, the planar handle with device pointers in place, interleave"""
-    got = device_call(kp, deinterleave(x, C), 'inplace', report=report, **kw)
+    got = call(kp, deinterleave(x, C), 'inplace', report=report, **kw)
     return (interleave(got[0], C), got[1]) if report else interleave(got, C)
-
-
-def channel_call(kc, x, mode, report=False, **kw):
-    if mode == 'host':
-        return kc.process_call(x, report=report, **kw)
-    if mode == 'offset':
-        return device_call(kc, x, 'device', report=report, offset=1, **kw)
-    return device_call(kc, x, mode, report=report, **kw)
 
 
 # ------------------------------------------------------------------------------------------------ 1. pure delay
@@ -108,7 +51,7 @@ def test_bypass_gain_returns_every_channel_delayed_by_256_samples(precision, mod
     kc.set_min_gain(1.0)
     x = interleave(streams(B, calls * n), C)  # [G, calls n C]
     parts = [np.ascontiguousarray(x[:, k * n * C:(k + 1) * n * C]) for k in range(calls)]
-    y = np.concatenate([channel_call(kc, p, mode) for p in parts], axis=1)
+    y = np.concatenate([call(kc, p, mode) for p in parts], axis=1)
     assert y.shape == (G, calls * n * C)
     assert np.array_equal(y[:, 256 * C:], x[:, :-256 * C]) and not y[:, :256 * C].any()
     px, py = deinterleave(x, C), deinterleave(y, C)
@@ -141,7 +84,7 @@ def test_a_channel_handle_is_interleave_of_the_planar_handle_of_deinterleave(C, 
     x = interleave(streams(B, 3 * T * F, seed=C), C)
     for k, mode in enumerate(('device', 'host', 'inplace')):
         part = np.ascontiguousarray(x[:, k * T * F * C:(k + 1) * T * F * C])
-        got, want = channel_call(kc, part, mode), planar_call(kp, part, C)
+        got, want = call(kc, part, mode), planar_call(kp, part, C)
         assert same(got, want), (mode, int((got != want).sum()))
     kc.delete(), kp.delete()
 
@@ -166,7 +109,7 @@ def test_a_format_channel_frame_handle_is_encode_of_the_s16_channel_handle_of_de
     x = format_signal(fmt, B // C, 3 * T * 256 * C, 5)
     for k, mode in enumerate(('host', 'device', 'offset')):
         part = np.ascontiguousarray(x[:, k * T * 256 * C:(k + 1) * T * 256 * C])
-        got = channel_call(kf, part, mode)
+        got = call(kf, part, mode)
         want = sf.encode(FMT[fmt], ks.process(sf.decode(FMT[fmt], part)))
         assert same(got, want), mode
     kf.delete(), ks.delete()
@@ -190,17 +133,6 @@ def test_a_format_channel_packet_handle_is_encode_of_the_s16_channel_handle_of_d
 
 
 # ------------------------------------------------------------------------------------------------ 4. packet handles, ragged
-
-def packet_device(kb, x, counts, restart=None):
-    """one packet call through device pointers, `enhanced` prefilled with MARK -> (the whole buffer as it came back, frames)"""
-    import torch
-    xd = torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    yd = torch.full(x.shape, MARK, dtype=torch.int16, device='cuda')
-    torch.cuda.synchronize()
-    frames = kb.process_device_packets(x.size // kb.num_streams, counts, xd.data_ptr(), yd.data_ptr(), restart)
-    kb.synchronize()
-    return yd.cpu().numpy(), frames
-
 
 @pytest.mark.parametrize('rate', [16000, 44100])
 def test_ragged_packet_calls_equal_the_planar_packet_handle(rate):
@@ -228,7 +160,7 @@ def test_ragged_packet_calls_equal_the_planar_packet_handle(rate):
             got, frames, rep = kc.process_packets(x, counts, restart, report=True)
             assert same(rep, want_rep), k
         else:
-            got, frames = packet_device(kc, x, counts, restart)
+            got, frames = packet_call(kc, x, counts, restart)
         assert np.array_equal(frames, want_frames), k
         for g in range(G):
             w = int(per_group[g]) * C
@@ -258,7 +190,7 @@ def test_resets_held_streams_min_gain_and_report_stay_per_stream(precision, mode
     parts = [np.ascontiguousarray(x[:, k * n * C:(k + 1) * n * C]) for k in range(6)]
 
     def both(k, rows=None, **kw):
-        got, want = channel_call(kc, parts[k], mode, **kw), planar_call(kp, parts[k], C, **kw)
+        got, want = call(kc, parts[k], mode, **kw), planar_call(kp, parts[k], C, **kw)
         if kw.get('report'):
             keep = slice(None) if rows is None else rows
             assert same(got[1][keep], want[1][keep]), k  # report[B][T][4], indexed by stream

@@ -7,12 +7,11 @@ import pytest
 
 import koala_amd
 from conftest import model_file, synth_streams
+from gpu_kit import BF16_TOL
 from koala_amd import corpus
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
-
-BF16_TOL = 5  # tests/test_gpu_parity.py
 
 
 @pytest.fixture(scope='module')

@@ -18,13 +18,12 @@ import koala_amd
 import packet_recipe as pr
 import sample_rate_recipe as srr
 from conftest import model_file, synth_streams
+from gpu_kit import BF16_TOL, BF16_WITHIN_1
 from koala_amd import formats
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
-BF16_TOL = 5            # tests/test_gpu_parity.py
-BF16_WITHIN_1 = 0.99    # tests/test_gpu_packets.py: a packet handle in other cuts
 NS = 5                  # streams
 N_MAX = 1000            # max_samples
 CALLS = 40

@@ -5,7 +5,7 @@ the kReport forms of koala_amd/csrc/kns_stft.hip's synthesis kernel under every 
 
 Expected rows come from tests/frame_report_recipe.py, the numpy float32 restatement of the spec.  fp32: e_in, e_out and mask_sum == the
 recipe.  bf16: e_in == the recipe (the spectrum is the spec's in both configurations); e_out relative and mask_sum / 257 absolute within
-BF16_E_OUT_REL and BF16_MEAN_GAIN_ABS below.  The `want_*` functions build every test's expected rows, so that tools/frame_report_bars.py
+BF16_E_OUT_REL and BF16_MEAN_GAIN_ABS of the recipe module.  The `want_*` functions build every test's expected rows, so that tools/frame_report_bars.py
 can run the same inputs through the plain and the jittered bf16 oracle on the CPU: the bars are 4 x the largest distance it finds.
 """
 import ctypes
@@ -15,30 +15,14 @@ import pytest
 
 import koala_amd
 from conftest import load_wav, synth_streams
-from frame_report_recipe import ReportRecipe
+from frame_report_recipe import BF16_E_OUT_REL, BF16_MEAN_GAIN_ABS, ReportRecipe
+from gpu_kit import DEV_LIB, ROUTE_RESETS, batch, call, classes, frames, route_of
 from koala_amd import corpus
 from koala_amd._batch import BatchCall
 from koala_amd._koala import fetch_error_stack
-from test_gpu_min_gain import DEV_LIB, GAINS, NCLS, ROUTE_RESETS, SHAPES, frames, route_of
+from min_gain_recipe import GAINS, NCLS, SHAPES
 
 pytestmark = pytest.mark.gpu
-
-# profiles/r10_frame_report.txt (tools/frame_report_bars.py, CPU): the largest distance between the plain and the jittered bf16 recipe over
-# every bf16 input of this module was 1.449e-3 relative in e_out and 5.320e-5 absolute in mask_sum / 257; the bars are 4 x those (the jitter
-# probe has under-predicted the device by about 2 x before, DESIGN.md section 5: one factor of 2 on top of that).
-BF16_E_OUT_REL = 4 * 1.449e-3
-BF16_MEAN_GAIN_ABS = 4 * 5.320e-5
-
-
-def batch(model, B, T, precision, lib=None):
-    return koala_amd.create_batch('key', B, T, precision, model_path=model, library_path=lib)
-
-
-def classes(B, seed):
-    cls = np.random.default_rng(seed).integers(0, NCLS, B)
-    cls[:NCLS] = np.arange(NCLS)  # (every class somewhere)
-    return cls
-
 
 def check(got, want, precision, what):
     """got, want float32 [..., 4].  Prints the figures before it asserts."""
@@ -58,35 +42,6 @@ def check(got, want, precision, what):
         assert rel.max() <= BF16_E_OUT_REL and mg.max() <= BF16_MEAN_GAIN_ABS, (what, float(rel.max()), float(mg.max()))
     else:
         assert np.array_equal(got[..., 1], want[..., 1]) and np.array_equal(got[..., 2], want[..., 2]), what
-
-
-def call(kb, x, mode, reset=None, hold=None, report=True):
-    """one call -> (enhanced, report or None): 'host' (pageable), 'device', 'inplace' (device, enhanced == pcm), 'async' (page-locked)"""
-    B, T = x.shape[0], x.shape[1] // 256
-    if mode == 'host':
-        r = kb.process_call(x, reset=reset, hold=hold, report=report)
-        return r if report else (r, None)
-    if mode == 'pinned':  # synchronous, page-locked buffers: the copy engines write the caller's arrays directly
-        a, b = kb.alloc_host(T), kb.alloc_host(T)
-        rep = kb.alloc_host_report(T) if report else None
-        a[:] = x
-        kb._call(T, a.ctypes.data, b.ctypes.data, reset, hold, rep.ctypes.data if report else None, False)
-        return b.copy(), (rep.copy() if report else None)
-    if mode == 'async':
-        a, b = kb.alloc_host(T), kb.alloc_host(T)
-        rep = kb.alloc_host_report(T) if report else None
-        a[:] = x
-        kb.process_async_call(a, b, report=rep, reset=reset)
-        kb.synchronize()
-        return b.copy(), (rep.copy() if report else None)
-    import torch
-    xd = torch.from_numpy(x).cuda()
-    yd = xd if mode == 'inplace' else torch.zeros_like(xd)
-    rd = torch.full((B, T, 4), -1.0, dtype=torch.float32, device='cuda') if report else None
-    torch.cuda.synchronize()
-    kb.process_device_call(T, xd.data_ptr(), yd.data_ptr(), rd.data_ptr() if report else 0, reset=reset, hold=hold)
-    kb.synchronize()
-    return yd.cpu().numpy(), (rd.cpu().numpy() if report else None)
 
 
 # ------------------------------------------------------------------------------------------------ expected rows (shared with the bars' probe)
@@ -151,7 +106,7 @@ def test_every_route_reports_the_recipe_and_changes_nothing_else(random_model, p
     if any(m != 'host' and m != 'async' for _, m in calls):
         pytest.importorskip('torch')
     xc, want = want_mixed(random_model, precision, calls)
-    cls = classes(B, B)
+    cls = classes(B, B, NCLS)
     x = xc[cls]
     # kb asks for the report (product library), plain never does; dev repeats kb's calls on the developer library, where the route is read back
     kb, plain, dev = batch(random_model, B, Tmax, precision), batch(random_model, B, Tmax, precision), batch(random_model, B, Tmax, precision, DEV_LIB)
@@ -161,9 +116,9 @@ def test_every_route_reports_the_recipe_and_changes_nothing_else(random_model, p
         for h in (kb, plain, dev):
             h.set_min_gain(gc)
         xn = frames(x, t0, t0 + T)
-        got, rep = call(kb, xn, mode)
-        base, _ = call(plain, xn, mode, report=False)
-        again, rep_dev = call(dev, xn, mode)
+        got, rep = call(kb, xn, mode, report=True)
+        base = call(plain, xn, mode)
+        again, rep_dev = call(dev, xn, mode, report=True)
         taken.add(route_of(dev))
         what = 'call %d (%d frames, %s)' % (n, T, mode)
         check(rep, want[n][cls], precision, what)
@@ -184,15 +139,15 @@ def test_sub_chunked_host_call_into_page_locked_buffers(random_model, precision)
     """a host call of 16 MiB from page-locked memory: every sub-chunk's report rows are copied straight into the caller's array, beside its
     samples -- the rows and samples of the same call through pageable memory (the staging path, checked against the recipe above)"""
     B, T = 1024, 32
-    x = synth_streams(NCLS, 2 * T, seed=53)[classes(B, 3)]
+    x = synth_streams(NCLS, 2 * T, seed=53)[classes(B, 3, NCLS)]
     pin, page, plain = batch(random_model, B, T, precision), batch(random_model, B, T, precision), batch(random_model, B, T, precision)
     for h in (pin, page, plain):
         h.set_min_gain(np.resize(GAINS, B))
     for n in range(2):
         xn = frames(x, n * T, (n + 1) * T)
-        y0, r0 = call(page, xn, 'host')
-        y1, r1 = call(pin, xn, 'pinned')
-        y2, _ = call(plain, xn, 'pinned', report=False)
+        y0, r0 = call(page, xn, 'host', report=True)
+        y1, r1 = call(pin, xn, 'pinned', report=True)
+        y2 = call(plain, xn, 'pinned')
         assert np.array_equal(r1, r0) and np.array_equal(y1, y0) and np.array_equal(y2, y0), n
         assert (r1[..., 0] > 0).all() and not r1[..., 3].any()
     for h in (pin, page, plain):
@@ -212,7 +167,7 @@ def test_unity_model_and_silence(unity_model, precision):
         kb.set_min_gain(np.resize(GAINS, B))
         t0 = 0
         for n, mode in seq:
-            _, rep = call(kb, frames(x, t0, t0 + n), mode)
+            _, rep = call(kb, frames(x, t0, t0 + n), mode, report=True)
             assert (rep[..., 2] == np.float32(257.0)).all() and np.array_equal(rep[..., 0], rep[..., 1]) and not rep[..., 3].any(), (B, n, mode)
             assert not rep[3][..., :2].any() and (rep[[b for b in range(B) if b not in (3, B - 1)]][..., 0] > 0).all()
             if t0 == 0:
@@ -230,16 +185,16 @@ def test_per_frame_resets(random_model, precision, mode):
         pytest.importorskip('torch')
     B, T = 40, 8
     xc, want = want_resets(random_model, precision, T)
-    cls = classes(B, 5)
+    cls = classes(B, 5, NCLS)
     rc = reset_masks(T)
     kb, plain, dev = batch(random_model, B, T, precision), batch(random_model, B, T, precision), batch(random_model, B, T, precision, DEV_LIB)
     for h in (kb, plain, dev):
         h.set_min_gain(GAINS[cls])
     for n in range(2):
         xn, r = frames(xc, n * T, (n + 1) * T)[cls], np.ascontiguousarray(rc[n][cls])
-        got, rep = call(kb, xn, mode, reset=r)
-        base, _ = call(plain, xn, mode, reset=r, report=False)
-        call(dev, xn, mode, reset=r)
+        got, rep = call(kb, xn, mode, reset=r, report=True)
+        base = call(plain, xn, mode, reset=r)
+        call(dev, xn, mode, reset=r, report=True)
         assert route_of(dev) == ROUTE_RESETS
         check(rep, want[n][cls], precision, 'resets, call %d (%s)' % (n, mode))  # a reset frame: the spectrum of [0 | frame]
         assert np.array_equal(got, base)
@@ -259,7 +214,7 @@ def test_per_frame_resets(random_model, precision, mode):
 def test_held_streams(random_model, precision):
     B, T = 40, 4
     xc, want, want_skipped = want_hold(random_model, precision, T)
-    cls = classes(B, 7)
+    cls = classes(B, 7, NCLS)
     hold = (np.random.default_rng(8).random(B) < 0.4).astype(np.uint8)
     hold[0], hold[1] = 1, 0
     free = hold == 0

@@ -12,15 +12,10 @@ import pytest
 
 import koala_amd
 from conftest import synth_streams
+from gpu_kit import BF16_TOL, FP32_TOL, lsb
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
-BF16_TOL = 5   # (a constant: tests/test_gpu_parity.py)
-FP32_TOL = 0   # fp32 engine = fp32 oracle, sample for sample
-
-
-def lsb(a, b):
-    return np.abs(a.astype(np.int64) - b.astype(np.int64))
 
 
 @pytest.mark.parametrize('precision,B,T,calls', [('fp32', 19, 3, 3), ('fp32', 1, 1, 7), ('bf16', 40, 8, 2), ('bf16', 272, 2, 4),

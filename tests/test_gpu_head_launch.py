@@ -24,12 +24,12 @@ import numpy as np
 import pytest
 
 import koala_amd
+from gpu_kit import ROUTE_CHUNKED, ROUTE_RESETS
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = (2, 5, 8)
 B = 32
-ROUTE_CHUNKED, ROUTE_CHUNKED_RESETS = 0, 6  # kns_engine.cpp, enum Route
 
 _ARM_SCRIPT = r'''
 import sys
@@ -93,7 +93,7 @@ def test_every_arm_took_the_resident_route(arms):
             want = 2 if arm == 'fused' else 0
             assert [int(a['heads_%d_%s' % (T, c)][0]) for c in ('0', '1', 'resets')] == [want] * 3, (arm, T)
             assert [int(a['route_%d_%d' % (T, c)][0]) for c in range(2)] == [ROUTE_CHUNKED] * 2, (arm, T)
-            assert int(a['route_%d_resets' % T][0]) == ROUTE_CHUNKED_RESETS, (arm, T)
+            assert int(a['route_%d_resets' % T][0]) == ROUTE_RESETS, (arm, T)
             assert a['pcm_%d_0' % T].any() and a['pcm_%d_1' % T].any(), (arm, T)
 
 

@@ -18,10 +18,10 @@ import pytest
 
 import koala_amd
 from conftest import model_file
+from gpu_kit import batch, call, cut, same
 from high_band_recipe import HighBand
 from koala_amd import KoalaInvalidArgumentError, formats
 from koala_amd.channels import deinterleave, interleave
-from test_gpu_channels import device_call, same
 
 pytestmark = pytest.mark.gpu
 
@@ -30,8 +30,7 @@ SEQ = (1, 1, 1, 3, 2, 1)
 
 
 def make(rate, precision, carry, **kw):
-    return koala_amd.create_batch('key', B, TMAX, precision, model_path=model_file('random'), sample_rate=rate,
-                                  high_band='carry' if carry else None, **kw)
+    return batch(model_file('random'), B, TMAX, precision, sample_rate=rate, high_band='carry' if carry else None, **kw)
 
 
 def noise(rate, frames, seed, peak=20000):
@@ -40,20 +39,6 @@ def noise(rate, frames, seed, peak=20000):
     x = rng.integers(-peak, peak + 1, size=(B, frames * rate * 256 // 16000)).astype(np.int16)
     x[B - 1] = 0
     return x
-
-
-def cut(x, rate, seq=SEQ):
-    F, out, t0 = rate * 256 // 16000, [], 0
-    for T in seq:
-        out.append(np.ascontiguousarray(x[:, t0 * F:(t0 + T) * F]))
-        t0 += T
-    return out
-
-
-def call(kb, x, mode, report=False, **kw):
-    if mode == 'host':
-        return kb.process_call(x, report=report, **kw)
-    return device_call(kb, x, mode, report=report, **kw)
 
 
 @pytest.mark.parametrize('mode', ['device', 'host'])
@@ -66,7 +51,7 @@ def test_carry_equals_the_recipe_over_the_plain_handle(rate, precision, mode):
     ref = HighBand(B, rate)
     for phase, gains in enumerate([None, (np.array([0.0, 0.25, 1.0, 0.25], np.float32), np.array([1.0, 0.0, 0.25, 1.0], np.float32))]):
         g = np.zeros(B, np.float32)
-        for i, x in enumerate(cut(noise(rate, sum(SEQ), 5 + phase), rate)):
+        for i, x in enumerate(cut(noise(rate, sum(SEQ), 5 + phase), rate, SEQ)):
             if gains is not None and i in (0, 3):
                 g = gains[i // 3]
                 ka.set_min_gain(g), kb.set_min_gain(g)
@@ -92,8 +77,8 @@ def test_with_the_bypass_gain_the_handle_is_a_pure_delay_to_one_lsb(rate, precis
     ka, kb = make(rate, precision, False), make(rate, precision, True)
     ka.set_min_gain(1.0), kb.set_min_gain(1.0)
     x = noise(rate, sum(SEQ), 9, peak=8192)
-    ya = np.concatenate([call(ka, p, 'device') for p in cut(x, rate)], axis=1)
-    yb = np.concatenate([call(kb, p, 'device') for p in cut(x, rate)], axis=1)
+    ya = np.concatenate([call(ka, p, 'device') for p in cut(x, rate, SEQ)], axis=1)
+    yb = np.concatenate([call(kb, p, 'device') for p in cut(x, rate, SEQ)], axis=1)
     F, D = rate * 256 // 16000, kb.delay_sample
     xd = np.concatenate([np.zeros((B, D), np.int16), x], axis=1)[:, :x.shape[1]].astype(int)
     err_b, err_a = np.abs(yb.astype(int) - xd)[:, 2 * F:], np.abs(ya.astype(int) - xd)[:, 2 * F:]
@@ -127,7 +112,7 @@ def test_resets_restart_the_high_band_with_the_stream(rate):
 def test_off_is_the_plain_handle_and_on_again_starts_the_high_band_afresh(rate):
     """case 4"""
     ka, kb, ref = make(rate, 'bf16', False), make(rate, 'bf16', True), HighBand(B, rate)
-    for i, x in enumerate(cut(noise(rate, sum(SEQ), 31), rate)):
+    for i, x in enumerate(cut(noise(rate, sum(SEQ), 31), rate, SEQ)):
         if i == 2:
             kb.set_high_band(None)
             assert kb.high_band is None
@@ -153,7 +138,7 @@ def test_formats_channels_and_the_link_stay_outside(mode):
     ka.set_min_gain(g), kb.set_min_gain(g)
     x = noise(rate, sum(SEQ), 41)
     x[B - 1] = x[0] // 2  # (every channel a signal: the group max is taken over unequal masks)
-    for i, p in enumerate(cut(x, rate)):
+    for i, p in enumerate(cut(x, rate, SEQ)):
         xf = formats.encode('f32', interleave(p, C))
         e, rep = call(ka, xf, mode, report=True)
         y = call(kb, xf, mode)

@@ -22,14 +22,12 @@ route 0, the chunked route, at both rates: flags on frame 0 alone are a masked r
 import numpy as np
 import pytest
 
-import koala_amd
 from conftest import model_file
+from gpu_kit import (DEV_LIB, ROUTE_CHUNKED, ROUTE_PIPELINED, ROUTE_QUAD1, ROUTE_SMALL, ROUTE_WAVE, batch, call, cut, replicas, route_info,
+                     route_of, same, tiled)
 from high_band_recipe import EDGE_GAINS, EDGE_SEQ, RATES, HighBand, edge_conditions, edge_streams
 from koala_amd import formats
 from koala_amd.channels import deinterleave, interleave
-from test_gpu_channels import same
-from test_gpu_high_band import call, cut
-from test_gpu_min_gain import DEV_LIB, ROUTE_CHUNKED, ROUTE_PIPELINED, ROUTE_QUAD1, ROUTE_SMALL, ROUTE_WAVE, route_of
 
 pytestmark = pytest.mark.gpu
 
@@ -39,8 +37,7 @@ FLAGGED = (2, 7, 11)  # the streams whose frame 0 carries a reset flag in the fl
 
 
 def make(B, Tmax, rate, precision, carry, **kw):
-    return koala_amd.create_batch('key', B, Tmax, precision, model_path=model_file('random'), library_path=DEV_LIB, sample_rate=rate,
-                                  high_band='carry' if carry else None, **kw)
+    return batch(model_file('random'), B, Tmax, precision, DEV_LIB, sample_rate=rate, high_band='carry' if carry else None, **kw)
 
 
 def noise(rate, frames, seed, peak=20000):
@@ -48,14 +45,6 @@ def noise(rate, frames, seed, peak=20000):
     x = np.random.default_rng(seed).integers(-peak, peak + 1, size=(R, frames * rate * 256 // 16000)).astype(np.int16)
     x[R - 1] = 0
     return x
-
-
-def tiled(a, B):
-    return np.ascontiguousarray(np.concatenate([a] * -(-B // a.shape[0]))[:B])
-
-
-def replicas(a):
-    return same(a, tiled(a[:R], a.shape[0]))
 
 
 # ------------------------------------------------------------------------------------------------ 1. routes
@@ -105,7 +94,7 @@ def test_every_route_equals_the_recipe_over_the_plain_handle(precision, rate, B,
         assert taken[-2:] == [route, route], (n, taken)
         want = ref.process(x16[n], e[:R], rep[:R, :, 2], gain)
         assert np.array_equal(y[:R], want), (n, mode, int((y[:R] != want).sum()), sorted(set(np.nonzero(y[:R] != want)[0].tolist())))
-        assert replicas(y), (n, mode)
+        assert replicas(y, R), (n, mode)
         assert rep_b is None or same(rep_b, rep), (n, mode)
         # a band was added on every stream but the silent one -- once a stream is older than D, which is longer than a frame: not in a first
         # call, and not on the streams that a one-frame call's flags have just made fresh
@@ -126,7 +115,7 @@ def test_six_one_frame_calls_on_the_quad_route_equal_one_six_frame_call():
     ys, reps = [], []
     for t, p in enumerate(cut(x, rate, [1] * K)):
         y, rep = call(k1, p, 'inplace' if t % 2 else 'device', report=True)
-        info = k1.debug_read('route', 1)
+        info = route_info(k1)
         assert int(info[0]) == ROUTE_QUAD1 and info[2] == 1, (t, info)  # the route, and the mask head rode in the synthesis launch
         ys.append(y), reps.append(rep)
     yt, rt = call(kt, x, 'device', report=True)
@@ -134,7 +123,7 @@ def test_six_one_frame_calls_on_the_quad_route_equal_one_six_frame_call():
     y1 = np.concatenate(ys, axis=1)
     assert np.array_equal(y1, yt), int((y1 != yt).sum())
     assert same(np.concatenate(reps, axis=1), rt)
-    assert replicas(yt) and (yt[:R - 1, -512:] != 0).any(axis=1).all()
+    assert replicas(yt, R) and (yt[:R - 1, -512:] != 0).any(axis=1).all()
     k1.delete(), kt.delete()
 
 

@@ -2,149 +2,34 @@
 Per-stream attenuation limit (include/pv_koala_batch.h: pv_koala_batch_set_min_gain, pv_koala_set_min_gain) on
 a real MI355X: the kMinGain arm of koala_amd/csrc/kns_stft.hip's synthesis kernel under every route of the dispatch table.
 
-The expected samples of a limited stream are built from the oracle's stage functions (`Recipe` below): `Oracle.process_with_mask` gives every
-frame's mask m, `Oracle.analysis` its spectrum, numpy float32 forms m' = g + (1 - g) m (one subtraction, one product, one sum, each rounded
-to float32) and `oracle.synthesis` makes the samples.  fp32 comparisons are == (FP32_TOL = 0); bf16 within the suite's bars (BF16_TOL,
-BF16_WITHIN_1 of tests/test_gpu_parity.py).  Two consequences hold exactly in both precisions and are tested with ==: gain 0 is the plain
-engine, gain 1 is the input delayed by delay_sample.
+The expected samples of a limited stream are built from the oracle's stage functions (tests/min_gain_recipe.py).  fp32 comparisons are ==
+(FP32_TOL = 0); bf16 within the suite's bars (BF16_TOL, BF16_WITHIN_1 of tests/gpu_kit.py).  Two consequences hold exactly in both
+precisions and are tested with ==: gain 0 is the plain engine, gain 1 is the input delayed by delay_sample.
 
 Streams are independent, so large batches are filled with copies of a few CLASSES of stream (a signal and a sequence of gains), scattered
 over the slots at random -- neighbouring rows of an m-tile carry different gains: the oracle runs once per class, every stream is compared.
+
+Every call goes through the older entry points (process, process_resets, process_hold and their device and asynchronous forms).
 """
+import functools
+
 import numpy as np
 import pytest
 
+import gpu_kit
 import koala_amd
 from conftest import synth_streams
-from oracle import oracle
-from test_stream_state import OFF_H, OFF_TAIL
+from gpu_kit import DEV_LIB, ROUTE_RESETS, check_pcm as check, classes, delayed, frames, route_of
+from min_gain_recipe import GAINS, NCLS, SHAPES, Recipe
+from stream_state_recipe import OFF_H, OFF_TAIL
 
 pytestmark = pytest.mark.gpu
 
-BF16_TOL, BF16_WITHIN_1, FP32_TOL = 5, 0.99, 0  # tests/test_gpu_parity.py
-DEV_LIB = koala_amd.developer_library_path()
-# kns_engine.cpp, enum Route
-ROUTE_CHUNKED, ROUTE_SMALL, ROUTE_SMALL_STEPS, ROUTE_QUAD1, ROUTE_WAVE, ROUTE_PIPELINED, ROUTE_RESETS = 0, 1, 2, 3, 4, 5, 6
-NCLS = 8
-# per class: 0 (no limit), 1 (bypass) and values in between; a call's gains are this list rotated by the call's number
-GAINS = np.array([0.0, 1.0, 0.25, 0.5, 0.1, 0.9, 0.031622775, 0.70710677], np.float32)
-
-
-def oracle_prec(precision):
-    return oracle.PREC_BF16 if precision == 'bf16' else oracle.PREC_FP32
-
-
-def frames(x, t0, t1):
-    return np.ascontiguousarray(x[:, t0 * 256:t1 * 256])
-
-
-def delayed(x):
-    """the input delayed by delay_sample = one frame"""
-    return np.concatenate([np.zeros((x.shape[0], 256), np.int16), x[:, :-256]], axis=1)
-
-
-def batch(model, B, T, precision, lib=DEV_LIB):
-    return koala_amd.create_batch('key', B, T, precision, model_path=model, library_path=lib)
-
-
-def route_of(kb):
-    return int(kb.debug_read('route', 1)[0])
-
-
-def check(got, want, precision, what):
-    """fp32: the recipe's samples; bf16: the suite's bars.  Prints the figures before it asserts."""
-    d = np.abs(got.astype(np.int64) - want.astype(np.int64))
-    print('%s %s: max |engine - recipe| = %d LSB, %.4f %% within 1, %d samples' % (what, precision, int(d.max()), 100.0 * (d <= 1).mean(), d.size))
-    if precision == 'bf16':
-        assert d.max() <= BF16_TOL and (d <= 1).mean() >= BF16_WITHIN_1, (what, int(d.max()), float((d <= 1).mean()))
-    else:
-        assert d.max() <= FP32_TOL, (what, int(d.max()))
-
-
-class Recipe:
-    """n streams of the spec with a minimum gain, from the oracle's stages (the module's docstring)"""
-
-    def __init__(self, model, n, precision):
-        self.o = oracle.Oracle(model, n, oracle_prec(precision))
-        self.n = n
-        self.hist = np.zeros((n, 256), np.int16)
-        self.tail = np.zeros((n, 256), np.float32)
-
-    def reset(self, rows):
-        rows = np.asarray(rows, bool)
-        if rows.any():
-            self.o.reset(rows.astype(np.uint8))
-            self.hist[rows] = 0
-            self.tail[rows] = 0
-
-    def process(self, x, gains):
-        x = np.ascontiguousarray(x, np.int16)
-        T = x.shape[1] // 256
-        _, mask = self.o.process_with_mask(x)
-        out = np.empty_like(x)
-        for b in range(self.n):
-            g = np.float32(gains[b])
-            u = np.float32(1.0) - g
-            for t in range(T):
-                fr = x[b, t * 256:(t + 1) * 256]
-                spec, _ = self.o.analysis(self.hist[b], fr)
-                m = mask[t, b].astype(np.float32)
-                mp = (g + (u * m).astype(np.float32)).astype(np.float32)
-                out[b, t * 256:(t + 1) * 256] = oracle.synthesis(spec, mp, self.tail[b])
-                self.hist[b] = fr
-        return out
-
-    def process_resets(self, x, gains, reset):
-        """per-frame stream resets [n, T]: frame by frame, a reset right before its frame"""
-        T = x.shape[1] // 256
-        outs = []
-        for t in range(T):
-            self.reset(reset[:, t] != 0)
-            outs.append(self.process(frames(x, t, t + 1), gains))
-        return np.concatenate(outs, axis=1)
-
-
-def call(kb, x, mode, reset=None):
-    """one call: 'host' (pageable), 'device', 'inplace' (device, enhanced == pcm), 'async' (page-locked, asynchronous, waited for)"""
-    T = x.shape[1] // 256
-    if mode == 'host':
-        return kb.process(x) if reset is None else kb.process_resets(x, reset)
-    if mode == 'async':
-        a, b = kb.alloc_host(T), kb.alloc_host(T)
-        a[:] = x
-        if reset is None:
-            kb.process_async(a, b)
-        else:
-            kb.process_async_resets(a, b, reset)
-        kb.synchronize()
-        return b.copy()
-    import torch
-    xd = torch.from_numpy(x).cuda()
-    yd = xd if mode == 'inplace' else torch.zeros_like(xd)
-    torch.cuda.synchronize()
-    if reset is None:
-        kb.process_device(T, xd.data_ptr(), yd.data_ptr())
-    else:
-        kb.process_device_resets(T, xd.data_ptr(), yd.data_ptr(), reset)
-    kb.synchronize()
-    return yd.cpu().numpy()
+batch = functools.partial(gpu_kit.batch, lib=DEV_LIB)
+call = functools.partial(gpu_kit.call, entry='classic')
 
 
 # ------------------------------------------------------------------------------------------------ 7. mixed gains, every route
-
-# (precision, streams, max frames, [(frames, mode)], routes that must have been taken)
-SHAPES = [
-    ('fp32', 21, 4, [(1, 'host'), (4, 'host'), (1, 'host'), (1, 'host'), (4, 'inplace')], (ROUTE_SMALL, ROUTE_WAVE)),
-    ('bf16', 21, 4, [(1, 'host'), (1, 'host'), (4, 'host'), (1, 'device'), (4, 'inplace')], (ROUTE_SMALL, ROUTE_WAVE)),
-    ('bf16', 1024, 48, [(48, 'device'), (1, 'device'), (32, 'device'), (1, 'host'), (8, 'inplace')],
-     (ROUTE_PIPELINED, ROUTE_QUAD1, ROUTE_CHUNKED)),
-    # host calls of 16 MiB: sub-chunks of 4 12 12 4 frames on three streams (each takes the route of a call of its length); asynchronous: whole
-    ('bf16', 1024, 32, [(32, 'host'), (32, 'async'), (32, 'host')], (ROUTE_PIPELINED,)),
-    ('bf16', 4100, 4, [(4, 'device'), (1, 'device'), (4, 'inplace')], (ROUTE_CHUNKED,)),  # resident8; 257 m-tiles, the last one ragged
-    ('fp32', 4100, 2, [(2, 'device'), (1, 'device'), (2, 'inplace')], (ROUTE_CHUNKED,)),  # fp32 chunked (more than 256 m-tiles)
-    ('fp32', 512, 4, [(4, 'device'), (1, 'host'), (4, 'host')], (ROUTE_WAVE, ROUTE_SMALL)),
-]
-
 
 @pytest.mark.parametrize('precision,B,Tmax,calls,routes', SHAPES, ids=['%s-%dx%d' % (s[0], s[1], s[2]) for s in SHAPES])
 def test_mixed_gains_match_the_recipe(random_model, precision, B, Tmax, calls, routes):
@@ -152,8 +37,7 @@ def test_mixed_gains_match_the_recipe(random_model, precision, B, Tmax, calls, r
         pytest.importorskip('torch')
     total = sum(T for T, _ in calls)
     xc = synth_streams(NCLS, total, seed=21)
-    cls = np.random.default_rng(B).integers(0, NCLS, B)
-    cls[:NCLS] = np.arange(NCLS)  # (every class somewhere)
+    cls = classes(B, B, NCLS)
     x = xc[cls]
     kb, plain = batch(random_model, B, Tmax, precision), batch(random_model, B, Tmax, precision)
     rec = Recipe(random_model, NCLS, precision)
@@ -255,8 +139,7 @@ def test_per_frame_resets_under_a_limit(random_model, precision, mode):
         pytest.importorskip('torch')
     B, T = 40, 8
     xc = synth_streams(NCLS, 2 * T + 1, seed=13)
-    cls = np.random.default_rng(5).integers(0, NCLS, B)
-    cls[:NCLS] = np.arange(NCLS)
+    cls = classes(B, 5, NCLS)
     rng = np.random.default_rng(6)
     rc = [(rng.random((NCLS, T)) < 0.2).astype(np.uint8) for _ in range(2)]
     rc[0][2, 0] = rc[0][2, 1] = rc[1][3, T - 1] = 1  # frame 0, adjacent frames, the last frame
@@ -265,7 +148,7 @@ def test_per_frame_resets_under_a_limit(random_model, precision, mode):
     kb.set_min_gain(GAINS[cls])
     for n in range(2):
         xn = frames(xc, n * T, (n + 1) * T)
-        got = call(kb, xn[cls], mode, np.ascontiguousarray(rc[n][cls]))
+        got = call(kb, xn[cls], mode, reset=np.ascontiguousarray(rc[n][cls]))
         assert route_of(kb) == ROUTE_RESETS
         check(got, rec.process_resets(xn, GAINS, rc[n])[cls], precision, 'resets, call %d (%s)' % (n, mode))
         assert np.array_equal(kb.min_gain(), GAINS[cls])  # a reset is no change of configuration
@@ -284,8 +167,7 @@ def test_per_frame_resets_under_a_limit(random_model, precision, mode):
 def test_held_streams_keep_their_limit_and_state(random_model, precision):
     B, T = 40, 4
     xc = synth_streams(NCLS, 3 * T, seed=17)
-    cls = np.random.default_rng(7).integers(0, NCLS, B)
-    cls[:NCLS] = np.arange(NCLS)
+    cls = classes(B, 7, NCLS)
     hold = (np.random.default_rng(8).random(B) < 0.4).astype(np.uint8)
     hold[0], hold[1] = 1, 0
     kb = batch(random_model, B, T, precision)

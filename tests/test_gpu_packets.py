@@ -18,24 +18,17 @@ import pytest
 import koala_amd
 import sample_rate_recipe as srr
 from conftest import model_file, synth_streams
+from frame_report_recipe import BF16_E_OUT_REL, BF16_MEAN_GAIN_ABS
+from gpu_kit import BF16_TOL, BF16_WITHIN_1, FP32_TOL, flen
 from koala_amd import KoalaInvalidArgumentError, packets
 from koala_amd._batch import BatchPackets
 from koala_amd._koala import PicovoiceStatuses
 
 pytestmark = pytest.mark.gpu
 
-BF16_TOL = 5            # tests/test_gpu_parity.py
-BF16_WITHIN_1 = 0.99    # tests/test_gpu_parity.py
-FP32_TOL = 0            # tests/test_gpu_parity.py
-BF16_E_OUT_REL = 4 * 1.449e-3       # tests/test_gpu_frame_report.py
-BF16_MEAN_GAIN_ABS = 4 * 5.320e-5   # tests/test_gpu_frame_report.py
 DELAY = {8000: 176, 16000: 256, 48000: 912, 32000: 608}  # the frame handles' delay_sample (include/pv_koala_batch.h)
 FRAMES = 10
 RATE_PREC = [(r, p) for r in (8000, 16000, 48000) for p in ('fp32', 'bf16')]
-
-
-def flen(rate):
-    return rate * 256 // 16000
 
 
 def packet_handle(model, B, N, precision, rate=16000):

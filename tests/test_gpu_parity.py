@@ -15,32 +15,16 @@ import pytest
 
 import koala_amd
 from conftest import model_file, synth_streams
+from gpu_kit import BF16_TOL, BF16_WITHIN_1, DEV_LIB, FP32_TOL, lsb
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
-# bf16 engine vs the oracle with the same rounding points: the two differ in the last bit of GEMM outputs (the bf16 MFMA truncates
-# far-apart addends inside its sums of eight, profiles/r05_mfma_probe.txt) and of the gate / head / log transcendentals (hardware
-# v_exp / v_rcp / v_log, <= 1 ulp from the correctly rounded functions the oracle uses), and such a bit now and then flips an fp16 /
-# bf16 rounding downstream.  Largest difference ever measured in this suite: see DESIGN.md section 5.
-# Bar 5 LSB (the same as __graft_entry__.smoke(), whose white-noise sample measures 4; this suite's own maximum is 3) plus the
-# distribution checked wherever a histogram is taken.  Constants, not knobs: nothing in the environment can loosen them.
-BF16_TOL = 5
-# share of samples within 1 LSB: 99.99 % over the bench's 16.8 M samples of synthetic streams (bench.py --full fails its run below
-# 99.9 %); on real speech through the random-weight model (test_bf16_against_both_oracles, 102 400 samples) 99.1 % measured
-BF16_WITHIN_1 = 0.99
-# fp32 engine: the oracle's values, every one of them
-FP32_TOL = 0
-# the -DKNS_DEV build of the same sources: the only library that reads the KOALA_AMD_* developer switches
-DEV_LIB = koala_amd.developer_library_path()
+# (the bars BF16_TOL, BF16_WITHIN_1 and FP32_TOL, with what they rest on: tests/gpu_kit.py)
 
 
 def run_oracle(model, x, precision=oracle.PREC_FP32):
     return oracle.Oracle(model, x.shape[0], precision).process(x)
-
-
-def lsb(a, b):
-    return np.abs(a.astype(np.int64) - b.astype(np.int64))
 
 
 @pytest.mark.parametrize('B,T,calls', [(1, 1, 4), (19, 3, 2), (40, 8, 1), (16, 1, 3)])

@@ -10,11 +10,11 @@ import pytest
 import koala_amd
 import sample_format_recipe as sf
 import test_gpu_sample_rate as every_rate
-from sample_rate_cases import BF16_TOL, CALLS, NCLS, batch, call, signal
+from gpu_kit import BF16_TOL, BF16_WITHIN_1, call
+from sample_rate_cases import CALLS, NCLS, batch, signal
 
 pytestmark = pytest.mark.gpu
 
-BF16_WITHIN_1 = 0.99    # tests/test_gpu_parity.py (a packet handle against a frame handle in other cuts: tests/test_gpu_packets.py)
 RATES = (12000, 24000)
 RATE_PREC = [(r, p) for r in RATES for p in ('fp32', 'bf16')]
 TMAX = max(CALLS[24000])

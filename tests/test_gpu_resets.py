@@ -8,19 +8,12 @@ import pytest
 
 import koala_amd
 from conftest import model_file, synth_streams
+from gpu_kit import BF16_TOL, DEV_LIB, ROUTE_RESETS, lsb
 from koala_amd import corpus
 from koala_amd._errors import KoalaInvalidArgumentError
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
-
-BF16_TOL = 5  # tests/test_gpu_parity.py
-DEV_LIB = koala_amd.developer_library_path()
-ROUTE_CHUNKED_RESETS = 6  # kns_engine.cpp, enum Route
-
-
-def lsb(a, b):
-    return np.abs(a.astype(np.int64) - b.astype(np.int64))
 
 
 def random_mask(rng, B, T):
@@ -57,7 +50,7 @@ def test_null_and_zero_mask_are_the_plain_call(random_model, precision, B, T):
         routes.append(kb.debug_read('route', T).tolist())
     kb.delete()
     assert routes[0] == routes[1] == routes[2], routes
-    assert routes[0][0] != ROUTE_CHUNKED_RESETS
+    assert routes[0][0] != ROUTE_RESETS
     assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[0], outs[2])
 
 
@@ -78,7 +71,7 @@ def test_random_masks_against_split_calls_on_the_oracle(kind, precision, B, T, c
         xc = np.ascontiguousarray(x[:, c * T * 256:(c + 1) * T * 256])
         m = random_mask(rng, B, T)
         y = kb.process_resets(xc, m)
-        assert int(kb.debug_read('route', T)[0]) == ROUTE_CHUNKED_RESETS
+        assert int(kb.debug_read('route', T)[0]) == ROUTE_RESETS
         want = corpus.process_split(ref, xc, m)
         d = lsb(y, want).reshape(B, T, 256).max(axis=2)  # [stream, frame]
         if precision == 'fp32':

@@ -14,6 +14,7 @@ import pytest
 import koala_amd
 import sample_format_recipe as sf
 from conftest import model_file
+from gpu_kit import call, flen, packet_call, same
 from koala_amd import KoalaInvalidArgumentError, KoalaRuntimeError
 from koala_amd._batch import BatchConfig
 from koala_amd._koala import PicovoiceStatuses
@@ -26,26 +27,12 @@ FMT = {'s16': sf.S16, 'f32': sf.F32, 'ulaw': sf.ULAW, 'alaw': sf.ALAW}
 MATRIX = [('f32', 16000), ('ulaw', 16000), ('alaw', 16000), ('ulaw', 8000), ('alaw', 8000), ('f32', 48000)]
 
 
-def flen(rate):
-    return rate * 256 // 16000
-
-
 def dec(fmt, a):
     return sf.decode(FMT[fmt], a)
 
 
 def enc(fmt, s):
     return sf.encode(FMT[fmt], s)
-
-
-def same(a, b):
-    """element for element, bit for bit (float rows compared as their bits: no -0 == 0, no NaN != NaN)"""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    if a.dtype == np.float32:
-        return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    return np.array_equal(a, b)
 
 
 def signal(fmt, B, n, seed=7):
@@ -64,22 +51,6 @@ def pair(model, B, precision, rate, fmt, T=TMAX, packet_samples=0):
     """(the format handle, its S16 twin)"""
     kw = dict(model_path=model, sample_rate=rate, packet_samples=packet_samples)
     return (koala_amd.create_batch('key', B, T, precision, sample_format=fmt, **kw), koala_amd.create_batch('key', B, T, precision, **kw))
-
-
-def call(kb, x, mode, **kw):
-    """one frame call through host pointers, device pointers or one device buffer in place -> enhanced (, report)"""
-    report = kw.pop('report', False)
-    if mode == 'host':
-        return kb.process_call(x, report=report, **kw)
-    import torch
-    T = x.shape[1] // kb.frame_length
-    xd = torch.from_numpy(x).cuda()
-    yd = xd if mode == 'inplace' else torch.empty_like(xd)
-    rd = torch.full((x.shape[0], T, 4), -1.0, dtype=torch.float32, device='cuda') if report else None
-    torch.cuda.synchronize()
-    kb.process_device_call(T, xd.data_ptr(), yd.data_ptr(), rd.data_ptr() if report else 0, **kw)
-    kb.synchronize()
-    return (yd.cpu().numpy(), rd.cpu().numpy()) if report else yd.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------ the format matrix
@@ -161,22 +132,6 @@ def test_report_min_gain_resets_and_held_streams_pass_through(fmt, rate, precisi
 
 # ------------------------------------------------------------------------------------------------ packet handles
 
-def packet_call(kb, pcm, counts, restart, mode, sentinel):
-    """one packet call into a sentinel-filled `enhanced` -> the whole matrix"""
-    N = pcm.shape[1]
-    if mode == 'host':
-        out = np.full_like(pcm, sentinel)
-        kb._packets(N, counts, pcm.ctypes.data, out.ctypes.data, restart, None, 0)
-        return out
-    import torch
-    xd = torch.from_numpy(pcm).cuda()
-    yd = torch.from_numpy(np.full_like(pcm, sentinel)).cuda()
-    torch.cuda.synchronize()
-    kb.process_device_packets(N, counts, xd.data_ptr(), yd.data_ptr(), restart)
-    kb.synchronize()
-    return yd.cpu().numpy()
-
-
 @pytest.mark.parametrize('mode', ['host', 'device'])
 @pytest.mark.parametrize('N', [1, 80, 701])
 @pytest.mark.parametrize('fmt,rate', [('f32', 16000), ('ulaw', 8000)])
@@ -197,8 +152,8 @@ def test_packet_handles_write_counted_rows_only_and_start_with_encoded_zeros(fmt
         pcm = np.zeros((B, N), x.dtype)
         for b in range(B):
             pcm[b, :counts[b]] = x[b, pos[b]:pos[b] + counts[b]]
-        got = packet_call(kf, pcm, counts, restart, mode, sentinel_f)
-        want = packet_call(ks, dec(fmt, pcm), counts, restart, mode, sentinel_s)
+        got = packet_call(kf, pcm, counts, restart, mode, sentinel_f)[0]
+        want = packet_call(ks, dec(fmt, pcm), counts, restart, mode, sentinel_s)[0]
         for b in range(B):
             c = counts[b]
             assert same(got[b, :c], enc(fmt, want[b, :c])), (i, b)
@@ -451,7 +406,7 @@ def test_a_refused_host_call_leaves_caller_and_streams_alone(precision):
 
     def accepted_packets():
         part = next(parts)
-        got, want = packet_call(kf, part, counts, None, 'host', np.float32(-7.5)), packet_call(ks, dec(fmt, part), counts, None, 'host', np.int16(-7))
+        got, want = packet_call(kf, part, counts, None, 'host', np.float32(-7.5))[0], packet_call(ks, dec(fmt, part), counts, None, 'host', np.int16(-7))[0]
         for b in range(B):
             assert same(got[b, :counts[b]], enc(fmt, want[b, :counts[b]])), b
         fill[:] = (fill + counts) % F

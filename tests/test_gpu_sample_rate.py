@@ -17,7 +17,8 @@ import pytest
 import koala_amd
 import sample_rate_recipe as srr
 from conftest import model_file, synth_streams
-from sample_rate_cases import CALLS, NCLS, TMAX, batch, call, check, classes, cut, expected, signal
+from gpu_kit import call
+from sample_rate_cases import CALLS, NCLS, TMAX, batch, check, classes, cut, expected, signal
 
 pytestmark = pytest.mark.gpu
 

@@ -16,56 +16,12 @@ import pytest
 import koala_amd
 from conftest import ROOT, synth_streams
 from koala_amd._errors import KoalaInvalidArgumentError, PicovoiceStatuses
+from gpu_kit import (BF16_TOL, DEV_LIB, ROUTE_CHUNKED, ROUTE_PIPELINED, ROUTE_QUAD1, ROUTE_SMALL, ROUTE_WAVE, batch, call, frames, lsb,
+                     oracle_prec, route_of, tol)
 from oracle import oracle
-from test_stream_state import record_size, unpack_record
+from stream_state_recipe import record_size, unpack_record
 
 pytestmark = pytest.mark.gpu
-
-BF16_TOL = 5  # tests/test_gpu_parity.py
-DEV_LIB = koala_amd.developer_library_path()
-# kns_engine.cpp, enum Route
-ROUTE_CHUNKED, ROUTE_SMALL, ROUTE_SMALL_STEPS, ROUTE_QUAD1, ROUTE_WAVE, ROUTE_PIPELINED = 0, 1, 2, 3, 4, 5
-
-
-def lsb(a, b):
-    return int(np.abs(np.asarray(a).astype(np.int64) - np.asarray(b).astype(np.int64)).max())
-
-
-def tol_of(precision):
-    return BF16_TOL if precision == 'bf16' else 0
-
-
-def oracle_prec(precision):
-    return oracle.PREC_BF16 if precision == 'bf16' else oracle.PREC_FP32
-
-
-def frames(x, t0, t1):
-    return np.ascontiguousarray(x[:, t0 * 256:t1 * 256])
-
-
-def batch(model, B, T, precision, lib=None):
-    return koala_amd.create_batch('key', B, T, precision, model_path=model, library_path=lib)
-
-
-def call(kb, x, hold=None, device=False):
-    """one call from host memory, or (device) from device memory: a host call of 4 MiB or more is cut into sub-chunks, which take the
-    routes of shorter calls"""
-    if not device:
-        return kb.process(x) if hold is None else kb.process_hold(x, hold)
-    import torch
-    xd = torch.from_numpy(x).cuda()
-    yd = torch.zeros_like(xd)
-    torch.cuda.synchronize()
-    if hold is None:
-        kb.process_device(x.shape[1] // 256, xd.data_ptr(), yd.data_ptr())
-    else:
-        kb.process_device_hold(x.shape[1] // 256, xd.data_ptr(), yd.data_ptr(), hold)
-    kb.synchronize()
-    return yd.cpu().numpy()
-
-
-def route_of(kb):
-    return int(kb.debug_read('route', 1)[0])
 
 
 # ------------------------------------------------------------------------------------------------ 1. what a record holds
@@ -168,7 +124,7 @@ def migrate(model, precision, n, first, B2, T2, second, slots_seed=3, expect_rou
         xb = np.zeros((B2, T * 256), np.int16)
         xb[dst] = frames(x, t0, t0 + T)
         t0 += T
-        outs.append(call(b, xb, device=device)[dst])
+        outs.append(call(b, xb, 'device' if device else 'host', entry='classic')[dst])
         routes.add(route_of(b))
     b.delete()
     for r in expect_routes:
@@ -188,17 +144,17 @@ def test_migration_matches_the_uninterrupted_oracle(random_model, precision, B2,
     if device:
         pytest.importorskip('torch')
     got, ref, _ = migrate(random_model, precision, 16, 2, B2, T2, second, expect_routes=routes, device=device)
-    d = lsb(got, ref)
+    d = lsb(got, ref).max()
     print('migration %s -> %d x %d: max |engine - oracle| = %d LSB' % (precision, B2, T2, d))
-    assert d <= tol_of(precision)
+    assert d <= tol(precision)
 
 
 @pytest.mark.parametrize('precision', ['fp32', 'bf16'])
 def test_migration_carries_the_feature_context(random5_model, precision):
     got, ref, _ = migrate(random5_model, precision, 12, 2, 96, 4, [4, 1, 1, 4, 1])
-    d = lsb(got, ref)
+    d = lsb(got, ref).max()
     print('migration random5 %s: max |engine - oracle| = %d LSB' % (precision, d))
-    assert d <= tol_of(precision)
+    assert d <= tol(precision)
 
 
 @pytest.mark.parametrize('precision', ['fp32', 'bf16'])
@@ -208,12 +164,12 @@ def test_migration_keeps_the_adapted_noise_floor(gate_model, precision):
     would see a reset."""
     n, first, second = 4, 12, [16, 1, 15]
     got, ref, x = migrate(gate_model, precision, n, first, 128, 16, second)
-    d = lsb(got, ref)
+    d = lsb(got, ref).max()
     restarted = oracle.Oracle(gate_model, n, oracle_prec(precision)).process(frames(x, 8 * first, 8 * first + sum(second)))
-    apart = lsb(restarted[:, 256:], ref[:, (8 * first + 1) * 256:])
+    apart = lsb(restarted[:, 256:], ref[:, (8 * first + 1) * 256:]).max()
     print('migration gate %s: max |engine - oracle| = %d LSB; a restarted stream is %d LSB away' % (precision, d, apart))
     assert apart > BF16_TOL  # (else this comparison could not tell a reset from a move)
-    assert d <= tol_of(precision)
+    assert d <= tol(precision)
 
 
 _CHILD = r'''
@@ -306,7 +262,7 @@ def test_held_streams_are_not_advanced(random_model, precision, B, Tmax, lengths
     cls[:classes] = np.arange(classes)
     kb = batch(random_model, B, Tmax, precision, DEV_LIB)
     refs = [oracle.Oracle(random_model, 1, oracle_prec(precision)) for _ in range(classes)]
-    tol, worst, seen, before = tol_of(precision), 0, set(), None
+    bar, worst, seen, before = tol(precision), 0, set(), None
     zero = np.flatnonzero(cls == 0)
     # (the required routes come round in the first calls, whatever the draw)
     plan = [lengths[-1]] + list(lengths) + [int(rng.choice(lengths)) for _ in range(calls - 1 - len(lengths))]
@@ -317,12 +273,12 @@ def test_held_streams_are_not_advanced(random_model, precision, B, Tmax, lengths
         if n == 3:
             held_c[:] = True  # (a call in which nobody advances)
         hold = held_c[cls].astype(np.uint8)
-        y = call(kb, np.ascontiguousarray(xc[cls]), hold, device)
+        y = call(kb, np.ascontiguousarray(xc[cls]), 'device' if device else 'host', hold=hold, entry='classic')
         seen.add(route_of(kb))
         for c in np.flatnonzero(~held_c):
             want = refs[c].process(xc[c])
             rows = y[cls == c]
-            worst = max(worst, lsb(rows, np.broadcast_to(want, rows.shape)))
+            worst = max(worst, int(lsb(rows, np.broadcast_to(want, rows.shape)).max()))
         if n == 0:
             before = kb.export_state(zero)
     print('hold %s %d x %d: routes %s, max |engine - oracle| = %d LSB' % (precision, B, Tmax, sorted(seen), worst))
@@ -330,7 +286,7 @@ def test_held_streams_are_not_advanced(random_model, precision, B, Tmax, lengths
     kb.delete()
     for r in routes:
         assert r in seen, (sorted(seen), routes)
-    assert worst <= tol
+    assert worst <= bar
 
 
 @pytest.mark.parametrize('precision,B,T', [('bf16', 4096, 64), ('bf16', 1024, 64), ('bf16', 1024, 1), ('fp32', 37, 5), ('bf16', 32, 1)])
