@@ -426,6 +426,39 @@ typedef enum { PV_KOALA_HIGH_BAND_NONE = 0, PV_KOALA_HIGH_BAND_CARRY = 1 } pv_ko
 PV_API pv_status_t pv_koala_batch_set_high_band(pv_koala_batch_t *object, int32_t mode);
 PV_API pv_status_t pv_koala_batch_get_high_band(const pv_koala_batch_t *object, int32_t *mode);
 
+/* BAND PROFILE (tenth extension): a floor and a ceiling on the mask per stream and per bin -- "at most 6 dB below
+ * 300 Hz", "leave 4-8 kHz alone" (floors); a high-pass under the speech band, the 300-3400 Hz limit in front of a G.711 trunk (ceilings).
+ * Every stream b has two curves of PV_KOALA_NUM_BINS = 257 fp32 values, bins 0 (DC) to 256 (Nyquist of the 16 kHz inner stream), 31.25 Hz
+ * apart: floor_b[k] and ceil_b[k], each in [0, 1], floor_b[k] <= ceil_b[k].  A new handle has floor = 0 and ceil = 1 everywhere, the
+ * NEUTRAL profile.  In every frame processed while a profile is in force, with m[k] the network's mask and g_b the stream's attenuation limit:
+ *     m1[k] = g_b + (1 - g_b) m[k]                      exactly as pv_koala_batch_set_min_gain states it
+ *     m'[k] = min(ceil_b[k], max(floor_b[k], m1[k]))    max first, then min; both exact
+ *     Y[k]  = m'[k] X[k]
+ * so the rule adds no rounding: an fp32 handle stays bit-exact against the oracle under it (koala_amd/bands.py states it in numpy).
+ *   Neutral profile: the same samples; with every stream neutral the handle takes the routes and kernels it always took.
+ *   floor = ceil = 1 on all bins: a pure delay by delay_sample, bit for bit, both precisions, any model.
+ *   ceil = 0 on all bins: e_out == 0 in every frame, digital silence once the last frame made under the old profile has left the overlap.
+ *   The network never sees its own output: stream state, records, e_in and mask_sum of the frame report are bit for bit those of the handle
+ *     without a profile; e_out is that of m'.
+ *   Configuration, not state: no reset, held call or record changes or carries it, and state_size is unchanged.
+ * pv_koala_batch_set_band_profile: floor[i] / ceil[i] (rows of 257) are the curves of stream streams[i]; streams == NULL means slots
+ * 0 .. count - 1; floor == NULL means zeros, ceil == NULL means ones; streams not listed keep theirs.  All arrays are HOST memory, read before
+ * the function returns.  No device work and no wait: the table travels with the next call and is uploaded only when it has changed
+ * (asynchronous host calls in flight keep the profile they were issued under).  PV_STATUS_INVALID_ARGUMENT, with a message on the error stack
+ * and NOTHING changed: a NULL object, count outside [1, num_streams], an index outside [0, num_streams), a slot listed twice, a value that
+ * is NaN or outside [0, 1], floor[k] > ceil[k] (the message names the entry and the bin, "profile 3, bin 17: ...").
+ * pv_koala_batch_get_band_profile: the curves in force of one stream (either out-pointer may be NULL).
+ * NOT YET, refused by name with PV_STATUS_INVALID_ARGUMENT, nothing processed and state unchanged: a call under a profile that is not neutral
+ * on a handle whose channel link is on, or whose high-band carry is on (its broadband gain would have to follow the profile). */
+#define PV_KOALA_NUM_BINS 257
+PV_API pv_status_t pv_koala_batch_set_band_profile(pv_koala_batch_t *object, int32_t count, const int32_t *streams,
+                                                   const float *floor /*[count][257] or NULL*/, const float *ceil /*[count][257] or NULL*/);
+PV_API pv_status_t pv_koala_batch_get_band_profile(const pv_koala_batch_t *object, int32_t stream, float *floor /*[257] or NULL*/,
+                                                   float *ceil /*[257] or NULL*/);
+/* The same for the single-stream handle of pv_koala.h: the profile of pv_koala_process from the next frame on. */
+PV_API pv_status_t pv_koala_set_band_profile(pv_koala_t *object, const float *floor /*[257] or NULL*/, const float *ceil /*[257] or NULL*/);
+PV_API pv_status_t pv_koala_get_band_profile(const pv_koala_t *object, float *floor /*[257] or NULL*/, float *ceil /*[257] or NULL*/);
+
 PV_API pv_status_t pv_koala_batch_num_streams(const pv_koala_batch_t *object, int32_t *num_streams);
 PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, int32_t *delay_sample);
 

@@ -12,6 +12,7 @@ import numpy as np
 
 from ._koala import (KoalaError, KoalaInvalidArgumentError, KoalaIOError, PicovoiceStatuses, attenuation_limit_to_gain, load_library,
                      raise_status)
+from . import bands
 from .channels import LINK_CHANNELS, MAX_CHANNELS
 from .formats import DTYPES, FORMATS
 from .packets import FRACTIONAL_UP, inner_samples
@@ -45,7 +46,7 @@ class KoalaBatch(object):
 
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
                  max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0, sample_format: str = 's16',
-                 channels: int = 1, channel_link: Optional[str] = None, high_band: Optional[str] = None) -> None:
+                 channels: int = 1, channel_link: Optional[str] = None, high_band: Optional[str] = None, band_profile=None) -> None:
         """`sample_rate`: 44100 or 22050 Hz make a packet handle around fractional converters (`packet_samples` > 0 is required; there is
         no frame length, `frame_length` is None, and stream records and the asynchronous calls are refused); otherwise
         8000, 12000, 16000, 24000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
@@ -68,7 +69,8 @@ class KoalaBatch(object):
         `channel_link`: None (default) or 'max' -- with 'max' (`channels` 2, 4 or 8) the channels of a group share one mask, the max of their
         own masks bin by bin, so the stereo image does not move (`set_channel_link`; koala_amd.channels.link_masks states the rule).
         `high_band`: None (default) or 'carry' -- a frame handle at 32000 or 48000 Hz adds the band above the 16 kHz call's, delayed like
-        the call and scaled by a broadband gain from the call's masks (`set_high_band`; koala_amd.highband states the rule)."""
+        the call and scaled by a broadband gain from the call's masks (`set_high_band`; koala_amd.highband states the rule).
+        `band_profile`: None (default) or (floor, ceiling) -- `set_band_profile(floor, ceiling)` on every stream of the new handle."""
         if not isinstance(access_key, str) or len(access_key) == 0:
             raise KoalaInvalidArgumentError("`access_key` should be a non-empty string.")
         if not os.path.exists(model_path):
@@ -92,6 +94,10 @@ class KoalaBatch(object):
         self.channels = channels
         link = self._link_value(channel_link)  # (checked before the handle is made)
         carry = self._high_band_value(high_band)
+        if band_profile is not None:  # (checked before any library is loaded)
+            if not isinstance(band_profile, (tuple, list)) or len(band_profile) != 2:
+                raise KoalaInvalidArgumentError("`band_profile` should be a pair (floor, ceiling) or None.")
+            band_profile = self._profile_arrays(band_profile[0], band_profile[1], num_streams)
         if carry and (sample_rate not in (32000, 48000) or packet_samples):
             raise KoalaInvalidArgumentError("`high_band` 'carry' needs a frame handle whose `sample_rate` is 32000 or 48000.")
         self.sample_format = sample_format
@@ -191,8 +197,10 @@ class KoalaBatch(object):
         if not fractional:
             self._check(lib.pv_koala_batch_state_size(self._handle, byref(d)), 'Failed to get the state size')
             self.state_size = d.value
-        if link or carry:
+        if link or carry or band_profile is not None:
             try:
+                if band_profile is not None:
+                    self.set_band_profile(band_profile[0], band_profile[1])
                 if link:
                     self.set_channel_link(channel_link)
                 if carry:
@@ -549,6 +557,38 @@ class KoalaBatch(object):
         out = np.empty(self.num_streams, np.float32)
         self._check(self._lib.pv_koala_batch_get_min_gain(self._handle, out.ctypes.data), 'min_gain failed')
         return out
+
+    @staticmethod
+    def _profile_arrays(floor, ceiling, rows):
+        try:
+            return bands.check(floor, ceiling, rows)
+        except ValueError as e:
+            raise KoalaInvalidArgumentError(str(e))
+
+    def _band_profile_fn(self, which, args):
+        # (bound at first use, like the high band's: developer A/B runs load libraries built before the entry points existed)
+        fn = getattr(self._lib, 'pv_koala_batch_%s_band_profile' % which)
+        fn.argtypes, fn.restype = args, PicovoiceStatuses
+        return fn
+
+    def set_band_profile(self, floor=None, ceiling=None, streams=None) -> None:
+        """Per-stream, per-bin floor and ceiling on the mask (include/pv_koala_batch.h, pv_koala_batch_set_band_profile): in every bin k
+        the mask m' under the attenuation limit becomes min(ceiling[k], max(floor[k], m')).  `floor`, `ceiling`: float32 [257] for all
+        the listed streams or [n, 257], one row per listed stream, values in [0, 1], floor <= ceiling; None: zeros / ones, so
+        `set_band_profile()` restores the neutral profile.  `streams`: indices (None: every stream, in order).  koala_amd.bands builds
+        curves (highpass, bandpass, depth_limit_db) and states the rule.  Holds from the next call on; configuration, not state.  A call
+        under a profile that is not neutral is refused while the channel link or the high-band carry is on."""
+        s, sp, n = self._stream_list(streams, None)
+        lo, hi = self._profile_arrays(floor, ceiling, n)
+        fn = self._band_profile_fn('set', [c_void_p, c_int32, c_void_p, c_void_p, c_void_p])
+        self._check(fn(self._handle, n, sp, lo.ctypes.data, hi.ctypes.data), 'set_band_profile failed')
+
+    def band_profile(self, stream: int):
+        """(floor, ceiling) in force of one stream, float32 [257] each."""
+        lo, hi = np.empty(bands.NUM_BINS, np.float32), np.empty(bands.NUM_BINS, np.float32)
+        fn = self._band_profile_fn('get', [c_void_p, c_int32, c_void_p, c_void_p])
+        self._check(fn(self._handle, int(stream), lo.ctypes.data, hi.ctypes.data), 'band_profile failed')
+        return lo, hi
 
     def reset(self, stream_mask: Optional[np.ndarray] = None) -> None:
         ptr = None

@@ -15,6 +15,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from . import bands
 from ._errors import *  # noqa: F401,F403  (re-exported: the reference keeps the exceptions in this module)
 from ._errors import STATUS_TO_EXCEPTION as _STATUS_TO_EXCEPTION
 from ._errors import KoalaInvalidArgumentError, KoalaIOError, PicovoiceStatuses
@@ -197,6 +198,30 @@ class Koala(object):
         if status is not PicovoiceStatuses.SUCCESS:
             raise_status(self._library, status, 'min_gain failed')
         return gain.value
+
+    def set_band_profile(self, floor=None, ceiling=None) -> None:
+        """Per-bin floor and ceiling on the mask from the next frame on (an extension: include/pv_koala_batch.h,
+        pv_koala_set_band_profile): float32 [257] each, values in [0, 1], floor <= ceiling; None: zeros / ones -- `set_band_profile()`
+        restores the neutral profile.  koala_amd.bands builds curves and states the rule.  `reset()` does not change the profile."""
+        try:
+            lo, hi = bands.check(floor, ceiling)
+        except ValueError as e:
+            raise KoalaInvalidArgumentError(str(e))
+        fn = self._library.pv_koala_set_band_profile
+        fn.argtypes, fn.restype = [POINTER(self.CKoala), c_void_p, c_void_p], PicovoiceStatuses
+        status = fn(self._handle, lo.ctypes.data, hi.ctypes.data)
+        if status is not PicovoiceStatuses.SUCCESS:
+            raise_status(self._library, status, 'set_band_profile failed')
+
+    def band_profile(self):
+        """(floor, ceiling) in force, float32 [257] each."""
+        lo, hi = np.empty(bands.NUM_BINS, np.float32), np.empty(bands.NUM_BINS, np.float32)
+        fn = self._library.pv_koala_get_band_profile
+        fn.argtypes, fn.restype = [POINTER(self.CKoala), c_void_p, c_void_p], PicovoiceStatuses
+        status = fn(self._handle, lo.ctypes.data, hi.ctypes.data)
+        if status is not PicovoiceStatuses.SUCCESS:
+            raise_status(self._library, status, 'band_profile failed')
+        return lo, hi
 
     def delete(self) -> None:
         """Releases the native stream."""

@@ -748,6 +748,7 @@ Engine::~Engine() {
     rsf_ring_.release();
     recof_ring_.release();
     mg_ring_.release();
+    pf_ring_.release();
     pk_ring_.release();
     fr_ring_.release();
     for (int i = 0; i < 4; ++i)
@@ -1036,6 +1037,48 @@ bool Engine::begin_min_gain(const Call &c, const float **table, std::string *err
         mg_valid_ = true;
     }
     *table = d_min_gain_;
+    return true;
+}
+
+// The band profile of the call about to run (Call::band_profile, float [B][kProfileRow] host memory in the table's own order), like the
+// limit above: nothing without one; otherwise the device table [Bpad][kProfileRow], uploaded through a slot of pf_ring_ (rows past B: zero)
+// on the handle's stream when the call's revision is not the table's -- 2 KiB per stream, so an unchanged profile costs a call nothing.  A
+// call in flight is in front of the copy on that stream: it keeps the profile it was issued under.
+bool Engine::begin_band_profile(const Call &c, const float **table, std::string *err) {
+    *table = nullptr;
+    if (!c.band_profile) return true;
+    if (c.channel_link || c.high_band || !c.min_gain) {  // (the owner refuses these by name before the engine is reached)
+        *err = !c.min_gain ? "a call with a band profile carries the handle's minimum gains (all zero where no limit is in force)."
+                           : "a band profile is not combined with linked channels nor with the high-band carry.";
+        return false;
+    }
+    const size_t row = (size_t) kProfileRow * 4;
+    if (!d_profile_) {  // first use: the ring and the device table
+        const bool ok = pf_ring_.ready((size_t) Bpad_ * row);
+        float *d = ok ? (float *) dalloc((size_t) Bpad_ * row, true) : nullptr;
+        if (!d) {
+            (void) hipGetLastError();
+            *err = "Failed to allocate the buffers of the band profile.";
+            return false;
+        }
+        d_profile_ = d;
+    }
+    if (!pf_valid_ || pf_rev_ != c.band_profile_rev) {
+        const int k = pf_ring_.acquire();
+        if (k >= 0) {
+            memcpy(pf_ring_.host[k], c.band_profile, (size_t) B_ * row);
+            memset((char *) pf_ring_.host[k] + (size_t) B_ * row, 0, (size_t) (Bpad_ - B_) * row);
+        }
+        if (k < 0 || hipMemcpyAsync(d_profile_, pf_ring_.host[k], (size_t) Bpad_ * row, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+            !pf_ring_.uploaded(k, stream_)) {
+            *err = hip_last_error();
+            pf_valid_ = false;
+            return false;
+        }
+        pf_rev_ = c.band_profile_rev;
+        pf_valid_ = true;
+    }
+    *table = d_profile_;
     return true;
 }
 
@@ -1561,6 +1604,7 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
         sy.rs_t0 = rs_t0 + t0c;
         sy.min_gain = slice.min_gain;
         sy.link = slice.link;
+        sy.profile = slice.profile;
         sy.report = slice.d_report ? slice.d_report + (size_t) t0c * 4 : nullptr;  // (like `out`: the slice's first frame, rows T frames apart)
         launch_synthesis(sy, st);
     };
@@ -1728,7 +1772,7 @@ std::vector<int> Engine::host_schedule(int T) const {
     return sched;
 }
 
-bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *resets, const float *min_gain, std::string *err) {
+bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *resets, const float *min_gain, const float *profile, std::string *err) {
     const int T = call.T;
     const int16_t *pcm = call.pcm;
     int16_t *out = call.out;
@@ -1767,7 +1811,7 @@ bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *r
         // ---- kernels (d_out_ slot s was last drained by the D2H of chunk c - 2)
         check(hipStreamWaitEvent(stream_, ev_in_[s], 0));
         if (c >= 2) check(hipStreamWaitEvent(stream_, ev_out_[s], 0));
-        if (ok && !run_device({first[c], tc, d_in_ + s * slot, d_out_ + s * slot, true, resets, min_gain, report ? d_report_ + s * rslot : nullptr}, err)) {
+        if (ok && !run_device({first[c], tc, d_in_ + s * slot, d_out_ + s * slot, true, resets, min_gain, report ? d_report_ + s * rslot : nullptr, 0, profile}, err)) {
             // copies of earlier sub-chunks may still be writing into the caller's buffers: let them finish first
             (void) hipStreamSynchronize(copy_in_);
             (void) hipStreamSynchronize(copy_out_);
@@ -1922,6 +1966,8 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
     if (!begin_resets(T, c.resets, &table, err)) return Status::kRuntime;  // (the mask is packed into a ring slot of this call: the caller may overwrite it now)
     const float *min_gain = nullptr;  // (the gains are copied into an upload slot of this call: the caller may change them now)
     if (!begin_min_gain(c, &min_gain, err)) return Status::kRuntime;
+    const float *profile = nullptr;  // (... and the band profile: this call keeps the one it was issued under)
+    if (!begin_band_profile(c, &profile, err)) return Status::kRuntime;
     int16_t *din = s ? d_in2_ : d_in_, *dout = s ? d_out2_ : d_out_;
     float *drep = c.report ? (s ? d_report2_ : d_report_) : nullptr;  // (part of the call's staging slot: free when its samples' slot is)
     bool ok = true;
@@ -1935,7 +1981,7 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
         (void) hipDeviceSynchronize();  // (a copy-in may have been enqueued: nothing of this call stays in flight)
         return Status::kRuntime;
     }
-    if (!run_device({0, T, din, dout, true, &table, min_gain, drep}, err)) {
+    if (!run_device({0, T, din, dout, true, &table, min_gain, drep, 0, profile}, err)) {
         (void) hipDeviceSynchronize();
         return Status::kRuntime;
     }
@@ -1981,6 +2027,8 @@ bool Engine::run_call(const Call &c, std::string *err) {
     const size_t rbytes = (size_t) B_ * T * 16;
     const float *min_gain = nullptr;  // (this call's attenuation limit on the device, on the handle's stream in front of everything below)
     if (!begin_min_gain(c, &min_gain, err)) return false;
+    const float *profile = nullptr;  // (... and its band profile)
+    if (!begin_band_profile(c, &profile, err)) return false;
     // (linked channels: such a handle's calls arrive here with device pointers -- process() has split the channels into device rows -- so
     // the host routes below, the one-frame graph among them, never see a linked call: no graph is captured with the linked kernel)
     const int link = c.channel_link ? ch_ : 0;
@@ -1991,7 +2039,7 @@ bool Engine::run_call(const Call &c, std::string *err) {
     if (kin == kPtrDevice) {
         const size_t n = (size_t) B_ * T * kFrame;
         const bool overlap = pcm < out + n && out < pcm + n;
-        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table, min_gain, report, link}, err);
+        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table, min_gain, report, link, profile}, err);
     }
     if (T > host_chunk_ && bytes >= host_pipeline_min_bytes_) {
         const char *pa = (const char *) pcm, *pb = (const char *) out;
@@ -2017,7 +2065,7 @@ bool Engine::run_call(const Call &c, std::string *err) {
                 stream_ = own_stream_;
         }
         const bool pinned = kin == kPtrPinned && kout == kPtrPinned && (!report || pointer_kind(report) == kPtrPinned);
-        const bool done = process_host_pipelined(c, pinned, &table, min_gain, err);
+        const bool done = process_host_pipelined(c, pinned, &table, min_gain, profile, err);
         stream_ = user;
         return done;
     }
@@ -2033,7 +2081,9 @@ bool Engine::run_call(const Call &c, std::string *err) {
         // limit" changes sets, a change of values only re-uploads the table, which begin_min_gain has put on the stream in front of the replay)
         // (... and the same again for calls that ask for the frame report: the kReport forms, writing into the report staging.  A handle that
         // alternates between asking and not asking switches sets; a call without a report replays the plain graphs)
-        const int parity = hs | (hist_cur_ << 1) | (tail_cur_ << 2) | (min_gain ? 8 : 0) | (report ? 16 : 0);
+        // (... and once more for calls under a band profile: the kProfile forms.  A change of the profile's values only re-uploads the table,
+        // which begin_band_profile has put on the stream in front of the replay)
+        const int parity = hs | (hist_cur_ << 1) | (tail_cur_ << 2) | (min_gain ? 8 : 0) | (report ? 16 : 0) | (profile ? 32 : 0);
         if (!frame_graph_[parity]) {
             hipGraph_t graph = nullptr;
             // (relaxed mode and one capture at a time in the process: other threads -- other handles being created, the
@@ -2048,7 +2098,7 @@ bool Engine::run_call(const Call &c, std::string *err) {
                 // (no reset table in the captured frame, whichever call happens to capture it: a one-frame call can restart a stream
                 // at frame 0 only, and that is the reset kernel begin_resets has already put in front of the graph)
                 float *rep = report ? (zero_copy ? h_report_ : d_report_) : nullptr;
-                ok = ok && run_device({0, 1, zero_copy ? h_in_ : d_in_, zero_copy ? h_out_ : d_out_, true, nullptr, min_gain, rep}, err);
+                ok = ok && run_device({0, 1, zero_copy ? h_in_ : d_in_, zero_copy ? h_out_ : d_out_, true, nullptr, min_gain, rep, 0, profile}, err);
                 ok = ok && (zero_copy || hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream_) == hipSuccess);
                 ok = ok && (zero_copy || !report || hipMemcpyAsync(h_report_, d_report_, rbytes, hipMemcpyDeviceToHost, stream_) == hipSuccess);
                 // zero-copy frames end with the completion word (the output is already in host memory when that node runs)
@@ -2115,7 +2165,7 @@ bool Engine::run_call(const Call &c, std::string *err) {
         }
     }
     if (hipMemcpyAsync(d_in_, h_in_, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) goto fail;
-    if (!run_device({0, T, d_in_, d_out_, true, &table, min_gain, report ? d_report_ : nullptr, link}, err)) return false;
+    if (!run_device({0, T, d_in_, d_out_, true, &table, min_gain, report ? d_report_ : nullptr, link, profile}, err)) return false;
     if (hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
     if (report && hipMemcpyAsync(h_report_, d_report_, rbytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
     if (hipStreamSynchronize(stream_) != hipSuccess) goto fail;
@@ -2201,6 +2251,7 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
         Call inner{T, d_in_, d_out_, c.resets};
         inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
         inner.channel_link = c.channel_link;
+        inner.band_profile = c.band_profile, inner.band_profile_rev = c.band_profile_rev;
         inner.report = c.report;
         // High-band carry: the kernel behind the out-stage reads the call's masks from its report -- an output only, so asking for it into a
         // buffer of the engine's changes no bit -- the in-stage's rows, which the device-pointer call leaves in d_in_ as they are, and the
@@ -2870,6 +2921,7 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string
         Call inner{c1 - c0, d_pk_in_ + (size_t) B_ * F * c0, d_pk_out_ + (size_t) B_ * F * c0};
         inner.hold = held ? hold.data() : nullptr;
         inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
+        inner.band_profile = c.band_profile, inner.band_profile_rev = c.band_profile_rev;
         inner.channel_link = c.channel_link;  // (packet_check: a group's streams share k_b, so a sub-call holds a group as a whole)
         inner.report = c.report ? d_pk_rep_ + (size_t) B_ * c0 * 4 : nullptr;
         if (process_frames(inner, err) != Status::kOk) return Status::kRuntime;
@@ -2986,6 +3038,7 @@ Status Engine::run_fractional(const PacketCall &c, std::string *err) {
     }
     // the inner call: an S16 call on device rows, without restarts (done above); its report rows and frame counts are this call's
     PacketCall in16{pk_max_, inner.data(), d_fr_in_, d_fr_out_, nullptr, io.report, io.report_frames, k.data(), c.min_gain, c.min_gain_rev};
+    in16.band_profile = c.band_profile, in16.band_profile_rev = c.band_profile_rev;
     in16.channel_link = c.channel_link;  // (the inner call's rows are the engine's: its `ch` is 1, the link is the handle's)
     st = run_packet_call(in16, kFmtS16, 1, err);
     if (st != Status::kOk) return st;

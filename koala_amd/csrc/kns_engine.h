@@ -74,6 +74,15 @@ struct Call {
     // `resets` behind frame 0.  0: the plain call -- same launches, same bits.
     int high_band = 0;
     unsigned high_band_epoch = 0;
+    // Band profile (tenth extension): host memory, float [num_streams][kProfileRow] -- every stream's 257 floors and
+    // ceilings in the order of profile_index (kns_kernels.h), every value in [0, 1] and floor <= ceiling (checked by the owner, the C ABI's
+    // handle).  Stream b's mask value of bin k becomes min(ceil_b[k], max(floor_b[k], m')) in every frame of the call, m' the value under
+    // `min_gain`, which the call then carries (all zero where no limit is in force: the profile kernels read that table).  Read before the
+    // call returns, like the gains: copied into an upload slot of the call when `band_profile_rev` differs from the one the engine's device
+    // table holds.  Not combined with `channel_link` nor with `high_band`.  nullptr: the neutral profile, the plain call -- same route, same
+    // kernels, same bits.
+    const float *band_profile = nullptr;
+    unsigned band_profile_rev = 0;
 };
 
 // kBadArgument: a stream list, a record or a combination of Call members that the engine refused before it touched anything (the C ABI
@@ -95,6 +104,8 @@ struct PacketCall {
     const float *min_gain = nullptr;   // as Call's
     unsigned min_gain_rev = 0;
     int channel_link = 0;              // as Call's; `restart`, and the streams' phase (the mirrors of fill and of N mod 441), must be equal within a group
+    const float *band_profile = nullptr;  // as Call's
+    unsigned band_profile_rev = 0;
 };
 
 class Engine {
@@ -270,6 +281,7 @@ private:
         const float *min_gain;  // the call's per-stream minimum gains on the device [Bpad] (begin_min_gain), nullptr: no limit in force
         float *d_report = nullptr;  // the slice's frame report [B][T][4] (device-visible memory, rows T frames apart), nullptr: not asked for
         int link = 0;  // the call's linked channels: channels() when Call::channel_link is set (then min_gain is not null), else 0
+        const float *profile = nullptr;  // the call's band profile on the device [Bpad][kProfileRow] (begin_band_profile; then min_gain is not null and link is 0), nullptr: neutral
     };
     bool run_device(const Slice &s, std::string *err);
     void *dalloc(size_t bytes, bool zero);
@@ -326,7 +338,7 @@ private:
     // staging for host-pointer calls: [B][Tmax * 256] each; chunked calls use them as two slots of [B][Tc * 256]
     int16_t *d_in_ = nullptr, *d_out_ = nullptr, *h_in_ = nullptr, *h_out_ = nullptr;
     // host-pointer calls with more than one sub-chunk: copy-in, compute and copy-out run on three streams
-    bool process_host_pipelined(const Call &c, bool pinned, ResetTable *resets, const float *min_gain, std::string *err);
+    bool process_host_pipelined(const Call &c, bool pinned, ResetTable *resets, const float *min_gain, const float *profile, std::string *err);
     std::vector<int> host_schedule(int T) const;  // its sub-chunk lengths
     std::vector<int> dev_host_sched_;             // developer override (KOALA_AMD_HOST_SCHED)
     // calls of several frames as a wavefront over (stage, frame): kns_engine.cpp, run_wave
@@ -354,14 +366,15 @@ private:
     size_t host_pipeline_min_bytes_ = 0;
 
     // hipGraph of one host-pointer frame (copy-in, 23 kernels, copy-out); built on first use
-    hipGraphExec_t frame_graph_[32] = {};  // one per combination of the hidden-state / history / tail ping-pong indices, (bit 3) of
+    hipGraphExec_t frame_graph_[64] = {};  // one per combination of the hidden-state / history / tail ping-pong indices, (bit 3) of
                                            // "an attenuation limit is in force": the captured synthesis kernel is the plain or the kMinGain form,
-                                           // and (bit 4) of "a frame report is asked for": the kReport forms, writing to the report staging
+                                           // (bit 4) of "a frame report is asked for": the kReport forms, writing to the report staging,
+                                           // and (bit 5) of "a band profile is in force": the kProfile forms (bit 3 is set then)
     // completion word of the zero-copy one-frame replays (kns_stft.hip, frame_done_kernel): the host spins on a word in page-locked
     // memory instead of sleeping in hipStreamSynchronize, whose wake-up is what made p99 drift away from p50 on a busy host
     unsigned *d_frame_count_ = nullptr, *h_frame_word_ = nullptr;
     unsigned frame_seq_ = 0;
-    bool frame_graph_signals_[32] = {};
+    bool frame_graph_signals_[64] = {};
     bool spin_wait_ = true;
     bool use_graph_ = true, no_small_ = false, no_zero_copy_ = false, no_recompute_ = false, debug_taps_ = false;
     // developer switches (all read once in init() through dev_env(): compiled out of the product library)
@@ -417,6 +430,15 @@ private:
     unsigned mg_rev_ = 0;
     bool mg_valid_ = false;
     bool begin_min_gain(const Call &c, const float **table, std::string *err);
+    // Band profile (Call::band_profile): the one device table float [Bpad][kProfileRow] and its upload ring, as the gains' -- configuration,
+    // not state.  begin_band_profile: the device table a call's synthesis kernels read (nullptr: neutral), uploaded on the handle's stream in
+    // front of the call's kernels or graph replay when the call's revision is not the table's; a profiled call that is linked, carries the high
+    // band or comes without the gains is the owner's to refuse, and fails here
+    float *d_profile_ = nullptr;
+    UploadRing pf_ring_;
+    unsigned pf_rev_ = 0;
+    bool pf_valid_ = false;
+    bool begin_band_profile(const Call &c, const float **table, std::string *err);
     // Frame report (Call::report) of host-pointer calls: device and page-locked host staging [B][Tmax][4] each, used like d_out_ / h_out_ (two
     // slots of [B][host_chunk_][4] by the sub-chunked calls; the one-frame graph writes into h_report_ or copies to it); d_report2_: the second
     // slot of asynchronous host calls.  Allocated by the first call that asks for a report.

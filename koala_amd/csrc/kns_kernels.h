@@ -103,8 +103,19 @@ struct SynthesisArgs {
     // tile, and every row's mask value becomes the max over its group's, in all 257 bins, behind the report's mask_sum and in front of the
     // minimum gain.  Selects the kernels' kLink arm, which reads `min_gain` (not null then); 0: today's instantiations
     int link = 0;
+    // optional: per-stream band profile (tenth extension), float [Bpad][kProfileRow] in the order of profile_index
+    // below.  Row b's mask value of bin k becomes min(ceil_b[k], max(floor_b[k], m')) behind the minimum gain and in front of Y = mask . X
+    // (and of the report's e_out).  Selects the kernels' kProfile arm, which reads `min_gain` (not null then) and has no linked form
+    // (link == 0); a null pointer: today's instantiations
+    const float *profile = nullptr;
 };
 void launch_synthesis(const SynthesisArgs &a, hipStream_t s);
+
+// A stream's row of the band-profile table, in the order the synthesis kernel's lanes consume it: the lane of column c owns the bins
+// c + 16 k2, k2 = 0 .. 15 -- its 16 floors, then its 16 ceilings, eight 16-byte words in a row -- and the row ends with one word
+// {floor[256], ceil[256], 0, 0} that all 16 lanes read.  which: 0 the floor, 1 the ceiling.
+constexpr int kProfileRow = 16 * 32 + 4;
+inline int profile_index(int k, int which) { return k == kBins - 1 ? 16 * 32 + which : (k & 15) * 32 + which * 16 + (k >> 4); }
 
 // ---- GEMM over all stream-frames: out = act(A . W + bias), A from up to two A-packed sources
 enum GemmOut {

@@ -294,6 +294,14 @@ __device__ __forceinline__ float link_max(float a, float b) {
     return __builtin_bit_cast(float, __builtin_elementwise_max(x, y));
 }
 
+// kProfile (SynthesisArgs::profile; the profile kernels below): m' held between a bin's floor and ceiling, the max first.  All three are finite
+// and not below +0 (m' = g + (1 - g) m of a sigmoid; the owner stores +0 for -0), where the order of the bit patterns is the order of the
+// values: one v_max_i32 and one v_min_i32, exact, as link_max
+__device__ __forceinline__ float profile_clamp(float lo, float hi, float m) {
+    const int x = __builtin_elementwise_max(__builtin_bit_cast(int, m), __builtin_bit_cast(int, lo));
+    return __builtin_bit_cast(float, __builtin_elementwise_min(x, __builtin_bit_cast(int, hi)));
+}
+
 // kReport (calls that ask for the frame report, SynthesisArgs::report; DESIGN.md section 2, step 4, second extension): three sums over the
 // row's 257 bins per emitted frame -- |X|^2, |Y|^2 and the raw mask -- formed where x[], y[] and mk[] are live, in the one order the spec
 // fixes: every lane its column's chain, then a butterfly over the row's lanes.
@@ -335,14 +343,14 @@ __device__ __forceinline__ float report_mask_sum(const float (&m)[17], int c) {
 // kMaskH: the mask travels as fp16 C fragments (bf16 configuration), else fp32
 template <bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets = false, bool kMinGain = false>
 __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_kernel(SynthesisArgs g) {
-    constexpr bool kReport = false, kLink = false;
+    constexpr bool kReport = false, kLink = false, kProfile = false;
 #include "kns_stft_synthesis.inc"
 }
 // the same forms with the frame report: kernels of their own name, the same text (kns_stft_synthesis.inc) -- a call that asks for no report
 // runs what it always ran
 template <bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets, bool kMinGain>
 __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_report_kernel(SynthesisArgs g) {
-    constexpr bool kReport = true, kLink = false;
+    constexpr bool kReport = true, kLink = false, kProfile = false;
 #include "kns_stft_synthesis.inc"
 }
 // kLink (handles with channels whose link is on, SynthesisArgs::link = C; DESIGN.md section 2, eighth extension): the mask of every bin
@@ -354,13 +362,26 @@ __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesi
 template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets>
 __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_link_kernel(SynthesisArgs g) {
     static_assert(kReport || !kRecompute, "linked, recomputed: report forms only");
-    constexpr bool kMinGain = true, kLink = true;
+    constexpr bool kMinGain = true, kLink = true, kProfile = false;
+#include "kns_stft_synthesis.inc"
+}
+// kProfile (handles with a band profile in force, SynthesisArgs::profile; DESIGN.md section 2, tenth extension): every bin's m' is held
+// between the row's floor and ceiling of that bin, behind the minimum gain and in front of Y and e_out.  A kernel of its own name once more,
+// so the forms above stay the instructions they were, and the arm implies kMinGain like the linked one (an all-zero gain table is exact):
+// 9 forms with the report + 9 without = 18 instantiations, not twice the number there was.  There is no linked form: the engine refuses the
+// combination.  The row's nine words are requested where they are consumed, four bins at a time (kns_stft_synthesis.inc): requested with the
+// frame's mask and held until then, they were 36 registers more than the budget of three waves per SIMD has
+template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets>
+__global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_profile_kernel(SynthesisArgs g) {
+    constexpr bool kMinGain = true, kLink = false, kProfile = true;
 #include "kns_stft_synthesis.inc"
 }
 
-template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets, bool kMinGain, bool kLink>
+template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets, bool kMinGain, bool kLink, bool kProfile>
 static void launch_synthesis_form(const SynthesisArgs &a, const dim3 grid, int threads, size_t lds, hipStream_t s) {
-    if constexpr (kLink)
+    if constexpr (kProfile)
+        hipLaunchKernelGGL((synthesis_profile_kernel<kReport, kRecompute, kMaskH, kMaskIn, kResets>), grid, dim3(threads), lds, s, a);
+    else if constexpr (kLink)
         hipLaunchKernelGGL((synthesis_link_kernel<kReport || kRecompute, kRecompute, kMaskH, kMaskIn, kResets>), grid, dim3(threads), lds, s, a);
     else if constexpr (kReport)
         hipLaunchKernelGGL((synthesis_report_kernel<kRecompute, kMaskH, kMaskIn, kResets, kMinGain>), grid, dim3(threads), lds, s, a);
@@ -369,28 +390,29 @@ static void launch_synthesis_form(const SynthesisArgs &a, const dim3 grid, int t
 }
 
 // the forms of one arm (kMinGain: with or without the per-stream minimum gain; kReport: with or without the frame report); the plain arm's
-// are the kernels of a handle without a limit in a call that asks for no report; kLink: the linked kernels, which carry the gain
-template <bool kMinGain, bool kReport, bool kLink = false>
+// are the kernels of a handle without a limit in a call that asks for no report; kLink: the linked kernels, which carry the gain; kProfile:
+// the profile kernels, which carry it too
+template <bool kMinGain, bool kReport, bool kLink = false, bool kProfile = false>
 static void launch_synthesis_arm(const SynthesisArgs &a, const dim3 grid, size_t lds, hipStream_t s) {
     if (a.resets) {  // (calls with per-frame stream resets: the reset arm; the engine does not put the mask head inside then)
         if (a.recompute && a.mask_fp16)
-            launch_synthesis_form<kReport, true, true, false, true, kMinGain, kLink>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, true, true, false, true, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
         else if (a.recompute)
-            launch_synthesis_form<kReport, true, false, false, true, kMinGain, kLink>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, true, false, false, true, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
         else if (a.mask_fp16)
-            launch_synthesis_form<kReport, false, true, false, true, kMinGain, kLink>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, false, true, false, true, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
         else
-            launch_synthesis_form<kReport, false, false, false, true, kMinGain, kLink>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, false, false, false, true, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
     } else if (a.mask_w && !a.recompute && a.mask_fp16 && a.T == 1)
-        launch_synthesis_form<kReport, false, true, true, false, kMinGain, kLink>(a, grid, 512, lds + kMaskTiles * 512, s);
+        launch_synthesis_form<kReport, false, true, true, false, kMinGain, kLink, kProfile>(a, grid, 512, lds + kMaskTiles * 512, s);
     else if (a.recompute && a.mask_fp16)
-        launch_synthesis_form<kReport, true, true, false, false, kMinGain, kLink>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, true, true, false, false, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
     else if (a.recompute)
-        launch_synthesis_form<kReport, true, false, false, false, kMinGain, kLink>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, true, false, false, false, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
     else if (a.mask_fp16)
-        launch_synthesis_form<kReport, false, true, false, false, kMinGain, kLink>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, false, true, false, false, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
     else
-        launch_synthesis_form<kReport, false, false, false, false, kMinGain, kLink>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, false, false, false, false, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
 }
 
 void launch_synthesis(const SynthesisArgs &a, hipStream_t s) {
@@ -400,7 +422,9 @@ void launch_synthesis(const SynthesisArgs &a, hipStream_t s) {
     (void) hipFuncSetAttribute((const void *) synthesis_kernel<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
     (void) hipFuncSetAttribute((const void *) synthesis_report_kernel<true, true, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
 #endif
-    if (a.link)  // (the engine hands a linked launch the gain table, all zero where no limit is in force)
+    if (a.profile)  // (the engine hands a profiled launch the gain table, all zero where no limit is in force, and no link)
+        a.report ? launch_synthesis_arm<true, true, false, true>(a, grid, lds, s) : launch_synthesis_arm<true, false, false, true>(a, grid, lds, s);
+    else if (a.link)  // (the engine hands a linked launch the gain table, all zero where no limit is in force)
         a.report ? launch_synthesis_arm<true, true, true>(a, grid, lds, s) : launch_synthesis_arm<true, false, true>(a, grid, lds, s);
     else if (a.report)
         a.min_gain ? launch_synthesis_arm<true, true>(a, grid, lds, s) : launch_synthesis_arm<false, true>(a, grid, lds, s);

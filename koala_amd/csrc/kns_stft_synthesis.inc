@@ -2,7 +2,7 @@
 // (kReport = false) and synthesis_report_kernel (kReport = true).  Text, not a function: the kernels of a call without a report must be the
 // instructions they were before the report existed (tools/asm_same.py), and a body inlined into two kernels through a function call was
 // not -- hipcc ordered and allocated it differently.  In scope: g (SynthesisArgs), kRecompute, kMaskH, kMaskIn, kResets, kMinGain, kReport,
-// kLink.
+// kLink, kProfile.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!kMaskIn || (kMaskH && !kRecompute), "mask head inside: bf16, stored spectrum");
     static_assert(!kMaskIn || !kResets, "resets: multi-frame form only");
@@ -53,6 +53,14 @@
         mg = g.min_gain[b];
         mu = 1.0f - mg;
     }
+    // kProfile: this lane's words of its row of the band-profile table (kns_kernels.h, profile_index: floors of its 16 bins, their ceilings,
+    // and the Nyquist pair behind the row's 16 lanes; the table has Bpad rows like the gains').  Nine 16-byte loads per frame through one
+    // wave-uniform descriptor over the wave's four rows -- what stays live across the frame loop is one offset register, not the table
+    const unsigned pf_off = (unsigned) q * (unsigned) (kProfileRow * 4) + (unsigned) c * 128u;
+    auto profile_word = [&](unsigned byte_off, unsigned imm) {
+        const __amdgpu_buffer_rsrc_t pr = make_rsrc(g.profile + (size_t) (mt * 16 + wave * 4) * kProfileRow, 4u * kProfileRow * 4u);
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pr, byte_off, imm, 0));
+    };
 
     int prev[8], cur[8], nxt[8];
     if (kRecompute) {
@@ -153,9 +161,11 @@
         const int tn = t + 1 < t1 ? t + 1 : t;
         // recompute: the mask is not needed before the first FFT and the spectrum are through (~700 instructions), so it is
         // requested here without a second register set; stored spectrum: mask and spectrum of the next frame in flight
+        // (kProfile, stored spectrum: the next frame's operands are requested behind m', where the profile's words have been consumed -- with
+        // both in flight at once the forms did not fit the registers of three waves per SIMD; the inverse FFT still lies in front of their use)
         if (kRecompute)
             mask_fetch(mk, t);
-        else
+        else if (!kProfile)
             mask_fetch(mkn, tn);
         if (kResets) {
             const unsigned rm = reset_rows(g.resets, g.rs_pitch, mt, g.rs_t0 + t);
@@ -177,7 +187,7 @@
             fft256_rows(v, twl_c, xw, xr);
             real_spectrum(v, x, tw_c, c);
         } else {
-            spec_fetch(xsn, tn);
+            if (!kProfile) spec_fetch(xsn, tn);
 #pragma unroll
             for (int k2 = 0; k2 < 16; ++k2) x[k2] = xs[k2];
         }
@@ -222,6 +232,28 @@
         if (kMinGain) {
 #pragma unroll
             for (int k2 = 0; k2 < 17; ++k2) mk[k2] = min_gain_mask(mg, mu, mk[k2]);
+        }
+        // (kProfile: m' = min(ceil, max(floor, m')), max first -- behind the gain, in front of Y and of e_out; exact)
+        if (kProfile) {
+            // four bins at a time -- a floor word, a ceiling word -- with the next four's words in flight: two groups live, never all nine
+            // words (left to itself hipcc requests all of them first, 36 registers that three waves per SIMD do not have)
+            f32x4 pfl = profile_word(pf_off, 0u), pce = profile_word(pf_off, 64u);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const f32x4 nfl = profile_word(i < 3 ? pf_off : (unsigned) q * (unsigned) (kProfileRow * 4), i < 3 ? 16u * (i + 1) : 2048u);
+                f32x4 nce = nfl;
+                if (i < 3) nce = profile_word(pf_off, 64u + 16u * (i + 1));
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) mk[4 * i + j] = profile_clamp(pfl[j], pce[j], mk[4 * i + j]);
+                __builtin_amdgcn_sched_barrier(0);
+                pfl = nfl, pce = nce;
+            }
+            mk[16] = profile_clamp(pfl[0], pfl[1], mk[16]);  // (the row's last word: floor[256], ceil[256])
+            if (!kRecompute) {
+                mask_fetch(mkn, tn);
+                spec_fetch(xsn, tn);
+            }
         }
         cpx y[16];
 #pragma unroll

@@ -148,9 +148,14 @@ pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std:
 
 // one call that advances the streams (arguments already checked), under the handle's attenuation limit
 pv_status_t advance(kns::Engine *engine, const MinGain &limit, kns::Call call, bool async = false) {
-    if (limit.any || limit.link) {
+    if (kns_api::check_band_profile(limit) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
+    if (limit.any || limit.link || limit.profile_any) {  // (the linked and the profile kernels read the gains, all zero where no limit is in force)
         call.min_gain = limit.gain.data();
         call.min_gain_rev = limit.rev;
+    }
+    if (limit.profile_any) {
+        call.band_profile = limit.profile.data();
+        call.band_profile_rev = limit.profile_rev;
     }
     call.channel_link = limit.link;
     if (limit.high_band) {  // what the high-band carry does not take yet: refused here, before the engine is reached
@@ -190,6 +195,20 @@ void push_error(unsigned code, const char *fmt, ...) {
     ::push_error(code, "%s", text);
 }
 pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std::string &err) { return ::engine_failure(status, runtime_code, err); }
+pv_status_t check_band_profile(const MinGain &limit) {
+    if (!limit.profile_any) return PV_STATUS_SUCCESS;
+    if (limit.link) {
+        ::push_error(0x66, "A band profile that is not neutral (pv_koala_batch_set_band_profile) is not available yet while the channel link is on "
+                           "(pv_koala_batch_set_channel_link).");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (limit.high_band) {
+        ::push_error(0x66, "A band profile that is not neutral (pv_koala_batch_set_band_profile) is not available yet while the high-band carry is on "
+                           "(pv_koala_batch_set_high_band): its broadband gain would have to follow the profile.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    return PV_STATUS_SUCCESS;
+}
 }  // namespace kns_api
 
 namespace {
@@ -386,6 +405,66 @@ pv_status_t set_min_gain(MinGain *limit, int32_t B, int32_t count, const int32_t
         ++limit->rev;
         return PV_STATUS_SUCCESS;
     });
+}
+
+// pv_koala_batch_set_band_profile / pv_koala_set_band_profile: every value is checked before anything is changed
+pv_status_t set_band_profile(MinGain *limit, int32_t B, int32_t count, const int32_t *streams, const float *floor, const float *ceil) {
+    if (count < 1 || count > B) {
+        push_error(0x66, "`count` %d is outside [1, %d].", count, B);
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    return guarded([&] {
+        constexpr int K = PV_KOALA_NUM_BINS, R = kns::kProfileRow;
+        std::vector<float> next(limit->profile);
+        if (next.empty()) {  // the neutral table
+            next.assign((size_t) B * R, 0.0f);
+            for (int32_t b = 0; b < B; ++b)
+                for (int k = 0; k < K; ++k) next[(size_t) b * R + kns::profile_index(k, 1)] = 1.0f;
+        }
+        std::vector<uint8_t> listed((size_t) B, 0);
+        for (int32_t i = 0; i < count; ++i) {
+            const int32_t b = streams ? streams[i] : i;
+            if (b < 0 || b >= B) {
+                push_error(0x66, "`streams[%d]` = %d is outside [0, %d).", i, b, B);
+                return PV_STATUS_INVALID_ARGUMENT;
+            }
+            if (listed[b]) {
+                push_error(0x66, "`streams[%d]`: slot %d is listed twice.", i, b);
+                return PV_STATUS_INVALID_ARGUMENT;
+            }
+            listed[b] = 1;
+            for (int k = 0; k < K; ++k) {
+                const float lo = floor ? floor[(size_t) i * K + k] : 0.0f, hi = ceil ? ceil[(size_t) i * K + k] : 1.0f;
+                if (!(lo >= 0.0f && lo <= 1.0f) || !(hi >= 0.0f && hi <= 1.0f)) {  // (NaN fails both comparisons)
+                    const bool is_floor = !(lo >= 0.0f && lo <= 1.0f);
+                    push_error(0x66, "profile %d, bin %d: %s %g is not in [0, 1].", i, k, is_floor ? "floor" : "ceiling", (double) (is_floor ? lo : hi));
+                    return PV_STATUS_INVALID_ARGUMENT;
+                }
+                if (lo > hi) {
+                    push_error(0x66, "profile %d, bin %d: floor %g is above ceiling %g.", i, k, (double) lo, (double) hi);
+                    return PV_STATUS_INVALID_ARGUMENT;
+                }
+                next[(size_t) b * R + kns::profile_index(k, 0)] = lo + 0.0f;  // (-0 -> +0: the kernel orders the bit patterns)
+                next[(size_t) b * R + kns::profile_index(k, 1)] = hi + 0.0f;
+            }
+        }
+        bool any = false;
+        for (int32_t b = 0; b < B && !any; ++b)
+            for (int k = 0; k < K && !any; ++k)
+                any = next[(size_t) b * R + kns::profile_index(k, 0)] != 0.0f || next[(size_t) b * R + kns::profile_index(k, 1)] != 1.0f;
+        limit->profile.swap(next);
+        limit->profile_any = any;
+        ++limit->profile_rev;
+        return PV_STATUS_SUCCESS;
+    });
+}
+
+void get_band_profile(const MinGain &limit, int32_t b, float *floor, float *ceil) {
+    for (int k = 0; k < PV_KOALA_NUM_BINS; ++k) {
+        const bool set = !limit.profile.empty();
+        if (floor) floor[k] = set ? limit.profile[(size_t) b * kns::kProfileRow + kns::profile_index(k, 0)] : 0.0f;
+        if (ceil) ceil[k] = set ? limit.profile[(size_t) b * kns::kProfileRow + kns::profile_index(k, 1)] : 1.0f;
+    }
 }
 
 int default_precision() {
@@ -675,6 +754,45 @@ PV_API pv_status_t pv_koala_get_min_gain(const pv_koala_t *object, float *gain) 
         return PV_STATUS_INVALID_ARGUMENT;
     }
     *gain = object->limit.gain[0];
+    return PV_STATUS_SUCCESS;
+}
+
+// ---- band profile
+
+PV_API pv_status_t pv_koala_batch_set_band_profile(pv_koala_batch_t *object, int32_t count, const int32_t *streams, const float *floor,
+                                                   const float *ceil) {
+    t_stack.clear();
+    if (!object) return check_object(object);
+    return set_band_profile(&object->limit, object->engine->num_streams(), count, streams, floor, ceil);
+}
+
+PV_API pv_status_t pv_koala_batch_get_band_profile(const pv_koala_batch_t *object, int32_t stream, float *floor, float *ceil) {
+    t_stack.clear();
+    if (!object) {
+        push_error(0x64, "Argument `object` is NULL.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    if (stream < 0 || stream >= object->engine->num_streams()) {
+        push_error(0x66, "`stream` %d is outside [0, %d).", stream, object->engine->num_streams());
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    get_band_profile(object->limit, stream, floor, ceil);
+    return PV_STATUS_SUCCESS;
+}
+
+PV_API pv_status_t pv_koala_set_band_profile(pv_koala_t *object, const float *floor, const float *ceil) {
+    t_stack.clear();
+    if (!object) return check_object(object);
+    return set_band_profile(&object->limit, 1, 1, nullptr, floor, ceil);
+}
+
+PV_API pv_status_t pv_koala_get_band_profile(const pv_koala_t *object, float *floor, float *ceil) {
+    t_stack.clear();
+    if (!object) {
+        push_error(0x64, "Argument `object` is NULL.");
+        return PV_STATUS_INVALID_ARGUMENT;
+    }
+    get_band_profile(object->limit, 0, floor, ceil);
     return PV_STATUS_SUCCESS;
 }
 

@@ -26,6 +26,13 @@ struct MinGain {
     // because every call that advances the streams passes through it.
     int high_band = 0;
     unsigned high_band_epoch = 0;
+    // Band profile (pv_koala_batch_set_band_profile): every stream's floors and ceilings [num_streams][kns::kProfileRow] in the order the
+    // engine's table has them (kns::profile_index), empty until the first accepted change; its revision counter, like `rev`; and whether
+    // any stream's profile is not the neutral one (none: the calls are the plain calls, no table at all).  Travels with the limit for the
+    // reason above (kns::Call::band_profile)
+    std::vector<float> profile;
+    unsigned profile_rev = 0;
+    bool profile_any = false;
 };
 struct pv_koala {
     kns::Engine *engine;
@@ -44,6 +51,8 @@ namespace kns_api {
 
 void clear_errors();                                   // every entry point first: the calling thread's error stack is emptied
 void push_error(unsigned code, const char *fmt, ...);  // one message onto it (at most 8 are kept)
+// A call under a band profile that is not neutral: what it is not combined with yet (PV_STATUS_INVALID_ARGUMENT and a message), else SUCCESS
+pv_status_t check_band_profile(const MinGain &limit);
 // what an engine call that did not succeed leaves on the stack: a refused argument, or a failure under the entry point's own code
 pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std::string &err);
 

@@ -67,6 +67,7 @@ def run_in_packets(args):
     meter = []  # report rows since the last printed line
     source = frames_from_wav(args.input_path, n, batch.sample_rate) if args.input_path else frames_from_raw(sys.stdin.buffer, n)
     batch.set_attenuation_limit(args.attenuation_limit_db)
+    set_band_profile(batch, args)
     t_start = time.perf_counter()
     try:
         with contextlib.ExitStack() as stack:
@@ -129,6 +130,7 @@ def run_raw_format(args):
                                    model_path=args.model_path, device=args.device, library_path=args.library_path,
                                    sample_rate=rate, packet_samples=n, sample_format=args.sample_format)
     batch.set_attenuation_limit(args.attenuation_limit_db)
+    set_band_profile(batch, args)
     samples = 0
     try:
         while True:
@@ -185,6 +187,9 @@ def run_channels(args):
                                        sample_rate=rate, packet_samples=n, sample_format=fmt, channels=C,
                                        channel_link='max' if args.link else None)
         batch.set_attenuation_limit(args.attenuation_limit_db)
+        if args.link and (args.highpass is not None or args.max_depth_db is not None):
+            raise ValueError('--link: not available with --highpass or --max_depth_db yet (the library refuses a band profile on linked channels)')
+        set_band_profile(batch, args)
         samples = 0
         try:
             while True:
@@ -206,6 +211,19 @@ def run_channels(args):
     return 0
 
 
+def set_band_profile(handle, args):
+    """--highpass HZ: nothing below HZ comes out (a ceiling, koala_amd.bands.highpass); --max_depth_db DB: no bin is suppressed by more than
+    DB dB (a floor, koala_amd.bands.depth_limit_db)"""
+    if args.highpass is None and args.max_depth_db is None:
+        return
+    from koala_amd import bands
+    ceiling = None if args.highpass is None else bands.highpass(args.highpass)
+    floor = None if args.max_depth_db is None else bands.depth_limit_db([(0.0, args.max_depth_db)])
+    if floor is not None and ceiling is not None:
+        floor = np.minimum(floor, ceiling)  # (below the high-pass the ceiling wins)
+    handle.set_band_profile(floor, ceiling)
+
+
 def run_high_band(args):
     """--high_band: a mono 16-bit WAV at --sample_rate 32000 or 48000 through one stream of a frame handle with the high-band carry
     (`koala_amd.create_batch(..., sample_rate=rate, high_band='carry')`): the band above the 16 kHz call's is delayed like the call, scaled
@@ -215,7 +233,8 @@ def run_high_band(args):
     rate = args.sample_rate
     if rate not in (32000, 48000):
         raise ValueError('--high_band: --sample_rate must be 32000 or 48000 (lower rates have no band to carry; the others are not available yet)')
-    for name, v in (('--meter', args.meter), ('--packet-ms', args.packet_ms), ('--sample_format', args.sample_format)):
+    for name, v in (('--meter', args.meter), ('--packet-ms', args.packet_ms), ('--sample_format', args.sample_format),
+                    ('--highpass', args.highpass is not None), ('--max_depth_db', args.max_depth_db is not None)):
         if v:
             raise ValueError('%s: not available with --high_band' % name)
     if args.input_path is None or args.output_path is None:
@@ -252,6 +271,10 @@ def main(argv=None):
     ap.add_argument('--realtime', action='store_true', help='pace a replayed file at 16 ms per frame, like a recorder')
     ap.add_argument('--attenuation_limit_db', type=float, default=None,
                     help='suppress by at most this many dB (0: bypass with unchanged latency; default: unlimited)')
+    ap.add_argument('--highpass', type=float, default=None, metavar='HZ',
+                    help='band profile: let nothing out below HZ (rumble, 50 / 60 Hz hum), a raised-cosine edge 62.5 Hz wide')
+    ap.add_argument('--max_depth_db', type=float, default=None, metavar='DB',
+                    help='band profile: suppress no bin by more than DB dB (a floor on the mask)')
     ap.add_argument('--meter', type=int, default=0, metavar='N',
                     help='every N frames print input level (dBFS), suppression (dB) and mean mask gain, from the frame report')
     ap.add_argument('--packet-ms', dest='packet_ms', type=int, default=0, choices=[10, 20],
@@ -305,6 +328,7 @@ def main(argv=None):
     koala = koala_amd.create(access_key=args.access_key, model_path=args.model_path, device=args.device,
                              library_path=args.library_path)
     koala.set_attenuation_limit(args.attenuation_limit_db)
+    set_band_profile(koala, args)
     print('Koala version: %s' % koala.version)
     n = koala.frame_length
     source = (frames_from_wav(args.input_path, n, koala.sample_rate) if args.input_path
