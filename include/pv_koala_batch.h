@@ -459,6 +459,65 @@ PV_API pv_status_t pv_koala_batch_get_band_profile(const pv_koala_batch_t *objec
 PV_API pv_status_t pv_koala_set_band_profile(pv_koala_t *object, const float *floor /*[257] or NULL*/, const float *ceil /*[257] or NULL*/);
 PV_API pv_status_t pv_koala_get_band_profile(const pv_koala_t *object, float *floor /*[257] or NULL*/, float *ceil /*[257] or NULL*/);
 
+/* OUTPUT LEVELLER (eleventh extension): a per-stream automatic gain behind the suppressor that adapts only on frames
+ * the network passed as speech, so it never pumps the noise floor back up.  It works on the samples E of the inner 16 kHz call, on the
+ * device, directly behind it: every rate, sample format, channel layout and packet handle gets it.  Per stream b there is a SETTING
+ * (pv_koala_level_t; a new handle: off) and two fp32 values of STATE, lvl (the tracked speech energy) and gain; fresh: lvl = 0, gain = 1.
+ * For every frame t a levelling stream completes, with e_out and mask_sum of its frame report row (FRAME REPORT above), all in fp32, one
+ * rounding per operation, the division and the square root correctly rounded:
+ *     speech = mask_sum * (1/257) >= theta  and  e_out > e_floor
+ *     if speech:  lvl = e_out if lvl == 0, else lvl + a * (e_out - lvl),  a = a_up if e_out > lvl else a_down
+ *     want   = 1 if lvl == 0, else min(max_boost, max(max_cut, sqrt(target / lvl)))
+ *     g_t    = gain + slew * (want - gain);  gain = g_t
+ *     out[256 t + n] = to_pcm(E[256 t + n] * fmaf(n / 256, g_t - g_{t-1}, g_{t-1}))     n = 0 .. 255
+ * to_pcm rounds half away from zero and saturates: SATURATION IS THE ONLY LIMITER, so choose max_boost and target with headroom.  e_out is
+ * an energy in the report's units: a stationary signal of RMS r (full scale = 1) reads 65536 r^2 (koala_amd/level.py, settings(), turns dBFS
+ * and milliseconds into the fields).  g_t is written to column 3 of the stream's report rows (0 for every other stream and handle).
+ *   - a per-frame `reset` at frame t, a packet call's `restart` and pv_koala_batch_reset make the state fresh before that frame: its ramp
+ *     starts from 1 (a per-frame `reset` of a stream whose leveller is off leaves the state alone, like every call does).
+ *     A stream that is switched off and on again continues from the state it was switched off with -- its first sample is under the old
+ *     gain, a step from 1 -- unless the caller sets (0, 1) with pv_koala_batch_set_level_state or resets the stream with pv_koala_batch_reset;
+ *   - a held stream (`hold`, a stalled stream of a packet call) keeps its state bit for bit;
+ *   - a stream whose leveller is off delivers E bit for bit and its state does not move; a handle on which no stream levels runs the
+ *     launches it always ran;
+ *   - the setting is configuration, like the attenuation limit: no reset, hold or record changes or carries it.  Stream records do not
+ *     change either (state_size, version, bytes): the two floats travel through pv_koala_batch_get_level_state / _set_level_state, eight
+ *     more bytes for a caller that moves a stream;
+ *   - host pointers on a plain 16 kHz handle: while some stream levels a call is one copy in, the device route, one copy out.
+ * pv_koala_batch_set_level: settings[i] is the setting of stream streams[i] (streams == NULL: slots 0 .. count - 1; streams not listed
+ * keep theirs).  `struct_size` of settings[0] is the distance between the entries: sizeof(pv_koala_level_t), or more from a caller built
+ * against a later header (the fields known here are read).  Everything is checked before anything changes; PV_STATUS_INVALID_ARGUMENT
+ * with a message that names the entry and the field ("setting 3: `max_cut` ..."): target not > 0, max_boost not >= 1, max_cut not in (0, 1],
+ * theta not in [0, 1], e_floor not >= 0, a_up / a_down / slew not in (0, 1], NaN or infinite anywhere, `on` not 0 or 1, a bad count, index
+ * or struct_size.  No device work and no wait: the table travels with the next call and is uploaded only when it has changed.
+ * pv_koala_batch_get_level: the caller sets setting->struct_size (sizeof(pv_koala_level_t) or more); the fields known here are written, nothing
+ * behind them.
+ * pv_koala_batch_get_level_state / _set_level_state: state[i] = {lvl, gain} of stream streams[i], HOST memory; they run on the handle's
+ * stream behind everything enqueued and return when done (a handle that never levelled answers (0, 1) at once and allocates nothing).  An index
+ * outside [0, num_streams) or a slot listed twice is refused, in either call.  Setting (0, 1) makes a stream fresh; lvl < 0, gain <= 0, NaN or infinity is refused.
+ * NOT YET, refused by name with PV_STATUS_INVALID_ARGUMENT, nothing processed and state unchanged, while some stream's leveller is on: a
+ * call with the channel link on (a group needs one gain), with the high-band carry on (its band would need the same gain), through the
+ * asynchronous entry points, or on a handle at 44 100 / 22 050 Hz. */
+typedef struct {
+    int32_t struct_size; /* sizeof(pv_koala_level_t) */
+    int32_t on;          /* 0: off (the other fields are kept but unused), 1: on */
+    float target;        /* the energy the stream's speech frames are brought to, in the report's units, > 0 */
+    float max_boost;     /* largest gain, >= 1 */
+    float max_cut;       /* smallest gain, in (0, 1] */
+    float theta;         /* a frame is speech when its mean mask is at least this, in [0, 1] */
+    float e_floor;       /* ... and its e_out is above this, >= 0 */
+    float a_up;          /* one-pole coefficient of lvl per frame when the energy rises, in (0, 1] */
+    float a_down;        /* ... when it falls, in (0, 1] */
+    float slew;          /* one-pole coefficient of the gain per frame, in (0, 1] */
+} pv_koala_level_t;
+PV_API pv_status_t pv_koala_batch_set_level(pv_koala_batch_t *object, int32_t count, const int32_t *streams, const pv_koala_level_t *settings);
+PV_API pv_status_t pv_koala_batch_get_level(const pv_koala_batch_t *object, int32_t stream, pv_koala_level_t *setting);
+PV_API pv_status_t pv_koala_batch_get_level_state(pv_koala_batch_t *object, int32_t count, const int32_t *streams, float *state /*[count][2]*/);
+PV_API pv_status_t pv_koala_batch_set_level_state(pv_koala_batch_t *object, int32_t count, const int32_t *streams, const float *state /*[count][2]*/);
+/* The same for the single-stream handle of pv_koala.h: the setting of pv_koala_process from the next frame on (pv_koala_reset makes its state fresh). */
+PV_API pv_status_t pv_koala_set_level(pv_koala_t *object, const pv_koala_level_t *setting);
+PV_API pv_status_t pv_koala_get_level(const pv_koala_t *object, pv_koala_level_t *setting);
+
 PV_API pv_status_t pv_koala_batch_num_streams(const pv_koala_batch_t *object, int32_t *num_streams);
 PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, int32_t *delay_sample);
 

@@ -13,6 +13,7 @@ import numpy as np
 from ._koala import (KoalaError, KoalaInvalidArgumentError, KoalaIOError, PicovoiceStatuses, attenuation_limit_to_gain, load_library,
                      raise_status)
 from . import bands
+from . import level as level_rule
 from .channels import LINK_CHANNELS, MAX_CHANNELS
 from .formats import DTYPES, FORMATS
 from .packets import FRACTIONAL_UP, inner_samples
@@ -40,13 +41,33 @@ class BatchConfig(Structure):
                 ('precision', c_int32), ('sample_rate', c_int32), ('sample_format', c_int32)]
 
 
+class LevelSetting(Structure):
+    """pv_koala_level_t (include/pv_koala_batch.h)"""
+    _fields_ = [('struct_size', c_int32), ('on', c_int32)] + [(name, c_float) for name in level_rule.FIELDS]
+
+    @classmethod
+    def of(cls, setting):
+        """a koala_amd.level.Setting, or None (off)"""
+        s = level_rule.OFF if setting is None else setting
+        if not isinstance(s, level_rule.Setting):
+            raise KoalaInvalidArgumentError("a level setting should be a koala_amd.level.Setting (koala_amd.level.settings(...)) or None")
+        try:
+            level_rule.check(s)
+        except (ValueError, TypeError) as e:
+            raise KoalaInvalidArgumentError(str(e))
+        return cls(sizeof(cls), int(s.on), *[float(v) for v in s[1:]])
+
+    def setting(self):
+        return level_rule.Setting(int(self.on), *[float(getattr(self, name)) for name in level_rule.FIELDS])
+
+
 class KoalaBatch(object):
     sample_format, _dtype, _dtype_name = 's16', np.int16, 'int16'  # (what a handle is unless it was made with a sample format)
     channels = 1  # (... or with channels)
 
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
                  max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0, sample_format: str = 's16',
-                 channels: int = 1, channel_link: Optional[str] = None, high_band: Optional[str] = None, band_profile=None) -> None:
+                 channels: int = 1, channel_link: Optional[str] = None, high_band: Optional[str] = None, band_profile=None, level=None) -> None:
         """`sample_rate`: 44100 or 22050 Hz make a packet handle around fractional converters (`packet_samples` > 0 is required; there is
         no frame length, `frame_length` is None, and stream records and the asynchronous calls are refused); otherwise
         8000, 12000, 16000, 24000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
@@ -70,7 +91,8 @@ class KoalaBatch(object):
         own masks bin by bin, so the stereo image does not move (`set_channel_link`; koala_amd.channels.link_masks states the rule).
         `high_band`: None (default) or 'carry' -- a frame handle at 32000 or 48000 Hz adds the band above the 16 kHz call's, delayed like
         the call and scaled by a broadband gain from the call's masks (`set_high_band`; koala_amd.highband states the rule).
-        `band_profile`: None (default) or (floor, ceiling) -- `set_band_profile(floor, ceiling)` on every stream of the new handle."""
+        `band_profile`: None (default) or (floor, ceiling) -- `set_band_profile(floor, ceiling)` on every stream of the new handle.
+        `level`: None (default) or a koala_amd.level.Setting -- `set_level(level)` on every stream of the new handle: the output leveller."""
         if not isinstance(access_key, str) or len(access_key) == 0:
             raise KoalaInvalidArgumentError("`access_key` should be a non-empty string.")
         if not os.path.exists(model_path):
@@ -94,6 +116,8 @@ class KoalaBatch(object):
         self.channels = channels
         link = self._link_value(channel_link)  # (checked before the handle is made)
         carry = self._high_band_value(high_band)
+        if level is not None:  # (checked before any library is loaded)
+            LevelSetting.of(level)
         if band_profile is not None:  # (checked before any library is loaded)
             if not isinstance(band_profile, (tuple, list)) or len(band_profile) != 2:
                 raise KoalaInvalidArgumentError("`band_profile` should be a pair (floor, ceiling) or None.")
@@ -197,8 +221,10 @@ class KoalaBatch(object):
         if not fractional:
             self._check(lib.pv_koala_batch_state_size(self._handle, byref(d)), 'Failed to get the state size')
             self.state_size = d.value
-        if link or carry or band_profile is not None:
+        if link or carry or band_profile is not None or level is not None:
             try:
+                if level is not None:
+                    self.set_level(level)
                 if band_profile is not None:
                     self.set_band_profile(band_profile[0], band_profile[1])
                 if link:
@@ -590,6 +616,50 @@ class KoalaBatch(object):
         self._check(fn(self._handle, int(stream), lo.ctypes.data, hi.ctypes.data), 'band_profile failed')
         return lo, hi
 
+    # ---- output leveller (include/pv_koala_batch.h, OUTPUT LEVELLER; koala_amd.level states the rule)
+
+    def _level_fn(self, name, args):
+        # (bound at first use, like the band profile's: developer A/B runs load libraries built before the entry points existed)
+        fn = getattr(self._lib, 'pv_koala_batch_' + name)
+        fn.argtypes, fn.restype = args, PicovoiceStatuses
+        return fn
+
+    def set_level(self, setting, streams=None) -> None:
+        """The output leveller of the listed streams (None: every stream): `setting` is a koala_amd.level.Setting
+        (koala_amd.level.settings(target_dbfs=-23, ...)), None for off, or a list with one of either per listed stream.  While a stream's
+        leveller is on, its samples are brought towards the target by a gain that adapts on speech frames only and ramps over every
+        frame; saturation is the only limiter.  Holds from the next call on; configuration, not state: resets, held streams and stream
+        records neither change nor carry it.  A call is refused while some stream levels and the channel link or the high-band carry is
+        on, on the asynchronous entry points and at 44100 / 22050 Hz."""
+        s, sp, n = self._stream_list(streams, None)
+        each = list(setting) if isinstance(setting, (list, tuple)) and not isinstance(setting, level_rule.Setting) else [setting] * n
+        if len(each) != n:
+            raise KoalaInvalidArgumentError("`setting` must be one setting or one per listed stream")
+        table = (LevelSetting * n)(*[LevelSetting.of(v) for v in each])
+        self._check(self._level_fn('set_level', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, byref(table)), 'set_level failed')
+
+    def level(self, stream: int):
+        """The koala_amd.level.Setting in force of one stream."""
+        out = LevelSetting(sizeof(LevelSetting))
+        self._check(self._level_fn('get_level', [c_void_p, c_int32, c_void_p])(self._handle, int(stream), byref(out)), 'level failed')
+        return out.setting()
+
+    def level_state(self, streams=None) -> np.ndarray:
+        """The leveller's state of the listed streams (None: all), float32 [n, 2] = lvl (the tracked speech energy), gain, behind
+        everything enqueued on the handle.  Stream records do not carry it: a caller that moves a stream moves these eight bytes too."""
+        s, sp, n = self._stream_list(streams, None)
+        out = np.empty((n, 2), np.float32)
+        self._check(self._level_fn('get_level_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, out.ctypes.data), 'level_state failed')
+        return out
+
+    def set_level_state(self, state, streams=None) -> None:
+        """Continues the leveller of the listed streams (None: slots 0 .. n - 1) from `state`, float32 [n, 2] = lvl, gain; (0, 1) is fresh."""
+        a = np.ascontiguousarray(state, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] == 0:
+            raise KoalaInvalidArgumentError("expected float32 state of shape [n, 2]")
+        s, sp, n = self._stream_list(streams, a.shape[0])
+        self._check(self._level_fn('set_level_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, a.ctypes.data), 'set_level_state failed')
+
     def reset(self, stream_mask: Optional[np.ndarray] = None) -> None:
         ptr = None
         if stream_mask is not None:
@@ -642,4 +712,4 @@ class KoalaBatch(object):
             pass
 
 
-__all__ = ['KoalaBatch', 'BatchCall', 'BatchPackets', 'BatchConfig', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']
+__all__ = ['KoalaBatch', 'BatchCall', 'BatchPackets', 'BatchConfig', 'LevelSetting', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']

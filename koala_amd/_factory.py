@@ -41,7 +41,8 @@ def create_batch(
         channels: int = 1,
         channel_link: Optional[str] = None,
         high_band: Optional[str] = None,
-        band_profile=None) -> KoalaBatch:
+        band_profile=None,
+        level=None) -> KoalaBatch:
     """`num_streams` independent streams advancing together on one GPU (see KoalaBatch), at 8000, 12000, 16000, 24000, 32000 or 48000 Hz.
     `packet_samples=N` makes a packet handle: streams that take and deliver any number of samples, up to N, per call
     (`KoalaBatch.process_packets`; `max_frames_per_call` is then derived from N).
@@ -54,7 +55,9 @@ def create_batch(
     `high_band='carry'` (a frame handle at 32000 or 48000 Hz): the band above the 16 kHz call's is carried around it and added back
     (`KoalaBatch.set_high_band`; `koala_amd.highband` has the rule).
     `band_profile=(floor, ceiling)`: a per-bin floor and ceiling on the mask of every stream (`KoalaBatch.set_band_profile`;
-    `koala_amd.bands` builds the curves and has the rule)."""
+    `koala_amd.bands` builds the curves and has the rule).
+    `level=koala_amd.level.settings(...)`: the output leveller on every stream, a speech-gated automatic gain behind the suppressor
+    (`KoalaBatch.set_level`; `koala_amd.level` has the rule)."""
     return KoalaBatch(
         access_key=access_key,
         model_path=default_model_path() if model_path is None else model_path,
@@ -69,7 +72,8 @@ def create_batch(
         channels=channels,
         channel_link=channel_link,
         high_band=high_band,
-        band_profile=band_profile)
+        band_profile=band_profile,
+        level=level)
 
 
 def available_devices(library_path: Optional[str] = None) -> Sequence[str]:

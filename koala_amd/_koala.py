@@ -10,7 +10,7 @@ Differences from the reference binding, on purpose:
 
 import math
 import os
-from ctypes import (POINTER, Structure, byref, c_char_p, c_float, c_int, c_int16, c_int32, c_short, c_void_p, cdll)
+from ctypes import (POINTER, Structure, byref, c_char_p, c_float, c_int, c_int16, c_int32, c_short, c_void_p, cdll, sizeof)
 from typing import Optional, Sequence
 
 import numpy as np
@@ -212,6 +212,29 @@ class Koala(object):
         status = fn(self._handle, lo.ctypes.data, hi.ctypes.data)
         if status is not PicovoiceStatuses.SUCCESS:
             raise_status(self._library, status, 'set_band_profile failed')
+
+    def set_level(self, setting) -> None:
+        """The output leveller from the next frame on (an extension: include/pv_koala_batch.h, pv_koala_set_level): a
+        koala_amd.level.Setting (koala_amd.level.settings(target_dbfs=-23, ...)) or None for off.  `reset()` makes its state fresh and
+        leaves the setting."""
+        from ._batch import LevelSetting
+        s = LevelSetting.of(setting)
+        fn = self._library.pv_koala_set_level
+        fn.argtypes, fn.restype = [POINTER(self.CKoala), c_void_p], PicovoiceStatuses
+        status = fn(self._handle, byref(s))
+        if status is not PicovoiceStatuses.SUCCESS:
+            raise_status(self._library, status, 'set_level failed')
+
+    def level(self):
+        """The koala_amd.level.Setting in force."""
+        from ._batch import LevelSetting
+        s = LevelSetting(sizeof(LevelSetting))
+        fn = self._library.pv_koala_get_level
+        fn.argtypes, fn.restype = [POINTER(self.CKoala), c_void_p], PicovoiceStatuses
+        status = fn(self._handle, byref(s))
+        if status is not PicovoiceStatuses.SUCCESS:
+            raise_status(self._library, status, 'level failed')
+        return s.setting()
 
     def band_profile(self):
         """(floor, ceiling) in force, float32 [257] each."""

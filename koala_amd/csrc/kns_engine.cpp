@@ -749,6 +749,8 @@ Engine::~Engine() {
     recof_ring_.release();
     mg_ring_.release();
     pf_ring_.release();
+    lv_ring_.release();
+    lvc_ring_.release();
     pk_ring_.release();
     fr_ring_.release();
     for (int i = 0; i < 4; ++i)
@@ -895,6 +897,7 @@ void Engine::launch_resets(const uint8_t *d_mask) {
         launch_resample_reset(d_rs_state_[1][0], d_rs_state_[1][1], rs_out_hist(rate_), d_mask, Bpad_, stream_);
         if (d_hb_rep_) launch_high_band_reset(d_hb_x_, d_hb_y_, d_hb_s_, rs_stage_out(rate_).U, d_mask, Bpad_, stream_);  // (the high-band carry's, once it exists)
     }
+    if (d_lv_state_) launch_level_reset(d_lv_state_, d_mask, Bpad_, stream_);  // (the leveller's, once it exists)
     if (pk_max_) launch_packet_reset(packet_state_args(), d_mask, stream_);
     if (fr_rate_) launch_fractional_reset(fractional_state_args(), d_mask, stream_);
 }
@@ -1898,6 +1901,10 @@ bool Engine::async_wait(int max_in_flight, std::string *err) {
 // once call n - 2's copy-out has -- both waited for on the device, by the stream that needs it.  A synchronous call of that size cannot
 // hide its first copy-in and last copy-out and has to cut its kernels into short, less efficient sub-chunks (process_host_pipelined).
 Status Engine::process_host_async(const Call &c, std::string *err) {
+    if (c.level) {
+        *err = "the output leveller is not available yet on the asynchronous entry points.";
+        return Status::kBadArgument;
+    }
     if (c.channel_link) {  // (its slices carry no link; the owner refuses the asynchronous calls on a handle with channels anyway)
         *err = "linked channels are not available in asynchronous calls.";
         return Status::kBadArgument;
@@ -2036,10 +2043,20 @@ bool Engine::run_call(const Call &c, std::string *err) {
         *err = !min_gain ? "a linked call carries the handle's minimum gains." : "a linked call runs on device rows only.";
         return false;
     }
+    // (output leveller: such a call arrives here with device pointers -- process() takes host memory through its staging -- so the host
+    // routes below never see it; never quietly unlevelled)
+    if (c.level && (kin != kPtrDevice || link || c.high_band)) {
+        *err = kin != kPtrDevice ? "a levelling call runs on device rows only." : "the output leveller is not combined with linked channels nor with the high-band carry.";
+        return false;
+    }
+    if (c.level && !begin_level(c, err)) return false;
     if (kin == kPtrDevice) {
         const size_t n = (size_t) B_ * T * kFrame;
         const bool overlap = pcm < out + n && out < pcm + n;
-        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table, min_gain, report, link, profile}, err);
+        // (a levelling call reads its own report -- an output only, so asking for it into a buffer of the engine's changes no bit)
+        float *rep = c.level && !report ? d_lv_rep_ : report;
+        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table, min_gain, rep, link, profile}, err) &&
+               (!c.level || run_level(c, rep, report != nullptr, err));
     }
     if (T > host_chunk_ && bytes >= host_pipeline_min_bytes_) {
         const char *pa = (const char *) pcm, *pb = (const char *) out;
@@ -2253,6 +2270,10 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
         inner.channel_link = c.channel_link;
         inner.band_profile = c.band_profile, inner.band_profile_rev = c.band_profile_rev;
         inner.report = c.report;
+        // (output leveller: it works on the inner 16 kHz samples, between the call and the out-stage; `hold` rides along for its tracker
+        // alone -- process_frames has put the held streams' records aside around this whole call)
+        inner.level = c.level, inner.level_rev = c.level_rev;
+        if (c.level) inner.hold = c.hold;
         // High-band carry: the kernel behind the out-stage reads the call's masks from its report -- an output only, so asking for it into a
         // buffer of the engine's changes no bit -- the in-stage's rows, which the device-pointer call leaves in d_in_ as they are, and the
         // call's input, of which a copy is kept where the out-stage writes over it.
@@ -2303,6 +2324,138 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
 fail:
     *err = hip_last_error();
     return false;
+}
+
+// ------------------------------------------------------------------------------------------------ output leveller
+
+// Output leveller (Call::level): every buffer of the feature at first use -- by a call that levels or by level_state -- all or nothing; the
+// state begins fresh, cleared on the handle's stream.
+bool Engine::level_ready(std::string *err) {
+    if (d_lv_state_) return true;
+    (void) hipSetDevice(device_);
+    const bool rings = lv_ring_.ready((size_t) Bpad_ * sizeof(LevelSetting)) && lvc_ring_.ready((size_t) B_ * (Tmax_ + 1));
+    if (rings && !d_lv_set_) d_lv_set_ = (LevelSetting *) dalloc((size_t) Bpad_ * sizeof(LevelSetting), true);
+    if (rings && !d_lv_gains_) d_lv_gains_ = (float *) dalloc((size_t) B_ * Tmax_ * 8, false);
+    if (rings && !d_lv_rep_) d_lv_rep_ = (float *) dalloc((size_t) B_ * Tmax_ * 16, false);
+    if (rings && !d_lv_ctl_) d_lv_ctl_ = (uint8_t *) dalloc((size_t) B_ * (Tmax_ + 1), false);
+    float *state = rings && d_lv_set_ && d_lv_gains_ && d_lv_rep_ && d_lv_ctl_ ? (float *) dalloc((size_t) Bpad_ * 8, false) : nullptr;
+    if (!state) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the buffers of the output leveller.";
+        return false;
+    }
+    launch_level_reset(state, nullptr, Bpad_, stream_);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        *err = hip_error(e);
+        return false;
+    }
+    d_lv_state_ = state;
+    return true;
+}
+
+// The settings of the call about to run, like the limit's table: through a slot of lv_ring_ (rows past B: off) to the device on the handle's
+// stream when the call's revision is not the table's.
+bool Engine::begin_level(const Call &c, std::string *err) {
+    if (!level_ready(err)) return false;
+    if (lv_valid_ && lv_rev_ == c.level_rev) return true;
+    const int k = lv_ring_.acquire();
+    if (k >= 0) {
+        memcpy(lv_ring_.host[k], c.level, (size_t) B_ * sizeof(LevelSetting));
+        memset((char *) lv_ring_.host[k] + (size_t) B_ * sizeof(LevelSetting), 0, (size_t) (Bpad_ - B_) * sizeof(LevelSetting));
+    }
+    if (k < 0 || hipMemcpyAsync(d_lv_set_, lv_ring_.host[k], (size_t) Bpad_ * sizeof(LevelSetting), hipMemcpyHostToDevice, stream_) != hipSuccess ||
+        !lv_ring_.uploaded(k, stream_)) {
+        *err = hip_last_error();
+        lv_valid_ = false;
+        return false;
+    }
+    lv_rev_ = c.level_rev;
+    lv_valid_ = true;
+    return true;
+}
+
+// The leveller's two launches behind the kernels of a device-pointer call (run_call): the call's `hold` and reset flags go to the device as
+// one row of T + 1 bytes per stream, only when one of them is set; `report` is what the call's synthesis kernels have written -- the
+// caller's (then column 3 of a levelling stream's rows becomes its gain) or the engine's.
+bool Engine::run_level(const Call &c, const float *report, bool callers_report, std::string *err) {
+    const int T = c.T;
+    bool any = false;
+    for (int b = 0; c.hold && b < B_ && !any; ++b) any = c.hold[b] != 0;
+    for (size_t i = 0; c.resets && i < (size_t) B_ * T && !any; ++i) any = c.resets[i] != 0;
+    if (any) {
+        const int k = lvc_ring_.acquire();
+        if (k >= 0) {
+            uint8_t *ctl = (uint8_t *) lvc_ring_.host[k];
+            for (int b = 0; b < B_; ++b) {
+                uint8_t *row = ctl + (size_t) b * (T + 1);
+                row[0] = c.hold && c.hold[b] ? 1 : 0;
+                for (int t = 0; t < T; ++t) row[1 + t] = c.resets && c.resets[(size_t) b * T + t] ? 1 : 0;
+            }
+        }
+        if (k < 0 || hipMemcpyAsync(d_lv_ctl_, lvc_ring_.host[k], (size_t) B_ * (T + 1), hipMemcpyHostToDevice, stream_) != hipSuccess ||
+            !lvc_ring_.uploaded(k, stream_)) {
+            *err = hip_last_error();
+            return false;
+        }
+    }
+    LevelArgs a;
+    a.set = d_lv_set_, a.state = d_lv_state_, a.ctl = any ? d_lv_ctl_ : nullptr;
+    a.report = report, a.report_out = callers_report ? (float *) report : nullptr;
+    a.gains = d_lv_gains_, a.out = c.out;
+    a.B = B_, a.T = T;
+    launch_level(a, stream_);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        *err = hip_error(e);
+        return false;
+    }
+    return true;
+}
+
+Status Engine::level_state(bool set, int count, const int32_t *streams, float *state, std::string *err) {
+    if (count < 1 || count > B_) {
+        *err = "`count` " + std::to_string(count) + " is outside [1, " + std::to_string(B_) + "].";
+        return Status::kBadArgument;
+    }
+    std::vector<uint8_t> listed((size_t) B_, 0);
+    for (int i = 0; i < count; ++i) {
+        const int b = streams ? streams[i] : i;
+        if (b < 0 || b >= B_) {
+            *err = "`streams[" + std::to_string(i) + "]` = " + std::to_string(b) + " is outside [0, " + std::to_string(B_) + ").";
+            return Status::kBadArgument;
+        }
+        if (listed[b]) {
+            *err = "`streams[" + std::to_string(i) + "]`: slot " + std::to_string(b) + " is listed twice.";
+            return Status::kBadArgument;
+        }
+        listed[b] = 1;
+    }
+    if (!set && !d_lv_state_) {  // a handle that never levelled: every stream is fresh, and nothing is allocated to say so
+        for (int i = 0; i < count; ++i) state[2 * i] = 0.0f, state[2 * i + 1] = 1.0f;
+        return Status::kOk;
+    }
+    (void) hipSetDevice(device_);
+    if (async_n_ && !drain_async(err)) return Status::kRuntime;
+    if (!level_ready(err)) return Status::kRuntime;
+    std::vector<float> all((size_t) B_ * 2);
+    hipError_t e = hipMemcpyAsync(all.data(), d_lv_state_, all.size() * 4, hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    for (int i = 0; e == hipSuccess && i < count; ++i) {
+        const int b = streams ? streams[i] : i;
+        float *mine = &all[(size_t) b * 2], *theirs = state + (size_t) i * 2;
+        memcpy(set ? mine : theirs, set ? theirs : mine, 8);
+    }
+    if (e == hipSuccess && set) {
+        e = hipMemcpyAsync(d_lv_state_, all.data(), all.size() * 4, hipMemcpyHostToDevice, stream_);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_);  // (`all` goes out of scope)
+    }
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        *err = hip_error(e);
+        return Status::kRuntime;
+    }
+    return Status::kOk;
 }
 
 // ------------------------------------------------------------------------------------------------ stream records
@@ -2586,7 +2739,15 @@ Status Engine::process(const Call &c, std::string *err) {
             return Status::kBadArgument;
         }
     }
-    if (rate_ == kRate16k && fmt_ == kFmtS16 && ch_ == 1) return process_frames(c, err);  // the plain handle
+    if (c.level && (c.channel_link || c.high_band || fr_rate_)) {  // output leveller: what it is not combined with yet (the owner refuses all of it by name first)
+        *err = c.channel_link ? "the output leveller is not available yet while the channel link is on." :
+               c.high_band   ? "the output leveller is not available yet while the high-band carry is on." :
+                               "the output leveller is not available yet on a handle at 44100 or 22050 Hz.";
+        return Status::kBadArgument;
+    }
+    // the plain handle -- but for a levelling call on host memory, which goes through the boundary below: one copy in, the device route and
+    // the leveller's launches behind it, one copy out (not the sub-chunk pipeline nor the one-frame graph, which end in host memory)
+    if (rate_ == kRate16k && fmt_ == kFmtS16 && ch_ == 1 && !(c.level && (c.host_contract || pointer_kind(c.pcm) != kPtrDevice))) return process_frames(c, err);
     (void) hipSetDevice(device_);
     bool host, late = false;
     if (!call_on_host(c.pcm, c.out, c.report, &host, err)) return Status::kRuntime;
@@ -2851,6 +3012,10 @@ Status Engine::packet_end(const PacketCall &c, int fmt, int ch, const PacketIo &
 }
 
 Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string *err) {
+    if (c.level && c.channel_link) {  // (the owner refuses it by name first)
+        *err = "the output leveller is not available yet while the channel link is on.";
+        return Status::kBadArgument;
+    }
     const int F = rs_frame_length(rate_);
     bool any_restart, any_count, nothing;
     Status st = packet_check(c, pk_max_, ch, &any_restart, &any_count, err);
@@ -2923,6 +3088,7 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string
         inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
         inner.band_profile = c.band_profile, inner.band_profile_rev = c.band_profile_rev;
         inner.channel_link = c.channel_link;  // (packet_check: a group's streams share k_b, so a sub-call holds a group as a whole)
+        inner.level = c.level, inner.level_rev = c.level_rev;  // (the sub-calls' `hold` keeps a stalled stream's leveller where it is)
         inner.report = c.report ? d_pk_rep_ + (size_t) B_ * c0 * 4 : nullptr;
         if (process_frames(inner, err) != Status::kOk) return Status::kRuntime;
     }
@@ -2988,6 +3154,10 @@ FractionalStateArgs Engine::fractional_state_args() const {
 // report rows and frame counts are the call's -- fractional_out_kernel, [format_out].  A call in which no stream yields an inner sample
 // still runs both stages: the in-stage's history and N advance, and the out-stage delivers from the inner output it holds.
 Status Engine::run_fractional(const PacketCall &c, std::string *err) {
+    if (c.level) {  // (the owner refuses it by name first)
+        *err = "the output leveller is not available yet on a handle at 44100 or 22050 Hz.";
+        return Status::kBadArgument;
+    }
     const int U = fr_up(fr_rate_);
     bool any_restart, any_count, nothing;
     Status st = packet_check(c, fr_max_, ch_, &any_restart, &any_count, err);

@@ -83,6 +83,15 @@ struct Call {
     // kernels, same bits.
     const float *band_profile = nullptr;
     unsigned band_profile_rev = 0;
+    // Output leveller (eleventh extension): host memory, LevelSetting [num_streams], every field checked by the owner,
+    // the C ABI's handle, which passes the table only while some stream's `on` is set.  Two launches directly behind the 16 kHz call
+    // (kns_level.hip) track each levelling stream's speech energy from the call's own frame report and rewrite its samples under a gain
+    // ramped over every frame; the state, two floats per stream, is the engine's (level_state, reset, `resets`, `hold`).  Read before the
+    // call returns, like the gains: uploaded when `level_rev` differs from the one the engine's device table holds.  Below the host
+    // boundary such a call runs on device pointers only.  Not combined with `channel_link`, `high_band` nor process_host_async.
+    // nullptr: the plain call -- same launches, same bits, and the state does not move.
+    const LevelSetting *level = nullptr;
+    unsigned level_rev = 0;
 };
 
 // kBadArgument: a stream list, a record or a combination of Call members that the engine refused before it touched anything (the C ABI
@@ -106,6 +115,8 @@ struct PacketCall {
     int channel_link = 0;              // as Call's; `restart`, and the streams' phase (the mirrors of fill and of N mod 441), must be equal within a group
     const float *band_profile = nullptr;  // as Call's
     unsigned band_profile_rev = 0;
+    const LevelSetting *level = nullptr;  // as Call's; not on a handle at 44 100 or 22 050 Hz
+    unsigned level_rev = 0;
 };
 
 class Engine {
@@ -147,6 +158,12 @@ public:
     size_t state_bytes() const { return state_record_bytes(taps_, rate_) + (pk_max_ ? pk_record_bytes(rate_) : 0); }
     Status export_state(int count, const int32_t *streams, void *host_records, std::string *err);
     Status import_state(int count, const int32_t *streams, const void *host_records, std::string *err);
+
+    // ---- output leveller: the state of the listed streams (nullptr: slots 0 .. count - 1), HOST memory float [count][2] = lvl, gain.  Runs
+    // on the handle's current stream behind everything enqueued, and returns when `state` is filled (set: may be reused).  The list is
+    // checked like a record list's (an index outside the handle, a slot twice: kBadArgument, nothing written); the values are the owner's
+    // to check.  Stream records do not carry these eight bytes: a caller that moves a stream moves them through this pair.
+    Status level_state(bool set, int count, const int32_t *streams, float *state, std::string *err);
 
     // ---- packet handles (fourth extension).  enable_packets, once, right after create(): the handle's streams take
     // and deliver up to max_samples samples per call through run_packets; the frame entries above are then the owner's to refuse.
@@ -439,6 +456,19 @@ private:
     unsigned pf_rev_ = 0;
     bool pf_valid_ = false;
     bool begin_band_profile(const Call &c, const float **table, std::string *err);
+    // Output leveller (Call::level): the settings' device table [Bpad] with its upload ring and revision, as the gains'; the state
+    // [Bpad][2], allocated fresh by the first call that levels or by level_state and part of every reset; a call's control bytes
+    // [B][Tmax + 1] (hold, reset flags) with their ring; the gain pairs [B][Tmax][2]; and the report [B][Tmax][4] of a call whose caller
+    // asked for none.  run_level: the two launches behind a device-pointer call's kernels
+    LevelSetting *d_lv_set_ = nullptr;
+    float *d_lv_state_ = nullptr, *d_lv_gains_ = nullptr, *d_lv_rep_ = nullptr;
+    uint8_t *d_lv_ctl_ = nullptr;
+    UploadRing lv_ring_, lvc_ring_;
+    unsigned lv_rev_ = 0;
+    bool lv_valid_ = false;
+    bool level_ready(std::string *err);
+    bool begin_level(const Call &c, std::string *err);
+    bool run_level(const Call &c, const float *report, bool callers_report, std::string *err);
     // Frame report (Call::report) of host-pointer calls: device and page-locked host staging [B][Tmax][4] each, used like d_out_ / h_out_ (two
     // slots of [B][host_chunk_][4] by the sub-chunked calls; the one-frame graph writes into h_report_ or copies to it); d_report2_: the second
     // slot of asynchronous host calls.  Allocated by the first call that asks for a report.

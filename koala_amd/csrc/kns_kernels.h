@@ -487,6 +487,26 @@ struct HighBandArgs {
 void launch_high_band(const HighBandArgs &a, hipStream_t s);
 // both copies of the three state arrays of the streams with mask[b] != 0 (null: all) := 0
 void launch_high_band_reset(int16_t *const xs[2], int16_t *const ys[2], float *const ss[2], int R, const uint8_t *mask, int Bpad, hipStream_t s);
+// ---- output leveller (kns_level.hip; DESIGN.md section 2, eleventh extension): a per-stream, speech-gated automatic gain on the samples of
+// the 16 kHz call, from the call's own frame report -- two launches directly behind the call.  Per stream: a setting (configuration, the
+// owner's, like the attenuation limit) and two floats of state, lvl (the tracked speech energy) and gain; fresh: (0, 1).
+struct LevelSetting {
+    int32_t on;
+    float target, max_boost, max_cut, theta, e_floor, a_up, a_down, slew;
+};
+struct LevelArgs {
+    const LevelSetting *set;  // [Bpad]
+    float *state;             // [Bpad][2]: lvl, gain -- updated in place (streams that are off or held: untouched)
+    const uint8_t *ctl;       // [B][T + 1] or nullptr (all zero): hold[b], then the call's reset flags of frames 0 .. T - 1
+    const float *report;      // [B][T][4]: the call's frame report (e_out, mask_sum)
+    float *report_out;        // the caller's report (then == report) or nullptr: column 3 of a levelling stream's rows := g_t
+    float *gains;             // scratch [B][T][2]: the gains at the first and behind the last sample of every frame
+    int16_t *out;             // [B][T 256]: the call's samples E, rewritten in place
+    int B, T;
+};
+void launch_level(const LevelArgs &a, hipStream_t s);  // the tracker, then the ramp over the samples
+// the state of the streams with mask[b] != 0 (null: all) := fresh
+void launch_level_reset(float *state, const uint8_t *mask, int Bpad, hipStream_t s);
 // last node of a captured one-frame replay: ++*counter (device memory), published to *host_word (page-locked host memory)
 void launch_frame_done(unsigned *counter, unsigned *host_word, hipStream_t s);
 

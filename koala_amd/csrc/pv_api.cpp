@@ -158,6 +158,11 @@ pv_status_t advance(kns::Engine *engine, const MinGain &limit, kns::Call call, b
         call.band_profile_rev = limit.profile_rev;
     }
     call.channel_link = limit.link;
+    if (kns_api::check_level(limit, engine, async) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
+    if (limit.level_any) {
+        call.level = limit.level.data();
+        call.level_rev = limit.level_rev;
+    }
     if (limit.high_band) {  // what the high-band carry does not take yet: refused here, before the engine is reached
         const int32_t B = engine->num_streams();
         for (int32_t b = 0; call.hold && b < B; ++b)
@@ -208,6 +213,16 @@ pv_status_t check_band_profile(const MinGain &limit) {
         return PV_STATUS_INVALID_ARGUMENT;
     }
     return PV_STATUS_SUCCESS;
+}
+pv_status_t check_level(const MinGain &limit, const kns::Engine *engine, bool async) {
+    if (!limit.level_any) return PV_STATUS_SUCCESS;
+    const char *what = limit.link                  ? "while the channel link is on (pv_koala_batch_set_channel_link): a group would need one gain" :
+                       limit.high_band             ? "while the high-band carry is on (pv_koala_batch_set_high_band): its band would need the same gain" :
+                       async                       ? "on the asynchronous entry points" :
+                       engine->fractional_rate()   ? "on a handle whose sample rate is 44100 or 22050" : nullptr;
+    if (!what) return PV_STATUS_SUCCESS;
+    ::push_error(0x66, "The output leveller (pv_koala_batch_set_level: some stream's `on` is set) is not available yet %s.", what);
+    return PV_STATUS_INVALID_ARGUMENT;
 }
 }  // namespace kns_api
 

@@ -101,6 +101,11 @@ PV_API pv_status_t pv_koala_batch_process_packets(pv_koala_batch_t *object, cons
         c.band_profile_rev = object->limit.profile_rev;
     }
     c.channel_link = object->limit.link;
+    if (kns_api::check_level(object->limit, object->engine, false) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
+    if (object->limit.level_any) {
+        c.level = object->limit.level.data();
+        c.level_rev = object->limit.level_rev;
+    }
     return kns_api::guarded([&] {
         std::string err;
         const kns::Status status = object->engine->run_packets(c, &err);

@@ -1,5 +1,5 @@
 // pv_api_internal.h -- what the translation units of the C ABI share: the handles behind the opaque pointers, the calling thread's error
-// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_extensions.cpp (packet handles, sample formats, channels and their link) uses it.
+// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_extensions.cpp (packet handles, sample formats, channels and their link) and pv_level.cpp (the output leveller) use it.
 // Nothing here leaves the library.
 #pragma once
 
@@ -33,6 +33,12 @@ struct MinGain {
     std::vector<float> profile;
     unsigned profile_rev = 0;
     bool profile_any = false;
+    // Output leveller (pv_koala_batch_set_level; pv_level.cpp): every stream's setting [num_streams], empty until the first accepted
+    // change; its revision counter, like `rev`; and whether any stream's leveller is on (none: the calls are the plain calls, no table at
+    // all).  Travels with the limit for the reason above (kns::Call::level).  The leveller's STATE is the engine's.
+    std::vector<kns::LevelSetting> level;
+    unsigned level_rev = 0;
+    bool level_any = false;
 };
 struct pv_koala {
     kns::Engine *engine;
@@ -53,6 +59,9 @@ void clear_errors();                                   // every entry point firs
 void push_error(unsigned code, const char *fmt, ...);  // one message onto it (at most 8 are kept)
 // A call under a band profile that is not neutral: what it is not combined with yet (PV_STATUS_INVALID_ARGUMENT and a message), else SUCCESS
 pv_status_t check_band_profile(const MinGain &limit);
+// A call while some stream's leveller is on: what it is not combined with yet -- the channel link, the high-band carry, the asynchronous
+// entry points, a handle at 44 100 or 22 050 Hz (PV_STATUS_INVALID_ARGUMENT and a message), else SUCCESS
+pv_status_t check_level(const MinGain &limit, const kns::Engine *engine, bool async);
 // what an engine call that did not succeed leaves on the stack: a refused argument, or a failure under the entry point's own code
 pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std::string &err);
 

@@ -68,6 +68,7 @@ def run_in_packets(args):
     source = frames_from_wav(args.input_path, n, batch.sample_rate) if args.input_path else frames_from_raw(sys.stdin.buffer, n)
     batch.set_attenuation_limit(args.attenuation_limit_db)
     set_band_profile(batch, args)
+    set_level(batch, args)
     t_start = time.perf_counter()
     try:
         with contextlib.ExitStack() as stack:
@@ -131,6 +132,7 @@ def run_raw_format(args):
                                    sample_rate=rate, packet_samples=n, sample_format=args.sample_format)
     batch.set_attenuation_limit(args.attenuation_limit_db)
     set_band_profile(batch, args)
+    set_level(batch, args)
     samples = 0
     try:
         while True:
@@ -190,6 +192,7 @@ def run_channels(args):
         if args.link and (args.highpass is not None or args.max_depth_db is not None):
             raise ValueError('--link: not available with --highpass or --max_depth_db yet (the library refuses a band profile on linked channels)')
         set_band_profile(batch, args)
+        set_level(batch, args)
         samples = 0
         try:
             while True:
@@ -224,6 +227,17 @@ def set_band_profile(handle, args):
     handle.set_band_profile(floor, ceiling)
 
 
+def set_level(handle, args):
+    """--level [DBFS]: the output leveller (koala_amd.level.settings(target_dbfs=DBFS), -23 when no value is given): speech is brought
+    towards DBFS by a gain that adapts on speech frames only; saturation is the only limiter"""
+    if args.level is None:
+        return
+    if args.link or args.sample_rate in (44100, 22050):
+        raise ValueError('--level: not available with --link nor at 44100 / 22050 Hz yet (the library refuses the call)')
+    from koala_amd import level
+    handle.set_level(level.settings(target_dbfs=args.level))
+
+
 def run_high_band(args):
     """--high_band: a mono 16-bit WAV at --sample_rate 32000 or 48000 through one stream of a frame handle with the high-band carry
     (`koala_amd.create_batch(..., sample_rate=rate, high_band='carry')`): the band above the 16 kHz call's is delayed like the call, scaled
@@ -234,7 +248,7 @@ def run_high_band(args):
     if rate not in (32000, 48000):
         raise ValueError('--high_band: --sample_rate must be 32000 or 48000 (lower rates have no band to carry; the others are not available yet)')
     for name, v in (('--meter', args.meter), ('--packet-ms', args.packet_ms), ('--sample_format', args.sample_format),
-                    ('--highpass', args.highpass is not None), ('--max_depth_db', args.max_depth_db is not None)):
+                    ('--highpass', args.highpass is not None), ('--max_depth_db', args.max_depth_db is not None), ('--level', args.level is not None)):
         if v:
             raise ValueError('%s: not available with --high_band' % name)
     if args.input_path is None or args.output_path is None:
@@ -275,6 +289,8 @@ def main(argv=None):
                     help='band profile: let nothing out below HZ (rumble, 50 / 60 Hz hum), a raised-cosine edge 62.5 Hz wide')
     ap.add_argument('--max_depth_db', type=float, default=None, metavar='DB',
                     help='band profile: suppress no bin by more than DB dB (a floor on the mask)')
+    ap.add_argument('--level', type=float, nargs='?', const=-23.0, default=None, metavar='DBFS',
+                    help='output leveller: bring speech towards DBFS (default -23) with a speech-gated automatic gain')
     ap.add_argument('--meter', type=int, default=0, metavar='N',
                     help='every N frames print input level (dBFS), suppression (dB) and mean mask gain, from the frame report')
     ap.add_argument('--packet-ms', dest='packet_ms', type=int, default=0, choices=[10, 20],
@@ -329,6 +345,7 @@ def main(argv=None):
                              library_path=args.library_path)
     koala.set_attenuation_limit(args.attenuation_limit_db)
     set_band_profile(koala, args)
+    set_level(koala, args)
     print('Koala version: %s' % koala.version)
     n = koala.frame_length
     source = (frames_from_wav(args.input_path, n, koala.sample_rate) if args.input_path

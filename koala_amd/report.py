@@ -1,5 +1,6 @@
 """
-Reading the frame report (include/pv_koala_batch.h, FRAME REPORT): rows of four float32 values -- e_in, e_out, mask_sum, 0 -- per stream and
+Reading the frame report (include/pv_koala_batch.h, FRAME REPORT): rows of four float32 values -- e_in, e_out, mask_sum and the output
+leveller's gain (0 for a stream that does not level) -- per stream and
 frame, as returned by KoalaBatch.process_call(..., report=True), Koala.process_with_report() and enhance_corpus(..., report=True).  numpy
 only; every function takes an array whose LAST axis is the row and returns an array without it.
 
@@ -40,4 +41,11 @@ def input_dbfs(report):
         return 10.0 * np.log10(np.asarray(report, np.float64)[..., 0] / ENERGY_AT_FULL_SCALE)
 
 
-__all__ = ['BINS', 'ENERGY_AT_FULL_SCALE', 'mean_gain', 'suppression_db', 'input_dbfs']
+def level_gain_db(report):
+    """Column 3 of the row as dB: the output leveller's gain behind the frame (koala_amd.level; include/pv_koala_batch.h, OUTPUT LEVELLER).
+    The column is 0 for a stream that does not level: 0 dB there."""
+    g = np.asarray(report, np.float64)[..., 3]
+    return 20.0 * np.log10(np.where(g > 0, g, 1.0))
+
+
+__all__ = ['BINS', 'ENERGY_AT_FULL_SCALE', 'mean_gain', 'suppression_db', 'input_dbfs', 'level_gain_db']
