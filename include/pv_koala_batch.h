@@ -518,6 +518,60 @@ PV_API pv_status_t pv_koala_batch_set_level_state(pv_koala_batch_t *object, int3
 PV_API pv_status_t pv_koala_set_level(pv_koala_t *object, const pv_koala_level_t *setting);
 PV_API pv_status_t pv_koala_get_level(const pv_koala_t *object, pv_koala_level_t *setting);
 
+/* COMFORT NOISE (twelfth extension): a low, stationary, spectrally shaped noise exactly where the mask removed energy,
+ * so a hard-gated stream does not fall to digital silence between words -- and nothing on top of passed speech.  It is added in the spectrum
+ * of the inner 16 kHz call, where the mask is applied: every rate, sample format, channel layout and packet handle gets it.  Per stream b
+ * there is a SETTING (pv_koala_comfort_t: on, seed; a new handle: off), an AMPLITUDE CURVE A_b[k], k = 0 .. 256, fp32, finite and >= 0, in the
+ * spectrum's units (the X of the FRAME REPORT: samples / 32768, sqrt-Hann, 512-point transform; koala_amd/comfort.py, curve(), turns an
+ * output level in dBFS into A), and one uint32 of STATE, n_b: the number of frames the stream has completed since it was fresh, counted
+ * only while its comfort noise is on, modulo 2^32.  In every frame a stream with comfort noise on completes, with m' the mask after the
+ * attenuation limit and the band profile (exactly pv_koala_batch_set_band_profile's m'), n the counter's value and X the frame's spectrum:
+ *     v  = seed ^ (n * 0x9E3779B9) ^ (k * 0x85EBCA6B)                          uint32, wrapping
+ *     v ^= v >> 16;  v *= 0x7FEB352D;  v ^= v >> 15;  v *= 0x846CA68B;  v ^= v >> 16
+ *     z_re = ((float) (v & 0xFFFF) - 32767.5f) * (1 / 32768)                   exact in fp32
+ *     z_im = ((float) (v >> 16)    - 32767.5f) * (1 / 32768)                   0 for k = 0 and k = 256
+ *     w = 1 - m'[k];  a = w * A[k];  Y_re = (m'[k] * X_re) + (a * z_re)        every operation rounded once, none fused; the same for im
+ * the frame is synthesised from Y as it is from m' X otherwise, n becomes n + 1, and e_out of the frame report is that of Y (e_in and
+ * mask_sum are unchanged).  So an fp32 handle stays bit-exact against the oracle under the rule (koala_amd/comfort.py states it in numpy).
+ *   - min_gain = 1, or a band profile with floor = ceil = 1: m' = 1, w = 0 -- the handle is still the pure delay, bit for bit;
+ *   - A = 0 delivers the samples of the stream with comfort noise off;
+ *   - the network never sees its output: hidden state, history, stream records, e_in and mask_sum are bit for bit those of the handle
+ *     without the feature;
+ *   - configuration, not state: no reset, hold or record changes or carries the setting or the curve; records keep their version and bytes.
+ *     The counter travels through pv_koala_batch_get_comfort_state / _set_comfort_state, four bytes for a caller that moves a stream;
+ *   - pv_koala_batch_reset (all or masked), a per-frame `reset` at frame t and a packet call's `restart` make n = 0 before that frame; a
+ *     held stream (`hold`, a stalled stream of a packet call) keeps n; a stream whose comfort noise is off does not count;
+ *   - two streams with equal seed, curve, counter and input deliver equal samples; different seeds give different noise;
+ *   - the output leveller runs behind the call and sees the samples with the noise in them;
+ *   - host pointers on a plain 16 kHz handle: while some stream's comfort noise is on a call is one copy in, the device route, one copy out.
+ * pv_koala_batch_set_comfort_noise: settings[i] (and amplitude[i], a row of 257; amplitude == NULL: every listed stream keeps its curve, all
+ * zero on a new handle) belong to stream streams[i]; streams == NULL means slots 0 .. count - 1; streams not listed keep theirs.
+ * `struct_size` of settings[0] is the distance between the entries: sizeof(pv_koala_comfort_t), or more from a later header.  All arrays
+ * are HOST memory, read before the function returns.  Everything is checked before anything changes; PV_STATUS_INVALID_ARGUMENT with a
+ * message that names the entry and the bin ("comfort 3, bin 17: ..."): an amplitude that is NaN, negative or infinite, `on` not 0 or 1, a bad
+ * count, index, duplicate slot or struct_size.  No device work and no wait: the tables travel with the next call and are uploaded only
+ * when they have changed.
+ * pv_koala_batch_get_comfort_noise: the setting (the caller sets setting->struct_size) and the curve in force of one stream; either
+ * out-pointer may be NULL.
+ * pv_koala_batch_get_comfort_state / _set_comfort_state: n[i] = the counter of stream streams[i], HOST memory; they run on the handle's stream
+ * behind everything enqueued and return when done (a handle that never filled answers 0 at once and allocates nothing).
+ * NOT YET, refused by name with PV_STATUS_INVALID_ARGUMENT, nothing processed and state unchanged, while some stream's comfort noise is on:
+ * a call with the channel link on, with the high-band carry on, through the asynchronous entry points, or on a handle at 44 100 / 22 050 Hz. */
+typedef struct {
+    int32_t struct_size; /* sizeof(pv_koala_comfort_t) */
+    int32_t on;          /* 0: off (seed and curve are kept but unused), 1: on */
+    uint32_t seed;       /* the stream's noise sequence */
+} pv_koala_comfort_t;
+PV_API pv_status_t pv_koala_batch_set_comfort_noise(pv_koala_batch_t *object, int32_t count, const int32_t *streams, const pv_koala_comfort_t *settings,
+                                                    const float *amplitude /*[count][257] or NULL: keep*/);
+PV_API pv_status_t pv_koala_batch_get_comfort_noise(const pv_koala_batch_t *object, int32_t stream, pv_koala_comfort_t *setting /*or NULL*/,
+                                                    float *amplitude /*[257] or NULL*/);
+PV_API pv_status_t pv_koala_batch_get_comfort_state(pv_koala_batch_t *object, int32_t count, const int32_t *streams, uint32_t *n /*[count]*/);
+PV_API pv_status_t pv_koala_batch_set_comfort_state(pv_koala_batch_t *object, int32_t count, const int32_t *streams, const uint32_t *n /*[count]*/);
+/* The same for the single-stream handle of pv_koala.h: the setting of pv_koala_process from the next frame on (pv_koala_reset makes n = 0). */
+PV_API pv_status_t pv_koala_set_comfort_noise(pv_koala_t *object, const pv_koala_comfort_t *setting, const float *amplitude /*[257] or NULL: keep*/);
+PV_API pv_status_t pv_koala_get_comfort_noise(const pv_koala_t *object, pv_koala_comfort_t *setting /*or NULL*/, float *amplitude /*[257] or NULL*/);
+
 PV_API pv_status_t pv_koala_batch_num_streams(const pv_koala_batch_t *object, int32_t *num_streams);
 PV_API pv_status_t pv_koala_batch_delay_sample(const pv_koala_batch_t *object, int32_t *delay_sample);
 

@@ -5,7 +5,7 @@ sample-for-sample what its own `Koala` instance would produce.
 """
 
 import os
-from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int32, c_int64, c_uint8, c_void_p, sizeof
+from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int32, c_int64, c_uint8, c_uint32, c_void_p, sizeof
 from typing import Optional
 
 import numpy as np
@@ -14,6 +14,7 @@ from ._koala import (KoalaError, KoalaInvalidArgumentError, KoalaIOError, Picovo
                      raise_status)
 from . import bands
 from . import level as level_rule
+from . import comfort as comfort_rule
 from .channels import LINK_CHANNELS, MAX_CHANNELS
 from .formats import DTYPES, FORMATS
 from .packets import FRACTIONAL_UP, inner_samples
@@ -61,13 +62,18 @@ class LevelSetting(Structure):
         return level_rule.Setting(int(self.on), *[float(getattr(self, name)) for name in level_rule.FIELDS])
 
 
+class ComfortSetting(Structure):
+    """pv_koala_comfort_t (include/pv_koala_batch.h)"""
+    _fields_ = [('struct_size', c_int32), ('on', c_int32), ('seed', c_uint32)]
+
+
 class KoalaBatch(object):
     sample_format, _dtype, _dtype_name = 's16', np.int16, 'int16'  # (what a handle is unless it was made with a sample format)
     channels = 1  # (... or with channels)
 
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
                  max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0, sample_format: str = 's16',
-                 channels: int = 1, channel_link: Optional[str] = None, high_band: Optional[str] = None, band_profile=None, level=None) -> None:
+                 channels: int = 1, channel_link: Optional[str] = None, high_band: Optional[str] = None, band_profile=None, level=None, comfort_noise=None) -> None:
         """`sample_rate`: 44100 or 22050 Hz make a packet handle around fractional converters (`packet_samples` > 0 is required; there is
         no frame length, `frame_length` is None, and stream records and the asynchronous calls are refused); otherwise
         8000, 12000, 16000, 24000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
@@ -92,7 +98,9 @@ class KoalaBatch(object):
         `high_band`: None (default) or 'carry' -- a frame handle at 32000 or 48000 Hz adds the band above the 16 kHz call's, delayed like
         the call and scaled by a broadband gain from the call's masks (`set_high_band`; koala_amd.highband states the rule).
         `band_profile`: None (default) or (floor, ceiling) -- `set_band_profile(floor, ceiling)` on every stream of the new handle.
-        `level`: None (default) or a koala_amd.level.Setting -- `set_level(level)` on every stream of the new handle: the output leveller."""
+        `level`: None (default) or a koala_amd.level.Setting -- `set_level(level)` on every stream of the new handle: the output leveller.
+        `comfort_noise`: None (default), an amplitude curve float32 [257] (koala_amd.comfort.curve(-60)) or a pair (curve, seed) --
+        `set_comfort_noise` on every stream of the new handle; with a bare curve or seed None stream b gets the seed b."""
         if not isinstance(access_key, str) or len(access_key) == 0:
             raise KoalaInvalidArgumentError("`access_key` should be a non-empty string.")
         if not os.path.exists(model_path):
@@ -118,6 +126,11 @@ class KoalaBatch(object):
         carry = self._high_band_value(high_band)
         if level is not None:  # (checked before any library is loaded)
             LevelSetting.of(level)
+        if comfort_noise is not None:  # (checked before any library is loaded)
+            pair = comfort_noise if isinstance(comfort_noise, tuple) else (comfort_noise, None)
+            if len(pair) != 2:
+                raise KoalaInvalidArgumentError("`comfort_noise` should be an amplitude curve, a pair (curve, seed) or None.")
+            comfort_noise = (self._comfort_curve(pair[0], num_streams), pair[1])
         if band_profile is not None:  # (checked before any library is loaded)
             if not isinstance(band_profile, (tuple, list)) or len(band_profile) != 2:
                 raise KoalaInvalidArgumentError("`band_profile` should be a pair (floor, ceiling) or None.")
@@ -221,8 +234,10 @@ class KoalaBatch(object):
         if not fractional:
             self._check(lib.pv_koala_batch_state_size(self._handle, byref(d)), 'Failed to get the state size')
             self.state_size = d.value
-        if link or carry or band_profile is not None or level is not None:
+        if link or carry or band_profile is not None or level is not None or comfort_noise is not None:
             try:
+                if comfort_noise is not None:
+                    self.set_comfort_noise(comfort_noise[0], comfort_noise[1])
                 if level is not None:
                     self.set_level(level)
                 if band_profile is not None:
@@ -660,6 +675,62 @@ class KoalaBatch(object):
         s, sp, n = self._stream_list(streams, a.shape[0])
         self._check(self._level_fn('set_level_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, a.ctypes.data), 'set_level_state failed')
 
+    # ---- comfort noise (include/pv_koala_batch.h, COMFORT NOISE; koala_amd.comfort states the rule)
+
+    @staticmethod
+    def _comfort_curve(amplitude, rows):
+        try:
+            return comfort_rule.check(amplitude, rows)
+        except (ValueError, TypeError) as e:
+            raise KoalaInvalidArgumentError(str(e))
+
+    def set_comfort_noise(self, amplitude=None, seed=None, streams=None, on=True) -> None:
+        """Comfort noise of the listed streams (None: every stream): a low, stationary, shaped noise exactly where the mask removed energy.
+        `amplitude`: float32 [257] for all the listed streams or [n, 257], one row per listed stream, finite and >= 0, in the spectrum's
+        units (koala_amd.comfort.curve(dbfs, shape) builds one); None: the streams keep their curves.  `seed`: one uint32 for all, one per
+        listed stream, or None: a stream keeps the seed it was given before, and one that never got a seed takes its index.  `on=False` (or `set_comfort_noise(on=False)`) switches the streams off and
+        keeps curve and seed.  Holds from the next call on; configuration, not state: resets, held streams and stream records neither
+        change nor carry it, and the frame counter travels through `comfort_state` / `set_comfort_state`.  A call is refused while some
+        stream's comfort noise is on and the channel link or the high-band carry is on, on the asynchronous entry points and at
+        44100 / 22050 Hz."""
+        s, sp, n = self._stream_list(streams, None)
+        amp = None if amplitude is None else self._comfort_curve(amplitude, n)
+        idx = np.arange(n) if s is None else np.asarray(s)
+        seeded = self.__dict__.setdefault('_comfort_seeded', set())  # (the streams whose seed is the caller's or an index handed out before)
+        if seed is None:
+            seeds = [self.comfort_noise(int(b))[1] if int(b) in seeded else int(b) for b in idx]
+        else:
+            seeds = np.broadcast_to(np.asarray(seed), (n,)) if np.ndim(seed) == 0 else np.asarray(seed)
+        if len(seeds) != n:
+            raise KoalaInvalidArgumentError("`seed` must be one seed or one per listed stream")
+        table = (ComfortSetting * n)(*[ComfortSetting(sizeof(ComfortSetting), 1 if on else 0, int(v) & 0xFFFFFFFF) for v in seeds])
+        fn = self._level_fn('set_comfort_noise', [c_void_p, c_int32, c_void_p, c_void_p, c_void_p])
+        self._check(fn(self._handle, n, sp, byref(table), None if amp is None else amp.ctypes.data), 'set_comfort_noise failed')
+        seeded.update(int(b) for b in idx)
+
+    def comfort_noise(self, stream: int):
+        """(on, seed, amplitude float32 [257]) in force of one stream."""
+        out, amp = ComfortSetting(sizeof(ComfortSetting)), np.empty(comfort_rule.NUM_BINS, np.float32)
+        fn = self._level_fn('get_comfort_noise', [c_void_p, c_int32, c_void_p, c_void_p])
+        self._check(fn(self._handle, int(stream), byref(out), amp.ctypes.data), 'comfort_noise failed')
+        return bool(out.on), int(out.seed), amp
+
+    def comfort_state(self, streams=None) -> np.ndarray:
+        """The frame counters of the listed streams (None: all), uint32 [n], behind everything enqueued on the handle.  Stream records do
+        not carry them: a caller that moves a stream moves these four bytes too."""
+        s, sp, n = self._stream_list(streams, None)
+        out = np.empty(n, np.uint32)
+        self._check(self._level_fn('get_comfort_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, out.ctypes.data), 'comfort_state failed')
+        return out
+
+    def set_comfort_state(self, state, streams=None) -> None:
+        """Continues the comfort noise of the listed streams (None: slots 0 .. n - 1) from the counters `state`, uint32 [n]; 0 is fresh."""
+        a = np.ascontiguousarray(state, dtype=np.uint32)
+        if a.ndim != 1 or a.shape[0] == 0:
+            raise KoalaInvalidArgumentError("expected uint32 counters of shape [n]")
+        s, sp, n = self._stream_list(streams, a.shape[0])
+        self._check(self._level_fn('set_comfort_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, a.ctypes.data), 'set_comfort_state failed')
+
     def reset(self, stream_mask: Optional[np.ndarray] = None) -> None:
         ptr = None
         if stream_mask is not None:
@@ -712,4 +783,4 @@ class KoalaBatch(object):
             pass
 
 
-__all__ = ['KoalaBatch', 'BatchCall', 'BatchPackets', 'BatchConfig', 'LevelSetting', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']
+__all__ = ['KoalaBatch', 'BatchCall', 'BatchPackets', 'BatchConfig', 'LevelSetting', 'ComfortSetting', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']

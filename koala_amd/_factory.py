@@ -42,7 +42,8 @@ def create_batch(
         channel_link: Optional[str] = None,
         high_band: Optional[str] = None,
         band_profile=None,
-        level=None) -> KoalaBatch:
+        level=None,
+        comfort_noise=None) -> KoalaBatch:
     """`num_streams` independent streams advancing together on one GPU (see KoalaBatch), at 8000, 12000, 16000, 24000, 32000 or 48000 Hz.
     `packet_samples=N` makes a packet handle: streams that take and deliver any number of samples, up to N, per call
     (`KoalaBatch.process_packets`; `max_frames_per_call` is then derived from N).
@@ -57,7 +58,9 @@ def create_batch(
     `band_profile=(floor, ceiling)`: a per-bin floor and ceiling on the mask of every stream (`KoalaBatch.set_band_profile`;
     `koala_amd.bands` builds the curves and has the rule).
     `level=koala_amd.level.settings(...)`: the output leveller on every stream, a speech-gated automatic gain behind the suppressor
-    (`KoalaBatch.set_level`; `koala_amd.level` has the rule)."""
+    (`KoalaBatch.set_level`; `koala_amd.level` has the rule).
+    `comfort_noise=koala_amd.comfort.curve(-60)` (or a pair (curve, seed)): comfort noise on every stream, a shaped noise exactly where the
+    mask removed energy (`KoalaBatch.set_comfort_noise`; `koala_amd.comfort` has the rule)."""
     return KoalaBatch(
         access_key=access_key,
         model_path=default_model_path() if model_path is None else model_path,
@@ -73,7 +76,8 @@ def create_batch(
         channel_link=channel_link,
         high_band=high_band,
         band_profile=band_profile,
-        level=level)
+        level=level,
+        comfort_noise=comfort_noise)
 
 
 def available_devices(library_path: Optional[str] = None) -> Sequence[str]:

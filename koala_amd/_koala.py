@@ -225,6 +225,34 @@ class Koala(object):
         if status is not PicovoiceStatuses.SUCCESS:
             raise_status(self._library, status, 'set_level failed')
 
+    def set_comfort_noise(self, amplitude=None, seed=None, on=True) -> None:
+        """Comfort noise from the next frame on (an extension: include/pv_koala_batch.h, pv_koala_set_comfort_noise): `amplitude` float32
+        [257], finite and >= 0 (koala_amd.comfort.curve(-60) builds one; None: keep the curve), `seed` a uint32 (None: keep the seed, 0 on
+        a new handle); `on=False` switches it off.  `reset()` makes the frame counter 0 and leaves the setting."""
+        from . import comfort
+        from ._batch import ComfortSetting
+        try:
+            amp = None if amplitude is None else comfort.check(amplitude)
+        except (ValueError, TypeError) as e:
+            raise KoalaInvalidArgumentError(str(e))
+        s = ComfortSetting(sizeof(ComfortSetting), 1 if on else 0, (self.comfort_noise()[1] if seed is None else int(seed)) & 0xFFFFFFFF)
+        fn = self._library.pv_koala_set_comfort_noise
+        fn.argtypes, fn.restype = [POINTER(self.CKoala), c_void_p, c_void_p], PicovoiceStatuses
+        status = fn(self._handle, byref(s), None if amp is None else amp.ctypes.data)
+        if status is not PicovoiceStatuses.SUCCESS:
+            raise_status(self._library, status, 'set_comfort_noise failed')
+
+    def comfort_noise(self):
+        """(on, seed, amplitude float32 [257]) in force."""
+        from ._batch import ComfortSetting
+        s, amp = ComfortSetting(sizeof(ComfortSetting)), np.empty(257, np.float32)
+        fn = self._library.pv_koala_get_comfort_noise
+        fn.argtypes, fn.restype = [POINTER(self.CKoala), c_void_p, c_void_p], PicovoiceStatuses
+        status = fn(self._handle, byref(s), amp.ctypes.data)
+        if status is not PicovoiceStatuses.SUCCESS:
+            raise_status(self._library, status, 'comfort_noise failed')
+        return bool(s.on), int(s.seed), amp
+
     def level(self):
         """The koala_amd.level.Setting in force."""
         from ._batch import LevelSetting

@@ -751,6 +751,9 @@ Engine::~Engine() {
     pf_ring_.release();
     lv_ring_.release();
     lvc_ring_.release();
+    cf_ring_.release();
+    cfa_ring_.release();
+    cfc_ring_.release();
     pk_ring_.release();
     fr_ring_.release();
     for (int i = 0; i < 4; ++i)
@@ -898,6 +901,7 @@ void Engine::launch_resets(const uint8_t *d_mask) {
         if (d_hb_rep_) launch_high_band_reset(d_hb_x_, d_hb_y_, d_hb_s_, rs_stage_out(rate_).U, d_mask, Bpad_, stream_);  // (the high-band carry's, once it exists)
     }
     if (d_lv_state_) launch_level_reset(d_lv_state_, d_mask, Bpad_, stream_);  // (the leveller's, once it exists)
+    if (d_cf_state_) launch_comfort_reset(d_cf_state_, d_mask, Bpad_, stream_);  // (the comfort noise's counters, once they exist)
     if (pk_max_) launch_packet_reset(packet_state_args(), d_mask, stream_);
     if (fr_rate_) launch_fractional_reset(fractional_state_args(), d_mask, stream_);
 }
@@ -1608,6 +1612,7 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
         sy.min_gain = slice.min_gain;
         sy.link = slice.link;
         sy.profile = slice.profile;
+        if (slice.comfort) sy.comfort_amp = d_cf_amp_, sy.comfort_set = d_cf_set_, sy.comfort_n = d_cf_n_ + t0c;  // (like `report`: rows T frames apart)
         sy.report = slice.d_report ? slice.d_report + (size_t) t0c * 4 : nullptr;  // (like `out`: the slice's first frame, rows T frames apart)
         launch_synthesis(sy, st);
     };
@@ -1905,6 +1910,10 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
         *err = "the output leveller is not available yet on the asynchronous entry points.";
         return Status::kBadArgument;
     }
+    if (c.comfort) {
+        *err = "comfort noise is not available yet on the asynchronous entry points.";
+        return Status::kBadArgument;
+    }
     if (c.channel_link) {  // (its slices carry no link; the owner refuses the asynchronous calls on a handle with channels anyway)
         *err = "linked channels are not available in asynchronous calls.";
         return Status::kBadArgument;
@@ -2050,12 +2059,22 @@ bool Engine::run_call(const Call &c, std::string *err) {
         return false;
     }
     if (c.level && !begin_level(c, err)) return false;
+    // (comfort noise: the same -- device rows only, never quietly without the fill; its kernels carry the gains and the profile's clamp)
+    if (c.comfort && (kin != kPtrDevice || link || c.high_band || !profile)) {
+        *err = kin != kPtrDevice ? "a call with comfort noise runs on device rows only." :
+               !profile         ? "a call with comfort noise carries the handle's band profile (neutral where none is in force)." :
+                                  "comfort noise is not combined with linked channels nor with the high-band carry.";
+        return false;
+    }
+    if (c.comfort && !begin_comfort(c, err)) return false;
     if (kin == kPtrDevice) {
         const size_t n = (size_t) B_ * T * kFrame;
         const bool overlap = pcm < out + n && out < pcm + n;
         // (a levelling call reads its own report -- an output only, so asking for it into a buffer of the engine's changes no bit)
         float *rep = c.level && !report ? d_lv_rep_ : report;
-        return begin_resets(T, c.resets, &table, err) && run_device({0, T, pcm, out, !overlap, &table, min_gain, rep, link, profile}, err) &&
+        // (comfort noise: the counter's launch in front of the call's kernels)
+        return begin_resets(T, c.resets, &table, err) && (!c.comfort || run_comfort(c, err)) &&
+               run_device({0, T, pcm, out, !overlap, &table, min_gain, rep, link, profile, c.comfort != nullptr}, err) &&
                (!c.level || run_level(c, rep, report != nullptr, err));
     }
     if (T > host_chunk_ && bytes >= host_pipeline_min_bytes_) {
@@ -2273,7 +2292,8 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
         // (output leveller: it works on the inner 16 kHz samples, between the call and the out-stage; `hold` rides along for its tracker
         // alone -- process_frames has put the held streams' records aside around this whole call)
         inner.level = c.level, inner.level_rev = c.level_rev;
-        if (c.level) inner.hold = c.hold;
+        inner.comfort = c.comfort, inner.comfort_amp = c.comfort_amp, inner.comfort_rev = c.comfort_rev;  // (comfort noise: the same, for its counters)
+        if (c.level || c.comfort) inner.hold = c.hold;
         // High-band carry: the kernel behind the out-stage reads the call's masks from its report -- an output only, so asking for it into a
         // buffer of the engine's changes no bit -- the in-stage's rows, which the device-pointer call leaves in d_in_ as they are, and the
         // call's input, of which a copy is kept where the out-stage writes over it.
@@ -2448,6 +2468,145 @@ Status Engine::level_state(bool set, int count, const int32_t *streams, float *s
     }
     if (e == hipSuccess && set) {
         e = hipMemcpyAsync(d_lv_state_, all.data(), all.size() * 4, hipMemcpyHostToDevice, stream_);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_);  // (`all` goes out of scope)
+    }
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        *err = hip_error(e);
+        return Status::kRuntime;
+    }
+    return Status::kOk;
+}
+
+// ------------------------------------------------------------------------------------------------ comfort noise
+
+// Comfort noise (Call::comfort): every buffer of the feature at first use -- by a call with some stream's comfort noise on or by
+// comfort_state -- all or nothing; the counters begin at 0, cleared on the handle's stream.
+bool Engine::comfort_ready(std::string *err) {
+    if (d_cf_state_) return true;
+    (void) hipSetDevice(device_);
+    const bool rings = cf_ring_.ready((size_t) Bpad_ * sizeof(ComfortSetting)) && cfa_ring_.ready((size_t) Bpad_ * kComfortRow * 4) &&
+                       cfc_ring_.ready((size_t) B_ * (Tmax_ + 1));
+    // (not zeroed: begin_comfort uploads every row of the two tables and comfort_count_kernel writes every row of a call's counter values,
+    // all on the call's stream in front of the kernels that read them -- a memset on the handle's own stream would be unordered with
+    // those after set_stream)
+    if (rings && !d_cf_set_) d_cf_set_ = (ComfortSetting *) dalloc((size_t) Bpad_ * sizeof(ComfortSetting), false);
+    if (rings && !d_cf_amp_) d_cf_amp_ = (float *) dalloc((size_t) Bpad_ * kComfortRow * 4, false);
+    if (rings && !d_cf_n_) d_cf_n_ = (uint32_t *) dalloc((size_t) Bpad_ * Tmax_ * 4, false);
+    if (rings && !d_cf_ctl_) d_cf_ctl_ = (uint8_t *) dalloc((size_t) B_ * (Tmax_ + 1), false);
+    uint32_t *state = rings && d_cf_set_ && d_cf_amp_ && d_cf_n_ && d_cf_ctl_ ? (uint32_t *) dalloc((size_t) Bpad_ * 4, false) : nullptr;
+    if (!state) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the buffers of the comfort noise.";
+        return false;
+    }
+    launch_comfort_reset(state, nullptr, Bpad_, stream_);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        *err = hip_error(e);
+        return false;
+    }
+    d_cf_state_ = state;
+    return true;
+}
+
+// The settings and the amplitude table of the call about to run, like the band profile's: through ring slots (rows past B: off, zero) to
+// the device on the handle's stream when the call's revision is not the tables' -- 1 KiB per stream, so an unchanged setting costs nothing.
+bool Engine::begin_comfort(const Call &c, std::string *err) {
+    if (!comfort_ready(err)) return false;
+    if (cf_valid_ && cf_rev_ == c.comfort_rev) return true;
+    const size_t sb = sizeof(ComfortSetting), ab = (size_t) kComfortRow * 4;
+    const int k = cf_ring_.acquire(), ka = k >= 0 ? cfa_ring_.acquire() : -1;
+    if (ka >= 0) {
+        memcpy(cf_ring_.host[k], c.comfort, (size_t) B_ * sb);
+        memset((char *) cf_ring_.host[k] + (size_t) B_ * sb, 0, (size_t) (Bpad_ - B_) * sb);
+        memcpy(cfa_ring_.host[ka], c.comfort_amp, (size_t) B_ * ab);
+        memset((char *) cfa_ring_.host[ka] + (size_t) B_ * ab, 0, (size_t) (Bpad_ - B_) * ab);
+    }
+    if (ka < 0 || hipMemcpyAsync(d_cf_set_, cf_ring_.host[k], (size_t) Bpad_ * sb, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+        !cf_ring_.uploaded(k, stream_) || hipMemcpyAsync(d_cf_amp_, cfa_ring_.host[ka], (size_t) Bpad_ * ab, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+        !cfa_ring_.uploaded(ka, stream_)) {
+        *err = hip_last_error();
+        cf_valid_ = false;
+        return false;
+    }
+    cf_rev_ = c.comfort_rev;
+    cf_valid_ = true;
+    return true;
+}
+
+// The counter's launch in front of the kernels of a device-pointer call (run_call): the call's `hold` and reset flags go to the device as
+// one row of T + 1 bytes per stream, only when one of them is set -- the leveller's layout.
+bool Engine::run_comfort(const Call &c, std::string *err) {
+    const int T = c.T;
+    bool any = false;
+    for (int b = 0; c.hold && b < B_ && !any; ++b) any = c.hold[b] != 0;
+    for (size_t i = 0; c.resets && i < (size_t) B_ * T && !any; ++i) any = c.resets[i] != 0;
+    if (any) {
+        const int k = cfc_ring_.acquire();
+        if (k >= 0) {
+            uint8_t *ctl = (uint8_t *) cfc_ring_.host[k];
+            for (int b = 0; b < B_; ++b) {
+                uint8_t *row = ctl + (size_t) b * (T + 1);
+                row[0] = c.hold && c.hold[b] ? 1 : 0;
+                for (int t = 0; t < T; ++t) row[1 + t] = c.resets && c.resets[(size_t) b * T + t] ? 1 : 0;
+            }
+        }
+        if (k < 0 || hipMemcpyAsync(d_cf_ctl_, cfc_ring_.host[k], (size_t) B_ * (T + 1), hipMemcpyHostToDevice, stream_) != hipSuccess ||
+            !cfc_ring_.uploaded(k, stream_)) {
+            *err = hip_last_error();
+            return false;
+        }
+    }
+    ComfortArgs a;
+    a.set = d_cf_set_, a.state = d_cf_state_, a.ctl = any ? d_cf_ctl_ : nullptr, a.n = d_cf_n_;
+    a.B = B_, a.Bpad = Bpad_, a.T = T;
+    launch_comfort(a, stream_);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        *err = hip_error(e);
+        return false;
+    }
+    return true;
+}
+
+Status Engine::comfort_state(bool set, int count, const int32_t *streams, uint32_t *n, std::string *err) {
+    if (count < 1 || count > B_) {
+        *err = "`count` " + std::to_string(count) + " is outside [1, " + std::to_string(B_) + "].";
+        return Status::kBadArgument;
+    }
+    std::vector<uint8_t> listed((size_t) B_, 0);
+    for (int i = 0; i < count; ++i) {
+        const int b = streams ? streams[i] : i;
+        if (b < 0 || b >= B_) {
+            *err = "`streams[" + std::to_string(i) + "]` = " + std::to_string(b) + " is outside [0, " + std::to_string(B_) + ").";
+            return Status::kBadArgument;
+        }
+        if (listed[b]) {
+            *err = "`streams[" + std::to_string(i) + "]`: slot " + std::to_string(b) + " is listed twice.";
+            return Status::kBadArgument;
+        }
+        listed[b] = 1;
+    }
+    if (!set && !d_cf_state_) {  // a handle that never filled: every counter is 0, and nothing is allocated to say so
+        for (int i = 0; i < count; ++i) n[i] = 0u;
+        return Status::kOk;
+    }
+    (void) hipSetDevice(device_);
+    if (async_n_ && !drain_async(err)) return Status::kRuntime;
+    if (!comfort_ready(err)) return Status::kRuntime;
+    std::vector<uint32_t> all((size_t) B_);
+    hipError_t e = hipMemcpyAsync(all.data(), d_cf_state_, all.size() * 4, hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    for (int i = 0; e == hipSuccess && i < count; ++i) {
+        const int b = streams ? streams[i] : i;
+        if (set)
+            all[(size_t) b] = n[i];
+        else
+            n[i] = all[(size_t) b];
+    }
+    if (e == hipSuccess && set) {
+        e = hipMemcpyAsync(d_cf_state_, all.data(), all.size() * 4, hipMemcpyHostToDevice, stream_);
         if (e == hipSuccess) e = hipStreamSynchronize(stream_);  // (`all` goes out of scope)
     }
     if (e != hipSuccess) {
@@ -2745,9 +2904,16 @@ Status Engine::process(const Call &c, std::string *err) {
                                "the output leveller is not available yet on a handle at 44100 or 22050 Hz.";
         return Status::kBadArgument;
     }
+    if (c.comfort && (c.channel_link || c.high_band || fr_rate_ || !c.comfort_amp || !c.band_profile)) {  // comfort noise: the same four, refused by the owner by name first
+        *err = c.channel_link ? "comfort noise is not available yet while the channel link is on." :
+               c.high_band   ? "comfort noise is not available yet while the high-band carry is on." :
+               fr_rate_      ? "comfort noise is not available yet on a handle at 44100 or 22050 Hz." :
+                               "a call with comfort noise carries the amplitude table and the handle's band profile (neutral where none is in force).";
+        return Status::kBadArgument;
+    }
     // the plain handle -- but for a levelling call on host memory, which goes through the boundary below: one copy in, the device route and
     // the leveller's launches behind it, one copy out (not the sub-chunk pipeline nor the one-frame graph, which end in host memory)
-    if (rate_ == kRate16k && fmt_ == kFmtS16 && ch_ == 1 && !(c.level && (c.host_contract || pointer_kind(c.pcm) != kPtrDevice))) return process_frames(c, err);
+    if (rate_ == kRate16k && fmt_ == kFmtS16 && ch_ == 1 && !((c.level || c.comfort) && (c.host_contract || pointer_kind(c.pcm) != kPtrDevice))) return process_frames(c, err);  // (comfort noise: as the leveller)
     (void) hipSetDevice(device_);
     bool host, late = false;
     if (!call_on_host(c.pcm, c.out, c.report, &host, err)) return Status::kRuntime;
@@ -3016,6 +3182,10 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string
         *err = "the output leveller is not available yet while the channel link is on.";
         return Status::kBadArgument;
     }
+    if (c.comfort && c.channel_link) {  // (the owner refuses it by name first)
+        *err = "comfort noise is not available yet while the channel link is on.";
+        return Status::kBadArgument;
+    }
     const int F = rs_frame_length(rate_);
     bool any_restart, any_count, nothing;
     Status st = packet_check(c, pk_max_, ch, &any_restart, &any_count, err);
@@ -3089,6 +3259,7 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string
         inner.band_profile = c.band_profile, inner.band_profile_rev = c.band_profile_rev;
         inner.channel_link = c.channel_link;  // (packet_check: a group's streams share k_b, so a sub-call holds a group as a whole)
         inner.level = c.level, inner.level_rev = c.level_rev;  // (the sub-calls' `hold` keeps a stalled stream's leveller where it is)
+        inner.comfort = c.comfort, inner.comfort_amp = c.comfort_amp, inner.comfort_rev = c.comfort_rev;  // (... and its comfort noise's counter)
         inner.report = c.report ? d_pk_rep_ + (size_t) B_ * c0 * 4 : nullptr;
         if (process_frames(inner, err) != Status::kOk) return Status::kRuntime;
     }
@@ -3156,6 +3327,10 @@ FractionalStateArgs Engine::fractional_state_args() const {
 Status Engine::run_fractional(const PacketCall &c, std::string *err) {
     if (c.level) {  // (the owner refuses it by name first)
         *err = "the output leveller is not available yet on a handle at 44100 or 22050 Hz.";
+        return Status::kBadArgument;
+    }
+    if (c.comfort) {  // (the owner refuses it by name first)
+        *err = "comfort noise is not available yet on a handle at 44100 or 22050 Hz.";
         return Status::kBadArgument;
     }
     const int U = fr_up(fr_rate_);

@@ -92,6 +92,17 @@ struct Call {
     // nullptr: the plain call -- same launches, same bits, and the state does not move.
     const LevelSetting *level = nullptr;
     unsigned level_rev = 0;
+    // Comfort noise (twelfth extension): host memory, ComfortSetting [num_streams] and the amplitude curves float
+    // [num_streams][kComfortRow] in the order of comfort_index (kns_kernels.h), every value finite and >= 0, checked by the owner, which passes
+    // the tables only while some stream's `on` is set -- and then `band_profile` and `min_gain` too (neutral, all zero where none is in force:
+    // the comfort kernels carry both).  A small launch in front of the call (kns_comfort.hip) counts every filling stream's frames; the
+    // synthesis kernels add the shaped noise where the mask removed energy.  The counter, one uint32 per stream, is the engine's
+    // (comfort_state, reset, `resets`, `hold`).  Uploaded when `comfort_rev` differs from the one the engine's device tables hold.  Below the
+    // host boundary such a call runs on device pointers only.  Not combined with `channel_link`, `high_band` nor process_host_async.
+    // nullptr: the plain call -- same launches, same bits, and the counters do not move.
+    const ComfortSetting *comfort = nullptr;
+    const float *comfort_amp = nullptr;
+    unsigned comfort_rev = 0;
 };
 
 // kBadArgument: a stream list, a record or a combination of Call members that the engine refused before it touched anything (the C ABI
@@ -117,6 +128,9 @@ struct PacketCall {
     unsigned band_profile_rev = 0;
     const LevelSetting *level = nullptr;  // as Call's; not on a handle at 44 100 or 22 050 Hz
     unsigned level_rev = 0;
+    const ComfortSetting *comfort = nullptr;  // as Call's; not on a handle at 44 100 or 22 050 Hz
+    const float *comfort_amp = nullptr;
+    unsigned comfort_rev = 0;
 };
 
 class Engine {
@@ -164,6 +178,9 @@ public:
     // checked like a record list's (an index outside the handle, a slot twice: kBadArgument, nothing written); the values are the owner's
     // to check.  Stream records do not carry these eight bytes: a caller that moves a stream moves them through this pair.
     Status level_state(bool set, int count, const int32_t *streams, float *state, std::string *err);
+    // ---- comfort noise: the frame counters of the listed streams, HOST memory uint32 [count]; everything else as level_state (a handle that
+    // never filled answers 0 at once and allocates nothing).  Stream records do not carry these four bytes.
+    Status comfort_state(bool set, int count, const int32_t *streams, uint32_t *n, std::string *err);
 
     // ---- packet handles (fourth extension).  enable_packets, once, right after create(): the handle's streams take
     // and deliver up to max_samples samples per call through run_packets; the frame entries above are then the owner's to refuse.
@@ -299,6 +316,7 @@ private:
         float *d_report = nullptr;  // the slice's frame report [B][T][4] (device-visible memory, rows T frames apart), nullptr: not asked for
         int link = 0;  // the call's linked channels: channels() when Call::channel_link is set (then min_gain is not null), else 0
         const float *profile = nullptr;  // the call's band profile on the device [Bpad][kProfileRow] (begin_band_profile; then min_gain is not null and link is 0), nullptr: neutral
+        bool comfort = false;  // the call's comfort noise: begin_comfort's tables and run_comfort's counter values (then profile is not null)
     };
     bool run_device(const Slice &s, std::string *err);
     void *dalloc(size_t bytes, bool zero);
@@ -469,6 +487,20 @@ private:
     bool level_ready(std::string *err);
     bool begin_level(const Call &c, std::string *err);
     bool run_level(const Call &c, const float *report, bool callers_report, std::string *err);
+    // Comfort noise (Call::comfort): the settings' device table [Bpad] and the amplitude table [Bpad][kComfortRow] with their upload rings and
+    // one revision, as the profile's; the counters [Bpad], allocated at 0 by the first call that fills or by comfort_state and part of every
+    // reset; a call's control bytes [B][Tmax + 1] with their ring (the leveller's layout); the counter values of a call's frames
+    // [Bpad][Tmax].  run_comfort: the counter's launch in front of a device-pointer call's kernels
+    ComfortSetting *d_cf_set_ = nullptr;
+    float *d_cf_amp_ = nullptr;
+    uint32_t *d_cf_state_ = nullptr, *d_cf_n_ = nullptr;
+    uint8_t *d_cf_ctl_ = nullptr;
+    UploadRing cf_ring_, cfa_ring_, cfc_ring_;
+    unsigned cf_rev_ = 0;
+    bool cf_valid_ = false;
+    bool comfort_ready(std::string *err);
+    bool begin_comfort(const Call &c, std::string *err);
+    bool run_comfort(const Call &c, std::string *err);
     // Frame report (Call::report) of host-pointer calls: device and page-locked host staging [B][Tmax][4] each, used like d_out_ / h_out_ (two
     // slots of [B][host_chunk_][4] by the sub-chunked calls; the one-frame graph writes into h_report_ or copies to it); d_report2_: the second
     // slot of asynchronous host calls.  Allocated by the first call that asks for a report.

@@ -65,6 +65,12 @@ struct AnalysisArgs {
 };
 void launch_analysis(const AnalysisArgs &a, hipStream_t s);
 
+// a stream's comfort-noise setting as the kernels read it (SynthesisArgs::comfort_set, ComfortArgs)
+struct ComfortSetting {
+    int32_t on;
+    uint32_t seed;
+};
+
 // ---- synthesis: mask x spectrum -> iFFT -> window -> overlap-add -> int16
 struct SynthesisArgs {
     const float *spec;      // as above
@@ -108,8 +114,34 @@ struct SynthesisArgs {
     // (and of the report's e_out).  Selects the kernels' kProfile arm, which reads `min_gain` (not null then) and has no linked form
     // (link == 0); a null pointer: today's instantiations
     const float *profile = nullptr;
+    // optional: comfort noise (twelfth extension).  comfort_amp: float [Bpad][kComfortRow], every stream's amplitude
+    // curve in the order of comfort_index below; comfort_set: [Bpad] (rows past B: off); comfort_n: uint32, the counter value of every
+    // frame, pointing at the slice's first frame like `report`, rows `pitch` frames apart (0: T), Bpad rows.  In every frame of a row whose
+    // `on` is set Y[k] = m'[k] X[k] + ((1 - m'[k]) A[k]) z[k], z the hash of (seed, n, k) -- behind the profile's clamp, in front of the
+    // report's e_out.  Selects the kernels' kComfort arm, which reads `min_gain` and `profile` (neither null then; link == 0); a null
+    // comfort_amp: today's instantiations
+    const float *comfort_amp = nullptr;
+    const ComfortSetting *comfort_set = nullptr;
+    const uint32_t *comfort_n = nullptr;
 };
 void launch_synthesis(const SynthesisArgs &a, hipStream_t s);
+
+// A stream's row of the comfort-noise amplitude table: laid out like the profile's -- the lane of
+// column c owns the bins c + 16 k2, four 16-byte words in a row -- and the row ends with one word {A[256], 0, 0, 0}.
+constexpr int kComfortRow = 16 * 16 + 4;
+inline int comfort_index(int k) { return k == kBins - 1 ? 16 * 16 : (k & 15) * 16 + (k >> 4); }
+// ---- comfort noise, the small launch in front of the call (kns_comfort.hip): one lane per stream walks the call's control bytes (the
+// leveller's layout) and writes the counter value of every frame, and the counter behind the call
+struct ComfortArgs {
+    const ComfortSetting *set;  // [Bpad]
+    uint32_t *state;            // [Bpad]: n_b -- updated in place (held: untouched; off: no frame counts, a per-frame reset still makes it 0)
+    const uint8_t *ctl;         // [B][T + 1] or nullptr (all zero): hold[b], then the call's reset flags of frames 0 .. T - 1
+    uint32_t *n;                // [Bpad][T]: the counter value of frame t of stream b (rows past B: 0)
+    int B, Bpad, T;
+};
+void launch_comfort(const ComfortArgs &a, hipStream_t s);
+// the counters of the streams with mask[b] != 0 (null: all) := 0
+void launch_comfort_reset(uint32_t *state, const uint8_t *mask, int Bpad, hipStream_t s);
 
 // A stream's row of the band-profile table, in the order the synthesis kernel's lanes consume it: the lane of column c owns the bins
 // c + 16 k2, k2 = 0 .. 15 -- its 16 floors, then its 16 ceilings, eight 16-byte words in a row -- and the row ends with one word

@@ -302,6 +302,30 @@ __device__ __forceinline__ float profile_clamp(float lo, float hi, float m) {
     return __builtin_bit_cast(float, __builtin_elementwise_min(x, __builtin_bit_cast(int, hi)));
 }
 
+// kComfort (SynthesisArgs::comfort_amp; the comfort kernels below; DESIGN.md section 2, twelfth extension): the variates of bin k of the
+// frame with counter value n -- base = seed ^ (n * 0x9E3779B9) -- are the two halves of one hashed word, uniform in (-1, 1), exact in fp32;
+// w = 1 - m', a = w A, Y = (m' X) + (a z): every operation rounded on its own, never fused, whatever the build's flags say
+__device__ __forceinline__ unsigned comfort_hash(unsigned base, unsigned k) {
+    unsigned v = base ^ (k * 0x85EBCA6Bu);
+    v ^= v >> 16;
+    v *= 0x7FEB352Du;
+    v ^= v >> 15;
+    v *= 0x846CA68Bu;
+    v ^= v >> 16;
+    return v;
+}
+__device__ __forceinline__ float comfort_variate(unsigned half) { return ((float) half - 32767.5f) * (1.0f / 32768.0f); }
+__device__ __forceinline__ float comfort_amplitude(float m, float amp) {
+#pragma clang fp contract(off)
+    const float w = 1.0f - m;
+    return w * amp;
+}
+__device__ __forceinline__ float comfort_mix(float p, float a, float z) {
+#pragma clang fp contract(off)
+    const float n = a * z;
+    return p + n;
+}
+
 // kReport (calls that ask for the frame report, SynthesisArgs::report; DESIGN.md section 2, step 4, second extension): three sums over the
 // row's 257 bins per emitted frame -- |X|^2, |Y|^2 and the raw mask -- formed where x[], y[] and mk[] are live, in the one order the spec
 // fixes: every lane its column's chain, then a butterfly over the row's lanes.
@@ -343,14 +367,14 @@ __device__ __forceinline__ float report_mask_sum(const float (&m)[17], int c) {
 // kMaskH: the mask travels as fp16 C fragments (bf16 configuration), else fp32
 template <bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets = false, bool kMinGain = false>
 __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_kernel(SynthesisArgs g) {
-    constexpr bool kReport = false, kLink = false, kProfile = false;
+    constexpr bool kReport = false, kLink = false, kProfile = false, kComfort = false;
 #include "kns_stft_synthesis.inc"
 }
 // the same forms with the frame report: kernels of their own name, the same text (kns_stft_synthesis.inc) -- a call that asks for no report
 // runs what it always ran
 template <bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets, bool kMinGain>
 __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_report_kernel(SynthesisArgs g) {
-    constexpr bool kReport = true, kLink = false, kProfile = false;
+    constexpr bool kReport = true, kLink = false, kProfile = false, kComfort = false;
 #include "kns_stft_synthesis.inc"
 }
 // kLink (handles with channels whose link is on, SynthesisArgs::link = C; DESIGN.md section 2, eighth extension): the mask of every bin
@@ -362,7 +386,7 @@ __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesi
 template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets>
 __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_link_kernel(SynthesisArgs g) {
     static_assert(kReport || !kRecompute, "linked, recomputed: report forms only");
-    constexpr bool kMinGain = true, kLink = true, kProfile = false;
+    constexpr bool kMinGain = true, kLink = true, kProfile = false, kComfort = false;
 #include "kns_stft_synthesis.inc"
 }
 // kProfile (handles with a band profile in force, SynthesisArgs::profile; DESIGN.md section 2, tenth extension): every bin's m' is held
@@ -373,13 +397,30 @@ __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesi
 // frame's mask and held until then, they were 36 registers more than the budget of three waves per SIMD has
 template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets>
 __global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : 3) void synthesis_profile_kernel(SynthesisArgs g) {
-    constexpr bool kMinGain = true, kLink = false, kProfile = true;
+    constexpr bool kMinGain = true, kLink = false, kProfile = true, kComfort = false;
+#include "kns_stft_synthesis.inc"
+}
+// kComfort (handles on which some stream's comfort noise is on, SynthesisArgs::comfort_amp; DESIGN.md section 2, twelfth extension): behind
+// m' every bin of a row whose comfort noise is on becomes Y = m' X + ((1 - m') A) z, in front of the inverse transform and of e_out.  A
+// kernel of its own name once more, so the forms above stay the instructions they were.  The arm implies kMinGain and carries the profile's
+// clamp (an all-zero gain table and the neutral profile are exact), so that a limit, a profile and comfort noise combine.  Nine
+// instantiations, all report forms: a call that asks for no report gives the report's descriptor no range and the hardware drops the
+// stores (without the report hipcc's allocation spills: some 270 bytes per lane recomputing, 12 to 20 stored).  The recomputing forms are
+// built for two waves per SIMD, not three, where they still spill five registers, and fetch the frame's mask behind the forward FFT.
+// There is no linked form: the engine refuses the combination.  In the stored-spectrum forms the next frame's operands are requested
+// behind Y, where x[] and the amplitude words have been consumed
+template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets>
+__global__ __launch_bounds__(kMaskIn ? 512 : 256, kMaskIn ? 1 : kRecompute ? 2 : 3) void synthesis_comfort_kernel(SynthesisArgs g) {
+    static_assert(kReport, "comfort noise: report forms only");
+    constexpr bool kMinGain = true, kLink = false, kProfile = true, kComfort = true;
 #include "kns_stft_synthesis.inc"
 }
 
-template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets, bool kMinGain, bool kLink, bool kProfile>
+template <bool kReport, bool kRecompute, bool kMaskH, bool kMaskIn, bool kResets, bool kMinGain, bool kLink, bool kProfile, bool kComfort>
 static void launch_synthesis_form(const SynthesisArgs &a, const dim3 grid, int threads, size_t lds, hipStream_t s) {
-    if constexpr (kProfile)
+    if constexpr (kComfort)
+        hipLaunchKernelGGL((synthesis_comfort_kernel<true, kRecompute, kMaskH, kMaskIn, kResets>), grid, dim3(threads), lds, s, a);
+    else if constexpr (kProfile)
         hipLaunchKernelGGL((synthesis_profile_kernel<kReport, kRecompute, kMaskH, kMaskIn, kResets>), grid, dim3(threads), lds, s, a);
     else if constexpr (kLink)
         hipLaunchKernelGGL((synthesis_link_kernel<kReport || kRecompute, kRecompute, kMaskH, kMaskIn, kResets>), grid, dim3(threads), lds, s, a);
@@ -391,28 +432,28 @@ static void launch_synthesis_form(const SynthesisArgs &a, const dim3 grid, int t
 
 // the forms of one arm (kMinGain: with or without the per-stream minimum gain; kReport: with or without the frame report); the plain arm's
 // are the kernels of a handle without a limit in a call that asks for no report; kLink: the linked kernels, which carry the gain; kProfile:
-// the profile kernels, which carry it too
-template <bool kMinGain, bool kReport, bool kLink = false, bool kProfile = false>
+// the profile kernels, which carry it too; kComfort: the comfort kernels, which carry the gain and the profile
+template <bool kMinGain, bool kReport, bool kLink = false, bool kProfile = false, bool kComfort = false>
 static void launch_synthesis_arm(const SynthesisArgs &a, const dim3 grid, size_t lds, hipStream_t s) {
     if (a.resets) {  // (calls with per-frame stream resets: the reset arm; the engine does not put the mask head inside then)
         if (a.recompute && a.mask_fp16)
-            launch_synthesis_form<kReport, true, true, false, true, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, true, true, false, true, kMinGain, kLink, kProfile, kComfort>(a, grid, 256, lds, s);
         else if (a.recompute)
-            launch_synthesis_form<kReport, true, false, false, true, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, true, false, false, true, kMinGain, kLink, kProfile, kComfort>(a, grid, 256, lds, s);
         else if (a.mask_fp16)
-            launch_synthesis_form<kReport, false, true, false, true, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, false, true, false, true, kMinGain, kLink, kProfile, kComfort>(a, grid, 256, lds, s);
         else
-            launch_synthesis_form<kReport, false, false, false, true, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
+            launch_synthesis_form<kReport, false, false, false, true, kMinGain, kLink, kProfile, kComfort>(a, grid, 256, lds, s);
     } else if (a.mask_w && !a.recompute && a.mask_fp16 && a.T == 1)
-        launch_synthesis_form<kReport, false, true, true, false, kMinGain, kLink, kProfile>(a, grid, 512, lds + kMaskTiles * 512, s);
+        launch_synthesis_form<kReport, false, true, true, false, kMinGain, kLink, kProfile, kComfort>(a, grid, 512, lds + kMaskTiles * 512, s);
     else if (a.recompute && a.mask_fp16)
-        launch_synthesis_form<kReport, true, true, false, false, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, true, true, false, false, kMinGain, kLink, kProfile, kComfort>(a, grid, 256, lds, s);
     else if (a.recompute)
-        launch_synthesis_form<kReport, true, false, false, false, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, true, false, false, false, kMinGain, kLink, kProfile, kComfort>(a, grid, 256, lds, s);
     else if (a.mask_fp16)
-        launch_synthesis_form<kReport, false, true, false, false, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, false, true, false, false, kMinGain, kLink, kProfile, kComfort>(a, grid, 256, lds, s);
     else
-        launch_synthesis_form<kReport, false, false, false, false, kMinGain, kLink, kProfile>(a, grid, 256, lds, s);
+        launch_synthesis_form<kReport, false, false, false, false, kMinGain, kLink, kProfile, kComfort>(a, grid, 256, lds, s);
 }
 
 void launch_synthesis(const SynthesisArgs &a, hipStream_t s) {
@@ -422,7 +463,9 @@ void launch_synthesis(const SynthesisArgs &a, hipStream_t s) {
     (void) hipFuncSetAttribute((const void *) synthesis_kernel<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
     (void) hipFuncSetAttribute((const void *) synthesis_report_kernel<true, true, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
 #endif
-    if (a.profile)  // (the engine hands a profiled launch the gain table, all zero where no limit is in force, and no link)
+    if (a.comfort_amp)  // (the engine hands such a launch the gain table and the profile, neutral where none is in force, and no link)
+        a.report ? launch_synthesis_arm<true, true, false, true, true>(a, grid, lds, s) : launch_synthesis_arm<true, false, false, true, true>(a, grid, lds, s);
+    else if (a.profile)  // (the engine hands a profiled launch the gain table, all zero where no limit is in force, and no link)
         a.report ? launch_synthesis_arm<true, true, false, true>(a, grid, lds, s) : launch_synthesis_arm<true, false, false, true>(a, grid, lds, s);
     else if (a.link)  // (the engine hands a linked launch the gain table, all zero where no limit is in force)
         a.report ? launch_synthesis_arm<true, true, true>(a, grid, lds, s) : launch_synthesis_arm<true, false, true>(a, grid, lds, s);

@@ -2,7 +2,7 @@
 // (kReport = false) and synthesis_report_kernel (kReport = true).  Text, not a function: the kernels of a call without a report must be the
 // instructions they were before the report existed (tools/asm_same.py), and a body inlined into two kernels through a function call was
 // not -- hipcc ordered and allocated it differently.  In scope: g (SynthesisArgs), kRecompute, kMaskH, kMaskIn, kResets, kMinGain, kReport,
-// kLink, kProfile.
+// kLink, kProfile, kComfort.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!kMaskIn || (kMaskH && !kRecompute), "mask head inside: bf16, stored spectrum");
     static_assert(!kMaskIn || !kResets, "resets: multi-frame form only");
@@ -60,6 +60,14 @@
     auto profile_word = [&](unsigned byte_off, unsigned imm) {
         const __amdgpu_buffer_rsrc_t pr = make_rsrc(g.profile + (size_t) (mt * 16 + wave * 4) * kProfileRow, 4u * kProfileRow * 4u);
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pr, byte_off, imm, 0));
+    };
+    // kComfort: the row's setting and the frame's counter value are fetched where they are used, through wave-uniform descriptors over the
+    // wave's four rows -- kept across the frame loop they were registers the recomputing forms do not have; the lane's words of the amplitude
+    // table (kns_kernels.h, comfort_index: four words of its 16 bins and the Nyquist word behind the row's 16 lanes) like the profile's
+    const unsigned cf_off = (unsigned) q * (unsigned) (kComfortRow * 4) + (unsigned) c * 64u;
+    auto comfort_word = [&](unsigned byte_off, unsigned imm) {
+        const __amdgpu_buffer_rsrc_t cr = make_rsrc(g.comfort_amp + (size_t) (mt * 16 + wave * 4) * kComfortRow, 4u * kComfortRow * 4u);
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(cr, byte_off, imm, 0));
     };
 
     int prev[8], cur[8], nxt[8];
@@ -163,9 +171,10 @@
         // requested here without a second register set; stored spectrum: mask and spectrum of the next frame in flight
         // (kProfile, stored spectrum: the next frame's operands are requested behind m', where the profile's words have been consumed -- with
         // both in flight at once the forms did not fit the registers of three waves per SIMD; the inverse FFT still lies in front of their use)
-        if (kRecompute)
-            mask_fetch(mk, t);
-        else if (!kProfile)
+        // (kComfort, recomputed: behind the forward FFT -- held across it, the 17 values were registers the forms do not have)
+        if (kRecompute) {
+            if (!kComfort) mask_fetch(mk, t);
+        } else if (!kProfile)
             mask_fetch(mkn, tn);
         if (kResets) {
             const unsigned rm = reset_rows(g.resets, g.rs_pitch, mt, g.rs_t0 + t);
@@ -186,6 +195,7 @@
             window_block(v, prev, cur, win_c);
             fft256_rows(v, twl_c, xw, xr);
             real_spectrum(v, x, tw_c, c);
+            if (kComfort) mask_fetch(mk, t);
         } else {
             if (!kProfile) spec_fetch(xsn, tn);
 #pragma unroll
@@ -204,8 +214,8 @@
             const int row0 = mt * 16 + wave * 4;
             const int rows_ok = row0 < g.B ? min(4, g.B - row0) : 0;
             const unsigned rep_row = (unsigned) (g.pitch ? g.pitch : g.T) * 16u;  // (bytes between two streams' rows: at most 2^20 frames)
-            // (kLink: the recomputing linked kernels are report forms only; a call that asks for no report has no rows in range)
-            const unsigned rspan = emit && rows_ok && (!kLink || g.report) ? (unsigned) (rows_ok - 1) * rep_row + 16u : 0u;
+            // (kLink, kComfort: the recomputing linked and comfort kernels are report forms only; a call that asks for no report has no rows in range)
+            const unsigned rspan = emit && rows_ok && (!(kLink || kComfort) || g.report) ? (unsigned) (rows_ok - 1) * rep_row + 16u : 0u;
             // (wave-uniform by construction; said explicitly, since hipcc otherwise keeps the loop-invariant product in a vector register)
             return make_rsrc((const char *) g.report + (size_t) row0 * rep_row + (size_t) t * 16, (unsigned) __builtin_amdgcn_readfirstlane((int) rspan));
         };
@@ -250,16 +260,56 @@
                 pfl = nfl, pce = nce;
             }
             mk[16] = profile_clamp(pfl[0], pfl[1], mk[16]);  // (the row's last word: floor[256], ceil[256])
-            if (!kRecompute) {
+            if (!kRecompute && !kComfort) {
                 mask_fetch(mkn, tn);
                 spec_fetch(xsn, tn);
             }
         }
         cpx y[16];
+        float y_nyq = 0.0f;  // (kComfort, column 0: Y[256])
+        if (kComfort) {
+            // Y = m' X + ((1 - m') A) z, z the hash of (seed, n, k): behind m', in front of e_out.  Four bins at a time, one word of the
+            // amplitude row each with the next in flight, like the profile's words; a row whose comfort noise is off keeps m' X, bit for bit
+            const int row0c = mt * 16 + wave * 4;
+            const unsigned npitch = (unsigned) (g.pitch ? g.pitch : g.T);
+            const __amdgpu_buffer_rsrc_t sr = make_rsrc(g.comfort_set + row0c, 4u * 8u);
+            const __amdgpu_buffer_rsrc_t nr = make_rsrc(g.comfort_n + (size_t) row0c * npitch + t, (3u * npitch + 1u) * 4u);
+            const int cn_on = __builtin_amdgcn_raw_buffer_load_b32(sr, (unsigned) q * 8u, 0u, 0);
+            const unsigned cn_seed = (unsigned) __builtin_amdgcn_raw_buffer_load_b32(sr, (unsigned) q * 8u, 4u, 0);
+            const unsigned cn_n = (unsigned) __builtin_amdgcn_raw_buffer_load_b32(nr, (unsigned) q * npitch * 4u, 0u, 0);
+            const unsigned base = cn_seed ^ (cn_n * 0x9E3779B9u);
+            f32x4 am = comfort_word(cf_off, 0u);
 #pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) y[k2] = cpx{mk[k2] * x[k2].x, mk[k2] * x[k2].y};
+            for (int i = 0; i < 4; ++i) {
+                const f32x4 nam = comfort_word(i < 3 ? cf_off : (unsigned) q * (unsigned) (kComfortRow * 4), i < 3 ? 16u * (i + 1) : 1024u);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int k2 = 4 * i + j;
+                    const unsigned v = comfort_hash(base, (unsigned) (c + 16 * k2));
+                    const float zi = (k2 == 0 && c == 0) ? 0.0f : comfort_variate(v >> 16);
+                    const float a = comfort_amplitude(mk[k2], am[j]);
+                    const float pr = mk[k2] * x[k2].x, pi = mk[k2] * x[k2].y;
+                    y[k2] = cpx{cn_on ? comfort_mix(pr, a, comfort_variate(v & 0xffffu)) : pr, cn_on ? comfort_mix(pi, a, zi) : pi};
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                am = nam;
+            }
+            {  // (the row's last word: A[256]; bin 256 is real and travels in bin 0's imaginary slot)
+                const unsigned v = comfort_hash(base, 256u);
+                const float pn = mk[16] * x[0].y;
+                y_nyq = cn_on ? comfort_mix(pn, comfort_amplitude(mk[16], am[0]), comfort_variate(v & 0xffffu)) : pn;
+            }
+            if (!kRecompute) {
+                mask_fetch(mkn, tn);
+                spec_fetch(xsn, tn);
+            }
+        } else {
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2) y[k2] = cpx{mk[k2] * x[k2].x, mk[k2] * x[k2].y};
+        }
         if (kReport)  // (column 0: Y[0] = m'[0] X0, Y[256] = m'[256] X256)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, report_energy(y, y[0].x, mk[16] * x[0].y, c)), report_rsrc(), roff, 4u, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, report_energy(y, y[0].x, kComfort ? y_nyq : mk[16] * x[0].y, c)), report_rsrc(), roff, 4u, 0);
         cpx yp[16];
         fft_partner(y, yp, c);
         cpx v[16];
@@ -267,8 +317,8 @@
         for (int k2 = 0; k2 < 16; ++k2) {
             cpx yk = y[k2], yq = yp[k2];  // Y[k], Y[256 - k]
             if (k2 == 0 && c == 0) {
-                yk = cpx{mk[0] * x[0].x, 0.0f};
-                yq = cpx{mk[16] * x[0].y, 0.0f};
+                yk = cpx{kComfort ? y[0].x : mk[0] * x[0].x, 0.0f};
+                yq = cpx{kComfort ? y_nyq : mk[16] * x[0].y, 0.0f};
             }
             const float2 w = *(const float2 *) (tw_c + k2 * 128);
             // e = Y[k] + conj(Y[256 - k]), d = Y[k] - conj(Y[256 - k]), o = conj(W^k) d

@@ -1,5 +1,5 @@
 // pv_api_internal.h -- what the translation units of the C ABI share: the handles behind the opaque pointers, the calling thread's error
-// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_extensions.cpp (packet handles, sample formats, channels and their link) and pv_level.cpp (the output leveller) use it.
+// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_extensions.cpp (packet handles, sample formats, channels and their link) pv_level.cpp (the output leveller) and pv_comfort.cpp (comfort noise) use it.
 // Nothing here leaves the library.
 #pragma once
 
@@ -39,6 +39,15 @@ struct MinGain {
     std::vector<kns::LevelSetting> level;
     unsigned level_rev = 0;
     bool level_any = false;
+    // Comfort noise (pv_koala_batch_set_comfort_noise; pv_comfort.cpp): every stream's setting [num_streams] and amplitude curve
+    // [num_streams][kns::kComfortRow] in the order the engine's table has them (kns::comfort_index), empty until the first accepted change;
+    // one revision counter for both; and whether any stream's comfort noise is on (none: the calls are the plain calls, no table at all).
+    // A call with comfort noise carries `gain` and `profile` too (pv_comfort.cpp makes `profile` the neutral table when it is still empty):
+    // the comfort kernels read both.  The frame COUNTERS are the engine's.
+    std::vector<kns::ComfortSetting> comfort;
+    std::vector<float> comfort_amp;
+    unsigned comfort_rev = 0;
+    bool comfort_any = false;
 };
 struct pv_koala {
     kns::Engine *engine;
@@ -62,6 +71,15 @@ pv_status_t check_band_profile(const MinGain &limit);
 // A call while some stream's leveller is on: what it is not combined with yet -- the channel link, the high-band carry, the asynchronous
 // entry points, a handle at 44 100 or 22 050 Hz (PV_STATUS_INVALID_ARGUMENT and a message), else SUCCESS
 pv_status_t check_level(const MinGain &limit, const kns::Engine *engine, bool async);
+// A call while some stream's comfort noise is on: the same four refusals, else SUCCESS; carry_comfort: what such a call takes to the engine
+pv_status_t check_comfort(const MinGain &limit, const kns::Engine *engine, bool async);
+template <class C>
+void carry_comfort(const MinGain &limit, C *call) {
+    if (!limit.comfort_any) return;
+    call->comfort = limit.comfort.data(), call->comfort_amp = limit.comfort_amp.data(), call->comfort_rev = limit.comfort_rev;
+    call->min_gain = limit.gain.data(), call->min_gain_rev = limit.rev;
+    call->band_profile = limit.profile.data(), call->band_profile_rev = limit.profile_rev;
+}
 // what an engine call that did not succeed leaves on the stack: a refused argument, or a failure under the entry point's own code
 pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std::string &err);
 

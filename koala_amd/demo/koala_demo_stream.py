@@ -69,6 +69,7 @@ def run_in_packets(args):
     batch.set_attenuation_limit(args.attenuation_limit_db)
     set_band_profile(batch, args)
     set_level(batch, args)
+    set_comfort(batch, args)
     t_start = time.perf_counter()
     try:
         with contextlib.ExitStack() as stack:
@@ -133,6 +134,7 @@ def run_raw_format(args):
     batch.set_attenuation_limit(args.attenuation_limit_db)
     set_band_profile(batch, args)
     set_level(batch, args)
+    set_comfort(batch, args)
     samples = 0
     try:
         while True:
@@ -193,6 +195,7 @@ def run_channels(args):
             raise ValueError('--link: not available with --highpass or --max_depth_db yet (the library refuses a band profile on linked channels)')
         set_band_profile(batch, args)
         set_level(batch, args)
+        set_comfort(batch, args)
         samples = 0
         try:
             while True:
@@ -225,6 +228,16 @@ def set_band_profile(handle, args):
     if floor is not None and ceiling is not None:
         floor = np.minimum(floor, ceiling)  # (below the high-pass the ceiling wins)
     handle.set_band_profile(floor, ceiling)
+
+
+def set_comfort(handle, args):
+    """--comfort_noise DBFS: white comfort noise of DBFS dB RMS where the mask removes everything (koala_amd.comfort.curve(DBFS))"""
+    if args.comfort_noise is None:
+        return
+    if args.link or args.sample_rate in (44100, 22050):
+        raise ValueError('--comfort_noise: not available with --link nor at 44100 / 22050 Hz yet (the library refuses the call)')
+    from koala_amd import comfort
+    handle.set_comfort_noise(comfort.curve(args.comfort_noise))
 
 
 def set_level(handle, args):
@@ -289,6 +302,8 @@ def main(argv=None):
                     help='band profile: let nothing out below HZ (rumble, 50 / 60 Hz hum), a raised-cosine edge 62.5 Hz wide')
     ap.add_argument('--max_depth_db', type=float, default=None, metavar='DB',
                     help='band profile: suppress no bin by more than DB dB (a floor on the mask)')
+    ap.add_argument('--comfort_noise', type=float, default=None, metavar='DBFS',
+                    help='comfort noise: fill what the mask removes with white noise of DBFS dB RMS (for instance -60)')
     ap.add_argument('--level', type=float, nargs='?', const=-23.0, default=None, metavar='DBFS',
                     help='output leveller: bring speech towards DBFS (default -23) with a speech-gated automatic gain')
     ap.add_argument('--meter', type=int, default=0, metavar='N',
@@ -346,6 +361,7 @@ def main(argv=None):
     koala.set_attenuation_limit(args.attenuation_limit_db)
     set_band_profile(koala, args)
     set_level(koala, args)
+    set_comfort(koala, args)
     print('Koala version: %s' % koala.version)
     n = koala.frame_length
     source = (frames_from_wav(args.input_path, n, koala.sample_rate) if args.input_path
