@@ -760,6 +760,9 @@ class KoalaBatch(object):
                   'mask': (2, (num_frames, self.num_streams, 257)), 'hidden': (3, (8, self.num_streams, 271)),
                   'embed': (4, (num_frames, self.num_streams, 271)),
                   'route': (6, (4,)),  # developer library only: [route, features not stored, mask head fused, spectrum stored]
+                  # developer library only: the same four, then the frames per time segment of the last analysis and of the last synthesis launch,
+                  # and the call's synthesis launches (the slices of the layer pipeline, or one)
+                  'segments': (6, (7,)),
                   'head_launches': (7, (1,))}  # developer library only: recurrent launches that carried their stage's narrow head
         code, shape = shapes[what]
         out = np.empty(shape, np.float32)

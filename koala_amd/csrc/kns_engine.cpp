@@ -1500,6 +1500,9 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
 
     const bool small_steps = T > 1 && mtb <= steps_mt && prec_ != kBf16 && !no_small_ && !wave && !resets;
     last_head_launches_ = 0;
+#ifdef KNS_DEV
+    last_synth_launches_ = 0;
+#endif
     last_route_ = resets ? kRouteChunkedResets : small ? kRouteSmall : wave ? kRouteWave : small_steps ? kRouteSmallSteps : quad ? kRouteQuad1 : kRouteChunked;
     // ---- mid-size batches: the layer pipeline over sub-chunks of frames (see the chunk loop below)
     const int pipe_chunk = dev_pipe_chunk_ > 0 ? dev_pipe_chunk_ : (T + 1) / 2;
@@ -1531,10 +1534,16 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
         int seg = Tc;
         while (seg > 1 && (Bpad_ / 16) * ((Tc + seg - 1) / seg) < 1024) seg = (seg + 1) / 2;
         a.seg = dev_analysis_seg_ > 0 ? (dev_analysis_seg_ < Tc ? dev_analysis_seg_ : Tc) : seg;
+#ifdef KNS_DEV
+        last_analysis_seg_ = a.seg;
+#endif
         launch_analysis(a, st);
     };
     if (!stft_sliced) {
         tick(kClsAnalysis);
+#ifdef KNS_DEV
+        last_analysis_seg_ = an.seg;
+#endif
         if (only < 0 || only == kClsAnalysis) launch_analysis(an, stream_);
         tock(kClsAnalysis);
     }
@@ -1614,6 +1623,10 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
         sy.profile = slice.profile;
         if (slice.comfort) sy.comfort_amp = d_cf_amp_, sy.comfort_set = d_cf_set_, sy.comfort_n = d_cf_n_ + t0c;  // (like `report`: rows T frames apart)
         sy.report = slice.d_report ? slice.d_report + (size_t) t0c * 4 : nullptr;  // (like `out`: the slice's first frame, rows T frames apart)
+#ifdef KNS_DEV
+        last_synth_seg_ = sy.seg;
+        ++last_synth_launches_;
+#endif
         launch_synthesis(sy, st);
     };
     if (pipelined) (void) hipEventRecord(pipe_fork_, stream_);
@@ -3558,13 +3571,19 @@ int64_t Engine::debug_read(int what, float *out, int64_t capacity, std::string *
                     out[((size_t) l * B_ + b) * kHidden + k] =
                         s[(((size_t) l * mtb + b / 16) * kUnitTiles + k / 16) * 256 + cpack_off(b % 16, k % 16)];
 #ifdef KNS_DEV
-    } else if (what == 6) {  // developer build: the route of the last call (enum Route), what rode inside other launches
+    } else if (what == 6) {  // developer build: the route of the last call (enum Route), what rode inside other launches; a reader with room
+        // for six or seven values also gets the time segments of its STFT launches (four-value readers get what they always got)
         if (capacity < 4) return -2;
         out[0] = (float) last_route_;
         out[1] = feat_valid_ ? 0.0f : 1.0f;   // front-end inside the analysis launch / features rolled into the history
         out[2] = mask_valid_ ? 0.0f : 1.0f;   // mask head inside the synthesis launch
         out[3] = spec_valid_ ? 1.0f : 0.0f;   // spectrum stored (not recomputed)
-        return 4;
+        if (capacity < 6) return 4;
+        out[4] = (float) last_analysis_seg_;  // frames per time segment of the last analysis launch
+        out[5] = (float) last_synth_seg_;     // ... and of the last synthesis launch
+        if (capacity < 7) return 6;
+        out[6] = (float) last_synth_launches_;  // synthesis launches of the call: the slices of the layer pipeline, or one
+        return 7;
     } else if (what == 7) {  // developer build: recurrent launches of the last call that carried their stage's narrow head
         if (capacity < 1) return -2;
         out[0] = (float) last_head_launches_;

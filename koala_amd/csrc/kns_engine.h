@@ -424,6 +424,11 @@ private:
     bool spec_valid_ = false, feat_valid_ = false, mask_valid_ = false;
     int last_head_launches_ = 0;  // recurrent launches of the last run_device() that carried their stage's head (debug tap 7)
     int last_route_ = 0;  // enum Route of the last run_device() (kns_engine.cpp; reported by the developer build's debug tap 6)
+#ifdef KNS_DEV
+    // frames per time segment of the last analysis / synthesis launch, and the synthesis launches of the last run_device() (one per slice
+    // of the layer pipeline where the STFT stages are sliced): debug tap 6, values 4 to 6
+    int last_analysis_seg_ = 0, last_synth_seg_ = 0, last_synth_launches_ = 0;
+#endif
 
     // A ring of page-locked upload slots, one per call that may still be in flight: a slot is handed out again once the copy that read
     // it kResetRing uses ago has completed (an event per slot).  Allocated at first use, all slots or none; release() frees it (~Engine).

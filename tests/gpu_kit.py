@@ -71,6 +71,11 @@ def route_of(kb):
     return int(route_info(kb)[0])
 
 
+def segments_of(kb):
+    """developer library: (frames per time segment of the last analysis launch, of the last synthesis launch, the last call's synthesis launches)"""
+    return tuple(int(v) for v in kb.debug_read('segments', 1)[4:])
+
+
 # ---------------------------------------------------------------------------------------------------- shapes and streams
 
 def flen(rate):
