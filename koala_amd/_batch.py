@@ -14,6 +14,7 @@ from ._koala import (KoalaError, KoalaInvalidArgumentError, KoalaIOError, Picovo
                      raise_status)
 from . import bands
 from . import level as level_rule
+from . import limiter as limiter_rule
 from . import comfort as comfort_rule
 from .channels import LINK_CHANNELS, MAX_CHANNELS
 from .formats import DTYPES, FORMATS
@@ -62,6 +63,26 @@ class LevelSetting(Structure):
         return level_rule.Setting(int(self.on), *[float(getattr(self, name)) for name in level_rule.FIELDS])
 
 
+class LimiterSetting(Structure):
+    """pv_koala_limiter_t (include/pv_koala_batch.h)"""
+    _fields_ = [('struct_size', c_int32), ('on', c_int32)] + [(name, c_float) for name in limiter_rule.FIELDS]
+
+    @classmethod
+    def of(cls, setting):
+        """a koala_amd.limiter.Setting, or None (off)"""
+        s = limiter_rule.OFF if setting is None else setting
+        if not isinstance(s, limiter_rule.Setting):
+            raise KoalaInvalidArgumentError("a limiter setting should be a koala_amd.limiter.Setting (koala_amd.limiter.settings(...)) or None")
+        try:
+            limiter_rule.check(s)
+        except (ValueError, TypeError) as e:
+            raise KoalaInvalidArgumentError(str(e))
+        return cls(sizeof(cls), int(s.on), *[float(v) for v in s[1:]])
+
+    def setting(self):
+        return limiter_rule.Setting(int(self.on), *[float(getattr(self, name)) for name in limiter_rule.FIELDS])
+
+
 class ComfortSetting(Structure):
     """pv_koala_comfort_t (include/pv_koala_batch.h)"""
     _fields_ = [('struct_size', c_int32), ('on', c_int32), ('seed', c_uint32)]
@@ -73,7 +94,7 @@ class KoalaBatch(object):
 
     def __init__(self, access_key: str, model_path: str, device: str, library_path: str, num_streams: int,
                  max_frames_per_call: int = 1, precision: str = 'fp32', sample_rate: int = 16000, packet_samples: int = 0, sample_format: str = 's16',
-                 channels: int = 1, channel_link: Optional[str] = None, high_band: Optional[str] = None, band_profile=None, level=None, comfort_noise=None) -> None:
+                 channels: int = 1, channel_link: Optional[str] = None, high_band: Optional[str] = None, band_profile=None, level=None, comfort_noise=None, limiter=None) -> None:
         """`sample_rate`: 44100 or 22050 Hz make a packet handle around fractional converters (`packet_samples` > 0 is required; there is
         no frame length, `frame_length` is None, and stream records and the asynchronous calls are refused); otherwise
         8000, 12000, 16000, 24000, 32000 or 48000 Hz, fixed for the handle (include/pv_koala_batch.h, pv_koala_batch_init_rate).  Every
@@ -99,6 +120,7 @@ class KoalaBatch(object):
         the call and scaled by a broadband gain from the call's masks (`set_high_band`; koala_amd.highband states the rule).
         `band_profile`: None (default) or (floor, ceiling) -- `set_band_profile(floor, ceiling)` on every stream of the new handle.
         `level`: None (default) or a koala_amd.level.Setting -- `set_level(level)` on every stream of the new handle: the output leveller.
+        `limiter`: None (default) or a koala_amd.limiter.Setting -- `set_limiter(limiter)` on every stream of the new handle: the peak limiter.
         `comfort_noise`: None (default), an amplitude curve float32 [257] (koala_amd.comfort.curve(-60)) or a pair (curve, seed) --
         `set_comfort_noise` on every stream of the new handle; with a bare curve or seed None stream b gets the seed b."""
         if not isinstance(access_key, str) or len(access_key) == 0:
@@ -126,6 +148,8 @@ class KoalaBatch(object):
         carry = self._high_band_value(high_band)
         if level is not None:  # (checked before any library is loaded)
             LevelSetting.of(level)
+        if limiter is not None:  # (checked before any library is loaded)
+            LimiterSetting.of(limiter)
         if comfort_noise is not None:  # (checked before any library is loaded)
             pair = comfort_noise if isinstance(comfort_noise, tuple) else (comfort_noise, None)
             if len(pair) != 2:
@@ -234,12 +258,14 @@ class KoalaBatch(object):
         if not fractional:
             self._check(lib.pv_koala_batch_state_size(self._handle, byref(d)), 'Failed to get the state size')
             self.state_size = d.value
-        if link or carry or band_profile is not None or level is not None or comfort_noise is not None:
+        if link or carry or band_profile is not None or level is not None or comfort_noise is not None or limiter is not None:
             try:
                 if comfort_noise is not None:
                     self.set_comfort_noise(comfort_noise[0], comfort_noise[1])
                 if level is not None:
                     self.set_level(level)
+                if limiter is not None:
+                    self.set_limiter(limiter)
                 if band_profile is not None:
                     self.set_band_profile(band_profile[0], band_profile[1])
                 if link:
@@ -643,7 +669,7 @@ class KoalaBatch(object):
         """The output leveller of the listed streams (None: every stream): `setting` is a koala_amd.level.Setting
         (koala_amd.level.settings(target_dbfs=-23, ...)), None for off, or a list with one of either per listed stream.  While a stream's
         leveller is on, its samples are brought towards the target by a gain that adapts on speech frames only and ramps over every
-        frame; saturation is the only limiter.  Holds from the next call on; configuration, not state: resets, held streams and stream
+        frame; what keeps the product under a ceiling is the peak limiter (`set_limiter`), without it saturation alone.  Holds from the next call on; configuration, not state: resets, held streams and stream
         records neither change nor carry it.  A call is refused while some stream levels and the channel link or the high-band carry is
         on, on the asynchronous entry points and at 44100 / 22050 Hz."""
         s, sp, n = self._stream_list(streams, None)
@@ -674,6 +700,44 @@ class KoalaBatch(object):
             raise KoalaInvalidArgumentError("expected float32 state of shape [n, 2]")
         s, sp, n = self._stream_list(streams, a.shape[0])
         self._check(self._level_fn('set_level_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, a.ctypes.data), 'set_level_state failed')
+
+    # ---- peak limiter (include/pv_koala_batch.h, PEAK LIMITER; koala_amd.limiter states the rule)
+
+    def set_limiter(self, setting, streams=None) -> None:
+        """The peak limiter of the listed streams (None: every stream): `setting` is a koala_amd.limiter.Setting
+        (koala_amd.limiter.settings(ceiling_dbfs=-1, release_ms=50)), None for off, or a list with one of either per listed stream.  While
+        a stream's limiter is on, no sample of its inner 16 kHz output is above the ceiling: the gain falls at once and recovers linearly,
+        behind the leveller's ramp and in front of its saturation.  Holds from the next call on; configuration, not state.  A call is
+        refused while some stream limits and the channel link or the high-band carry is on, on the asynchronous entry points and at
+        44100 / 22050 Hz."""
+        s, sp, n = self._stream_list(streams, None)
+        each = list(setting) if isinstance(setting, (list, tuple)) and not isinstance(setting, limiter_rule.Setting) else [setting] * n
+        if len(each) != n:
+            raise KoalaInvalidArgumentError("`setting` must be one setting or one per listed stream")
+        table = (LimiterSetting * n)(*[LimiterSetting.of(v) for v in each])
+        self._check(self._level_fn('set_limiter', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, byref(table)), 'set_limiter failed')
+
+    def limiter(self, stream: int):
+        """The koala_amd.limiter.Setting in force of one stream."""
+        out = LimiterSetting(sizeof(LimiterSetting))
+        self._check(self._level_fn('get_limiter', [c_void_p, c_int32, c_void_p])(self._handle, int(stream), byref(out)), 'limiter failed')
+        return out.setting()
+
+    def limiter_state(self, streams=None) -> np.ndarray:
+        """The limiter's state of the listed streams (None: all), float32 [n] = g, the gain behind each stream's last sample, behind
+        everything enqueued on the handle.  Stream records do not carry it: a caller that moves a stream moves these four bytes too."""
+        s, sp, n = self._stream_list(streams, None)
+        out = np.empty(n, np.float32)
+        self._check(self._level_fn('get_limiter_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, out.ctypes.data), 'limiter_state failed')
+        return out
+
+    def set_limiter_state(self, state, streams=None) -> None:
+        """Continues the limiter of the listed streams (None: slots 0 .. n - 1) from `state`, float32 [n] = g in (0, 1]; 1 is fresh."""
+        a = np.ascontiguousarray(state, dtype=np.float32)
+        if a.ndim != 1 or a.shape[0] == 0:
+            raise KoalaInvalidArgumentError("expected float32 state of shape [n]")
+        s, sp, n = self._stream_list(streams, a.shape[0])
+        self._check(self._level_fn('set_limiter_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, a.ctypes.data), 'set_limiter_state failed')
 
     # ---- comfort noise (include/pv_koala_batch.h, COMFORT NOISE; koala_amd.comfort states the rule)
 
@@ -786,4 +850,4 @@ class KoalaBatch(object):
             pass
 
 
-__all__ = ['KoalaBatch', 'BatchCall', 'BatchPackets', 'BatchConfig', 'LevelSetting', 'ComfortSetting', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']
+__all__ = ['KoalaBatch', 'BatchCall', 'BatchPackets', 'BatchConfig', 'LevelSetting', 'LimiterSetting', 'ComfortSetting', 'PRECISION_FP32', 'PRECISION_BF16', 'KERNEL_CLASSES']

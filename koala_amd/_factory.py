@@ -43,7 +43,8 @@ def create_batch(
         high_band: Optional[str] = None,
         band_profile=None,
         level=None,
-        comfort_noise=None) -> KoalaBatch:
+        comfort_noise=None,
+        limiter=None) -> KoalaBatch:
     """`num_streams` independent streams advancing together on one GPU (see KoalaBatch), at 8000, 12000, 16000, 24000, 32000 or 48000 Hz.
     `packet_samples=N` makes a packet handle: streams that take and deliver any number of samples, up to N, per call
     (`KoalaBatch.process_packets`; `max_frames_per_call` is then derived from N).
@@ -59,6 +60,8 @@ def create_batch(
     `koala_amd.bands` builds the curves and has the rule).
     `level=koala_amd.level.settings(...)`: the output leveller on every stream, a speech-gated automatic gain behind the suppressor
     (`KoalaBatch.set_level`; `koala_amd.level` has the rule).
+    `limiter=koala_amd.limiter.settings(ceiling_dbfs=-1)`: the peak limiter on every stream, a ceiling on the output with instant attack and
+    linear release, behind the leveller (`KoalaBatch.set_limiter`; `koala_amd.limiter` has the rule).
     `comfort_noise=koala_amd.comfort.curve(-60)` (or a pair (curve, seed)): comfort noise on every stream, a shaped noise exactly where the
     mask removed energy (`KoalaBatch.set_comfort_noise`; `koala_amd.comfort` has the rule)."""
     return KoalaBatch(
@@ -77,7 +80,8 @@ def create_batch(
         high_band=high_band,
         band_profile=band_profile,
         level=level,
-        comfort_noise=comfort_noise)
+        comfort_noise=comfort_noise,
+        limiter=limiter)
 
 
 def available_devices(library_path: Optional[str] = None) -> Sequence[str]:

@@ -225,6 +225,29 @@ class Koala(object):
         if status is not PicovoiceStatuses.SUCCESS:
             raise_status(self._library, status, 'set_level failed')
 
+    def set_limiter(self, setting) -> None:
+        """The peak limiter from the next frame on (an extension: include/pv_koala_batch.h, pv_koala_set_limiter): a
+        koala_amd.limiter.Setting (koala_amd.limiter.settings(ceiling_dbfs=-1, release_ms=50)) or None for off.  `reset()` sets its gain
+        to 1 and leaves the setting."""
+        from ._batch import LimiterSetting
+        s = LimiterSetting.of(setting)
+        fn = self._library.pv_koala_set_limiter
+        fn.argtypes, fn.restype = [POINTER(self.CKoala), c_void_p], PicovoiceStatuses
+        status = fn(self._handle, byref(s))
+        if status is not PicovoiceStatuses.SUCCESS:
+            raise_status(self._library, status, 'set_limiter failed')
+
+    def limiter(self):
+        """The koala_amd.limiter.Setting in force."""
+        from ._batch import LimiterSetting
+        s = LimiterSetting(sizeof(LimiterSetting))
+        fn = self._library.pv_koala_get_limiter
+        fn.argtypes, fn.restype = [POINTER(self.CKoala), c_void_p], PicovoiceStatuses
+        status = fn(self._handle, byref(s))
+        if status is not PicovoiceStatuses.SUCCESS:
+            raise_status(self._library, status, 'limiter failed')
+        return s.setting()
+
     def set_comfort_noise(self, amplitude=None, seed=None, on=True) -> None:
         """Comfort noise from the next frame on (an extension: include/pv_koala_batch.h, pv_koala_set_comfort_noise): `amplitude` float32
         [257], finite and >= 0 (koala_amd.comfort.curve(-60) builds one; None: keep the curve), `seed` a uint32 (None: keep the seed, 0 on

@@ -751,6 +751,7 @@ Engine::~Engine() {
     pf_ring_.release();
     lv_ring_.release();
     lvc_ring_.release();
+    lm_ring_.release();
     cf_ring_.release();
     cfa_ring_.release();
     cfc_ring_.release();
@@ -901,6 +902,7 @@ void Engine::launch_resets(const uint8_t *d_mask) {
         if (d_hb_rep_) launch_high_band_reset(d_hb_x_, d_hb_y_, d_hb_s_, rs_stage_out(rate_).U, d_mask, Bpad_, stream_);  // (the high-band carry's, once it exists)
     }
     if (d_lv_state_) launch_level_reset(d_lv_state_, d_mask, Bpad_, stream_);  // (the leveller's, once it exists)
+    if (d_lm_state_) launch_limit_reset(d_lm_state_, d_mask, Bpad_, stream_);  // (the limiter's, once it exists)
     if (d_cf_state_) launch_comfort_reset(d_cf_state_, d_mask, Bpad_, stream_);  // (the comfort noise's counters, once they exist)
     if (pk_max_) launch_packet_reset(packet_state_args(), d_mask, stream_);
     if (fr_rate_) launch_fractional_reset(fractional_state_args(), d_mask, stream_);
@@ -1923,6 +1925,10 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
         *err = "the output leveller is not available yet on the asynchronous entry points.";
         return Status::kBadArgument;
     }
+    if (c.limiter) {
+        *err = "the peak limiter is not available yet on the asynchronous entry points.";
+        return Status::kBadArgument;
+    }
     if (c.comfort) {
         *err = "comfort noise is not available yet on the asynchronous entry points.";
         return Status::kBadArgument;
@@ -2072,6 +2078,12 @@ bool Engine::run_call(const Call &c, std::string *err) {
         return false;
     }
     if (c.level && !begin_level(c, err)) return false;
+    // (peak limiter: the same, and its launch stands in the place of the leveller's second one)
+    if (c.limiter && (kin != kPtrDevice || link || c.high_band)) {
+        *err = kin != kPtrDevice ? "a limiting call runs on device rows only." : "the peak limiter is not combined with linked channels nor with the high-band carry.";
+        return false;
+    }
+    if (c.limiter && !begin_limiter(c, err)) return false;
     // (comfort noise: the same -- device rows only, never quietly without the fill; its kernels carry the gains and the profile's clamp)
     if (c.comfort && (kin != kPtrDevice || link || c.high_band || !profile)) {
         *err = kin != kPtrDevice ? "a call with comfort noise runs on device rows only." :
@@ -2088,7 +2100,7 @@ bool Engine::run_call(const Call &c, std::string *err) {
         // (comfort noise: the counter's launch in front of the call's kernels)
         return begin_resets(T, c.resets, &table, err) && (!c.comfort || run_comfort(c, err)) &&
                run_device({0, T, pcm, out, !overlap, &table, min_gain, rep, link, profile, c.comfort != nullptr}, err) &&
-               (!c.level || run_level(c, rep, report != nullptr, err));
+               ((!c.level && !c.limiter) || run_level(c, rep, report != nullptr, err));
     }
     if (T > host_chunk_ && bytes >= host_pipeline_min_bytes_) {
         const char *pa = (const char *) pcm, *pb = (const char *) out;
@@ -2305,8 +2317,9 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
         // (output leveller: it works on the inner 16 kHz samples, between the call and the out-stage; `hold` rides along for its tracker
         // alone -- process_frames has put the held streams' records aside around this whole call)
         inner.level = c.level, inner.level_rev = c.level_rev;
+        inner.limiter = c.limiter, inner.limiter_rev = c.limiter_rev;  // (peak limiter: in the same place, `hold` for its g)
         inner.comfort = c.comfort, inner.comfort_amp = c.comfort_amp, inner.comfort_rev = c.comfort_rev;  // (comfort noise: the same, for its counters)
-        if (c.level || c.comfort) inner.hold = c.hold;
+        if (c.level || c.limiter || c.comfort) inner.hold = c.hold;
         // High-band carry: the kernel behind the out-stage reads the call's masks from its report -- an output only, so asking for it into a
         // buffer of the engine's changes no bit -- the in-stage's rows, which the device-pointer call leaves in d_in_ as they are, and the
         // call's input, of which a copy is kept where the out-stage writes over it.
@@ -2410,7 +2423,9 @@ bool Engine::begin_level(const Call &c, std::string *err) {
 
 // The leveller's two launches behind the kernels of a device-pointer call (run_call): the call's `hold` and reset flags go to the device as
 // one row of T + 1 bytes per stream, only when one of them is set; `report` is what the call's synthesis kernels have written -- the
-// caller's (then column 3 of a levelling stream's rows becomes its gain) or the engine's.
+// caller's (then column 3 of a levelling stream's rows becomes its gain) or the engine's.  A call on which some stream limits
+// (Call::limiter) runs the tracker only if some stream levels, and then the limiter's launch, which applies the ramp too, in the place of
+// level_apply_kernel.
 bool Engine::run_level(const Call &c, const float *report, bool callers_report, std::string *err) {
     const int T = c.T;
     bool any = false;
@@ -2437,7 +2452,16 @@ bool Engine::run_level(const Call &c, const float *report, bool callers_report, 
     a.report = report, a.report_out = callers_report ? (float *) report : nullptr;
     a.gains = d_lv_gains_, a.out = c.out;
     a.B = B_, a.T = T;
-    launch_level(a, stream_);
+    if (!c.limiter) {
+        launch_level(a, stream_);
+    } else {
+        if (c.level) launch_level_track(a, stream_);
+        LimitArgs m;
+        m.set = d_lm_set_, m.state = d_lm_state_, m.ctl = a.ctl;
+        m.gains = c.level ? d_lv_gains_ : nullptr, m.out = c.out;
+        m.B = B_, m.T = T;
+        launch_limit(m, stream_);
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         *err = hip_error(e);
@@ -2481,6 +2505,98 @@ Status Engine::level_state(bool set, int count, const int32_t *streams, float *s
     }
     if (e == hipSuccess && set) {
         e = hipMemcpyAsync(d_lv_state_, all.data(), all.size() * 4, hipMemcpyHostToDevice, stream_);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_);  // (`all` goes out of scope)
+    }
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        *err = hip_error(e);
+        return Status::kRuntime;
+    }
+    return Status::kOk;
+}
+
+// ------------------------------------------------------------------------------------------------ peak limiter
+
+// Peak limiter (Call::limiter): every buffer of the feature at first use -- by a call that limits or by limiter_state -- all or nothing, the
+// leveller's among them (the limiter's launch reads its control rows and gain pairs); g begins at 1, set on the handle's stream.
+bool Engine::limiter_ready(std::string *err) {
+    if (d_lm_state_) return true;
+    if (!level_ready(err)) return false;
+    (void) hipSetDevice(device_);
+    const bool ring = lm_ring_.ready((size_t) Bpad_ * sizeof(LimiterSetting));
+    if (ring && !d_lm_set_) d_lm_set_ = (LimiterSetting *) dalloc((size_t) Bpad_ * sizeof(LimiterSetting), true);
+    float *state = ring && d_lm_set_ ? (float *) dalloc((size_t) Bpad_ * 4, false) : nullptr;
+    if (!state) {
+        (void) hipGetLastError();
+        *err = "Failed to allocate the buffers of the peak limiter.";
+        return false;
+    }
+    launch_limit_reset(state, nullptr, Bpad_, stream_);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        *err = hip_error(e);
+        return false;
+    }
+    d_lm_state_ = state;
+    return true;
+}
+
+// The settings of the call about to run, like the leveller's: through a slot of lm_ring_ (rows past B: off) to the device on the handle's
+// stream when the call's revision is not the table's.
+bool Engine::begin_limiter(const Call &c, std::string *err) {
+    if (!limiter_ready(err)) return false;
+    if (lm_valid_ && lm_rev_ == c.limiter_rev) return true;
+    const int k = lm_ring_.acquire();
+    if (k >= 0) {
+        memcpy(lm_ring_.host[k], c.limiter, (size_t) B_ * sizeof(LimiterSetting));
+        memset((char *) lm_ring_.host[k] + (size_t) B_ * sizeof(LimiterSetting), 0, (size_t) (Bpad_ - B_) * sizeof(LimiterSetting));
+    }
+    if (k < 0 || hipMemcpyAsync(d_lm_set_, lm_ring_.host[k], (size_t) Bpad_ * sizeof(LimiterSetting), hipMemcpyHostToDevice, stream_) != hipSuccess ||
+        !lm_ring_.uploaded(k, stream_)) {
+        *err = hip_last_error();
+        lm_valid_ = false;
+        return false;
+    }
+    lm_rev_ = c.limiter_rev;
+    lm_valid_ = true;
+    return true;
+}
+
+Status Engine::limiter_state(bool set, int count, const int32_t *streams, float *state, std::string *err) {
+    if (count < 1 || count > B_) {
+        *err = "`count` " + std::to_string(count) + " is outside [1, " + std::to_string(B_) + "].";
+        return Status::kBadArgument;
+    }
+    std::vector<uint8_t> listed((size_t) B_, 0);
+    for (int i = 0; i < count; ++i) {
+        const int b = streams ? streams[i] : i;
+        if (b < 0 || b >= B_) {
+            *err = "`streams[" + std::to_string(i) + "]` = " + std::to_string(b) + " is outside [0, " + std::to_string(B_) + ").";
+            return Status::kBadArgument;
+        }
+        if (listed[b]) {
+            *err = "`streams[" + std::to_string(i) + "]`: slot " + std::to_string(b) + " is listed twice.";
+            return Status::kBadArgument;
+        }
+        listed[b] = 1;
+    }
+    if (!set && !d_lm_state_) {  // a handle that never limited: every stream is fresh, and nothing is allocated to say so
+        for (int i = 0; i < count; ++i) state[i] = 1.0f;
+        return Status::kOk;
+    }
+    (void) hipSetDevice(device_);
+    if (async_n_ && !drain_async(err)) return Status::kRuntime;
+    if (!limiter_ready(err)) return Status::kRuntime;
+    std::vector<float> all((size_t) B_);
+    hipError_t e = hipMemcpyAsync(all.data(), d_lm_state_, all.size() * 4, hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    for (int i = 0; e == hipSuccess && i < count; ++i) {
+        const int b = streams ? streams[i] : i;
+        if (set) all[(size_t) b] = state[i];
+        else state[i] = all[(size_t) b];
+    }
+    if (e == hipSuccess && set) {
+        e = hipMemcpyAsync(d_lm_state_, all.data(), all.size() * 4, hipMemcpyHostToDevice, stream_);
         if (e == hipSuccess) e = hipStreamSynchronize(stream_);  // (`all` goes out of scope)
     }
     if (e != hipSuccess) {
@@ -2917,6 +3033,12 @@ Status Engine::process(const Call &c, std::string *err) {
                                "the output leveller is not available yet on a handle at 44100 or 22050 Hz.";
         return Status::kBadArgument;
     }
+    if (c.limiter && (c.channel_link || c.high_band || fr_rate_)) {  // peak limiter: the same four, refused by the owner by name first
+        *err = c.channel_link ? "the peak limiter is not available yet while the channel link is on." :
+               c.high_band   ? "the peak limiter is not available yet while the high-band carry is on." :
+                               "the peak limiter is not available yet on a handle at 44100 or 22050 Hz.";
+        return Status::kBadArgument;
+    }
     if (c.comfort && (c.channel_link || c.high_band || fr_rate_ || !c.comfort_amp || !c.band_profile)) {  // comfort noise: the same four, refused by the owner by name first
         *err = c.channel_link ? "comfort noise is not available yet while the channel link is on." :
                c.high_band   ? "comfort noise is not available yet while the high-band carry is on." :
@@ -2926,7 +3048,7 @@ Status Engine::process(const Call &c, std::string *err) {
     }
     // the plain handle -- but for a levelling call on host memory, which goes through the boundary below: one copy in, the device route and
     // the leveller's launches behind it, one copy out (not the sub-chunk pipeline nor the one-frame graph, which end in host memory)
-    if (rate_ == kRate16k && fmt_ == kFmtS16 && ch_ == 1 && !((c.level || c.comfort) && (c.host_contract || pointer_kind(c.pcm) != kPtrDevice))) return process_frames(c, err);  // (comfort noise: as the leveller)
+    if (rate_ == kRate16k && fmt_ == kFmtS16 && ch_ == 1 && !((c.level || c.limiter || c.comfort) && (c.host_contract || pointer_kind(c.pcm) != kPtrDevice))) return process_frames(c, err);  // (peak limiter, comfort noise: as the leveller)
     (void) hipSetDevice(device_);
     bool host, late = false;
     if (!call_on_host(c.pcm, c.out, c.report, &host, err)) return Status::kRuntime;
@@ -3195,6 +3317,10 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string
         *err = "the output leveller is not available yet while the channel link is on.";
         return Status::kBadArgument;
     }
+    if (c.limiter && c.channel_link) {  // (the owner refuses it by name first)
+        *err = "the peak limiter is not available yet while the channel link is on.";
+        return Status::kBadArgument;
+    }
     if (c.comfort && c.channel_link) {  // (the owner refuses it by name first)
         *err = "comfort noise is not available yet while the channel link is on.";
         return Status::kBadArgument;
@@ -3272,6 +3398,7 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string
         inner.band_profile = c.band_profile, inner.band_profile_rev = c.band_profile_rev;
         inner.channel_link = c.channel_link;  // (packet_check: a group's streams share k_b, so a sub-call holds a group as a whole)
         inner.level = c.level, inner.level_rev = c.level_rev;  // (the sub-calls' `hold` keeps a stalled stream's leveller where it is)
+        inner.limiter = c.limiter, inner.limiter_rev = c.limiter_rev;  // (... and its limiter's g)
         inner.comfort = c.comfort, inner.comfort_amp = c.comfort_amp, inner.comfort_rev = c.comfort_rev;  // (... and its comfort noise's counter)
         inner.report = c.report ? d_pk_rep_ + (size_t) B_ * c0 * 4 : nullptr;
         if (process_frames(inner, err) != Status::kOk) return Status::kRuntime;
@@ -3340,6 +3467,10 @@ FractionalStateArgs Engine::fractional_state_args() const {
 Status Engine::run_fractional(const PacketCall &c, std::string *err) {
     if (c.level) {  // (the owner refuses it by name first)
         *err = "the output leveller is not available yet on a handle at 44100 or 22050 Hz.";
+        return Status::kBadArgument;
+    }
+    if (c.limiter) {  // (the owner refuses it by name first)
+        *err = "the peak limiter is not available yet on a handle at 44100 or 22050 Hz.";
         return Status::kBadArgument;
     }
     if (c.comfort) {  // (the owner refuses it by name first)

@@ -92,6 +92,14 @@ struct Call {
     // nullptr: the plain call -- same launches, same bits, and the state does not move.
     const LevelSetting *level = nullptr;
     unsigned level_rev = 0;
+    // Peak limiter (thirteenth extension): host memory, LimiterSetting [num_streams], every field checked by the owner,
+    // which passes the table only while some stream's `on` is set.  One launch (kns_limit.hip) directly behind the 16 kHz call, in the
+    // place of the leveller's second one, applies the leveller's ramp and holds every limiting stream's samples under its ceiling; the
+    // state, one float per stream, is the engine's (limiter_state, reset, `resets`, `hold`).  Uploaded when `limiter_rev` differs from the
+    // one the engine's device table holds.  Everything else as `level`: device pointers below the host boundary, not combined with
+    // `channel_link`, `high_band` nor process_host_async.  nullptr: the call without it -- same launches, same bits, the state does not move.
+    const LimiterSetting *limiter = nullptr;
+    unsigned limiter_rev = 0;
     // Comfort noise (twelfth extension): host memory, ComfortSetting [num_streams] and the amplitude curves float
     // [num_streams][kComfortRow] in the order of comfort_index (kns_kernels.h), every value finite and >= 0, checked by the owner, which passes
     // the tables only while some stream's `on` is set -- and then `band_profile` and `min_gain` too (neutral, all zero where none is in force:
@@ -128,6 +136,8 @@ struct PacketCall {
     unsigned band_profile_rev = 0;
     const LevelSetting *level = nullptr;  // as Call's; not on a handle at 44 100 or 22 050 Hz
     unsigned level_rev = 0;
+    const LimiterSetting *limiter = nullptr;  // as Call's; not on a handle at 44 100 or 22 050 Hz
+    unsigned limiter_rev = 0;
     const ComfortSetting *comfort = nullptr;  // as Call's; not on a handle at 44 100 or 22 050 Hz
     const float *comfort_amp = nullptr;
     unsigned comfort_rev = 0;
@@ -178,6 +188,9 @@ public:
     // checked like a record list's (an index outside the handle, a slot twice: kBadArgument, nothing written); the values are the owner's
     // to check.  Stream records do not carry these eight bytes: a caller that moves a stream moves them through this pair.
     Status level_state(bool set, int count, const int32_t *streams, float *state, std::string *err);
+    // ---- peak limiter: g of the listed streams, HOST memory float [count]; everything else as level_state (a handle that never limited
+    // answers 1 at once and allocates nothing).  Stream records do not carry these four bytes.
+    Status limiter_state(bool set, int count, const int32_t *streams, float *state, std::string *err);
     // ---- comfort noise: the frame counters of the listed streams, HOST memory uint32 [count]; everything else as level_state (a handle that
     // never filled answers 0 at once and allocates nothing).  Stream records do not carry these four bytes.
     Status comfort_state(bool set, int count, const int32_t *streams, uint32_t *n, std::string *err);
@@ -492,6 +505,16 @@ private:
     bool level_ready(std::string *err);
     bool begin_level(const Call &c, std::string *err);
     bool run_level(const Call &c, const float *report, bool callers_report, std::string *err);
+    // Peak limiter (Call::limiter): the settings' device table [Bpad] with its upload ring and revision, and g of every stream [Bpad],
+    // allocated at 1 by the first call that limits or by limiter_state -- together with the leveller's buffers, whose control rows and
+    // gain pairs the limiter's launch reads -- and part of every reset.  run_level launches it in level_apply_kernel's place
+    LimiterSetting *d_lm_set_ = nullptr;
+    float *d_lm_state_ = nullptr;
+    UploadRing lm_ring_;
+    unsigned lm_rev_ = 0;
+    bool lm_valid_ = false;
+    bool limiter_ready(std::string *err);
+    bool begin_limiter(const Call &c, std::string *err);
     // Comfort noise (Call::comfort): the settings' device table [Bpad] and the amplitude table [Bpad][kComfortRow] with their upload rings and
     // one revision, as the profile's; the counters [Bpad], allocated at 0 by the first call that fills or by comfort_state and part of every
     // reset; a call's control bytes [B][Tmax + 1] with their ring (the leveller's layout); the counter values of a call's frames

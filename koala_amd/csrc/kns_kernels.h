@@ -539,6 +539,25 @@ struct LevelArgs {
 void launch_level(const LevelArgs &a, hipStream_t s);  // the tracker, then the ramp over the samples
 // the state of the streams with mask[b] != 0 (null: all) := fresh
 void launch_level_reset(float *state, const uint8_t *mask, int Bpad, hipStream_t s);
+// ---- peak limiter (kns_limit.hip; DESIGN.md section 2, thirteenth extension): a per-stream ceiling on the samples of the 16 kHz call with
+// instant attack and linear release, in the leveller's place -- ONE launch applies the leveller's ramp and the limiter, instead of
+// level_apply_kernel.  Per stream: a setting (configuration, the owner's) and one float of state, the gain g behind the last sample; fresh: 1.
+struct LimiterSetting {
+    int32_t on;
+    float ceiling, release;  // c in sample units, 1 <= c <= 32767; the gain recovered per sample, 0 < release <= 1
+};
+struct LimitArgs {
+    const LimiterSetting *set;  // [Bpad]
+    float *state;               // [Bpad]: g -- updated in place (streams that are off or held: untouched)
+    const uint8_t *ctl;         // [B][T + 1] or nullptr (all zero): the leveller's control rows
+    const float *gains;         // [B][T][2], the tracker's pairs of this call, or nullptr: no stream levels, every pair is (1, 1)
+    int16_t *out;               // [B][T 256]: the call's samples E, rewritten in place
+    int B, T;
+};
+void launch_level_track(const LevelArgs &a, hipStream_t s);  // the leveller's tracker alone: the pairs for launch_limit
+void launch_limit(const LimitArgs &a, hipStream_t s);        // the leveller's ramp and the limiter over the samples
+// g of the streams with mask[b] != 0 (null: all) := 1
+void launch_limit_reset(float *state, const uint8_t *mask, int Bpad, hipStream_t s);
 // last node of a captured one-frame replay: ++*counter (device memory), published to *host_word (page-locked host memory)
 void launch_frame_done(unsigned *counter, unsigned *host_word, hipStream_t s);
 

@@ -14,7 +14,8 @@
 // level_apply_kernel: out[256 t + n] = to_pcm(E[256 t + n] * fmaf(n / 256, g_t - g_{t-1}, g_{t-1})), in place.  32 lanes per frame, eight
 //   samples (one 16-byte word) per lane, eight frames per workgroup; rows that are not 16-byte aligned move sample by sample,
 //   lane-consecutive.  A frame whose two gains are both exactly 1 is not touched: off and held streams cost no memory traffic.
-// Saturation in to_pcm is the only limiter.  Precision-blind: int16 samples and the float report only.  Plain HIP C++, vector loads and
+// Saturation in to_pcm is all that bounds the product here; a stream that needs a ceiling below the rails, or a levelled one that must not
+// clip, turns the peak limiter on (kns_limit.hip), whose one launch then takes level_apply_kernel's place.  Precision-blind: int16 samples and the float report only.  Plain HIP C++, vector loads and
 // stores only.
 #include "kns_kernels.h"
 
@@ -100,6 +101,10 @@ void launch_level(const LevelArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(level_track_kernel, dim3((a.B + 255) / 256), dim3(256), 0, s, a);
     const int frames = a.B * a.T;
     hipLaunchKernelGGL(level_apply_kernel, dim3((frames + 7) / 8), dim3(256), 0, s, a.gains, a.out, frames, ((uintptr_t) a.out & 15) == 0 ? 1 : 0);
+}
+
+void launch_level_track(const LevelArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(level_track_kernel, dim3((a.B + 255) / 256), dim3(256), 0, s, a);
 }
 
 void launch_level_reset(float *state, const uint8_t *mask, int Bpad, hipStream_t s) {

@@ -163,6 +163,8 @@ pv_status_t advance(kns::Engine *engine, const MinGain &limit, kns::Call call, b
         call.level = limit.level.data();
         call.level_rev = limit.level_rev;
     }
+    if (kns_api::check_limiter(limit, engine, async) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
+    kns_api::carry_limiter(limit, &call);
     if (kns_api::check_comfort(limit, engine, async) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
     kns_api::carry_comfort(limit, &call);
     if (limit.high_band) {  // what the high-band carry does not take yet: refused here, before the engine is reached
@@ -224,6 +226,16 @@ pv_status_t check_level(const MinGain &limit, const kns::Engine *engine, bool as
                        engine->fractional_rate()   ? "on a handle whose sample rate is 44100 or 22050" : nullptr;
     if (!what) return PV_STATUS_SUCCESS;
     ::push_error(0x66, "The output leveller (pv_koala_batch_set_level: some stream's `on` is set) is not available yet %s.", what);
+    return PV_STATUS_INVALID_ARGUMENT;
+}
+pv_status_t check_limiter(const MinGain &limit, const kns::Engine *engine, bool async) {
+    if (!limit.limiter_any) return PV_STATUS_SUCCESS;
+    const char *what = limit.link                  ? "while the channel link is on (pv_koala_batch_set_channel_link): a group would need one gain" :
+                       limit.high_band             ? "while the high-band carry is on (pv_koala_batch_set_high_band): its band would need the same gain" :
+                       async                       ? "on the asynchronous entry points" :
+                       engine->fractional_rate()   ? "on a handle whose sample rate is 44100 or 22050" : nullptr;
+    if (!what) return PV_STATUS_SUCCESS;
+    ::push_error(0x66, "The peak limiter (pv_koala_batch_set_limiter: some stream's `on` is set) is not available yet %s.", what);
     return PV_STATUS_INVALID_ARGUMENT;
 }
 pv_status_t check_comfort(const MinGain &limit, const kns::Engine *engine, bool async) {

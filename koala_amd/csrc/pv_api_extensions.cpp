@@ -106,6 +106,8 @@ PV_API pv_status_t pv_koala_batch_process_packets(pv_koala_batch_t *object, cons
         c.level = object->limit.level.data();
         c.level_rev = object->limit.level_rev;
     }
+    if (kns_api::check_limiter(object->limit, object->engine, false) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
+    kns_api::carry_limiter(object->limit, &c);
     if (kns_api::check_comfort(object->limit, object->engine, false) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
     kns_api::carry_comfort(object->limit, &c);
     return kns_api::guarded([&] {

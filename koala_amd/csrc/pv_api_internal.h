@@ -1,5 +1,5 @@
 // pv_api_internal.h -- what the translation units of the C ABI share: the handles behind the opaque pointers, the calling thread's error
-// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_extensions.cpp (packet handles, sample formats, channels and their link) pv_level.cpp (the output leveller) and pv_comfort.cpp (comfort noise) use it.
+// stack and the exception barrier.  pv_api.cpp owns all of it; pv_api_extensions.cpp (packet handles, sample formats, channels and their link) pv_level.cpp (the output leveller), pv_limiter.cpp (the peak limiter) and pv_comfort.cpp (comfort noise) use it.
 // Nothing here leaves the library.
 #pragma once
 
@@ -39,6 +39,10 @@ struct MinGain {
     std::vector<kns::LevelSetting> level;
     unsigned level_rev = 0;
     bool level_any = false;
+    // Peak limiter (pv_koala_batch_set_limiter; pv_limiter.cpp): the same three for it (kns::Call::limiter).  Its STATE, g, is the engine's.
+    std::vector<kns::LimiterSetting> limiter;
+    unsigned limiter_rev = 0;
+    bool limiter_any = false;
     // Comfort noise (pv_koala_batch_set_comfort_noise; pv_comfort.cpp): every stream's setting [num_streams] and amplitude curve
     // [num_streams][kns::kComfortRow] in the order the engine's table has them (kns::comfort_index), empty until the first accepted change;
     // one revision counter for both; and whether any stream's comfort noise is on (none: the calls are the plain calls, no table at all).
@@ -71,6 +75,12 @@ pv_status_t check_band_profile(const MinGain &limit);
 // A call while some stream's leveller is on: what it is not combined with yet -- the channel link, the high-band carry, the asynchronous
 // entry points, a handle at 44 100 or 22 050 Hz (PV_STATUS_INVALID_ARGUMENT and a message), else SUCCESS
 pv_status_t check_level(const MinGain &limit, const kns::Engine *engine, bool async);
+// A call while some stream's limiter is on: the same four refusals, else SUCCESS; carry_limiter: what such a call takes to the engine
+pv_status_t check_limiter(const MinGain &limit, const kns::Engine *engine, bool async);
+template <class C>
+void carry_limiter(const MinGain &limit, C *call) {
+    if (limit.limiter_any) call->limiter = limit.limiter.data(), call->limiter_rev = limit.limiter_rev;
+}
 // A call while some stream's comfort noise is on: the same four refusals, else SUCCESS; carry_comfort: what such a call takes to the engine
 pv_status_t check_comfort(const MinGain &limit, const kns::Engine *engine, bool async);
 template <class C>

@@ -242,13 +242,18 @@ def set_comfort(handle, args):
 
 def set_level(handle, args):
     """--level [DBFS]: the output leveller (koala_amd.level.settings(target_dbfs=DBFS), -23 when no value is given): speech is brought
-    towards DBFS by a gain that adapts on speech frames only; saturation is the only limiter"""
-    if args.level is None:
-        return
-    if args.link or args.sample_rate in (44100, 22050):
-        raise ValueError('--level: not available with --link nor at 44100 / 22050 Hz yet (the library refuses the call)')
-    from koala_amd import level
-    handle.set_level(level.settings(target_dbfs=args.level))
+    towards DBFS by a gain that adapts on speech frames only.  --limiter DBFS: the peak limiter behind it
+    (koala_amd.limiter.settings(ceiling_dbfs=DBFS)): no inner sample above DBFS, instant attack, 50 ms linear release; without it
+    saturation alone bounds the levelled samples"""
+    for name, value in (('--level', args.level), ('--limiter', args.limiter)):
+        if value is not None and (args.link or args.sample_rate in (44100, 22050)):
+            raise ValueError('%s: not available with --link nor at 44100 / 22050 Hz yet (the library refuses the call)' % name)
+    if args.level is not None:
+        from koala_amd import level
+        handle.set_level(level.settings(target_dbfs=args.level))
+    if args.limiter is not None:
+        from koala_amd import limiter
+        handle.set_limiter(limiter.settings(ceiling_dbfs=args.limiter))
 
 
 def run_high_band(args):
@@ -261,7 +266,8 @@ def run_high_band(args):
     if rate not in (32000, 48000):
         raise ValueError('--high_band: --sample_rate must be 32000 or 48000 (lower rates have no band to carry; the others are not available yet)')
     for name, v in (('--meter', args.meter), ('--packet-ms', args.packet_ms), ('--sample_format', args.sample_format),
-                    ('--highpass', args.highpass is not None), ('--max_depth_db', args.max_depth_db is not None), ('--level', args.level is not None)):
+                    ('--highpass', args.highpass is not None), ('--max_depth_db', args.max_depth_db is not None), ('--level', args.level is not None),
+                    ('--limiter', args.limiter is not None)):
         if v:
             raise ValueError('%s: not available with --high_band' % name)
     if args.input_path is None or args.output_path is None:
@@ -306,6 +312,8 @@ def main(argv=None):
                     help='comfort noise: fill what the mask removes with white noise of DBFS dB RMS (for instance -60)')
     ap.add_argument('--level', type=float, nargs='?', const=-23.0, default=None, metavar='DBFS',
                     help='output leveller: bring speech towards DBFS (default -23) with a speech-gated automatic gain')
+    ap.add_argument('--limiter', type=float, default=None, metavar='DBFS',
+                    help='peak limiter: no sample of the 16 kHz output above DBFS (for instance -1), instant attack, linear release')
     ap.add_argument('--meter', type=int, default=0, metavar='N',
                     help='every N frames print input level (dBFS), suppression (dB) and mean mask gain, from the frame report')
     ap.add_argument('--packet-ms', dest='packet_ms', type=int, default=0, choices=[10, 20],

@@ -14,7 +14,8 @@ speech energy) and gain; fresh: lvl = 0, gain = 1.  For every frame t, with e_ou
     out[256 t + n] = to_pcm(E[256 t + n] * fma(n / 256, g_t - g_{t-1}, g_{t-1}))      n = 0 .. 255
 
 Every operation is one float32 operation, in this order; `fma32` is an exact float32 fused multiply-add; to_pcm rounds half away from zero
-and saturates -- saturation is the only limiter.  A reset makes the state fresh before its frame (the ramp then starts from 1), a held
+and saturates; a ceiling below the rails, and a gain that gives way before the product clips, is the peak limiter's
+(koala_amd.limiter), which takes this product before to_pcm.  A reset makes the state fresh before its frame (the ramp then starts from 1), a held
 stream keeps its state, a stream that is off delivers E and its state does not move.  Self-contained: numpy only.
 """
 import math
