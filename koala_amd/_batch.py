@@ -665,6 +665,35 @@ class KoalaBatch(object):
         fn.argtypes, fn.restype = args, PicovoiceStatuses
         return fn
 
+    # the leveller's, the limiter's and the comfort noise's entry points are one ctypes call each: a table of settings for a stream list,
+    # one setting back, the state of a stream list out and in
+
+    def _set_stage(self, name, struct, rule, setting, streams):
+        s, sp, n = self._stream_list(streams, None)
+        each = list(setting) if isinstance(setting, (list, tuple)) and not isinstance(setting, rule.Setting) else [setting] * n
+        if len(each) != n:
+            raise KoalaInvalidArgumentError("`setting` must be one setting or one per listed stream")
+        table = (struct * n)(*[struct.of(v) for v in each])
+        self._check(self._level_fn('set_' + name, [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, byref(table)), 'set_%s failed' % name)
+
+    def _get_stage(self, name, struct, stream):
+        out = struct(sizeof(struct))
+        self._check(self._level_fn('get_' + name, [c_void_p, c_int32, c_void_p])(self._handle, int(stream), byref(out)), name + ' failed')
+        return out.setting()
+
+    def _stage_state(self, name, shape, dtype, streams):
+        s, sp, n = self._stream_list(streams, None)
+        out = np.empty((n,) + shape, dtype)
+        self._check(self._level_fn('get_%s_state' % name, [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, out.ctypes.data), name + '_state failed')
+        return out
+
+    def _set_stage_state(self, name, shape, dtype, what, state, streams):
+        a = np.ascontiguousarray(state, dtype=dtype)
+        if a.shape[1:] != shape or a.ndim != 1 + len(shape) or a.shape[0] == 0:
+            raise KoalaInvalidArgumentError("expected %s of shape [n%s]" % (what, ''.join(', %d' % d for d in shape)))
+        s, sp, n = self._stream_list(streams, a.shape[0])
+        self._check(self._level_fn('set_%s_state' % name, [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, a.ctypes.data), 'set_%s_state failed' % name)
+
     def set_level(self, setting, streams=None) -> None:
         """The output leveller of the listed streams (None: every stream): `setting` is a koala_amd.level.Setting
         (koala_amd.level.settings(target_dbfs=-23, ...)), None for off, or a list with one of either per listed stream.  While a stream's
@@ -672,34 +701,20 @@ class KoalaBatch(object):
         frame; what keeps the product under a ceiling is the peak limiter (`set_limiter`), without it saturation alone.  Holds from the next call on; configuration, not state: resets, held streams and stream
         records neither change nor carry it.  A call is refused while some stream levels and the channel link or the high-band carry is
         on, on the asynchronous entry points and at 44100 / 22050 Hz."""
-        s, sp, n = self._stream_list(streams, None)
-        each = list(setting) if isinstance(setting, (list, tuple)) and not isinstance(setting, level_rule.Setting) else [setting] * n
-        if len(each) != n:
-            raise KoalaInvalidArgumentError("`setting` must be one setting or one per listed stream")
-        table = (LevelSetting * n)(*[LevelSetting.of(v) for v in each])
-        self._check(self._level_fn('set_level', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, byref(table)), 'set_level failed')
+        self._set_stage('level', LevelSetting, level_rule, setting, streams)
 
     def level(self, stream: int):
         """The koala_amd.level.Setting in force of one stream."""
-        out = LevelSetting(sizeof(LevelSetting))
-        self._check(self._level_fn('get_level', [c_void_p, c_int32, c_void_p])(self._handle, int(stream), byref(out)), 'level failed')
-        return out.setting()
+        return self._get_stage('level', LevelSetting, stream)
 
     def level_state(self, streams=None) -> np.ndarray:
         """The leveller's state of the listed streams (None: all), float32 [n, 2] = lvl (the tracked speech energy), gain, behind
         everything enqueued on the handle.  Stream records do not carry it: a caller that moves a stream moves these eight bytes too."""
-        s, sp, n = self._stream_list(streams, None)
-        out = np.empty((n, 2), np.float32)
-        self._check(self._level_fn('get_level_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, out.ctypes.data), 'level_state failed')
-        return out
+        return self._stage_state('level', (2,), np.float32, streams)
 
     def set_level_state(self, state, streams=None) -> None:
         """Continues the leveller of the listed streams (None: slots 0 .. n - 1) from `state`, float32 [n, 2] = lvl, gain; (0, 1) is fresh."""
-        a = np.ascontiguousarray(state, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] == 0:
-            raise KoalaInvalidArgumentError("expected float32 state of shape [n, 2]")
-        s, sp, n = self._stream_list(streams, a.shape[0])
-        self._check(self._level_fn('set_level_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, a.ctypes.data), 'set_level_state failed')
+        self._set_stage_state('level', (2,), np.float32, 'float32 state', state, streams)
 
     # ---- peak limiter (include/pv_koala_batch.h, PEAK LIMITER; koala_amd.limiter states the rule)
 
@@ -710,34 +725,20 @@ class KoalaBatch(object):
         behind the leveller's ramp and in front of its saturation.  Holds from the next call on; configuration, not state.  A call is
         refused while some stream limits and the channel link or the high-band carry is on, on the asynchronous entry points and at
         44100 / 22050 Hz."""
-        s, sp, n = self._stream_list(streams, None)
-        each = list(setting) if isinstance(setting, (list, tuple)) and not isinstance(setting, limiter_rule.Setting) else [setting] * n
-        if len(each) != n:
-            raise KoalaInvalidArgumentError("`setting` must be one setting or one per listed stream")
-        table = (LimiterSetting * n)(*[LimiterSetting.of(v) for v in each])
-        self._check(self._level_fn('set_limiter', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, byref(table)), 'set_limiter failed')
+        self._set_stage('limiter', LimiterSetting, limiter_rule, setting, streams)
 
     def limiter(self, stream: int):
         """The koala_amd.limiter.Setting in force of one stream."""
-        out = LimiterSetting(sizeof(LimiterSetting))
-        self._check(self._level_fn('get_limiter', [c_void_p, c_int32, c_void_p])(self._handle, int(stream), byref(out)), 'limiter failed')
-        return out.setting()
+        return self._get_stage('limiter', LimiterSetting, stream)
 
     def limiter_state(self, streams=None) -> np.ndarray:
         """The limiter's state of the listed streams (None: all), float32 [n] = g, the gain behind each stream's last sample, behind
         everything enqueued on the handle.  Stream records do not carry it: a caller that moves a stream moves these four bytes too."""
-        s, sp, n = self._stream_list(streams, None)
-        out = np.empty(n, np.float32)
-        self._check(self._level_fn('get_limiter_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, out.ctypes.data), 'limiter_state failed')
-        return out
+        return self._stage_state('limiter', (), np.float32, streams)
 
     def set_limiter_state(self, state, streams=None) -> None:
         """Continues the limiter of the listed streams (None: slots 0 .. n - 1) from `state`, float32 [n] = g in (0, 1]; 1 is fresh."""
-        a = np.ascontiguousarray(state, dtype=np.float32)
-        if a.ndim != 1 or a.shape[0] == 0:
-            raise KoalaInvalidArgumentError("expected float32 state of shape [n]")
-        s, sp, n = self._stream_list(streams, a.shape[0])
-        self._check(self._level_fn('set_limiter_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, a.ctypes.data), 'set_limiter_state failed')
+        self._set_stage_state('limiter', (), np.float32, 'float32 state', state, streams)
 
     # ---- comfort noise (include/pv_koala_batch.h, COMFORT NOISE; koala_amd.comfort states the rule)
 
@@ -782,18 +783,11 @@ class KoalaBatch(object):
     def comfort_state(self, streams=None) -> np.ndarray:
         """The frame counters of the listed streams (None: all), uint32 [n], behind everything enqueued on the handle.  Stream records do
         not carry them: a caller that moves a stream moves these four bytes too."""
-        s, sp, n = self._stream_list(streams, None)
-        out = np.empty(n, np.uint32)
-        self._check(self._level_fn('get_comfort_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, out.ctypes.data), 'comfort_state failed')
-        return out
+        return self._stage_state('comfort', (), np.uint32, streams)
 
     def set_comfort_state(self, state, streams=None) -> None:
         """Continues the comfort noise of the listed streams (None: slots 0 .. n - 1) from the counters `state`, uint32 [n]; 0 is fresh."""
-        a = np.ascontiguousarray(state, dtype=np.uint32)
-        if a.ndim != 1 or a.shape[0] == 0:
-            raise KoalaInvalidArgumentError("expected uint32 counters of shape [n]")
-        s, sp, n = self._stream_list(streams, a.shape[0])
-        self._check(self._level_fn('set_comfort_state', [c_void_p, c_int32, c_void_p, c_void_p])(self._handle, n, sp, a.ctypes.data), 'set_comfort_state failed')
+        self._set_stage_state('comfort', (), np.uint32, 'uint32 counters', state, streams)
 
     def reset(self, stream_mask: Optional[np.ndarray] = None) -> None:
         ptr = None

@@ -747,14 +747,8 @@ Engine::~Engine() {
     rs_ring_.release();
     rsf_ring_.release();
     recof_ring_.release();
-    mg_ring_.release();
-    pf_ring_.release();
-    lv_ring_.release();
-    lvc_ring_.release();
-    lm_ring_.release();
-    cf_ring_.release();
-    cfa_ring_.release();
-    cfc_ring_.release();
+    for (SettingTable *t : {&mg_tab_, &pf_tab_, &lv_tab_, &lm_tab_, &cf_tab_, &cfa_tab_}) t->ring.release();
+    ctl_ring_.release();
     pk_ring_.release();
     fr_ring_.release();
     for (int i = 0; i < 4; ++i)
@@ -1011,83 +1005,63 @@ bool Engine::begin_resets(int T, const uint8_t *mask, ResetTable *table, std::st
     return true;
 }
 
-// The attenuation limit of the call about to run (Call::min_gain, float [B] host memory), before anything of the call is enqueued and outside
-// any capture.  No limit: *table = nullptr and nothing else happens.  Otherwise *table = the device table [Bpad]; when the call's revision is
-// not the one the table holds, the gains go through a slot of mg_ring_ (rows past B: 0) to the device on the handle's stream, where every
-// kernel of the previous call is in front of the copy and every kernel of this one behind it.  The caller's vector has been read when this
-// returns; a device-pointer caller waits only when it is four changed tables ahead of the GPU.
-bool Engine::begin_min_gain(const Call &c, const float **table, std::string *err) {
-    *table = nullptr;
-    if (!c.min_gain) return true;
-    if (!d_min_gain_) {  // first use: the ring and the device table
-        const bool ok = mg_ring_.ready((size_t) Bpad_ * 4);
-        float *d = ok ? (float *) dalloc((size_t) Bpad_ * 4, true) : nullptr;
-        if (!d) {
-            (void) hipGetLastError();
-            *err = "Failed to allocate the buffers of the per-stream attenuation limit.";
-            return false;
-        }
-        d_min_gain_ = d;
+bool Engine::table_alloc(SettingTable *t, size_t row) {
+    if (t->d) return true;
+    t->row = row;
+    t->d = t->ring.ready((size_t) Bpad_ * row) ? dalloc((size_t) Bpad_ * row, false) : nullptr;
+    return t->d != nullptr;
+}
+
+// A per-stream setting of the call about to run (`rows`: host memory, B rows of `row` bytes), before anything of the call is enqueued and
+// outside any capture.  When the call's revision is not the one the device table holds, the rows go through a slot of the table's ring (rows
+// past B: zero) to the device on the handle's stream, where every kernel of the previous call is in front of the copy -- a call in flight
+// keeps the setting it was issued under -- and every kernel of this one behind it; an unchanged setting costs a call nothing.  The caller's
+// rows have been read when this returns; a device-pointer caller waits only when it is four changed tables ahead of the GPU.
+bool Engine::put_table(SettingTable *t, size_t row, const void *rows, unsigned rev, const char *what, std::string *err) {
+    if (!table_alloc(t, row)) {
+        (void) hipGetLastError();
+        *err = std::string("Failed to allocate the buffers of ") + what + ".";
+        return false;
     }
-    if (!mg_valid_ || mg_rev_ != c.min_gain_rev) {
-        const int k = mg_ring_.acquire();
-        if (k >= 0) {
-            float *slot = (float *) mg_ring_.host[k];
-            memcpy(slot, c.min_gain, (size_t) B_ * 4);
-            for (int b = B_; b < Bpad_; ++b) slot[b] = 0.0f;
-        }
-        if (k < 0 || hipMemcpyAsync(d_min_gain_, mg_ring_.host[k], (size_t) Bpad_ * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-            !mg_ring_.uploaded(k, stream_)) {
-            *err = hip_last_error();
-            mg_valid_ = false;
-            return false;
-        }
-        mg_rev_ = c.min_gain_rev;
-        mg_valid_ = true;
+    if (t->valid && t->rev == rev) return true;
+    const int k = t->ring.acquire();
+    if (k >= 0) {
+        memcpy(t->ring.host[k], rows, (size_t) B_ * row);
+        memset((char *) t->ring.host[k] + (size_t) B_ * row, 0, (size_t) (Bpad_ - B_) * row);
     }
-    *table = d_min_gain_;
+    if (k < 0 || hipMemcpyAsync(t->d, t->ring.host[k], (size_t) Bpad_ * row, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+        !t->ring.uploaded(k, stream_)) {
+        *err = hip_last_error();
+        t->valid = false;
+        return false;
+    }
+    t->rev = rev;
+    t->valid = true;
     return true;
 }
 
-// The band profile of the call about to run (Call::band_profile, float [B][kProfileRow] host memory in the table's own order), like the
-// limit above: nothing without one; otherwise the device table [Bpad][kProfileRow], uploaded through a slot of pf_ring_ (rows past B: zero)
-// on the handle's stream when the call's revision is not the table's -- 2 KiB per stream, so an unchanged profile costs a call nothing.  A
-// call in flight is in front of the copy on that stream: it keeps the profile it was issued under.
+// The attenuation limit of the call about to run (StreamOptions::min_gain, float [B]).  No limit: *table = nullptr and nothing else happens.
+// Otherwise *table = the device table [Bpad] (put_table).
+bool Engine::begin_min_gain(const Call &c, const float **table, std::string *err) {
+    *table = nullptr;
+    if (!c.opt.min_gain) return true;
+    if (!put_table(&mg_tab_, 4, c.opt.min_gain, c.opt.min_gain_rev, "the per-stream attenuation limit", err)) return false;
+    *table = (const float *) mg_tab_.d;
+    return true;
+}
+
+// The band profile of the call about to run (StreamOptions::band_profile, float [B][kProfileRow] in the table's own order), like the limit
+// above: nothing without one; otherwise the device table [Bpad][kProfileRow] -- 2 KiB per stream.
 bool Engine::begin_band_profile(const Call &c, const float **table, std::string *err) {
     *table = nullptr;
-    if (!c.band_profile) return true;
-    if (c.channel_link || c.high_band || !c.min_gain) {  // (the owner refuses these by name before the engine is reached)
-        *err = !c.min_gain ? "a call with a band profile carries the handle's minimum gains (all zero where no limit is in force)."
-                           : "a band profile is not combined with linked channels nor with the high-band carry.";
+    if (!c.opt.band_profile) return true;
+    if (c.opt.channel_link || c.high_band || !c.opt.min_gain) {  // (the owner refuses these by name before the engine is reached)
+        *err = !c.opt.min_gain ? "a call with a band profile carries the handle's minimum gains (all zero where no limit is in force)."
+                               : "a band profile is not combined with linked channels nor with the high-band carry.";
         return false;
     }
-    const size_t row = (size_t) kProfileRow * 4;
-    if (!d_profile_) {  // first use: the ring and the device table
-        const bool ok = pf_ring_.ready((size_t) Bpad_ * row);
-        float *d = ok ? (float *) dalloc((size_t) Bpad_ * row, true) : nullptr;
-        if (!d) {
-            (void) hipGetLastError();
-            *err = "Failed to allocate the buffers of the band profile.";
-            return false;
-        }
-        d_profile_ = d;
-    }
-    if (!pf_valid_ || pf_rev_ != c.band_profile_rev) {
-        const int k = pf_ring_.acquire();
-        if (k >= 0) {
-            memcpy(pf_ring_.host[k], c.band_profile, (size_t) B_ * row);
-            memset((char *) pf_ring_.host[k] + (size_t) B_ * row, 0, (size_t) (Bpad_ - B_) * row);
-        }
-        if (k < 0 || hipMemcpyAsync(d_profile_, pf_ring_.host[k], (size_t) Bpad_ * row, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-            !pf_ring_.uploaded(k, stream_)) {
-            *err = hip_last_error();
-            pf_valid_ = false;
-            return false;
-        }
-        pf_rev_ = c.band_profile_rev;
-        pf_valid_ = true;
-    }
-    *table = d_profile_;
+    if (!put_table(&pf_tab_, (size_t) kProfileRow * 4, c.opt.band_profile, c.opt.band_profile_rev, "the band profile", err)) return false;
+    *table = (const float *) pf_tab_.d;
     return true;
 }
 
@@ -1623,7 +1597,7 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
         sy.min_gain = slice.min_gain;
         sy.link = slice.link;
         sy.profile = slice.profile;
-        if (slice.comfort) sy.comfort_amp = d_cf_amp_, sy.comfort_set = d_cf_set_, sy.comfort_n = d_cf_n_ + t0c;  // (like `report`: rows T frames apart)
+        if (slice.comfort) sy.comfort_amp = (const float *) cfa_tab_.d, sy.comfort_set = (const ComfortSetting *) cf_tab_.d, sy.comfort_n = d_cf_n_ + t0c;  // (like `report`: rows T frames apart)
         sy.report = slice.d_report ? slice.d_report + (size_t) t0c * 4 : nullptr;  // (like `out`: the slice's first frame, rows T frames apart)
 #ifdef KNS_DEV
         last_synth_seg_ = sy.seg;
@@ -1913,6 +1887,30 @@ bool Engine::async_wait(int max_in_flight, std::string *err) {
     return true;
 }
 
+// The output stages behind the mask (leveller, limiter, comfort noise) and what a refusal calls them.  Every site that refuses a stage -- an
+// entry, a route or a handle the stage is not combined with yet -- walks this table, in the order the stages have always been checked.
+namespace {
+struct OutputStage {
+    const char *name, *call;             // "<name> is not ...", "<call> runs on ..."
+    bool (*on)(const StreamOptions &o);  // present on this call
+    bool carries_profile;                // its kernels carry the band profile's clamp: such a call comes with the profile (and its own tables)
+};
+const OutputStage kOutputStages[] = {
+    {"the output leveller", "a levelling call", [](const StreamOptions &o) { return o.level != nullptr; }, false},
+    {"the peak limiter", "a limiting call", [](const StreamOptions &o) { return o.limiter != nullptr; }, false},
+    {"comfort noise", "a call with comfort noise", [](const StreamOptions &o) { return o.comfort != nullptr; }, true},
+};
+// the first stage present on the call is refused for `why`
+bool refuse_stages(const StreamOptions &o, const char *why, std::string *err) {
+    for (const OutputStage &s : kOutputStages)
+        if (s.on(o)) {
+            *err = std::string(s.name) + why;
+            return true;
+        }
+    return false;
+}
+}  // namespace
+
 // One asynchronous host call = H2D on copy_in_, the kernels on the handle's stream, D2H on copy_out_, chained by events.  Up to
 // THREE calls are in flight: with two, a caller alternating between two buffer pairs cannot issue call n + 2 before call n's copy-out has
 // finished, which puts a slot's copy-in, kernels and copy-out in series (measured: 4.03 ms per 4096 x 64 frames = (2.8 + 2.6 + 2.8) / 2);
@@ -1921,19 +1919,8 @@ bool Engine::async_wait(int max_in_flight, std::string *err) {
 // once call n - 2's copy-out has -- both waited for on the device, by the stream that needs it.  A synchronous call of that size cannot
 // hide its first copy-in and last copy-out and has to cut its kernels into short, less efficient sub-chunks (process_host_pipelined).
 Status Engine::process_host_async(const Call &c, std::string *err) {
-    if (c.level) {
-        *err = "the output leveller is not available yet on the asynchronous entry points.";
-        return Status::kBadArgument;
-    }
-    if (c.limiter) {
-        *err = "the peak limiter is not available yet on the asynchronous entry points.";
-        return Status::kBadArgument;
-    }
-    if (c.comfort) {
-        *err = "comfort noise is not available yet on the asynchronous entry points.";
-        return Status::kBadArgument;
-    }
-    if (c.channel_link) {  // (its slices carry no link; the owner refuses the asynchronous calls on a handle with channels anyway)
+    if (refuse_stages(c.opt, " is not available yet on the asynchronous entry points.", err)) return Status::kBadArgument;
+    if (c.opt.channel_link) {  // (its slices carry no link; the owner refuses the asynchronous calls on a handle with channels anyway)
         *err = "linked channels are not available in asynchronous calls.";
         return Status::kBadArgument;
     }
@@ -2066,41 +2053,40 @@ bool Engine::run_call(const Call &c, std::string *err) {
     if (!begin_band_profile(c, &profile, err)) return false;
     // (linked channels: such a handle's calls arrive here with device pointers -- process() has split the channels into device rows -- so
     // the host routes below, the one-frame graph among them, never see a linked call: no graph is captured with the linked kernel)
-    const int link = c.channel_link ? ch_ : 0;
+    const int link = c.opt.channel_link ? ch_ : 0;
     if (link && (!min_gain || kin != kPtrDevice)) {  // (never quietly unlinked: the host routes below build their slices without the link)
         *err = !min_gain ? "a linked call carries the handle's minimum gains." : "a linked call runs on device rows only.";
         return false;
     }
-    // (output leveller: such a call arrives here with device pointers -- process() takes host memory through its staging -- so the host
-    // routes below never see it; never quietly unlevelled)
-    if (c.level && (kin != kPtrDevice || link || c.high_band)) {
-        *err = kin != kPtrDevice ? "a levelling call runs on device rows only." : "the output leveller is not combined with linked channels nor with the high-band carry.";
-        return false;
+    // (output stages: such a call arrives here with device pointers -- process() takes host memory through its staging -- so the host routes
+    // below never see it; never quietly without a stage.  Comfort noise: its kernels carry the gains and the profile's clamp)
+    bool stages = false;
+    for (const OutputStage &s : kOutputStages) {
+        if (!s.on(c.opt)) continue;
+        stages = true;
+        if (kin != kPtrDevice || (s.carries_profile && !profile) || link || c.high_band) {
+            *err = kin != kPtrDevice                 ? std::string(s.call) + " runs on device rows only." :
+                   s.carries_profile && !profile ? std::string(s.call) + " carries the handle's band profile (neutral where none is in force)." :
+                                                   std::string(s.name) + " is not combined with linked channels nor with the high-band carry.";
+            return false;
+        }
     }
-    if (c.level && !begin_level(c, err)) return false;
-    // (peak limiter: the same, and its launch stands in the place of the leveller's second one)
-    if (c.limiter && (kin != kPtrDevice || link || c.high_band)) {
-        *err = kin != kPtrDevice ? "a limiting call runs on device rows only." : "the peak limiter is not combined with linked channels nor with the high-band carry.";
+    // (their settings on the device; the limiter's launch stands in the place of the leveller's second one)
+    if (c.opt.level && !(level_ready(err) && put_table(&lv_tab_, sizeof(LevelSetting), c.opt.level, c.opt.level_rev, "the output leveller", err))) return false;
+    if (c.opt.limiter && !(limiter_ready(err) && put_table(&lm_tab_, sizeof(LimiterSetting), c.opt.limiter, c.opt.limiter_rev, "the peak limiter", err))) return false;
+    if (c.opt.comfort && !(comfort_ready(err) && put_table(&cf_tab_, sizeof(ComfortSetting), c.opt.comfort, c.opt.comfort_rev, "the comfort noise", err) &&
+                           put_table(&cfa_tab_, (size_t) kComfortRow * 4, c.opt.comfort_amp, c.opt.comfort_rev, "the comfort noise", err)))
         return false;
-    }
-    if (c.limiter && !begin_limiter(c, err)) return false;
-    // (comfort noise: the same -- device rows only, never quietly without the fill; its kernels carry the gains and the profile's clamp)
-    if (c.comfort && (kin != kPtrDevice || link || c.high_band || !profile)) {
-        *err = kin != kPtrDevice ? "a call with comfort noise runs on device rows only." :
-               !profile         ? "a call with comfort noise carries the handle's band profile (neutral where none is in force)." :
-                                  "comfort noise is not combined with linked channels nor with the high-band carry.";
-        return false;
-    }
-    if (c.comfort && !begin_comfort(c, err)) return false;
     if (kin == kPtrDevice) {
         const size_t n = (size_t) B_ * T * kFrame;
         const bool overlap = pcm < out + n && out < pcm + n;
         // (a levelling call reads its own report -- an output only, so asking for it into a buffer of the engine's changes no bit)
-        float *rep = c.level && !report ? d_lv_rep_ : report;
+        float *rep = c.opt.level && !report ? d_lv_rep_ : report;
+        const uint8_t *ctl = nullptr;  // (the stages' control rows, once for all of them)
         // (comfort noise: the counter's launch in front of the call's kernels)
-        return begin_resets(T, c.resets, &table, err) && (!c.comfort || run_comfort(c, err)) &&
-               run_device({0, T, pcm, out, !overlap, &table, min_gain, rep, link, profile, c.comfort != nullptr}, err) &&
-               ((!c.level && !c.limiter) || run_level(c, rep, report != nullptr, err));
+        return begin_resets(T, c.resets, &table, err) && (!stages || control_rows(c, &ctl, err)) && (!c.opt.comfort || run_comfort(c, ctl, err)) &&
+               run_device({0, T, pcm, out, !overlap, &table, min_gain, rep, link, profile, c.opt.comfort != nullptr}, err) &&
+               ((!c.opt.level && !c.opt.limiter) || run_level(c, rep, report != nullptr, ctl, err));
     }
     if (T > host_chunk_ && bytes >= host_pipeline_min_bytes_) {
         const char *pa = (const char *) pcm, *pb = (const char *) out;
@@ -2310,16 +2296,11 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
     if (c.high_band && !high_band_ready(c, err)) return false;
     {
         Call inner{T, d_in_, d_out_, c.resets};
-        inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
-        inner.channel_link = c.channel_link;
-        inner.band_profile = c.band_profile, inner.band_profile_rev = c.band_profile_rev;
+        inner.opt = c.opt;
         inner.report = c.report;
-        // (output leveller: it works on the inner 16 kHz samples, between the call and the out-stage; `hold` rides along for its tracker
+        // (output stages: they work on the inner 16 kHz samples, between the call and the out-stage; `hold` rides along for their state
         // alone -- process_frames has put the held streams' records aside around this whole call)
-        inner.level = c.level, inner.level_rev = c.level_rev;
-        inner.limiter = c.limiter, inner.limiter_rev = c.limiter_rev;  // (peak limiter: in the same place, `hold` for its g)
-        inner.comfort = c.comfort, inner.comfort_amp = c.comfort_amp, inner.comfort_rev = c.comfort_rev;  // (comfort noise: the same, for its counters)
-        if (c.level || c.limiter || c.comfort) inner.hold = c.hold;
+        if (c.opt.level || c.opt.limiter || c.opt.comfort) inner.hold = c.hold;
         // High-band carry: the kernel behind the out-stage reads the call's masks from its report -- an output only, so asking for it into a
         // buffer of the engine's changes no bit -- the in-stage's rows, which the device-pointer call leaves in d_in_ as they are, and the
         // call's input, of which a copy is kept where the out-stage writes over it.
@@ -2355,11 +2336,11 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
         if (c.high_band) {
             HighBandArgs h;
             h.x = hb_x, h.y = d_in_, h.out = c.out, h.report = inner.report;
-            h.min_gain = c.min_gain ? d_min_gain_ : nullptr;  // (begin_min_gain has put the call's table on the stream)
+            h.min_gain = c.opt.min_gain ? (const float *) mg_tab_.d : nullptr;  // (begin_min_gain has put the call's table on the stream)
             h.resets = flags;
             h.xs = d_hb_x_[hb_cur_], h.ys = d_hb_y_[hb_cur_], h.ss = d_hb_s_[hb_cur_];
             h.xs_next = d_hb_x_[hb_cur_ ^ 1], h.ys_next = d_hb_y_[hb_cur_ ^ 1], h.ss_next = d_hb_s_[hb_cur_ ^ 1];
-            h.B = B_, h.T = T, h.R = so.U, h.link = c.channel_link ? ch_ : 0;
+            h.B = B_, h.T = T, h.R = so.U, h.link = c.opt.channel_link ? ch_ : 0;
             memcpy(h.taps, rs_taps_[1].data(), sizeof(h.taps));
             launch_high_band(h, stream_);
             if (hipGetLastError() != hipSuccess) goto fail;
@@ -2374,17 +2355,83 @@ fail:
 
 // ------------------------------------------------------------------------------------------------ output leveller
 
-// Output leveller (Call::level): every buffer of the feature at first use -- by a call that levels or by level_state -- all or nothing; the
-// state begins fresh, cleared on the handle's stream.
+// The control rows' buffer and ring, at the first use of an output stage.
+bool Engine::ctl_ready() {
+    if (!d_ctl_) d_ctl_ = ctl_ring_.ready((size_t) B_ * (Tmax_ + 1)) ? (uint8_t *) dalloc((size_t) B_ * (Tmax_ + 1), false) : nullptr;
+    return d_ctl_ != nullptr;
+}
+
+// The call's `hold` and reset flags as one row of T + 1 bytes per stream (run_call: in front of the call's first launch), only when one of
+// them is set: the comfort counter's launch, the leveller's tracker and the limiter's launch read the same rows.
+bool Engine::control_rows(const Call &c, const uint8_t **ctl, std::string *err) {
+    const int T = c.T;
+    bool any = false;
+    for (int b = 0; c.hold && b < B_ && !any; ++b) any = c.hold[b] != 0;
+    for (size_t i = 0; c.resets && i < (size_t) B_ * T && !any; ++i) any = c.resets[i] != 0;
+    *ctl = nullptr;
+    if (!any) return true;
+    const int k = ctl_ring_.acquire();
+    if (k >= 0) {
+        uint8_t *rows = (uint8_t *) ctl_ring_.host[k];
+        for (int b = 0; b < B_; ++b) {
+            uint8_t *row = rows + (size_t) b * (T + 1);
+            row[0] = c.hold && c.hold[b] ? 1 : 0;
+            for (int t = 0; t < T; ++t) row[1 + t] = c.resets && c.resets[(size_t) b * T + t] ? 1 : 0;
+        }
+    }
+    if (k < 0 || hipMemcpyAsync(d_ctl_, ctl_ring_.host[k], (size_t) B_ * (T + 1), hipMemcpyHostToDevice, stream_) != hipSuccess ||
+        !ctl_ring_.uploaded(k, stream_)) {
+        *err = hip_last_error();
+        return false;
+    }
+    *ctl = d_ctl_;
+    return true;
+}
+
+// The state of an output stage, N values of type T per stream (level_state, limiter_state, comfort_state): on the handle's current stream
+// behind everything enqueued.  A handle that never used the stage answers `fresh` at once and allocates nothing to say so.
+template <class T, int N>
+Status Engine::stage_state(bool set, int count, const int32_t *streams, T *state, const T (&fresh)[N], T *Engine::*dev, bool (Engine::*ready)(std::string *),
+                           std::string *err) {
+    const Status listed = check_stream_list(count, streams, nullptr, err);
+    if (listed != Status::kOk) return listed;
+    if (!set && !(this->*dev)) {
+        for (int i = 0; i < count; ++i) memcpy(state + (size_t) i * N, fresh, sizeof(fresh));
+        return Status::kOk;
+    }
+    (void) hipSetDevice(device_);
+    if (async_n_ && !drain_async(err)) return Status::kRuntime;
+    if (!(this->*ready)(err)) return Status::kRuntime;
+    std::vector<T> all((size_t) B_ * N);
+    hipError_t e = hipMemcpyAsync(all.data(), this->*dev, all.size() * sizeof(T), hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    for (int i = 0; e == hipSuccess && i < count; ++i) {
+        T *mine = &all[(size_t) (streams ? streams[i] : i) * N], *theirs = state + (size_t) i * N;
+        memcpy(set ? mine : theirs, set ? theirs : mine, sizeof(fresh));
+    }
+    if (e == hipSuccess && set) {
+        e = hipMemcpyAsync(this->*dev, all.data(), all.size() * sizeof(T), hipMemcpyHostToDevice, stream_);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_);  // (`all` goes out of scope)
+    }
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        *err = hip_error(e);
+        return Status::kRuntime;
+    }
+    return Status::kOk;
+}
+
+// ------------------------------------------------------------------------------------------------ output leveller
+
+// Output leveller (StreamOptions::level): every buffer of the feature at first use -- by a call that levels or by level_state -- all or
+// nothing; the state begins fresh, cleared on the handle's stream.
 bool Engine::level_ready(std::string *err) {
     if (d_lv_state_) return true;
     (void) hipSetDevice(device_);
-    const bool rings = lv_ring_.ready((size_t) Bpad_ * sizeof(LevelSetting)) && lvc_ring_.ready((size_t) B_ * (Tmax_ + 1));
-    if (rings && !d_lv_set_) d_lv_set_ = (LevelSetting *) dalloc((size_t) Bpad_ * sizeof(LevelSetting), true);
-    if (rings && !d_lv_gains_) d_lv_gains_ = (float *) dalloc((size_t) B_ * Tmax_ * 8, false);
-    if (rings && !d_lv_rep_) d_lv_rep_ = (float *) dalloc((size_t) B_ * Tmax_ * 16, false);
-    if (rings && !d_lv_ctl_) d_lv_ctl_ = (uint8_t *) dalloc((size_t) B_ * (Tmax_ + 1), false);
-    float *state = rings && d_lv_set_ && d_lv_gains_ && d_lv_rep_ && d_lv_ctl_ ? (float *) dalloc((size_t) Bpad_ * 8, false) : nullptr;
+    const bool tables = table_alloc(&lv_tab_, sizeof(LevelSetting)) && ctl_ready();
+    if (tables && !d_lv_gains_) d_lv_gains_ = (float *) dalloc((size_t) B_ * Tmax_ * 8, false);
+    if (tables && !d_lv_rep_) d_lv_rep_ = (float *) dalloc((size_t) B_ * Tmax_ * 16, false);
+    float *state = tables && d_lv_gains_ && d_lv_rep_ ? (float *) dalloc((size_t) Bpad_ * 8, false) : nullptr;
     if (!state) {
         (void) hipGetLastError();
         *err = "Failed to allocate the buffers of the output leveller.";
@@ -2400,66 +2447,24 @@ bool Engine::level_ready(std::string *err) {
     return true;
 }
 
-// The settings of the call about to run, like the limit's table: through a slot of lv_ring_ (rows past B: off) to the device on the handle's
-// stream when the call's revision is not the table's.
-bool Engine::begin_level(const Call &c, std::string *err) {
-    if (!level_ready(err)) return false;
-    if (lv_valid_ && lv_rev_ == c.level_rev) return true;
-    const int k = lv_ring_.acquire();
-    if (k >= 0) {
-        memcpy(lv_ring_.host[k], c.level, (size_t) B_ * sizeof(LevelSetting));
-        memset((char *) lv_ring_.host[k] + (size_t) B_ * sizeof(LevelSetting), 0, (size_t) (Bpad_ - B_) * sizeof(LevelSetting));
-    }
-    if (k < 0 || hipMemcpyAsync(d_lv_set_, lv_ring_.host[k], (size_t) Bpad_ * sizeof(LevelSetting), hipMemcpyHostToDevice, stream_) != hipSuccess ||
-        !lv_ring_.uploaded(k, stream_)) {
-        *err = hip_last_error();
-        lv_valid_ = false;
-        return false;
-    }
-    lv_rev_ = c.level_rev;
-    lv_valid_ = true;
-    return true;
-}
-
-// The leveller's two launches behind the kernels of a device-pointer call (run_call): the call's `hold` and reset flags go to the device as
-// one row of T + 1 bytes per stream, only when one of them is set; `report` is what the call's synthesis kernels have written -- the
-// caller's (then column 3 of a levelling stream's rows becomes its gain) or the engine's.  A call on which some stream limits
-// (Call::limiter) runs the tracker only if some stream levels, and then the limiter's launch, which applies the ramp too, in the place of
-// level_apply_kernel.
-bool Engine::run_level(const Call &c, const float *report, bool callers_report, std::string *err) {
-    const int T = c.T;
-    bool any = false;
-    for (int b = 0; c.hold && b < B_ && !any; ++b) any = c.hold[b] != 0;
-    for (size_t i = 0; c.resets && i < (size_t) B_ * T && !any; ++i) any = c.resets[i] != 0;
-    if (any) {
-        const int k = lvc_ring_.acquire();
-        if (k >= 0) {
-            uint8_t *ctl = (uint8_t *) lvc_ring_.host[k];
-            for (int b = 0; b < B_; ++b) {
-                uint8_t *row = ctl + (size_t) b * (T + 1);
-                row[0] = c.hold && c.hold[b] ? 1 : 0;
-                for (int t = 0; t < T; ++t) row[1 + t] = c.resets && c.resets[(size_t) b * T + t] ? 1 : 0;
-            }
-        }
-        if (k < 0 || hipMemcpyAsync(d_lv_ctl_, lvc_ring_.host[k], (size_t) B_ * (T + 1), hipMemcpyHostToDevice, stream_) != hipSuccess ||
-            !lvc_ring_.uploaded(k, stream_)) {
-            *err = hip_last_error();
-            return false;
-        }
-    }
+// The leveller's two launches behind the kernels of a device-pointer call (run_call); `ctl`: the call's control rows (control_rows);
+// `report` is what the call's synthesis kernels have written -- the caller's (then column 3 of a levelling stream's rows becomes its gain)
+// or the engine's.  A call on which some stream limits (StreamOptions::limiter) runs the tracker only if some stream levels, and then the
+// limiter's launch, which applies the ramp too, in the place of level_apply_kernel.
+bool Engine::run_level(const Call &c, const float *report, bool callers_report, const uint8_t *ctl, std::string *err) {
     LevelArgs a;
-    a.set = d_lv_set_, a.state = d_lv_state_, a.ctl = any ? d_lv_ctl_ : nullptr;
+    a.set = (const LevelSetting *) lv_tab_.d, a.state = d_lv_state_, a.ctl = ctl;
     a.report = report, a.report_out = callers_report ? (float *) report : nullptr;
     a.gains = d_lv_gains_, a.out = c.out;
-    a.B = B_, a.T = T;
-    if (!c.limiter) {
+    a.B = B_, a.T = c.T;
+    if (!c.opt.limiter) {
         launch_level(a, stream_);
     } else {
-        if (c.level) launch_level_track(a, stream_);
+        if (c.opt.level) launch_level_track(a, stream_);
         LimitArgs m;
-        m.set = d_lm_set_, m.state = d_lm_state_, m.ctl = a.ctl;
-        m.gains = c.level ? d_lv_gains_ : nullptr, m.out = c.out;
-        m.B = B_, m.T = T;
+        m.set = (const LimiterSetting *) lm_tab_.d, m.state = d_lm_state_, m.ctl = ctl;
+        m.gains = c.opt.level ? d_lv_gains_ : nullptr, m.out = c.out;
+        m.B = B_, m.T = c.T;
         launch_limit(m, stream_);
     }
     const hipError_t e = hipGetLastError();
@@ -2471,61 +2476,19 @@ bool Engine::run_level(const Call &c, const float *report, bool callers_report, 
 }
 
 Status Engine::level_state(bool set, int count, const int32_t *streams, float *state, std::string *err) {
-    if (count < 1 || count > B_) {
-        *err = "`count` " + std::to_string(count) + " is outside [1, " + std::to_string(B_) + "].";
-        return Status::kBadArgument;
-    }
-    std::vector<uint8_t> listed((size_t) B_, 0);
-    for (int i = 0; i < count; ++i) {
-        const int b = streams ? streams[i] : i;
-        if (b < 0 || b >= B_) {
-            *err = "`streams[" + std::to_string(i) + "]` = " + std::to_string(b) + " is outside [0, " + std::to_string(B_) + ").";
-            return Status::kBadArgument;
-        }
-        if (listed[b]) {
-            *err = "`streams[" + std::to_string(i) + "]`: slot " + std::to_string(b) + " is listed twice.";
-            return Status::kBadArgument;
-        }
-        listed[b] = 1;
-    }
-    if (!set && !d_lv_state_) {  // a handle that never levelled: every stream is fresh, and nothing is allocated to say so
-        for (int i = 0; i < count; ++i) state[2 * i] = 0.0f, state[2 * i + 1] = 1.0f;
-        return Status::kOk;
-    }
-    (void) hipSetDevice(device_);
-    if (async_n_ && !drain_async(err)) return Status::kRuntime;
-    if (!level_ready(err)) return Status::kRuntime;
-    std::vector<float> all((size_t) B_ * 2);
-    hipError_t e = hipMemcpyAsync(all.data(), d_lv_state_, all.size() * 4, hipMemcpyDeviceToHost, stream_);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-    for (int i = 0; e == hipSuccess && i < count; ++i) {
-        const int b = streams ? streams[i] : i;
-        float *mine = &all[(size_t) b * 2], *theirs = state + (size_t) i * 2;
-        memcpy(set ? mine : theirs, set ? theirs : mine, 8);
-    }
-    if (e == hipSuccess && set) {
-        e = hipMemcpyAsync(d_lv_state_, all.data(), all.size() * 4, hipMemcpyHostToDevice, stream_);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream_);  // (`all` goes out of scope)
-    }
-    if (e != hipSuccess) {
-        (void) hipGetLastError();
-        *err = hip_error(e);
-        return Status::kRuntime;
-    }
-    return Status::kOk;
+    static const float fresh[2] = {0.0f, 1.0f};  // lvl, gain
+    return stage_state(set, count, streams, state, fresh, &Engine::d_lv_state_, &Engine::level_ready, err);
 }
 
 // ------------------------------------------------------------------------------------------------ peak limiter
 
-// Peak limiter (Call::limiter): every buffer of the feature at first use -- by a call that limits or by limiter_state -- all or nothing, the
-// leveller's among them (the limiter's launch reads its control rows and gain pairs); g begins at 1, set on the handle's stream.
+// Peak limiter (StreamOptions::limiter): every buffer of the feature at first use -- by a call that limits or by limiter_state -- all or
+// nothing, the leveller's among them (the limiter's launch reads its gain pairs); g begins at 1, set on the handle's stream.
 bool Engine::limiter_ready(std::string *err) {
     if (d_lm_state_) return true;
     if (!level_ready(err)) return false;
     (void) hipSetDevice(device_);
-    const bool ring = lm_ring_.ready((size_t) Bpad_ * sizeof(LimiterSetting));
-    if (ring && !d_lm_set_) d_lm_set_ = (LimiterSetting *) dalloc((size_t) Bpad_ * sizeof(LimiterSetting), true);
-    float *state = ring && d_lm_set_ ? (float *) dalloc((size_t) Bpad_ * 4, false) : nullptr;
+    float *state = table_alloc(&lm_tab_, sizeof(LimiterSetting)) ? (float *) dalloc((size_t) Bpad_ * 4, false) : nullptr;
     if (!state) {
         (void) hipGetLastError();
         *err = "Failed to allocate the buffers of the peak limiter.";
@@ -2541,89 +2504,22 @@ bool Engine::limiter_ready(std::string *err) {
     return true;
 }
 
-// The settings of the call about to run, like the leveller's: through a slot of lm_ring_ (rows past B: off) to the device on the handle's
-// stream when the call's revision is not the table's.
-bool Engine::begin_limiter(const Call &c, std::string *err) {
-    if (!limiter_ready(err)) return false;
-    if (lm_valid_ && lm_rev_ == c.limiter_rev) return true;
-    const int k = lm_ring_.acquire();
-    if (k >= 0) {
-        memcpy(lm_ring_.host[k], c.limiter, (size_t) B_ * sizeof(LimiterSetting));
-        memset((char *) lm_ring_.host[k] + (size_t) B_ * sizeof(LimiterSetting), 0, (size_t) (Bpad_ - B_) * sizeof(LimiterSetting));
-    }
-    if (k < 0 || hipMemcpyAsync(d_lm_set_, lm_ring_.host[k], (size_t) Bpad_ * sizeof(LimiterSetting), hipMemcpyHostToDevice, stream_) != hipSuccess ||
-        !lm_ring_.uploaded(k, stream_)) {
-        *err = hip_last_error();
-        lm_valid_ = false;
-        return false;
-    }
-    lm_rev_ = c.limiter_rev;
-    lm_valid_ = true;
-    return true;
-}
-
 Status Engine::limiter_state(bool set, int count, const int32_t *streams, float *state, std::string *err) {
-    if (count < 1 || count > B_) {
-        *err = "`count` " + std::to_string(count) + " is outside [1, " + std::to_string(B_) + "].";
-        return Status::kBadArgument;
-    }
-    std::vector<uint8_t> listed((size_t) B_, 0);
-    for (int i = 0; i < count; ++i) {
-        const int b = streams ? streams[i] : i;
-        if (b < 0 || b >= B_) {
-            *err = "`streams[" + std::to_string(i) + "]` = " + std::to_string(b) + " is outside [0, " + std::to_string(B_) + ").";
-            return Status::kBadArgument;
-        }
-        if (listed[b]) {
-            *err = "`streams[" + std::to_string(i) + "]`: slot " + std::to_string(b) + " is listed twice.";
-            return Status::kBadArgument;
-        }
-        listed[b] = 1;
-    }
-    if (!set && !d_lm_state_) {  // a handle that never limited: every stream is fresh, and nothing is allocated to say so
-        for (int i = 0; i < count; ++i) state[i] = 1.0f;
-        return Status::kOk;
-    }
-    (void) hipSetDevice(device_);
-    if (async_n_ && !drain_async(err)) return Status::kRuntime;
-    if (!limiter_ready(err)) return Status::kRuntime;
-    std::vector<float> all((size_t) B_);
-    hipError_t e = hipMemcpyAsync(all.data(), d_lm_state_, all.size() * 4, hipMemcpyDeviceToHost, stream_);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-    for (int i = 0; e == hipSuccess && i < count; ++i) {
-        const int b = streams ? streams[i] : i;
-        if (set) all[(size_t) b] = state[i];
-        else state[i] = all[(size_t) b];
-    }
-    if (e == hipSuccess && set) {
-        e = hipMemcpyAsync(d_lm_state_, all.data(), all.size() * 4, hipMemcpyHostToDevice, stream_);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream_);  // (`all` goes out of scope)
-    }
-    if (e != hipSuccess) {
-        (void) hipGetLastError();
-        *err = hip_error(e);
-        return Status::kRuntime;
-    }
-    return Status::kOk;
+    static const float fresh[1] = {1.0f};  // g
+    return stage_state(set, count, streams, state, fresh, &Engine::d_lm_state_, &Engine::limiter_ready, err);
 }
 
 // ------------------------------------------------------------------------------------------------ comfort noise
 
-// Comfort noise (Call::comfort): every buffer of the feature at first use -- by a call with some stream's comfort noise on or by
-// comfort_state -- all or nothing; the counters begin at 0, cleared on the handle's stream.
+// Comfort noise (StreamOptions::comfort): every buffer of the feature at first use -- by a call with some stream's comfort noise on or by
+// comfort_state -- all or nothing; the counters begin at 0, cleared on the handle's stream.  (d_cf_n_ is not zeroed: comfort_count_kernel
+// writes every row of a call's counter values on the call's stream in front of the kernels that read them.)
 bool Engine::comfort_ready(std::string *err) {
     if (d_cf_state_) return true;
     (void) hipSetDevice(device_);
-    const bool rings = cf_ring_.ready((size_t) Bpad_ * sizeof(ComfortSetting)) && cfa_ring_.ready((size_t) Bpad_ * kComfortRow * 4) &&
-                       cfc_ring_.ready((size_t) B_ * (Tmax_ + 1));
-    // (not zeroed: begin_comfort uploads every row of the two tables and comfort_count_kernel writes every row of a call's counter values,
-    // all on the call's stream in front of the kernels that read them -- a memset on the handle's own stream would be unordered with
-    // those after set_stream)
-    if (rings && !d_cf_set_) d_cf_set_ = (ComfortSetting *) dalloc((size_t) Bpad_ * sizeof(ComfortSetting), false);
-    if (rings && !d_cf_amp_) d_cf_amp_ = (float *) dalloc((size_t) Bpad_ * kComfortRow * 4, false);
-    if (rings && !d_cf_n_) d_cf_n_ = (uint32_t *) dalloc((size_t) Bpad_ * Tmax_ * 4, false);
-    if (rings && !d_cf_ctl_) d_cf_ctl_ = (uint8_t *) dalloc((size_t) B_ * (Tmax_ + 1), false);
-    uint32_t *state = rings && d_cf_set_ && d_cf_amp_ && d_cf_n_ && d_cf_ctl_ ? (uint32_t *) dalloc((size_t) Bpad_ * 4, false) : nullptr;
+    const bool tables = table_alloc(&cf_tab_, sizeof(ComfortSetting)) && table_alloc(&cfa_tab_, (size_t) kComfortRow * 4) && ctl_ready();
+    if (tables && !d_cf_n_) d_cf_n_ = (uint32_t *) dalloc((size_t) Bpad_ * Tmax_ * 4, false);
+    uint32_t *state = tables && d_cf_n_ ? (uint32_t *) dalloc((size_t) Bpad_ * 4, false) : nullptr;
     if (!state) {
         (void) hipGetLastError();
         *err = "Failed to allocate the buffers of the comfort noise.";
@@ -2639,57 +2535,11 @@ bool Engine::comfort_ready(std::string *err) {
     return true;
 }
 
-// The settings and the amplitude table of the call about to run, like the band profile's: through ring slots (rows past B: off, zero) to
-// the device on the handle's stream when the call's revision is not the tables' -- 1 KiB per stream, so an unchanged setting costs nothing.
-bool Engine::begin_comfort(const Call &c, std::string *err) {
-    if (!comfort_ready(err)) return false;
-    if (cf_valid_ && cf_rev_ == c.comfort_rev) return true;
-    const size_t sb = sizeof(ComfortSetting), ab = (size_t) kComfortRow * 4;
-    const int k = cf_ring_.acquire(), ka = k >= 0 ? cfa_ring_.acquire() : -1;
-    if (ka >= 0) {
-        memcpy(cf_ring_.host[k], c.comfort, (size_t) B_ * sb);
-        memset((char *) cf_ring_.host[k] + (size_t) B_ * sb, 0, (size_t) (Bpad_ - B_) * sb);
-        memcpy(cfa_ring_.host[ka], c.comfort_amp, (size_t) B_ * ab);
-        memset((char *) cfa_ring_.host[ka] + (size_t) B_ * ab, 0, (size_t) (Bpad_ - B_) * ab);
-    }
-    if (ka < 0 || hipMemcpyAsync(d_cf_set_, cf_ring_.host[k], (size_t) Bpad_ * sb, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-        !cf_ring_.uploaded(k, stream_) || hipMemcpyAsync(d_cf_amp_, cfa_ring_.host[ka], (size_t) Bpad_ * ab, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-        !cfa_ring_.uploaded(ka, stream_)) {
-        *err = hip_last_error();
-        cf_valid_ = false;
-        return false;
-    }
-    cf_rev_ = c.comfort_rev;
-    cf_valid_ = true;
-    return true;
-}
-
-// The counter's launch in front of the kernels of a device-pointer call (run_call): the call's `hold` and reset flags go to the device as
-// one row of T + 1 bytes per stream, only when one of them is set -- the leveller's layout.
-bool Engine::run_comfort(const Call &c, std::string *err) {
-    const int T = c.T;
-    bool any = false;
-    for (int b = 0; c.hold && b < B_ && !any; ++b) any = c.hold[b] != 0;
-    for (size_t i = 0; c.resets && i < (size_t) B_ * T && !any; ++i) any = c.resets[i] != 0;
-    if (any) {
-        const int k = cfc_ring_.acquire();
-        if (k >= 0) {
-            uint8_t *ctl = (uint8_t *) cfc_ring_.host[k];
-            for (int b = 0; b < B_; ++b) {
-                uint8_t *row = ctl + (size_t) b * (T + 1);
-                row[0] = c.hold && c.hold[b] ? 1 : 0;
-                for (int t = 0; t < T; ++t) row[1 + t] = c.resets && c.resets[(size_t) b * T + t] ? 1 : 0;
-            }
-        }
-        if (k < 0 || hipMemcpyAsync(d_cf_ctl_, cfc_ring_.host[k], (size_t) B_ * (T + 1), hipMemcpyHostToDevice, stream_) != hipSuccess ||
-            !cfc_ring_.uploaded(k, stream_)) {
-            *err = hip_last_error();
-            return false;
-        }
-    }
+// The counter's launch in front of the kernels of a device-pointer call (run_call); `ctl`: the call's control rows (control_rows).
+bool Engine::run_comfort(const Call &c, const uint8_t *ctl, std::string *err) {
     ComfortArgs a;
-    a.set = d_cf_set_, a.state = d_cf_state_, a.ctl = any ? d_cf_ctl_ : nullptr, a.n = d_cf_n_;
-    a.B = B_, a.Bpad = Bpad_, a.T = T;
+    a.set = (const ComfortSetting *) cf_tab_.d, a.state = d_cf_state_, a.ctl = ctl, a.n = d_cf_n_;
+    a.B = B_, a.Bpad = Bpad_, a.T = c.T;
     launch_comfort(a, stream_);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -2700,50 +2550,8 @@ bool Engine::run_comfort(const Call &c, std::string *err) {
 }
 
 Status Engine::comfort_state(bool set, int count, const int32_t *streams, uint32_t *n, std::string *err) {
-    if (count < 1 || count > B_) {
-        *err = "`count` " + std::to_string(count) + " is outside [1, " + std::to_string(B_) + "].";
-        return Status::kBadArgument;
-    }
-    std::vector<uint8_t> listed((size_t) B_, 0);
-    for (int i = 0; i < count; ++i) {
-        const int b = streams ? streams[i] : i;
-        if (b < 0 || b >= B_) {
-            *err = "`streams[" + std::to_string(i) + "]` = " + std::to_string(b) + " is outside [0, " + std::to_string(B_) + ").";
-            return Status::kBadArgument;
-        }
-        if (listed[b]) {
-            *err = "`streams[" + std::to_string(i) + "]`: slot " + std::to_string(b) + " is listed twice.";
-            return Status::kBadArgument;
-        }
-        listed[b] = 1;
-    }
-    if (!set && !d_cf_state_) {  // a handle that never filled: every counter is 0, and nothing is allocated to say so
-        for (int i = 0; i < count; ++i) n[i] = 0u;
-        return Status::kOk;
-    }
-    (void) hipSetDevice(device_);
-    if (async_n_ && !drain_async(err)) return Status::kRuntime;
-    if (!comfort_ready(err)) return Status::kRuntime;
-    std::vector<uint32_t> all((size_t) B_);
-    hipError_t e = hipMemcpyAsync(all.data(), d_cf_state_, all.size() * 4, hipMemcpyDeviceToHost, stream_);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-    for (int i = 0; e == hipSuccess && i < count; ++i) {
-        const int b = streams ? streams[i] : i;
-        if (set)
-            all[(size_t) b] = n[i];
-        else
-            n[i] = all[(size_t) b];
-    }
-    if (e == hipSuccess && set) {
-        e = hipMemcpyAsync(d_cf_state_, all.data(), all.size() * 4, hipMemcpyHostToDevice, stream_);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream_);  // (`all` goes out of scope)
-    }
-    if (e != hipSuccess) {
-        (void) hipGetLastError();
-        *err = hip_error(e);
-        return Status::kRuntime;
-    }
-    return Status::kOk;
+    static const uint32_t fresh[1] = {0u};
+    return stage_state(set, count, streams, n, fresh, &Engine::d_cf_state_, &Engine::comfort_ready, err);
 }
 
 // ------------------------------------------------------------------------------------------------ stream records
@@ -2781,25 +2589,33 @@ bool Engine::state_ready(std::string *err) {
 
 // Checks a stream list (nullptr: 0 .. count - 1) and uploads its inverse -- stream -> record, -1 = not listed -- on the handle's stream
 // from the next slot of a page-locked ring (a slot is rewritten once the copy that read it four uploads back has completed).
-Status Engine::state_list(int count, const int32_t *streams, std::string *err) {
+Status Engine::check_stream_list(int count, const int32_t *streams, std::vector<int32_t> *inv, std::string *err) const {
     if (count < 1 || count > B_) {
         *err = "`count` " + std::to_string(count) + " is outside [1, " + std::to_string(B_) + "].";
         return Status::kBadArgument;
     }
-    for (int i = 0; streams && i < count; ++i)
-        if (streams[i] < 0 || streams[i] >= B_) {
-            *err = "`streams[" + std::to_string(i) + "]` = " + std::to_string(streams[i]) + " is outside [0, " + std::to_string(B_) + ").";
-            return Status::kBadArgument;
-        }
-    std::vector<int32_t> inv((size_t) Bpad_, -1);
+    std::vector<int32_t> mine;
+    if (!inv) inv = &mine;
+    inv->assign((size_t) Bpad_, -1);
     for (int i = 0; i < count; ++i) {
         const int b = streams ? streams[i] : i;
-        if (inv[b] >= 0) {  // (refused for export too: one stream -> record table serves both directions)
+        if (b < 0 || b >= B_) {
+            *err = "`streams[" + std::to_string(i) + "]` = " + std::to_string(b) + " is outside [0, " + std::to_string(B_) + ").";
+            return Status::kBadArgument;
+        }
+        if ((*inv)[b] >= 0) {  // (refused for export too: one stream -> record table serves both directions)
             *err = "`streams[" + std::to_string(i) + "]`: slot " + std::to_string(b) + " is listed twice.";
             return Status::kBadArgument;
         }
-        inv[b] = i;
+        (*inv)[b] = i;
     }
+    return Status::kOk;
+}
+
+Status Engine::state_list(int count, const int32_t *streams, std::string *err) {
+    std::vector<int32_t> inv;
+    const Status listed = check_stream_list(count, streams, &inv, err);
+    if (listed != Status::kOk) return listed;
     if (!state_ready(err)) return Status::kRuntime;
     const int k = recof_ring_.acquire();
     if (k >= 0) memcpy(recof_ring_.host[k], inv.data(), (size_t) Bpad_ * 4);
@@ -2994,12 +2810,12 @@ Status Engine::process(const Call &c, std::string *err) {
         *err = "held streams are not combined with per-frame stream resets in one call.";
         return Status::kBadArgument;
     }
-    if (c.channel_link) {  // linked channels: the handle, the table the linked kernels read, and a group that is held as a whole or not at all
+    if (c.opt.channel_link) {  // linked channels: the handle, the table the linked kernels read, and a group that is held as a whole or not at all
         if (!channel_link_ok(ch_)) {
             *err = "linked channels need a handle whose `channels` is 2, 4 or 8 (this handle's `channels` = " + std::to_string(ch_) + ").";
             return Status::kBadArgument;
         }
-        if (!c.min_gain) {
+        if (!c.opt.min_gain) {
             *err = "a linked call carries the handle's minimum gains (all zero where no limit is in force).";
             return Status::kBadArgument;
         }
@@ -3027,28 +2843,23 @@ Status Engine::process(const Call &c, std::string *err) {
             return Status::kBadArgument;
         }
     }
-    if (c.level && (c.channel_link || c.high_band || fr_rate_)) {  // output leveller: what it is not combined with yet (the owner refuses all of it by name first)
-        *err = c.channel_link ? "the output leveller is not available yet while the channel link is on." :
-               c.high_band   ? "the output leveller is not available yet while the high-band carry is on." :
-                               "the output leveller is not available yet on a handle at 44100 or 22050 Hz.";
-        return Status::kBadArgument;
-    }
-    if (c.limiter && (c.channel_link || c.high_band || fr_rate_)) {  // peak limiter: the same four, refused by the owner by name first
-        *err = c.channel_link ? "the peak limiter is not available yet while the channel link is on." :
-               c.high_band   ? "the peak limiter is not available yet while the high-band carry is on." :
-                               "the peak limiter is not available yet on a handle at 44100 or 22050 Hz.";
-        return Status::kBadArgument;
-    }
-    if (c.comfort && (c.channel_link || c.high_band || fr_rate_ || !c.comfort_amp || !c.band_profile)) {  // comfort noise: the same four, refused by the owner by name first
-        *err = c.channel_link ? "comfort noise is not available yet while the channel link is on." :
-               c.high_band   ? "comfort noise is not available yet while the high-band carry is on." :
-               fr_rate_      ? "comfort noise is not available yet on a handle at 44100 or 22050 Hz." :
-                               "a call with comfort noise carries the amplitude table and the handle's band profile (neutral where none is in force).";
-        return Status::kBadArgument;
+    // the output stages: what they are not combined with yet (the owner refuses all of it by name first)
+    for (const OutputStage &s : kOutputStages) {
+        if (!s.on(c.opt)) continue;
+        if (c.opt.channel_link || c.high_band || fr_rate_) {
+            *err = std::string(s.name) + (c.opt.channel_link ? " is not available yet while the channel link is on." :
+                                          c.high_band        ? " is not available yet while the high-band carry is on." :
+                                                               " is not available yet on a handle at 44100 or 22050 Hz.");
+            return Status::kBadArgument;
+        }
+        if (s.carries_profile && (!c.opt.comfort_amp || !c.opt.band_profile)) {
+            *err = std::string(s.call) + " carries the amplitude table and the handle's band profile (neutral where none is in force).";
+            return Status::kBadArgument;
+        }
     }
     // the plain handle -- but for a levelling call on host memory, which goes through the boundary below: one copy in, the device route and
     // the leveller's launches behind it, one copy out (not the sub-chunk pipeline nor the one-frame graph, which end in host memory)
-    if (rate_ == kRate16k && fmt_ == kFmtS16 && ch_ == 1 && !((c.level || c.limiter || c.comfort) && (c.host_contract || pointer_kind(c.pcm) != kPtrDevice))) return process_frames(c, err);  // (peak limiter, comfort noise: as the leveller)
+    if (rate_ == kRate16k && fmt_ == kFmtS16 && ch_ == 1 && !((c.opt.level || c.opt.limiter || c.opt.comfort) && (c.host_contract || pointer_kind(c.pcm) != kPtrDevice))) return process_frames(c, err);  // (peak limiter, comfort noise: as the leveller)
     (void) hipSetDevice(device_);
     bool host, late = false;
     if (!call_on_host(c.pcm, c.out, c.report, &host, err)) return Status::kRuntime;
@@ -3209,12 +3020,12 @@ Status Engine::packet_check(const PacketCall &c, int most, int ch, bool *any_res
     }
     // linked channels (ch_: the handle's, also in a fractional handle's inner call): the sub-calls hold the streams by their frame count, so a
     // group's streams must complete the same frames -- equal `restart`, equal phase (the mirrors of fill and, at 44.1 / 22.05 kHz, N mod 441)
-    if (c.channel_link && (!channel_link_ok(ch_) || !c.min_gain)) {
-        *err = !c.min_gain ? "a linked call carries the handle's minimum gains (all zero where no limit is in force)."
+    if (c.opt.channel_link && (!channel_link_ok(ch_) || !c.opt.min_gain)) {
+        *err = !c.opt.min_gain ? "a linked call carries the handle's minimum gains (all zero where no limit is in force)."
                            : "linked channels need a handle whose `channels` is 2, 4 or 8 (this handle's `channels` = " + std::to_string(ch_) + ").";
         return Status::kBadArgument;
     }
-    for (int b = 0; c.channel_link && b < B_; ++b) {
+    for (int b = 0; c.opt.channel_link && b < B_; ++b) {
         const int first = b - b % ch_;
         const std::string who = ": streams " + std::to_string(first) + " and " + std::to_string(b) + " are channels of group " + std::to_string(b / ch_) +
                                 ", whose masks are linked (`channels` = " + std::to_string(ch_) + ")";
@@ -3313,18 +3124,8 @@ Status Engine::packet_end(const PacketCall &c, int fmt, int ch, const PacketIo &
 }
 
 Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string *err) {
-    if (c.level && c.channel_link) {  // (the owner refuses it by name first)
-        *err = "the output leveller is not available yet while the channel link is on.";
-        return Status::kBadArgument;
-    }
-    if (c.limiter && c.channel_link) {  // (the owner refuses it by name first)
-        *err = "the peak limiter is not available yet while the channel link is on.";
-        return Status::kBadArgument;
-    }
-    if (c.comfort && c.channel_link) {  // (the owner refuses it by name first)
-        *err = "comfort noise is not available yet while the channel link is on.";
-        return Status::kBadArgument;
-    }
+    // (the owner refuses it by name first)
+    if (c.opt.channel_link && refuse_stages(c.opt, " is not available yet while the channel link is on.", err)) return Status::kBadArgument;
     const int F = rs_frame_length(rate_);
     bool any_restart, any_count, nothing;
     Status st = packet_check(c, pk_max_, ch, &any_restart, &any_count, err);
@@ -3394,12 +3195,9 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string
         for (int b = 0; b < B_; ++b) held = (hold[b] = k[b] < c1) || held;
         Call inner{c1 - c0, d_pk_in_ + (size_t) B_ * F * c0, d_pk_out_ + (size_t) B_ * F * c0};
         inner.hold = held ? hold.data() : nullptr;
-        inner.min_gain = c.min_gain, inner.min_gain_rev = c.min_gain_rev;
-        inner.band_profile = c.band_profile, inner.band_profile_rev = c.band_profile_rev;
-        inner.channel_link = c.channel_link;  // (packet_check: a group's streams share k_b, so a sub-call holds a group as a whole)
-        inner.level = c.level, inner.level_rev = c.level_rev;  // (the sub-calls' `hold` keeps a stalled stream's leveller where it is)
-        inner.limiter = c.limiter, inner.limiter_rev = c.limiter_rev;  // (... and its limiter's g)
-        inner.comfort = c.comfort, inner.comfort_amp = c.comfort_amp, inner.comfort_rev = c.comfort_rev;  // (... and its comfort noise's counter)
+        // (the link -- packet_check: a group's streams share k_b, so a sub-call holds a group as a whole; the output stages -- the sub-calls'
+        // `hold` keeps a stalled stream's leveller, its limiter's g and its comfort noise's counter where they are)
+        inner.opt = c.opt;
         inner.report = c.report ? d_pk_rep_ + (size_t) B_ * c0 * 4 : nullptr;
         if (process_frames(inner, err) != Status::kOk) return Status::kRuntime;
     }
@@ -3465,18 +3263,8 @@ FractionalStateArgs Engine::fractional_state_args() const {
 // report rows and frame counts are the call's -- fractional_out_kernel, [format_out].  A call in which no stream yields an inner sample
 // still runs both stages: the in-stage's history and N advance, and the out-stage delivers from the inner output it holds.
 Status Engine::run_fractional(const PacketCall &c, std::string *err) {
-    if (c.level) {  // (the owner refuses it by name first)
-        *err = "the output leveller is not available yet on a handle at 44100 or 22050 Hz.";
-        return Status::kBadArgument;
-    }
-    if (c.limiter) {  // (the owner refuses it by name first)
-        *err = "the peak limiter is not available yet on a handle at 44100 or 22050 Hz.";
-        return Status::kBadArgument;
-    }
-    if (c.comfort) {  // (the owner refuses it by name first)
-        *err = "comfort noise is not available yet on a handle at 44100 or 22050 Hz.";
-        return Status::kBadArgument;
-    }
+    // (the owner refuses it by name first)
+    if (refuse_stages(c.opt, " is not available yet on a handle at 44100 or 22050 Hz.", err)) return Status::kBadArgument;
     const int U = fr_up(fr_rate_);
     bool any_restart, any_count, nothing;
     Status st = packet_check(c, fr_max_, ch_, &any_restart, &any_count, err);
@@ -3526,9 +3314,9 @@ Status Engine::run_fractional(const PacketCall &c, std::string *err) {
         return Status::kRuntime;
     }
     // the inner call: an S16 call on device rows, without restarts (done above); its report rows and frame counts are this call's
-    PacketCall in16{pk_max_, inner.data(), d_fr_in_, d_fr_out_, nullptr, io.report, io.report_frames, k.data(), c.min_gain, c.min_gain_rev};
-    in16.band_profile = c.band_profile, in16.band_profile_rev = c.band_profile_rev;
-    in16.channel_link = c.channel_link;  // (the inner call's rows are the engine's: its `ch` is 1, the link is the handle's)
+    // (its settings: the gains, the profile and the link -- the inner call's rows are the engine's: its `ch` is 1, the link is the handle's; the
+    // output stages were refused above)
+    PacketCall in16{pk_max_, inner.data(), d_fr_in_, d_fr_out_, nullptr, io.report, io.report_frames, k.data(), c.opt};
     st = run_packet_call(in16, kFmtS16, 1, err);
     if (st != Status::kOk) return st;
     a.in = d_fr_out_;

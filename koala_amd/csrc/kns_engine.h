@@ -34,46 +34,20 @@ LoadResult load_params(const char *path, Params *out, std::string *err);
 constexpr int kNumKernelClasses = 5;
 enum KernelClass { kClsAnalysis = 0, kClsGemmIn = 1, kClsGru = 2, kClsGemmHead = 3, kClsSynthesis = 4 };
 
-// One call that advances the streams, with everything it carries.  pcm/out: [B][T*frame_length] at the handle's sample rate (256 at
-// 16 kHz), host or device pointers (both of the same kind).  On a handle with a sample format (Engine::set_format) they point to elements
-// of that format -- float or uint8 -- behind the int16 type: the entry casts, and every size is a count of sample_bytes().  Host pointers
-// are the entry's business (Engine::process): below it a call of a handle that is not the plain one carries device pointers only.
-struct Call {
-    int T;
-    const int16_t *pcm;
-    int16_t *out;
-    // Per-frame stream resets: host memory, uint8 [num_streams][T] (non-zero at [b][t]: stream b restarts from the fresh state right before
-    // frame t).  Consumed before the call returns -- packed into the reset ring (kns_engine.cpp, begin_resets) -- so the caller may
-    // overwrite it then.  nullptr or all zero: the plain call.
-    const uint8_t *resets = nullptr;
-    // Held streams: host memory, uint8 [num_streams].  The streams with hold[b] != 0 are not advanced: their state after the call is bit for
-    // bit what it was before it (exported to a device scratch in front of the whole call and imported back behind it); their rows of `out`
-    // are unspecified.  nullptr or all zero: the plain call.  Not combined with `resets`, not taken by process_host_async.
-    const uint8_t *hold = nullptr;
-    bool host_contract = false;  // pcm/out are host memory by the entry point's contract: no driver query per frame on the latency path
+// The per-stream settings a call carries ("Per-stream settings"): the owner's -- the C ABI's handle, which checks every
+// value and counts its changes -- and the same for a frame call and a packet call, whose sub-calls and inner calls take them on as they are.
+struct StreamOptions {
     // Per-stream attenuation limit: host memory, float [num_streams], every value in [0, 1] (checked by the owner, the C ABI's handle).
     // Stream b's mask value m becomes min_gain[b] + (1 - min_gain[b]) m in every frame of the call.  Read before
     // the call returns (copied into an upload slot of the call when `min_gain_rev` differs from the one the engine's device table holds: the
     // owner counts its changes).  nullptr: every gain is 0, the plain call -- same route, same kernels, same bits.
     const float *min_gain = nullptr;
     unsigned min_gain_rev = 0;
-    // Frame report: float [num_streams][T][4], memory of the same kind as `out` (host with host, device with device; process_host_async:
-    // page-locked).  Row [b][t] = e_in, e_out, mask_sum, 0 of stream b's frame t (DESIGN.md section 2, step 4: three sums the synthesis kernel
-    // forms in a fixed order); complete when `out` is.  An output only: the streams' evolution and `out` do not depend on whether it was asked
-    // for.  Held streams' rows are unspecified.  nullptr: the plain call -- same route, same kernels, same bits.
-    float *report = nullptr;
     // Linked channels (eighth extension; a handle with channels() == 2, 4 or 8 only): non-zero, and the mask applied to
     // a stream in every frame of the call is the max over the masks of its group's streams, bin by bin.  The call then carries `min_gain`
     // (all zero where no limit is in force: the linked kernels read the table), and `hold` must be equal within a group.  The owner's
     // setting, like the limit: the engine keeps nothing of it between calls.  0: the plain call -- same route, same kernels, same bits.
     int channel_link = 0;
-    // High-band carry (DESIGN.md section 2, ninth extension; a frame handle at 32 or 48 kHz only): non-zero, and the band above the stages'
-    // pass band is added to `out`, delayed like the call and scaled by a broadband gain from the call's masks (kns_highband.hip).  The
-    // owner's setting, like the link; `high_band_epoch` counts the times the owner turned it on: the engine allocates the feature's
-    // per-stream state at the first such call and clears it when the epoch is not the one it saw last.  Not combined with `hold`, nor with
-    // `resets` behind frame 0.  0: the plain call -- same launches, same bits.
-    int high_band = 0;
-    unsigned high_band_epoch = 0;
     // Band profile (tenth extension): host memory, float [num_streams][kProfileRow] -- every stream's 257 floors and
     // ceilings in the order of profile_index (kns_kernels.h), every value in [0, 1] and floor <= ceiling (checked by the owner, the C ABI's
     // handle).  Stream b's mask value of bin k becomes min(ceil_b[k], max(floor_b[k], m')) in every frame of the call, m' the value under
@@ -113,6 +87,38 @@ struct Call {
     unsigned comfort_rev = 0;
 };
 
+// One call that advances the streams, with everything it carries.  pcm/out: [B][T*frame_length] at the handle's sample rate (256 at
+// 16 kHz), host or device pointers (both of the same kind).  On a handle with a sample format (Engine::set_format) they point to elements
+// of that format -- float or uint8 -- behind the int16 type: the entry casts, and every size is a count of sample_bytes().  Host pointers
+// are the entry's business (Engine::process): below it a call of a handle that is not the plain one carries device pointers only.
+struct Call {
+    int T;
+    const int16_t *pcm;
+    int16_t *out;
+    // Per-frame stream resets: host memory, uint8 [num_streams][T] (non-zero at [b][t]: stream b restarts from the fresh state right before
+    // frame t).  Consumed before the call returns -- packed into the reset ring (kns_engine.cpp, begin_resets) -- so the caller may
+    // overwrite it then.  nullptr or all zero: the plain call.
+    const uint8_t *resets = nullptr;
+    // Held streams: host memory, uint8 [num_streams].  The streams with hold[b] != 0 are not advanced: their state after the call is bit for
+    // bit what it was before it (exported to a device scratch in front of the whole call and imported back behind it); their rows of `out`
+    // are unspecified.  nullptr or all zero: the plain call.  Not combined with `resets`, not taken by process_host_async.
+    const uint8_t *hold = nullptr;
+    bool host_contract = false;  // pcm/out are host memory by the entry point's contract: no driver query per frame on the latency path
+    // Frame report: float [num_streams][T][4], memory of the same kind as `out` (host with host, device with device; process_host_async:
+    // page-locked).  Row [b][t] = e_in, e_out, mask_sum, 0 of stream b's frame t (DESIGN.md section 2, step 4: three sums the synthesis kernel
+    // forms in a fixed order); complete when `out` is.  An output only: the streams' evolution and `out` do not depend on whether it was asked
+    // for.  Held streams' rows are unspecified.  nullptr: the plain call -- same route, same kernels, same bits.
+    float *report = nullptr;
+    // High-band carry (DESIGN.md section 2, ninth extension; a frame handle at 32 or 48 kHz only): non-zero, and the band above the stages'
+    // pass band is added to `out`, delayed like the call and scaled by a broadband gain from the call's masks (kns_highband.hip).  The
+    // owner's setting, like the link; `high_band_epoch` counts the times the owner turned it on: the engine allocates the feature's
+    // per-stream state at the first such call and clears it when the epoch is not the one it saw last.  Not combined with `hold`, nor with
+    // `resets` behind frame 0.  0: the plain call -- same launches, same bits.
+    int high_band = 0;
+    unsigned high_band_epoch = 0;
+    StreamOptions opt;  // the per-stream settings, above
+};
+
 // kBadArgument: a stream list, a record or a combination of Call members that the engine refused before it touched anything (the C ABI
 // reports INVALID_ARGUMENT).  kRuntime: a HIP failure, and the refusals the ABI has always reported as a runtime error (pointer kinds,
 // overlapping buffers).
@@ -129,18 +135,9 @@ struct PacketCall {
     float *report = nullptr;           // [num_streams][report_frames][4], memory of out's kind, or nullptr
     int report_frames = 0;
     int32_t *frames = nullptr;         // host [num_streams] or nullptr, out: frames completed by the call
-    const float *min_gain = nullptr;   // as Call's
-    unsigned min_gain_rev = 0;
-    int channel_link = 0;              // as Call's; `restart`, and the streams' phase (the mirrors of fill and of N mod 441), must be equal within a group
-    const float *band_profile = nullptr;  // as Call's
-    unsigned band_profile_rev = 0;
-    const LevelSetting *level = nullptr;  // as Call's; not on a handle at 44 100 or 22 050 Hz
-    unsigned level_rev = 0;
-    const LimiterSetting *limiter = nullptr;  // as Call's; not on a handle at 44 100 or 22 050 Hz
-    unsigned limiter_rev = 0;
-    const ComfortSetting *comfort = nullptr;  // as Call's; not on a handle at 44 100 or 22 050 Hz
-    const float *comfort_amp = nullptr;
-    unsigned comfort_rev = 0;
+    // as Call's.  `channel_link`: `restart`, and the streams' phase (the mirrors of fill and of N mod 441), must be equal within a group;
+    // `level`, `limiter`, `comfort`: not on a handle at 44 100 or 22 050 Hz
+    StreamOptions opt;
 };
 
 class Engine {
@@ -226,7 +223,7 @@ public:
     // C == 1 allocates and changes nothing.
     bool enable_channels(int C, std::string *err);
     int channels() const { return ch_; }
-    // (linked channels, Call::channel_link: a group must lie inside one 16-row mask tile)
+    // (linked channels, StreamOptions::channel_link: a group must lie inside one 16-row mask tile)
     static bool channel_link_ok(int C) { return C == 2 || C == 4 || C == 8; }
 
     void profile_enable(bool on);
@@ -327,9 +324,9 @@ private:
         ResetTable *resets;
         const float *min_gain;  // the call's per-stream minimum gains on the device [Bpad] (begin_min_gain), nullptr: no limit in force
         float *d_report = nullptr;  // the slice's frame report [B][T][4] (device-visible memory, rows T frames apart), nullptr: not asked for
-        int link = 0;  // the call's linked channels: channels() when Call::channel_link is set (then min_gain is not null), else 0
+        int link = 0;  // the call's linked channels: channels() when StreamOptions::channel_link is set (then min_gain is not null), else 0
         const float *profile = nullptr;  // the call's band profile on the device [Bpad][kProfileRow] (begin_band_profile; then min_gain is not null and link is 0), nullptr: neutral
-        bool comfort = false;  // the call's comfort noise: begin_comfort's tables and run_comfort's counter values (then profile is not null)
+        bool comfort = false;  // the call's comfort noise: its two tables (cf_tab_, cfa_tab_) and run_comfort's counter values (then profile is not null)
     };
     bool run_device(const Slice &s, std::string *err);
     void *dalloc(size_t bytes, bool zero);
@@ -475,60 +472,55 @@ private:
     uint8_t *d_state_ = nullptr;
     int32_t *d_recof_ = nullptr;
     UploadRing recof_ring_;
-    // Per-stream attenuation limit (Call::min_gain): the one device table float [Bpad] and its upload ring.  The table is configuration, not
-    // state: no reset, record or held stream touches it.  begin_min_gain: the device table a call's synthesis kernels read (nullptr: no
-    // limit), uploaded on the handle's stream -- in front of the call's kernels or graph replay -- when the call's revision is not the table's
-    float *d_min_gain_ = nullptr;
-    UploadRing mg_ring_;
-    unsigned mg_rev_ = 0;
-    bool mg_valid_ = false;
+    // Per-stream settings (StreamOptions; DESIGN.md section 2, "Per-stream settings"): a feature's device table [Bpad][row] with its upload
+    // ring, and the owner's revision the table holds.  Configuration, not state: no reset, record or held stream touches a table.
+    // put_table: the table of the call about to run, on the handle's stream in front of the call's kernels or graph replay -- allocated at
+    // first use (`what`: the feature's name in the failure message), uploaded through a ring slot (rows past B: zero) when the call's
+    // revision is not the table's.  A table is never zeroed at allocation: all Bpad rows are uploaded, on the call's stream, before a kernel
+    // is given the pointer -- a memset on the handle's own stream would be unordered with that copy after set_stream.
+    struct SettingTable {
+        void *d = nullptr;
+        UploadRing ring;
+        size_t row = 0;  // bytes per stream
+        unsigned rev = 0;
+        bool valid = false;
+    };
+    bool table_alloc(SettingTable *t, size_t row);  // the ring and the device table, both or neither
+    bool put_table(SettingTable *t, size_t row, const void *rows, unsigned rev, const char *what, std::string *err);
+    SettingTable mg_tab_, pf_tab_, lv_tab_, lm_tab_, cf_tab_, cfa_tab_;  // gains, band profile, leveller, limiter, comfort settings and amplitudes
+    // begin_min_gain / begin_band_profile: the device table a call's synthesis kernels read (nullptr: no limit / the neutral profile); a
+    // profiled call that is linked, carries the high band or comes without the gains is the owner's to refuse, and fails here
     bool begin_min_gain(const Call &c, const float **table, std::string *err);
-    // Band profile (Call::band_profile): the one device table float [Bpad][kProfileRow] and its upload ring, as the gains' -- configuration,
-    // not state.  begin_band_profile: the device table a call's synthesis kernels read (nullptr: neutral), uploaded on the handle's stream in
-    // front of the call's kernels or graph replay when the call's revision is not the table's; a profiled call that is linked, carries the high
-    // band or comes without the gains is the owner's to refuse, and fails here
-    float *d_profile_ = nullptr;
-    UploadRing pf_ring_;
-    unsigned pf_rev_ = 0;
-    bool pf_valid_ = false;
     bool begin_band_profile(const Call &c, const float **table, std::string *err);
-    // Output leveller (Call::level): the settings' device table [Bpad] with its upload ring and revision, as the gains'; the state
-    // [Bpad][2], allocated fresh by the first call that levels or by level_state and part of every reset; a call's control bytes
-    // [B][Tmax + 1] (hold, reset flags) with their ring; the gain pairs [B][Tmax][2]; and the report [B][Tmax][4] of a call whose caller
-    // asked for none.  run_level: the two launches behind a device-pointer call's kernels
-    LevelSetting *d_lv_set_ = nullptr;
+    // The control rows of a call with an output stage: `hold` and the reset flags as uint8 [B][T + 1], uploaded once per call, in front of its
+    // first launch that reads them, and only when some byte is set (*ctl = nullptr otherwise).  One buffer [B][Tmax + 1] and one ring,
+    // allocated by whichever stage is used first (ctl_ready)
+    uint8_t *d_ctl_ = nullptr;
+    UploadRing ctl_ring_;
+    bool ctl_ready();
+    bool control_rows(const Call &c, const uint8_t **ctl, std::string *err);
+    // Output leveller (StreamOptions::level): the state [Bpad][2], allocated fresh by the first call that levels or by level_state and part
+    // of every reset; the gain pairs [B][Tmax][2]; and the report [B][Tmax][4] of a call whose caller asked for none.  run_level: the two
+    // launches behind a device-pointer call's kernels
     float *d_lv_state_ = nullptr, *d_lv_gains_ = nullptr, *d_lv_rep_ = nullptr;
-    uint8_t *d_lv_ctl_ = nullptr;
-    UploadRing lv_ring_, lvc_ring_;
-    unsigned lv_rev_ = 0;
-    bool lv_valid_ = false;
     bool level_ready(std::string *err);
-    bool begin_level(const Call &c, std::string *err);
-    bool run_level(const Call &c, const float *report, bool callers_report, std::string *err);
-    // Peak limiter (Call::limiter): the settings' device table [Bpad] with its upload ring and revision, and g of every stream [Bpad],
-    // allocated at 1 by the first call that limits or by limiter_state -- together with the leveller's buffers, whose control rows and
-    // gain pairs the limiter's launch reads -- and part of every reset.  run_level launches it in level_apply_kernel's place
-    LimiterSetting *d_lm_set_ = nullptr;
+    bool run_level(const Call &c, const float *report, bool callers_report, const uint8_t *ctl, std::string *err);
+    // Peak limiter (StreamOptions::limiter): g of every stream [Bpad], allocated at 1 by the first call that limits or by limiter_state --
+    // together with the leveller's buffers, whose gain pairs the limiter's launch reads -- and part of every reset.  run_level launches it in
+    // level_apply_kernel's place
     float *d_lm_state_ = nullptr;
-    UploadRing lm_ring_;
-    unsigned lm_rev_ = 0;
-    bool lm_valid_ = false;
     bool limiter_ready(std::string *err);
-    bool begin_limiter(const Call &c, std::string *err);
-    // Comfort noise (Call::comfort): the settings' device table [Bpad] and the amplitude table [Bpad][kComfortRow] with their upload rings and
-    // one revision, as the profile's; the counters [Bpad], allocated at 0 by the first call that fills or by comfort_state and part of every
-    // reset; a call's control bytes [B][Tmax + 1] with their ring (the leveller's layout); the counter values of a call's frames
-    // [Bpad][Tmax].  run_comfort: the counter's launch in front of a device-pointer call's kernels
-    ComfortSetting *d_cf_set_ = nullptr;
-    float *d_cf_amp_ = nullptr;
+    // Comfort noise (StreamOptions::comfort): the counters [Bpad], allocated at 0 by the first call that fills or by comfort_state and part of
+    // every reset; the counter values of a call's frames [Bpad][Tmax].  run_comfort: the counter's launch in front of a device-pointer
+    // call's kernels
     uint32_t *d_cf_state_ = nullptr, *d_cf_n_ = nullptr;
-    uint8_t *d_cf_ctl_ = nullptr;
-    UploadRing cf_ring_, cfa_ring_, cfc_ring_;
-    unsigned cf_rev_ = 0;
-    bool cf_valid_ = false;
     bool comfort_ready(std::string *err);
-    bool begin_comfort(const Call &c, std::string *err);
-    bool run_comfort(const Call &c, std::string *err);
+    bool run_comfort(const Call &c, const uint8_t *ctl, std::string *err);
+    // level_state, limiter_state, comfort_state: N values of type T per stream, `fresh` on a handle that never used the stage
+    template <class T, int N>
+    Status stage_state(bool set, int count, const int32_t *streams, T *state, const T (&fresh)[N], T *Engine::*dev, bool (Engine::*ready)(std::string *), std::string *err);
+    // a stream list (nullptr: slots 0 .. count - 1): count, range and "no slot twice"; inv [Bpad]: stream -> place in the list, -1 = not listed
+    Status check_stream_list(int count, const int32_t *streams, std::vector<int32_t> *inv, std::string *err) const;
     // Frame report (Call::report) of host-pointer calls: device and page-locked host staging [B][Tmax][4] each, used like d_out_ / h_out_ (two
     // slots of [B][host_chunk_][4] by the sub-chunked calls; the one-frame graph writes into h_report_ or copies to it); d_report2_: the second
     // slot of asynchronous host calls.  Allocated by the first call that asks for a report.

@@ -113,7 +113,7 @@ pv_status_t check_records(const pv_koala_batch_t *object) {
                    object->sample_rate);
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    if (object->limit.high_band) {  // (a record would need the feature's per-stream state)
+    if (object->settings.high_band) {  // (a record would need the feature's per-stream state)
         push_error(0x66, "Stream records (state_size, export_state, import_state) are not available yet while the high-band carry is on "
                          "(pv_koala_batch_set_high_band).");
         return PV_STATUS_INVALID_ARGUMENT;
@@ -146,28 +146,11 @@ pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std:
     return PV_STATUS_RUNTIME_ERROR;
 }
 
-// one call that advances the streams (arguments already checked), under the handle's attenuation limit
-pv_status_t advance(kns::Engine *engine, const MinGain &limit, kns::Call call, bool async = false) {
-    if (kns_api::check_band_profile(limit) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
-    if (limit.any || limit.link || limit.profile_any) {  // (the linked and the profile kernels read the gains, all zero where no limit is in force)
-        call.min_gain = limit.gain.data();
-        call.min_gain_rev = limit.rev;
-    }
-    if (limit.profile_any) {
-        call.band_profile = limit.profile.data();
-        call.band_profile_rev = limit.profile_rev;
-    }
-    call.channel_link = limit.link;
-    if (kns_api::check_level(limit, engine, async) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
-    if (limit.level_any) {
-        call.level = limit.level.data();
-        call.level_rev = limit.level_rev;
-    }
-    if (kns_api::check_limiter(limit, engine, async) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
-    kns_api::carry_limiter(limit, &call);
-    if (kns_api::check_comfort(limit, engine, async) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
-    kns_api::carry_comfort(limit, &call);
-    if (limit.high_band) {  // what the high-band carry does not take yet: refused here, before the engine is reached
+// one call that advances the streams (arguments already checked), under the handle's settings
+pv_status_t advance(kns::Engine *engine, const HandleSettings &settings, kns::Call call, bool async = false) {
+    if (kns_api::check_settings(settings, engine, async) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
+    kns_api::carry(settings, &call.opt);
+    if (settings.high_band) {  // what the high-band carry does not take yet: refused here, before the engine is reached
         const int32_t B = engine->num_streams();
         for (int32_t b = 0; call.hold && b < B; ++b)
             if (call.hold[b]) {
@@ -181,7 +164,7 @@ pv_status_t advance(kns::Engine *engine, const MinGain &limit, kns::Call call, b
                                      "per-frame stream resets at frame 0 only (not yet).", b, t);
                     return PV_STATUS_INVALID_ARGUMENT;
                 }
-        call.high_band = limit.high_band, call.high_band_epoch = limit.high_band_epoch;
+        call.high_band = settings.high_band, call.high_band_epoch = settings.high_band_epoch;
     }
     return guarded([&] {
         std::string err;
@@ -204,49 +187,36 @@ void push_error(unsigned code, const char *fmt, ...) {
     ::push_error(code, "%s", text);
 }
 pv_status_t engine_failure(kns::Status status, unsigned runtime_code, const std::string &err) { return ::engine_failure(status, runtime_code, err); }
-pv_status_t check_band_profile(const MinGain &limit) {
-    if (!limit.profile_any) return PV_STATUS_SUCCESS;
-    if (limit.link) {
+// an output stage that is on: `stage`, `setter`: what the message calls it; `link`, `high_band`: why not with the link / the carry
+static pv_status_t check_stage(bool on, const char *stage, const char *setter, const char *link, const char *high_band, const HandleSettings &s,
+                               const kns::Engine *engine, bool async) {
+    if (!on) return PV_STATUS_SUCCESS;
+    const char *what = s.link                  ? "while the channel link is on (pv_koala_batch_set_channel_link): " :
+                       s.high_band             ? "while the high-band carry is on (pv_koala_batch_set_high_band): " :
+                       async                   ? "on the asynchronous entry points" :
+                       engine->fractional_rate() ? "on a handle whose sample rate is 44100 or 22050" : nullptr;
+    if (!what) return PV_STATUS_SUCCESS;
+    ::push_error(0x66, "%s (%s: some stream's `on` is set) is not available yet %s%s.", stage, setter, what, s.link ? link : s.high_band ? high_band : "");
+    return PV_STATUS_INVALID_ARGUMENT;
+}
+pv_status_t check_settings(const HandleSettings &s, const kns::Engine *engine, bool async) {
+    if (s.profile_any && s.link) {
         ::push_error(0x66, "A band profile that is not neutral (pv_koala_batch_set_band_profile) is not available yet while the channel link is on "
                            "(pv_koala_batch_set_channel_link).");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    if (limit.high_band) {
+    if (s.profile_any && s.high_band) {
         ::push_error(0x66, "A band profile that is not neutral (pv_koala_batch_set_band_profile) is not available yet while the high-band carry is on "
                            "(pv_koala_batch_set_high_band): its broadband gain would have to follow the profile.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
+    const char *one_gain = "a group would need one gain", *same_gain = "its band would need the same gain";
+    if (check_stage(s.level_any, "The output leveller", "pv_koala_batch_set_level", one_gain, same_gain, s, engine, async) != PV_STATUS_SUCCESS ||
+        check_stage(s.limiter_any, "The peak limiter", "pv_koala_batch_set_limiter", one_gain, same_gain, s, engine, async) != PV_STATUS_SUCCESS ||
+        check_stage(s.comfort_any, "Comfort noise", "pv_koala_batch_set_comfort_noise", "a group would need one fill",
+                    "its broadband gain would have to see the fill", s, engine, async) != PV_STATUS_SUCCESS)
+        return PV_STATUS_INVALID_ARGUMENT;
     return PV_STATUS_SUCCESS;
-}
-pv_status_t check_level(const MinGain &limit, const kns::Engine *engine, bool async) {
-    if (!limit.level_any) return PV_STATUS_SUCCESS;
-    const char *what = limit.link                  ? "while the channel link is on (pv_koala_batch_set_channel_link): a group would need one gain" :
-                       limit.high_band             ? "while the high-band carry is on (pv_koala_batch_set_high_band): its band would need the same gain" :
-                       async                       ? "on the asynchronous entry points" :
-                       engine->fractional_rate()   ? "on a handle whose sample rate is 44100 or 22050" : nullptr;
-    if (!what) return PV_STATUS_SUCCESS;
-    ::push_error(0x66, "The output leveller (pv_koala_batch_set_level: some stream's `on` is set) is not available yet %s.", what);
-    return PV_STATUS_INVALID_ARGUMENT;
-}
-pv_status_t check_limiter(const MinGain &limit, const kns::Engine *engine, bool async) {
-    if (!limit.limiter_any) return PV_STATUS_SUCCESS;
-    const char *what = limit.link                  ? "while the channel link is on (pv_koala_batch_set_channel_link): a group would need one gain" :
-                       limit.high_band             ? "while the high-band carry is on (pv_koala_batch_set_high_band): its band would need the same gain" :
-                       async                       ? "on the asynchronous entry points" :
-                       engine->fractional_rate()   ? "on a handle whose sample rate is 44100 or 22050" : nullptr;
-    if (!what) return PV_STATUS_SUCCESS;
-    ::push_error(0x66, "The peak limiter (pv_koala_batch_set_limiter: some stream's `on` is set) is not available yet %s.", what);
-    return PV_STATUS_INVALID_ARGUMENT;
-}
-pv_status_t check_comfort(const MinGain &limit, const kns::Engine *engine, bool async) {
-    if (!limit.comfort_any) return PV_STATUS_SUCCESS;
-    const char *what = limit.link                  ? "while the channel link is on (pv_koala_batch_set_channel_link): a group would need one fill" :
-                       limit.high_band             ? "while the high-band carry is on (pv_koala_batch_set_high_band): its broadband gain would have to see the fill" :
-                       async                       ? "on the asynchronous entry points" :
-                       engine->fractional_rate()   ? "on a handle whose sample rate is 44100 or 22050" : nullptr;
-    if (!what) return PV_STATUS_SUCCESS;
-    ::push_error(0x66, "Comfort noise (pv_koala_batch_set_comfort_noise: some stream's `on` is set) is not available yet %s.", what);
-    return PV_STATUS_INVALID_ARGUMENT;
 }
 }  // namespace kns_api
 
@@ -393,7 +363,7 @@ pv_status_t make_handle(kns::Engine *e, H **object) {
     try {
         o = new H();
         o->engine = e;
-        o->limit.gain.assign((size_t) e->num_streams(), 0.0f);
+        o->settings.gain.assign((size_t) e->num_streams(), 0.0f);
     } catch (...) {
         delete o;
         o = nullptr;
@@ -408,7 +378,7 @@ pv_status_t make_handle(kns::Engine *e, H **object) {
 }
 
 // pv_koala_batch_set_min_gain / pv_koala_set_min_gain: every entry is checked before anything is changed
-pv_status_t set_min_gain(MinGain *limit, int32_t B, int32_t count, const int32_t *streams, const float *gains) {
+pv_status_t set_min_gain(HandleSettings *settings, int32_t B, int32_t count, const int32_t *streams, const float *gains) {
     if (!gains) {
         push_error(0x64, "Argument `gains` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
@@ -418,19 +388,11 @@ pv_status_t set_min_gain(MinGain *limit, int32_t B, int32_t count, const int32_t
         return PV_STATUS_INVALID_ARGUMENT;
     }
     return guarded([&] {
-        std::vector<float> next(limit->gain);
+        std::vector<float> next(settings->gain);
         std::vector<uint8_t> listed((size_t) B, 0);
         for (int32_t i = 0; i < count; ++i) {
-            const int32_t b = streams ? streams[i] : i;
-            if (b < 0 || b >= B) {
-                push_error(0x66, "`streams[%d]` = %d is outside [0, %d).", i, b, B);
-                return PV_STATUS_INVALID_ARGUMENT;
-            }
-            if (listed[b]) {
-                push_error(0x66, "`streams[%d]`: slot %d is listed twice.", i, b);
-                return PV_STATUS_INVALID_ARGUMENT;
-            }
-            listed[b] = 1;
+            const int32_t b = kns_api::listed_stream(&listed, streams, i);
+            if (b < 0) return PV_STATUS_INVALID_ARGUMENT;
             if (!(gains[i] >= 0.0f && gains[i] <= 1.0f)) {  // (NaN fails both comparisons)
                 push_error(0x66, "gain %d: %g is not a minimum gain in [0, 1].", i, (double) gains[i]);
                 return PV_STATUS_INVALID_ARGUMENT;
@@ -439,22 +401,22 @@ pv_status_t set_min_gain(MinGain *limit, int32_t B, int32_t count, const int32_t
         }
         bool any = false;
         for (float g : next) any = any || g != 0.0f;
-        limit->gain.swap(next);
-        limit->any = any;
-        ++limit->rev;
+        settings->gain.swap(next);
+        settings->any = any;
+        ++settings->rev;
         return PV_STATUS_SUCCESS;
     });
 }
 
 // pv_koala_batch_set_band_profile / pv_koala_set_band_profile: every value is checked before anything is changed
-pv_status_t set_band_profile(MinGain *limit, int32_t B, int32_t count, const int32_t *streams, const float *floor, const float *ceil) {
+pv_status_t set_band_profile(HandleSettings *settings, int32_t B, int32_t count, const int32_t *streams, const float *floor, const float *ceil) {
     if (count < 1 || count > B) {
         push_error(0x66, "`count` %d is outside [1, %d].", count, B);
         return PV_STATUS_INVALID_ARGUMENT;
     }
     return guarded([&] {
         constexpr int K = PV_KOALA_NUM_BINS, R = kns::kProfileRow;
-        std::vector<float> next(limit->profile);
+        std::vector<float> next(settings->profile);
         if (next.empty()) {  // the neutral table
             next.assign((size_t) B * R, 0.0f);
             for (int32_t b = 0; b < B; ++b)
@@ -462,16 +424,8 @@ pv_status_t set_band_profile(MinGain *limit, int32_t B, int32_t count, const int
         }
         std::vector<uint8_t> listed((size_t) B, 0);
         for (int32_t i = 0; i < count; ++i) {
-            const int32_t b = streams ? streams[i] : i;
-            if (b < 0 || b >= B) {
-                push_error(0x66, "`streams[%d]` = %d is outside [0, %d).", i, b, B);
-                return PV_STATUS_INVALID_ARGUMENT;
-            }
-            if (listed[b]) {
-                push_error(0x66, "`streams[%d]`: slot %d is listed twice.", i, b);
-                return PV_STATUS_INVALID_ARGUMENT;
-            }
-            listed[b] = 1;
+            const int32_t b = kns_api::listed_stream(&listed, streams, i);
+            if (b < 0) return PV_STATUS_INVALID_ARGUMENT;
             for (int k = 0; k < K; ++k) {
                 const float lo = floor ? floor[(size_t) i * K + k] : 0.0f, hi = ceil ? ceil[(size_t) i * K + k] : 1.0f;
                 if (!(lo >= 0.0f && lo <= 1.0f) || !(hi >= 0.0f && hi <= 1.0f)) {  // (NaN fails both comparisons)
@@ -491,18 +445,18 @@ pv_status_t set_band_profile(MinGain *limit, int32_t B, int32_t count, const int
         for (int32_t b = 0; b < B && !any; ++b)
             for (int k = 0; k < K && !any; ++k)
                 any = next[(size_t) b * R + kns::profile_index(k, 0)] != 0.0f || next[(size_t) b * R + kns::profile_index(k, 1)] != 1.0f;
-        limit->profile.swap(next);
-        limit->profile_any = any;
-        ++limit->profile_rev;
+        settings->profile.swap(next);
+        settings->profile_any = any;
+        ++settings->profile_rev;
         return PV_STATUS_SUCCESS;
     });
 }
 
-void get_band_profile(const MinGain &limit, int32_t b, float *floor, float *ceil) {
+void get_band_profile(const HandleSettings &settings, int32_t b, float *floor, float *ceil) {
     for (int k = 0; k < PV_KOALA_NUM_BINS; ++k) {
-        const bool set = !limit.profile.empty();
-        if (floor) floor[k] = set ? limit.profile[(size_t) b * kns::kProfileRow + kns::profile_index(k, 0)] : 0.0f;
-        if (ceil) ceil[k] = set ? limit.profile[(size_t) b * kns::kProfileRow + kns::profile_index(k, 1)] : 1.0f;
+        const bool set = !settings.profile.empty();
+        if (floor) floor[k] = set ? settings.profile[(size_t) b * kns::kProfileRow + kns::profile_index(k, 0)] : 0.0f;
+        if (ceil) ceil[k] = set ? settings.profile[(size_t) b * kns::kProfileRow + kns::profile_index(k, 1)] : 1.0f;
     }
 }
 
@@ -592,7 +546,7 @@ PV_API pv_status_t pv_koala_process(pv_koala_t *object, const int16_t *pcm, int1
         push_error(0x64, "Argument `enhanced_pcm` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    return advance(object->engine, object->limit, {1, pcm, enhanced_pcm, nullptr, nullptr, /*host_contract=*/true});
+    return advance(object->engine, object->settings, {1, pcm, enhanced_pcm, nullptr, nullptr, /*host_contract=*/true});
 }
 
 PV_API pv_status_t pv_koala_process_report(pv_koala_t *object, const int16_t *pcm, int16_t *enhanced_pcm, float report[4]) {
@@ -604,7 +558,7 @@ PV_API pv_status_t pv_koala_process_report(pv_koala_t *object, const int16_t *pc
     }
     kns::Call call{1, pcm, enhanced_pcm, nullptr, nullptr, /*host_contract=*/true};
     call.report = report;
-    return advance(object->engine, object->limit, call);
+    return advance(object->engine, object->settings, call);
 }
 
 PV_API pv_status_t pv_koala_reset(pv_koala_t *object) {
@@ -700,7 +654,7 @@ PV_API pv_status_t pv_koala_batch_process_chunk(pv_koala_batch_t *object, int32_
     t_stack.clear();
     const pv_status_t st = check_call(object, num_frames, pcm, enhanced);
     if (st != PV_STATUS_SUCCESS) return st;
-    return advance(object->engine, object->limit, {num_frames, pcm, enhanced});
+    return advance(object->engine, object->settings, {num_frames, pcm, enhanced});
 }
 
 PV_API pv_status_t pv_koala_batch_process_chunk_async(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
@@ -709,7 +663,7 @@ PV_API pv_status_t pv_koala_batch_process_chunk_async(pv_koala_batch_t *object, 
     pv_status_t st = check_call(object, num_frames, pcm, enhanced);
     if (st == PV_STATUS_SUCCESS) st = check_synchronous(object);
     if (st != PV_STATUS_SUCCESS) return st;
-    return advance(object->engine, object->limit, {num_frames, pcm, enhanced}, /*async=*/true);
+    return advance(object->engine, object->settings, {num_frames, pcm, enhanced}, /*async=*/true);
 }
 
 PV_API pv_status_t pv_koala_batch_process_chunk_resets(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
@@ -718,7 +672,7 @@ PV_API pv_status_t pv_koala_batch_process_chunk_resets(pv_koala_batch_t *object,
     pv_status_t st = check_call(object, num_frames, pcm, enhanced);
     if (st == PV_STATUS_SUCCESS) st = check_resets(object, num_frames, reset);
     if (st != PV_STATUS_SUCCESS) return st;
-    return advance(object->engine, object->limit, {num_frames, pcm, enhanced, reset});
+    return advance(object->engine, object->settings, {num_frames, pcm, enhanced, reset});
 }
 
 PV_API pv_status_t pv_koala_batch_process_chunk_resets_async(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
@@ -728,7 +682,7 @@ PV_API pv_status_t pv_koala_batch_process_chunk_resets_async(pv_koala_batch_t *o
     if (st == PV_STATUS_SUCCESS) st = check_resets(object, num_frames, reset);
     if (st == PV_STATUS_SUCCESS) st = check_synchronous(object);
     if (st != PV_STATUS_SUCCESS) return st;
-    return advance(object->engine, object->limit, {num_frames, pcm, enhanced, reset}, /*async=*/true);
+    return advance(object->engine, object->settings, {num_frames, pcm, enhanced, reset}, /*async=*/true);
 }
 
 PV_API pv_status_t pv_koala_batch_process_chunk_hold(pv_koala_batch_t *object, int32_t num_frames, const int16_t *pcm,
@@ -736,7 +690,7 @@ PV_API pv_status_t pv_koala_batch_process_chunk_hold(pv_koala_batch_t *object, i
     t_stack.clear();
     const pv_status_t st = check_call(object, num_frames, pcm, enhanced);
     if (st != PV_STATUS_SUCCESS) return st;
-    return advance(object->engine, object->limit, {num_frames, pcm, enhanced, nullptr, hold});
+    return advance(object->engine, object->settings, {num_frames, pcm, enhanced, nullptr, hold});
 }
 
 // ---- one extensible entry point (the frame report rides on it)
@@ -759,7 +713,7 @@ PV_API pv_status_t pv_koala_batch_process_call(pv_koala_batch_t *object, const p
     kns::Call c{call->num_frames, call->pcm, call->enhanced, call->reset, call->hold};
     c.report = call->report;
     // (hold with reset, hold with asynchronous: refused by the engine before it touches anything, as for the dedicated entry points)
-    return advance(object->engine, object->limit, c, call->asynchronous != 0);
+    return advance(object->engine, object->settings, c, call->asynchronous != 0);
 }
 
 // ---- attenuation limit
@@ -767,7 +721,7 @@ PV_API pv_status_t pv_koala_batch_process_call(pv_koala_batch_t *object, const p
 PV_API pv_status_t pv_koala_batch_set_min_gain(pv_koala_batch_t *object, int32_t count, const int32_t *streams, const float *gains) {
     t_stack.clear();
     if (!object) return check_object(object);
-    return set_min_gain(&object->limit, object->engine->num_streams(), count, streams, gains);
+    return set_min_gain(&object->settings, object->engine->num_streams(), count, streams, gains);
 }
 
 PV_API pv_status_t pv_koala_batch_get_min_gain(const pv_koala_batch_t *object, float *gains) {
@@ -776,14 +730,14 @@ PV_API pv_status_t pv_koala_batch_get_min_gain(const pv_koala_batch_t *object, f
         push_error(0x64, "Argument `%s` is NULL.", object ? "gains" : "object");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    memcpy(gains, object->limit.gain.data(), object->limit.gain.size() * sizeof(float));
+    memcpy(gains, object->settings.gain.data(), object->settings.gain.size() * sizeof(float));
     return PV_STATUS_SUCCESS;
 }
 
 PV_API pv_status_t pv_koala_set_min_gain(pv_koala_t *object, float gain) {
     t_stack.clear();
     if (!object) return check_object(object);
-    return set_min_gain(&object->limit, 1, 1, nullptr, &gain);
+    return set_min_gain(&object->settings, 1, 1, nullptr, &gain);
 }
 
 PV_API pv_status_t pv_koala_get_min_gain(const pv_koala_t *object, float *gain) {
@@ -792,7 +746,7 @@ PV_API pv_status_t pv_koala_get_min_gain(const pv_koala_t *object, float *gain) 
         push_error(0x64, "Argument `%s` is NULL.", object ? "gain" : "object");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    *gain = object->limit.gain[0];
+    *gain = object->settings.gain[0];
     return PV_STATUS_SUCCESS;
 }
 
@@ -802,7 +756,7 @@ PV_API pv_status_t pv_koala_batch_set_band_profile(pv_koala_batch_t *object, int
                                                    const float *ceil) {
     t_stack.clear();
     if (!object) return check_object(object);
-    return set_band_profile(&object->limit, object->engine->num_streams(), count, streams, floor, ceil);
+    return set_band_profile(&object->settings, object->engine->num_streams(), count, streams, floor, ceil);
 }
 
 PV_API pv_status_t pv_koala_batch_get_band_profile(const pv_koala_batch_t *object, int32_t stream, float *floor, float *ceil) {
@@ -815,14 +769,14 @@ PV_API pv_status_t pv_koala_batch_get_band_profile(const pv_koala_batch_t *objec
         push_error(0x66, "`stream` %d is outside [0, %d).", stream, object->engine->num_streams());
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    get_band_profile(object->limit, stream, floor, ceil);
+    get_band_profile(object->settings, stream, floor, ceil);
     return PV_STATUS_SUCCESS;
 }
 
 PV_API pv_status_t pv_koala_set_band_profile(pv_koala_t *object, const float *floor, const float *ceil) {
     t_stack.clear();
     if (!object) return check_object(object);
-    return set_band_profile(&object->limit, 1, 1, nullptr, floor, ceil);
+    return set_band_profile(&object->settings, 1, 1, nullptr, floor, ceil);
 }
 
 PV_API pv_status_t pv_koala_get_band_profile(const pv_koala_t *object, float *floor, float *ceil) {
@@ -831,7 +785,7 @@ PV_API pv_status_t pv_koala_get_band_profile(const pv_koala_t *object, float *fl
         push_error(0x64, "Argument `object` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    get_band_profile(object->limit, 0, floor, ceil);
+    get_band_profile(object->settings, 0, floor, ceil);
     return PV_STATUS_SUCCESS;
 }
 

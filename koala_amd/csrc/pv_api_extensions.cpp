@@ -91,25 +91,8 @@ PV_API pv_status_t pv_koala_batch_process_packets(pv_koala_batch_t *object, cons
         return PV_STATUS_INVALID_ARGUMENT;
     }
     kns::PacketCall c{call->max_samples, call->counts, call->pcm, call->enhanced, call->restart, call->report, call->report_frames, call->frames};
-    if (kns_api::check_band_profile(object->limit) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
-    if (object->limit.any || object->limit.link || object->limit.profile_any) {
-        c.min_gain = object->limit.gain.data();
-        c.min_gain_rev = object->limit.rev;
-    }
-    if (object->limit.profile_any) {
-        c.band_profile = object->limit.profile.data();
-        c.band_profile_rev = object->limit.profile_rev;
-    }
-    c.channel_link = object->limit.link;
-    if (kns_api::check_level(object->limit, object->engine, false) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
-    if (object->limit.level_any) {
-        c.level = object->limit.level.data();
-        c.level_rev = object->limit.level_rev;
-    }
-    if (kns_api::check_limiter(object->limit, object->engine, false) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
-    kns_api::carry_limiter(object->limit, &c);
-    if (kns_api::check_comfort(object->limit, object->engine, false) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
-    kns_api::carry_comfort(object->limit, &c);
+    if (kns_api::check_settings(object->settings, object->engine, false) != PV_STATUS_SUCCESS) return PV_STATUS_INVALID_ARGUMENT;
+    kns_api::carry(object->settings, &c.opt);
     return kns_api::guarded([&] {
         std::string err;
         const kns::Status status = object->engine->run_packets(c, &err);
@@ -244,7 +227,7 @@ PV_API pv_status_t pv_koala_batch_set_channel_link(pv_koala_batch_t *object, int
                          "lie inside one 16-row mask tile.", channels);
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    object->limit.link = link;
+    object->settings.link = link;
     return PV_STATUS_SUCCESS;
 }
 
@@ -254,7 +237,7 @@ PV_API pv_status_t pv_koala_batch_get_channel_link(const pv_koala_batch_t *objec
         push_error(0x64, "Argument `%s` is NULL.", object ? "link" : "object");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    *link = object->limit.link;
+    *link = object->settings.link;
     return PV_STATUS_SUCCESS;
 }
 
@@ -281,8 +264,8 @@ PV_API pv_status_t pv_koala_batch_set_high_band(pv_koala_batch_t *object, int32_
         push_error(0x66, "PV_KOALA_HIGH_BAND_CARRY is not available yet on a packet handle.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    if (mode == PV_KOALA_HIGH_BAND_CARRY && !object->limit.high_band) ++object->limit.high_band_epoch;
-    object->limit.high_band = mode;
+    if (mode == PV_KOALA_HIGH_BAND_CARRY && !object->settings.high_band) ++object->settings.high_band_epoch;
+    object->settings.high_band = mode;
     return PV_STATUS_SUCCESS;
 }
 
@@ -292,6 +275,6 @@ PV_API pv_status_t pv_koala_batch_get_high_band(const pv_koala_batch_t *object, 
         push_error(0x64, "Argument `%s` is NULL.", object ? "mode" : "object");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    *mode = object->limit.high_band;
+    *mode = object->settings.high_band;
     return PV_STATUS_SUCCESS;
 }

@@ -1,8 +1,7 @@
 // pv_level.cpp -- the C ABI of the output leveller (include/pv_koala_batch.h, OUTPUT LEVELLER; DESIGN.md section 2, eleventh extension):
 // pv_koala_batch_set_level / _get_level, pv_koala_batch_get_level_state / _set_level_state, pv_koala_set_level / _get_level.  The setting is
-// the handle's (pv_api_internal.h, MinGain::level) and travels with every call; the state is the engine's.
+// the handle's (pv_api_internal.h, HandleSettings::level) and travels with every call; the state is the engine's.
 #include <cmath>
-#include <string.h>
 
 #include "pv_api_internal.h"
 
@@ -44,64 +43,23 @@ bool check_setting(int32_t i, const pv_koala_level_t &s) {
 // what a handle holds for a stream until its first accepted change: off, and fields that would be accepted as they are
 kns::LevelSetting neutral() { return kns::LevelSetting{0, 1.0f, 1.0f, 1.0f, 1.0f, 0.0f, 1.0f, 1.0f, 1.0f}; }
 
-// pv_koala_batch_set_level / pv_koala_set_level: every entry is checked before anything is changed
-pv_status_t set_level(MinGain *limit, int32_t B, int32_t count, const int32_t *streams, const pv_koala_level_t *settings) {
-    if (!settings) {
-        push_error(0x64, "Argument `settings` is NULL.");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    if (count < 1 || count > B) {
-        push_error(0x66, "`count` %d is outside [1, %d].", count, B);
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    const int32_t stride = settings[0].struct_size;
-    if (stride < kSize || stride % 4 != 0) {
-        push_error(0x66, "`struct_size` %d is not sizeof(pv_koala_level_t) = %d (or more, in whole words, from a later header).", stride, kSize);
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    return kns_api::guarded([&] {
-        std::vector<kns::LevelSetting> next(limit->level);
-        if (next.empty()) next.assign((size_t) B, neutral());
-        std::vector<uint8_t> listed((size_t) B, 0);
-        for (int32_t i = 0; i < count; ++i) {
-            const int32_t b = streams ? streams[i] : i;
-            if (b < 0 || b >= B) {
-                push_error(0x66, "`streams[%d]` = %d is outside [0, %d).", i, b, B);
-                return PV_STATUS_INVALID_ARGUMENT;
-            }
-            if (listed[b]) {
-                push_error(0x66, "`streams[%d]`: slot %d is listed twice.", i, b);
-                return PV_STATUS_INVALID_ARGUMENT;
-            }
-            listed[b] = 1;
-            pv_koala_level_t s;
-            memcpy(&s, (const char *) settings + (size_t) i * stride, sizeof(s));
-            if (s.struct_size != stride) {
-                push_error(0x66, "setting %d: `struct_size` %d differs from that of setting 0, %d.", i, s.struct_size, stride);
-                return PV_STATUS_INVALID_ARGUMENT;
-            }
-            if (!check_setting(i, s)) return PV_STATUS_INVALID_ARGUMENT;
-            next[b] = kns::LevelSetting{s.on, s.target, s.max_boost, s.max_cut, s.theta, s.e_floor + 0.0f, s.a_up, s.a_down, s.slew};
-        }
-        bool any = false;
-        for (const kns::LevelSetting &s : next) any = any || s.on != 0;
-        limit->level.swap(next);
-        limit->level_any = any;
-        ++limit->level_rev;
-        return PV_STATUS_SUCCESS;
-    });
+// pv_koala_batch_set_level / pv_koala_set_level (kns_api::set_table: every entry is checked before anything is changed)
+pv_status_t set_level(HandleSettings *h, int32_t B, int32_t count, const int32_t *streams, const pv_koala_level_t *settings) {
+    return kns_api::set_table(&h->level, &h->level_any, &h->level_rev, neutral(), B, count, streams, settings, "pv_koala_level_t", "setting", "setting 0",
+                              [](int32_t i, int32_t, const pv_koala_level_t &s, kns::LevelSetting *to) {
+                                  if (!check_setting(i, s)) return false;
+                                  *to = kns::LevelSetting{s.on, s.target, s.max_boost, s.max_cut, s.theta, s.e_floor + 0.0f, s.a_up, s.a_down, s.slew};
+                                  return true;
+                              });
 }
 
-pv_status_t get_level(const MinGain &limit, int32_t b, pv_koala_level_t *setting) {
+pv_status_t get_level(const HandleSettings &h, int32_t b, pv_koala_level_t *setting) {
     if (!setting) {
         push_error(0x64, "Argument `setting` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    if (setting->struct_size < kSize) {
-        push_error(0x66, "`struct_size` %d is not sizeof(pv_koala_level_t) = %d (or more, from a later header).", setting->struct_size, kSize);
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    const kns::LevelSetting s = limit.level.empty() ? neutral() : limit.level[(size_t) b];
+    if (!kns_api::getter_size_ok(setting->struct_size, kSize, "pv_koala_level_t")) return PV_STATUS_INVALID_ARGUMENT;
+    const kns::LevelSetting s = h.level.empty() ? neutral() : h.level[(size_t) b];
     setting->on = s.on;
     setting->target = s.target, setting->max_boost = s.max_boost, setting->max_cut = s.max_cut, setting->theta = s.theta;
     setting->e_floor = s.e_floor, setting->a_up = s.a_up, setting->a_down = s.a_down, setting->slew = s.slew;
@@ -109,32 +67,19 @@ pv_status_t get_level(const MinGain &limit, int32_t b, pv_koala_level_t *setting
 }
 
 pv_status_t level_state(pv_koala_batch_t *object, bool set, int32_t count, const int32_t *streams, float *state) {
-    kns_api::clear_errors();
-    if (!object || !state) {
-        push_error(0x64, "Argument `%s` is NULL.", object ? "state" : "object");
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    const int32_t B = object->engine->num_streams();
-    if (count < 1 || count > B) {
-        push_error(0x66, "`count` %d is outside [1, %d].", count, B);
-        return PV_STATUS_INVALID_ARGUMENT;
-    }
-    for (int32_t i = 0; set && i < count; ++i) {
+    const auto value_ok = [&](int32_t i) {
         const float lvl = state[2 * i], gain = state[2 * i + 1];
         if (!(lvl >= 0.0f) || !std::isfinite(lvl)) {
             push_error(0x66, "state %d: `lvl` %g is not an energy >= 0.", i, (double) lvl);
-            return PV_STATUS_INVALID_ARGUMENT;
+            return false;
         }
         if (!(gain > 0.0f) || !std::isfinite(gain)) {
             push_error(0x66, "state %d: `gain` %g is not a gain > 0.", i, (double) gain);
-            return PV_STATUS_INVALID_ARGUMENT;
+            return false;
         }
-    }
-    return kns_api::guarded([&] {
-        std::string err;
-        const kns::Status status = object->engine->level_state(set, count, streams, state, &err);
-        return status == kns::Status::kOk ? PV_STATUS_SUCCESS : kns_api::engine_failure(status, 0x33E, err);
-    });
+        return true;
+    };
+    return kns_api::stage_state(object, set, count, streams, state, "state", value_ok, &kns::Engine::level_state, 0x33E);
 }
 
 }  // namespace
@@ -145,7 +90,7 @@ PV_API pv_status_t pv_koala_batch_set_level(pv_koala_batch_t *object, int32_t co
         push_error(0x64, "Argument `object` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    return set_level(&object->limit, object->engine->num_streams(), count, streams, settings);
+    return set_level(&object->settings, object->engine->num_streams(), count, streams, settings);
 }
 
 PV_API pv_status_t pv_koala_batch_get_level(const pv_koala_batch_t *object, int32_t stream, pv_koala_level_t *setting) {
@@ -158,7 +103,7 @@ PV_API pv_status_t pv_koala_batch_get_level(const pv_koala_batch_t *object, int3
         push_error(0x66, "`stream` %d is outside [0, %d).", stream, object->engine->num_streams());
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    return get_level(object->limit, stream, setting);
+    return get_level(object->settings, stream, setting);
 }
 
 PV_API pv_status_t pv_koala_batch_get_level_state(pv_koala_batch_t *object, int32_t count, const int32_t *streams, float *state) {
@@ -175,7 +120,7 @@ PV_API pv_status_t pv_koala_set_level(pv_koala_t *object, const pv_koala_level_t
         push_error(0x64, "Argument `object` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    return set_level(&object->limit, 1, 1, nullptr, setting);
+    return set_level(&object->settings, 1, 1, nullptr, setting);
 }
 
 PV_API pv_status_t pv_koala_get_level(const pv_koala_t *object, pv_koala_level_t *setting) {
@@ -184,5 +129,5 @@ PV_API pv_status_t pv_koala_get_level(const pv_koala_t *object, pv_koala_level_t
         push_error(0x64, "Argument `object` is NULL.");
         return PV_STATUS_INVALID_ARGUMENT;
     }
-    return get_level(object->limit, 0, setting);
+    return get_level(object->settings, 0, setting);
 }

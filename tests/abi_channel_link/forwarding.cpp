@@ -41,29 +41,29 @@ int main(int argc, char **argv) {
     // link off, no limit: the plain call -- no table, no link
     for (int w = 0; w < 4; ++w) {
         frame_call(w);
-        EXPECT(kns::g_seen_call.channel_link == 0 && kns::g_seen_call.min_gain == nullptr);
+        EXPECT(kns::g_seen_call.opt.channel_link == 0 && kns::g_seen_call.opt.min_gain == nullptr);
     }
     // link on, no limit: the setting, and the gain table (all zero) with it -- the linked kernels read it
     EXPECT(pv_koala_batch_set_channel_link(h, PV_KOALA_CHANNEL_LINK_MAX) == PV_STATUS_SUCCESS);
     for (int w = 0; w < 4; ++w) {
         frame_call(w);
-        EXPECT(kns::g_seen_call.channel_link == 1 && kns::g_seen_call.min_gain != nullptr);
-        for (int b = 0; kns::g_seen_call.min_gain && b < B; ++b) EXPECT(kns::g_seen_call.min_gain[b] == 0.0f);
+        EXPECT(kns::g_seen_call.opt.channel_link == 1 && kns::g_seen_call.opt.min_gain != nullptr);
+        for (int b = 0; kns::g_seen_call.opt.min_gain && b < B; ++b) EXPECT(kns::g_seen_call.opt.min_gain[b] == 0.0f);
     }
     // link on beside a limit: the handle's gains and their revision
     g[1] = 0.5f;
     EXPECT(pv_koala_batch_set_min_gain(h, B, nullptr, g.data()) == PV_STATUS_SUCCESS);
-    const unsigned rev0 = kns::g_seen_call.min_gain_rev;
+    const unsigned rev0 = kns::g_seen_call.opt.min_gain_rev;
     frame_call(0);
-    EXPECT(kns::g_seen_call.channel_link == 1 && kns::g_seen_call.min_gain && kns::g_seen_call.min_gain[1] == 0.5f && kns::g_seen_call.min_gain_rev != rev0);
+    EXPECT(kns::g_seen_call.opt.channel_link == 1 && kns::g_seen_call.opt.min_gain && kns::g_seen_call.opt.min_gain[1] == 0.5f && kns::g_seen_call.opt.min_gain_rev != rev0);
     // link off again, the limit stays: the table still travels, the link does not
     EXPECT(pv_koala_batch_set_channel_link(h, PV_KOALA_CHANNEL_LINK_NONE) == PV_STATUS_SUCCESS);
     frame_call(0);
-    EXPECT(kns::g_seen_call.channel_link == 0 && kns::g_seen_call.min_gain && kns::g_seen_call.min_gain[1] == 0.5f);
+    EXPECT(kns::g_seen_call.opt.channel_link == 0 && kns::g_seen_call.opt.min_gain && kns::g_seen_call.opt.min_gain[1] == 0.5f);
     // a refused change leaves what the next call carries
     EXPECT(pv_koala_batch_set_channel_link(h, 2) == PV_STATUS_INVALID_ARGUMENT && drain() == 1);
     frame_call(3);
-    EXPECT(kns::g_seen_call.channel_link == 0);
+    EXPECT(kns::g_seen_call.opt.channel_link == 0);
     pv_koala_batch_delete(h);
 
     // ---- a packet handle: PacketCall
@@ -80,13 +80,13 @@ int main(int argc, char **argv) {
         EXPECT(pv_koala_batch_process_packets(h, &call) == PV_STATUS_SUCCESS && kns::g_seen_packet_calls == before + 1);
     };
     packet_call();
-    EXPECT(kns::g_seen_packets.channel_link == 0 && kns::g_seen_packets.min_gain == nullptr);
+    EXPECT(kns::g_seen_packets.opt.channel_link == 0 && kns::g_seen_packets.opt.min_gain == nullptr);
     EXPECT(pv_koala_batch_set_channel_link(h, PV_KOALA_CHANNEL_LINK_MAX) == PV_STATUS_SUCCESS);
     packet_call();
-    EXPECT(kns::g_seen_packets.channel_link == 1 && kns::g_seen_packets.min_gain != nullptr && kns::g_seen_packets.min_gain[0] == 0.0f);
+    EXPECT(kns::g_seen_packets.opt.channel_link == 1 && kns::g_seen_packets.opt.min_gain != nullptr && kns::g_seen_packets.opt.min_gain[0] == 0.0f);
     EXPECT(pv_koala_batch_set_channel_link(h, PV_KOALA_CHANNEL_LINK_NONE) == PV_STATUS_SUCCESS);
     packet_call();
-    EXPECT(kns::g_seen_packets.channel_link == 0 && kns::g_seen_packets.min_gain == nullptr);
+    EXPECT(kns::g_seen_packets.opt.channel_link == 0 && kns::g_seen_packets.opt.min_gain == nullptr);
     pv_koala_batch_delete(h);
     if (g_fail) fprintf(stderr, "%d expectation(s) failed\n", g_fail);
     return g_fail ? 1 : 0;
