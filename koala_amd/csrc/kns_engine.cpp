@@ -938,8 +938,8 @@ void Engine::UploadRing::release() {
     }
 }
 
-// Per-frame stream resets of the call about to run (Call::resets, uint8 [B][T] host memory), before anything of the call is enqueued;
-// `table` is the caller's, fresh.  Resets at frame 0 only: the reset kernel in front of the call, which then takes its normal route.
+// Per-frame stream resets of the call about to run (Call::resets, uint8 [B][T] host memory), before anything of the call is enqueued
+// (begin_call); `table` is the setup's, fresh.  Resets at frame 0 only: the reset kernel in front of the call, which then takes its normal route.
 // Resets at some frame t > 0 (refused for a several-frame front-end, whose feature history the reset arms do not rebuild): the mask is
 // packed per (m-tile, frame) into a page-locked ring slot -- bit r of word [mt][t] = stream 16 mt + r restarts right before frame t -- and
 // `table` says so; run_device uploads the slot on the stream of the call's kernels and reads it through the kernels' reset arms
@@ -1040,29 +1040,66 @@ bool Engine::put_table(SettingTable *t, size_t row, const void *rows, unsigned r
     return true;
 }
 
-// The attenuation limit of the call about to run (StreamOptions::min_gain, float [B]).  No limit: *table = nullptr and nothing else happens.
-// Otherwise *table = the device table [Bpad] (put_table).
-bool Engine::begin_min_gain(const Call &c, const float **table, std::string *err) {
-    *table = nullptr;
-    if (!c.opt.min_gain) return true;
-    if (!put_table(&mg_tab_, 4, c.opt.min_gain, c.opt.min_gain_rev, "the per-stream attenuation limit", err)) return false;
-    *table = (const float *) mg_tab_.d;
-    return true;
+const Engine::OutputStage (&Engine::output_stages())[3] {
+    static const OutputStage stages[3] = {
+        {kStageLevel, "the output leveller", "a levelling call", "the output leveller", false, &Engine::level_ready, &StreamOptions::level_rev,
+         {{&Engine::lv_tab_, sizeof(LevelSetting), [](const StreamOptions &o) -> const void * { return o.level; }}, {}}},
+        {kStageLimiter, "the peak limiter", "a limiting call", "the peak limiter", false, &Engine::limiter_ready, &StreamOptions::limiter_rev,
+         {{&Engine::lm_tab_, sizeof(LimiterSetting), [](const StreamOptions &o) -> const void * { return o.limiter; }}, {}}},
+        {kStageComfort, "comfort noise", "a call with comfort noise", "the comfort noise", true, &Engine::comfort_ready, &StreamOptions::comfort_rev,
+         {{&Engine::cf_tab_, sizeof(ComfortSetting), [](const StreamOptions &o) -> const void * { return o.comfort; }},
+          {&Engine::cfa_tab_, (size_t) kComfortRow * 4, [](const StreamOptions &o) -> const void * { return o.comfort_amp; }}}},
+    };
+    return stages;
 }
 
-// The band profile of the call about to run (StreamOptions::band_profile, float [B][kProfileRow] in the table's own order), like the limit
-// above: nothing without one; otherwise the device table [Bpad][kProfileRow] -- 2 KiB per stream.
-bool Engine::begin_band_profile(const Call &c, const float **table, std::string *err) {
-    *table = nullptr;
-    if (!c.opt.band_profile) return true;
-    if (c.opt.channel_link || c.high_band || !c.opt.min_gain) {  // (the owner refuses these by name before the engine is reached)
-        *err = !c.opt.min_gain ? "a call with a band profile carries the handle's minimum gains (all zero where no limit is in force)."
-                               : "a band profile is not combined with linked channels nor with the high-band carry.";
+bool Engine::refuse_stages(const StreamOptions &o, const char *why, std::string *err) {
+    for (const OutputStage &s : output_stages())
+        if (s.on(o)) {
+            *err = std::string(s.name) + why;
+            return true;
+        }
+    return false;
+}
+
+bool Engine::begin_call(const Call &c, bool device_rows, CallSetup *cs, std::string *err) {
+    const StreamOptions &o = c.opt;
+    if (o.band_profile && (o.channel_link || c.high_band || !o.min_gain)) {
+        *err = !o.min_gain ? "a call with a band profile carries the handle's minimum gains (all zero where no limit is in force)."
+                           : "a band profile is not combined with linked channels nor with the high-band carry.";
         return false;
     }
-    if (!put_table(&pf_tab_, (size_t) kProfileRow * 4, c.opt.band_profile, c.opt.band_profile_rev, "the band profile", err)) return false;
-    *table = (const float *) pf_tab_.d;
-    return true;
+    // (linked channels and output stages: process() hands such a call on with device rows, so the host routes, the one-frame graph among
+    // them, never see one: never quietly unlinked or without a stage.  Comfort noise: its kernels carry the gains and the profile's clamp)
+    cs->link = o.channel_link ? ch_ : 0;
+    if (cs->link && (!o.min_gain || !device_rows)) {
+        *err = !o.min_gain ? "a linked call carries the handle's minimum gains." : "a linked call runs on device rows only.";
+        return false;
+    }
+    for (const OutputStage &s : output_stages()) {
+        if (!s.on(o)) continue;
+        cs->stages |= s.bit;
+        if (!device_rows || (s.carries_profile && !o.band_profile) || cs->link || c.high_band) {
+            *err = !device_rows                          ? std::string(s.call) + " runs on device rows only." :
+                   s.carries_profile && !o.band_profile ? std::string(s.call) + " carries the handle's band profile (neutral where none is in force)." :
+                                                          std::string(s.name) + " is not combined with linked channels nor with the high-band carry.";
+            return false;
+        }
+    }
+    // (the reset mask, the gains and the profile are copied into upload slots of this call: the caller may overwrite them when this returns)
+    if (!begin_resets(c.T, c.resets, &cs->resets, err)) return false;
+    if (o.min_gain && !put_table(&mg_tab_, 4, o.min_gain, o.min_gain_rev, "the per-stream attenuation limit", err)) return false;
+    if (o.band_profile && !put_table(&pf_tab_, (size_t) kProfileRow * 4, o.band_profile, o.band_profile_rev, "the band profile", err)) return false;
+    cs->min_gain = o.min_gain ? (const float *) mg_tab_.d : nullptr;
+    cs->profile = o.band_profile ? (const float *) pf_tab_.d : nullptr;
+    for (const OutputStage &s : output_stages()) {
+        if (!(cs->stages & s.bit)) continue;
+        if (!(this->*s.ready)(err)) return false;
+        for (const OutputStage::Table &t : s.table)
+            if (t.tab && !put_table(&(this->*t.tab), t.row, t.rows(o), o.*s.rev, s.what, err)) return false;
+    }
+    if (cs->stages & kStageComfort) cs->comfort_set = (const ComfortSetting *) cf_tab_.d, cs->comfort_amp = (const float *) cfa_tab_.d;
+    return !cs->stages || control_rows(c, &cs->ctl, err);
 }
 
 // The staging of the frame report of host-pointer calls, before anything of the call is enqueued and outside any capture.
@@ -1281,7 +1318,7 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
     const int mtb = Bpad_ / 16;
     last_T_ = T;
     // per-frame stream resets in these frames (begin_resets): the chunked route with the kernels' reset arms, whatever the batch size
-    ResetTable *table = slice.resets && slice.resets->slot >= 0 ? slice.resets : nullptr;
+    ResetTable *table = !slice.without_reset_table && slice.call->resets.slot >= 0 ? &slice.call->resets : nullptr;
     const bool resets = table && std::any_of(table->frame.begin() + slice.t0, table->frame.begin() + slice.t0 + T, [](uint8_t v) { return v != 0; });
     if (resets && !table->uploaded) {  // the call's table, on the stream of its kernels (its first sub-chunk that needs it)
         (void) hipMemcpyAsync(d_rs_, rs_ring_.host[table->slot], (size_t) mtb * table->T * 4, hipMemcpyHostToDevice, stream_);
@@ -1594,10 +1631,11 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
         sy.resets = rs;
         sy.rs_pitch = rs_pitch;
         sy.rs_t0 = rs_t0 + t0c;
-        sy.min_gain = slice.min_gain;
-        sy.link = slice.link;
-        sy.profile = slice.profile;
-        if (slice.comfort) sy.comfort_amp = (const float *) cfa_tab_.d, sy.comfort_set = (const ComfortSetting *) cf_tab_.d, sy.comfort_n = d_cf_n_ + t0c;  // (like `report`: rows T frames apart)
+        const CallSetup &cs = *slice.call;  // (what the call has prepared: read here and nowhere else below)
+        sy.min_gain = cs.min_gain;
+        sy.link = cs.link;
+        sy.profile = cs.profile;
+        if (cs.comfort_set) sy.comfort_amp = cs.comfort_amp, sy.comfort_set = cs.comfort_set, sy.comfort_n = d_cf_n_ + t0c;  // (like `report`: rows T frames apart)
         sy.report = slice.d_report ? slice.d_report + (size_t) t0c * 4 : nullptr;  // (like `out`: the slice's first frame, rows T frames apart)
 #ifdef KNS_DEV
         last_synth_seg_ = sy.seg;
@@ -1769,7 +1807,7 @@ std::vector<int> Engine::host_schedule(int T) const {
     return sched;
 }
 
-bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *resets, const float *min_gain, const float *profile, std::string *err) {
+bool Engine::process_host_pipelined(const Call &call, bool pinned, CallSetup *setup, std::string *err) {
     const int T = call.T;
     const int16_t *pcm = call.pcm;
     int16_t *out = call.out;
@@ -1808,7 +1846,7 @@ bool Engine::process_host_pipelined(const Call &call, bool pinned, ResetTable *r
         // ---- kernels (d_out_ slot s was last drained by the D2H of chunk c - 2)
         check(hipStreamWaitEvent(stream_, ev_in_[s], 0));
         if (c >= 2) check(hipStreamWaitEvent(stream_, ev_out_[s], 0));
-        if (ok && !run_device({first[c], tc, d_in_ + s * slot, d_out_ + s * slot, true, resets, min_gain, report ? d_report_ + s * rslot : nullptr, 0, profile}, err)) {
+        if (ok && !run_device({first[c], tc, d_in_ + s * slot, d_out_ + s * slot, true, report ? d_report_ + s * rslot : nullptr, setup}, err)) {
             // copies of earlier sub-chunks may still be writing into the caller's buffers: let them finish first
             (void) hipStreamSynchronize(copy_in_);
             (void) hipStreamSynchronize(copy_out_);
@@ -1887,30 +1925,6 @@ bool Engine::async_wait(int max_in_flight, std::string *err) {
     return true;
 }
 
-// The output stages behind the mask (leveller, limiter, comfort noise) and what a refusal calls them.  Every site that refuses a stage -- an
-// entry, a route or a handle the stage is not combined with yet -- walks this table, in the order the stages have always been checked.
-namespace {
-struct OutputStage {
-    const char *name, *call;             // "<name> is not ...", "<call> runs on ..."
-    bool (*on)(const StreamOptions &o);  // present on this call
-    bool carries_profile;                // its kernels carry the band profile's clamp: such a call comes with the profile (and its own tables)
-};
-const OutputStage kOutputStages[] = {
-    {"the output leveller", "a levelling call", [](const StreamOptions &o) { return o.level != nullptr; }, false},
-    {"the peak limiter", "a limiting call", [](const StreamOptions &o) { return o.limiter != nullptr; }, false},
-    {"comfort noise", "a call with comfort noise", [](const StreamOptions &o) { return o.comfort != nullptr; }, true},
-};
-// the first stage present on the call is refused for `why`
-bool refuse_stages(const StreamOptions &o, const char *why, std::string *err) {
-    for (const OutputStage &s : kOutputStages)
-        if (s.on(o)) {
-            *err = std::string(s.name) + why;
-            return true;
-        }
-    return false;
-}
-}  // namespace
-
 // One asynchronous host call = H2D on copy_in_, the kernels on the handle's stream, D2H on copy_out_, chained by events.  Up to
 // THREE calls are in flight: with two, a caller alternating between two buffer pairs cannot issue call n + 2 before call n's copy-out has
 // finished, which puts a slot's copy-in, kernels and copy-out in series (measured: 4.03 ms per 4096 x 64 frames = (2.8 + 2.6 + 2.8) / 2);
@@ -1984,12 +1998,8 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
         }
         async_busy_[ring3] = false;
     }
-    ResetTable table;
-    if (!begin_resets(T, c.resets, &table, err)) return Status::kRuntime;  // (the mask is packed into a ring slot of this call: the caller may overwrite it now)
-    const float *min_gain = nullptr;  // (the gains are copied into an upload slot of this call: the caller may change them now)
-    if (!begin_min_gain(c, &min_gain, err)) return Status::kRuntime;
-    const float *profile = nullptr;  // (... and the band profile: this call keeps the one it was issued under)
-    if (!begin_band_profile(c, &profile, err)) return Status::kRuntime;
+    CallSetup setup;  // (this call keeps the mask, the gains and the profile it was issued under: the caller may change them now)
+    if (!begin_call(c, false, &setup, err)) return Status::kRuntime;
     int16_t *din = s ? d_in2_ : d_in_, *dout = s ? d_out2_ : d_out_;
     float *drep = c.report ? (s ? d_report2_ : d_report_) : nullptr;  // (part of the call's staging slot: free when its samples' slot is)
     bool ok = true;
@@ -2003,7 +2013,7 @@ Status Engine::process_host_async(const Call &c, std::string *err) {
         (void) hipDeviceSynchronize();  // (a copy-in may have been enqueued: nothing of this call stays in flight)
         return Status::kRuntime;
     }
-    if (!run_device({0, T, din, dout, true, &table, min_gain, drep, 0, profile}, err)) {
+    if (!run_device({0, T, din, dout, true, drep, &setup}, err)) {
         (void) hipDeviceSynchronize();
         return Status::kRuntime;
     }
@@ -2032,7 +2042,6 @@ bool Engine::run_call(const Call &c, std::string *err) {
     int16_t *out = c.out;
     (void) hipSetDevice(device_);
     if (async_n_ && !drain_async(err)) return false;
-    ResetTable table;  // (this call's, filled by begin_resets: nothing of it outlives the call)
     const size_t bytes = (size_t) B_ * T * kFrame * 2;
     // (the single-stream ABI takes host buffers by contract: no driver query per frame on the latency path)
     const PointerKind kin = c.host_contract ? kPtrPageable : pointer_kind(pcm), kout = c.host_contract ? kPtrPageable : pointer_kind(out);
@@ -2047,57 +2056,26 @@ bool Engine::run_call(const Call &c, std::string *err) {
     }
     if (report && kin != kPtrDevice && !report_ready(false, err)) return false;
     const size_t rbytes = (size_t) B_ * T * 16;
-    const float *min_gain = nullptr;  // (this call's attenuation limit on the device, on the handle's stream in front of everything below)
-    if (!begin_min_gain(c, &min_gain, err)) return false;
-    const float *profile = nullptr;  // (... and its band profile)
-    if (!begin_band_profile(c, &profile, err)) return false;
-    // (linked channels: such a handle's calls arrive here with device pointers -- process() has split the channels into device rows -- so
-    // the host routes below, the one-frame graph among them, never see a linked call: no graph is captured with the linked kernel)
-    const int link = c.opt.channel_link ? ch_ : 0;
-    if (link && (!min_gain || kin != kPtrDevice)) {  // (never quietly unlinked: the host routes below build their slices without the link)
-        *err = !min_gain ? "a linked call carries the handle's minimum gains." : "a linked call runs on device rows only.";
+    const bool pipelined = kin != kPtrDevice && T > host_chunk_ && bytes >= host_pipeline_min_bytes_;
+    const char *pa = (const char *) pcm, *pb = (const char *) out;
+    // partial overlap: chunk c's copy-out would land on input chunks not yet read.  EXACT aliasing (enhanced == pcm) is fine:
+    // chunk c's output columns are chunk c's own input columns, which have been staged by then
+    if (pipelined && pa != pb && pa < pb + bytes && pb < pa + bytes) {
+        *err = "`pcm` and `enhanced` overlap: host-memory calls of this size are pipelined in sub-chunks and need disjoint buffers.";
         return false;
     }
-    // (output stages: such a call arrives here with device pointers -- process() takes host memory through its staging -- so the host routes
-    // below never see it; never quietly without a stage.  Comfort noise: its kernels carry the gains and the profile's clamp)
-    bool stages = false;
-    for (const OutputStage &s : kOutputStages) {
-        if (!s.on(c.opt)) continue;
-        stages = true;
-        if (kin != kPtrDevice || (s.carries_profile && !profile) || link || c.high_band) {
-            *err = kin != kPtrDevice                 ? std::string(s.call) + " runs on device rows only." :
-                   s.carries_profile && !profile ? std::string(s.call) + " carries the handle's band profile (neutral where none is in force)." :
-                                                   std::string(s.name) + " is not combined with linked channels nor with the high-band carry.";
-            return false;
-        }
-    }
-    // (their settings on the device; the limiter's launch stands in the place of the leveller's second one)
-    if (c.opt.level && !(level_ready(err) && put_table(&lv_tab_, sizeof(LevelSetting), c.opt.level, c.opt.level_rev, "the output leveller", err))) return false;
-    if (c.opt.limiter && !(limiter_ready(err) && put_table(&lm_tab_, sizeof(LimiterSetting), c.opt.limiter, c.opt.limiter_rev, "the peak limiter", err))) return false;
-    if (c.opt.comfort && !(comfort_ready(err) && put_table(&cf_tab_, sizeof(ComfortSetting), c.opt.comfort, c.opt.comfort_rev, "the comfort noise", err) &&
-                           put_table(&cfa_tab_, (size_t) kComfortRow * 4, c.opt.comfort_amp, c.opt.comfort_rev, "the comfort noise", err)))
-        return false;
+    CallSetup setup;  // (this call's tables, on the handle's stream in front of everything below: nothing of it outlives the call)
+    if (!begin_call(c, kin == kPtrDevice, &setup, err)) return false;
     if (kin == kPtrDevice) {
         const size_t n = (size_t) B_ * T * kFrame;
         const bool overlap = pcm < out + n && out < pcm + n;
         // (a levelling call reads its own report -- an output only, so asking for it into a buffer of the engine's changes no bit)
-        float *rep = c.opt.level && !report ? d_lv_rep_ : report;
-        const uint8_t *ctl = nullptr;  // (the stages' control rows, once for all of them)
-        // (comfort noise: the counter's launch in front of the call's kernels)
-        return begin_resets(T, c.resets, &table, err) && (!stages || control_rows(c, &ctl, err)) && (!c.opt.comfort || run_comfort(c, ctl, err)) &&
-               run_device({0, T, pcm, out, !overlap, &table, min_gain, rep, link, profile, c.opt.comfort != nullptr}, err) &&
-               ((!c.opt.level && !c.opt.limiter) || run_level(c, rep, report != nullptr, ctl, err));
+        float *rep = (setup.stages & kStageLevel) && !report ? d_lv_rep_ : report;
+        // (comfort noise: the counter's launch in front of the call's kernels; the limiter's stands in the place of the leveller's second one)
+        return (!(setup.stages & kStageComfort) || run_comfort(c, setup, err)) && run_device({0, T, pcm, out, !overlap, rep, &setup}, err) &&
+               (!(setup.stages & (kStageLevel | kStageLimiter)) || run_level(c, rep, report != nullptr, setup, err));
     }
-    if (T > host_chunk_ && bytes >= host_pipeline_min_bytes_) {
-        const char *pa = (const char *) pcm, *pb = (const char *) out;
-        // partial overlap: chunk c's copy-out would land on input chunks not yet read.  EXACT aliasing (enhanced == pcm) is fine:
-        // chunk c's output columns are chunk c's own input columns, which have been staged by then
-        if (pa != pb && pa < pb + bytes && pb < pa + bytes) {
-            *err = "`pcm` and `enhanced` overlap: host-memory calls of this size are pipelined in sub-chunks and need "
-                   "disjoint buffers.";
-            return false;
-        }
-        if (!begin_resets(T, c.resets, &table, err)) return false;
+    if (pipelined) {
         // On a caller's stream the kernels of the sub-chunks still run on the handle's OWN stream, fenced behind whatever the caller
         // has enqueued (the call is synchronous, so everything the caller enqueues later is behind it anyway): the handle's three
         // streams were created together and sit on three different hardware queues, while a foreign stream may share its queue with
@@ -2112,25 +2090,17 @@ bool Engine::run_call(const Call &c, std::string *err) {
                 stream_ = own_stream_;
         }
         const bool pinned = kin == kPtrPinned && kout == kPtrPinned && (!report || pointer_kind(report) == kPtrPinned);
-        const bool done = process_host_pipelined(c, pinned, &table, min_gain, profile, err);
+        const bool done = process_host_pipelined(c, pinned, &setup, err);
         stream_ = user;
         return done;
     }
-    if (!begin_resets(T, c.resets, &table, err)) return false;
     memcpy(h_in_, pcm, bytes);
-    if (T == 1 && use_graph_ && stream_ == own_stream_ && !profiling_ && !link) {
-        // frame-by-frame streaming: (copy-in,) the kernels of one frame (and copy-out) replayed as one hipGraph
-        // A captured frame has the state buffers it reads and writes baked in: one graph per combination of the three
-        // ping-pong indices.  (A single-frame call leaves history and tail in place and flips the hidden state only, but
-        // multi-frame calls in between flip the other two as well.)
+    if (T == 1 && use_graph_ && stream_ == own_stream_ && !profiling_ && !setup.link) {
+        // frame-by-frame streaming: (copy-in,) the kernels of one frame (and copy-out) replayed as one hipGraph.  A handle that crosses
+        // between "no limit" and "some limit", asking and not asking for the report, or a profile and none changes graphs; a change of a
+        // table's values only re-uploads it, which begin_call has put on the stream in front of the replay
         const int hs = hs_cur_;
-        // (... and one set for the plain synthesis kernel, one for its kMinGain form: a handle that crosses between "no limit" and "some
-        // limit" changes sets, a change of values only re-uploads the table, which begin_min_gain has put on the stream in front of the replay)
-        // (... and the same again for calls that ask for the frame report: the kReport forms, writing into the report staging.  A handle that
-        // alternates between asking and not asking switches sets; a call without a report replays the plain graphs)
-        // (... and once more for calls under a band profile: the kProfile forms.  A change of the profile's values only re-uploads the table,
-        // which begin_band_profile has put on the stream in front of the replay)
-        const int parity = hs | (hist_cur_ << 1) | (tail_cur_ << 2) | (min_gain ? 8 : 0) | (report ? 16 : 0) | (profile ? 32 : 0);
+        const int parity = frame_graph_index(setup, report != nullptr);
         if (!frame_graph_[parity]) {
             hipGraph_t graph = nullptr;
             // (relaxed mode and one capture at a time in the process: other threads -- other handles being created, the
@@ -2144,8 +2114,9 @@ bool Engine::run_call(const Call &c, std::string *err) {
                 ok = zero_copy || hipMemcpyAsync(d_in_, h_in_, bytes, hipMemcpyHostToDevice, stream_) == hipSuccess;
                 // (no reset table in the captured frame, whichever call happens to capture it: a one-frame call can restart a stream
                 // at frame 0 only, and that is the reset kernel begin_resets has already put in front of the graph)
-                float *rep = report ? (zero_copy ? h_report_ : d_report_) : nullptr;
-                ok = ok && run_device({0, 1, zero_copy ? h_in_ : d_in_, zero_copy ? h_out_ : d_out_, true, nullptr, min_gain, rep, 0, profile}, err);
+                Slice frame{0, 1, zero_copy ? h_in_ : d_in_, zero_copy ? h_out_ : d_out_, true, report ? (zero_copy ? h_report_ : d_report_) : nullptr, &setup};
+                frame.without_reset_table = true;
+                ok = ok && run_device(frame, err);
                 ok = ok && (zero_copy || hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream_) == hipSuccess);
                 ok = ok && (zero_copy || !report || hipMemcpyAsync(h_report_, d_report_, rbytes, hipMemcpyDeviceToHost, stream_) == hipSuccess);
                 // zero-copy frames end with the completion word (the output is already in host memory when that node runs)
@@ -2212,7 +2183,7 @@ bool Engine::run_call(const Call &c, std::string *err) {
         }
     }
     if (hipMemcpyAsync(d_in_, h_in_, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) goto fail;
-    if (!run_device({0, T, d_in_, d_out_, true, &table, min_gain, report ? d_report_ : nullptr, link, profile}, err)) return false;
+    if (!run_device({0, T, d_in_, d_out_, true, report ? d_report_ : nullptr, &setup}, err)) return false;
     if (hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
     if (report && hipMemcpyAsync(h_report_, d_report_, rbytes, hipMemcpyDeviceToHost, stream_) != hipSuccess) goto fail;
     if (hipStreamSynchronize(stream_) != hipSuccess) goto fail;
@@ -2336,7 +2307,7 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
         if (c.high_band) {
             HighBandArgs h;
             h.x = hb_x, h.y = d_in_, h.out = c.out, h.report = inner.report;
-            h.min_gain = c.opt.min_gain ? (const float *) mg_tab_.d : nullptr;  // (begin_min_gain has put the call's table on the stream)
+            h.min_gain = c.opt.min_gain ? (const float *) mg_tab_.d : nullptr;  // (the inner call's begin_call has put the table on the stream)
             h.resets = flags;
             h.xs = d_hb_x_[hb_cur_], h.ys = d_hb_y_[hb_cur_], h.ss = d_hb_s_[hb_cur_];
             h.xs_next = d_hb_x_[hb_cur_ ^ 1], h.ys_next = d_hb_y_[hb_cur_ ^ 1], h.ss_next = d_hb_s_[hb_cur_ ^ 1];
@@ -2447,23 +2418,23 @@ bool Engine::level_ready(std::string *err) {
     return true;
 }
 
-// The leveller's two launches behind the kernels of a device-pointer call (run_call); `ctl`: the call's control rows (control_rows);
+// The leveller's two launches behind the kernels of a device-pointer call (run_call), under the control rows of the call's setup;
 // `report` is what the call's synthesis kernels have written -- the caller's (then column 3 of a levelling stream's rows becomes its gain)
 // or the engine's.  A call on which some stream limits (StreamOptions::limiter) runs the tracker only if some stream levels, and then the
 // limiter's launch, which applies the ramp too, in the place of level_apply_kernel.
-bool Engine::run_level(const Call &c, const float *report, bool callers_report, const uint8_t *ctl, std::string *err) {
+bool Engine::run_level(const Call &c, const float *report, bool callers_report, const CallSetup &setup, std::string *err) {
     LevelArgs a;
-    a.set = (const LevelSetting *) lv_tab_.d, a.state = d_lv_state_, a.ctl = ctl;
+    a.set = (const LevelSetting *) lv_tab_.d, a.state = d_lv_state_, a.ctl = setup.ctl;
     a.report = report, a.report_out = callers_report ? (float *) report : nullptr;
     a.gains = d_lv_gains_, a.out = c.out;
     a.B = B_, a.T = c.T;
-    if (!c.opt.limiter) {
+    if (!(setup.stages & kStageLimiter)) {
         launch_level(a, stream_);
     } else {
-        if (c.opt.level) launch_level_track(a, stream_);
+        if (setup.stages & kStageLevel) launch_level_track(a, stream_);
         LimitArgs m;
-        m.set = (const LimiterSetting *) lm_tab_.d, m.state = d_lm_state_, m.ctl = ctl;
-        m.gains = c.opt.level ? d_lv_gains_ : nullptr, m.out = c.out;
+        m.set = (const LimiterSetting *) lm_tab_.d, m.state = d_lm_state_, m.ctl = setup.ctl;
+        m.gains = setup.stages & kStageLevel ? d_lv_gains_ : nullptr, m.out = c.out;
         m.B = B_, m.T = c.T;
         launch_limit(m, stream_);
     }
@@ -2535,10 +2506,10 @@ bool Engine::comfort_ready(std::string *err) {
     return true;
 }
 
-// The counter's launch in front of the kernels of a device-pointer call (run_call); `ctl`: the call's control rows (control_rows).
-bool Engine::run_comfort(const Call &c, const uint8_t *ctl, std::string *err) {
+// The counter's launch in front of the kernels of a device-pointer call (run_call), under the control rows of the call's setup.
+bool Engine::run_comfort(const Call &c, const CallSetup &setup, std::string *err) {
     ComfortArgs a;
-    a.set = (const ComfortSetting *) cf_tab_.d, a.state = d_cf_state_, a.ctl = ctl, a.n = d_cf_n_;
+    a.set = setup.comfort_set, a.state = d_cf_state_, a.ctl = setup.ctl, a.n = d_cf_n_;
     a.B = B_, a.Bpad = Bpad_, a.T = c.T;
     launch_comfort(a, stream_);
     const hipError_t e = hipGetLastError();
@@ -2844,7 +2815,7 @@ Status Engine::process(const Call &c, std::string *err) {
         }
     }
     // the output stages: what they are not combined with yet (the owner refuses all of it by name first)
-    for (const OutputStage &s : kOutputStages) {
+    for (const OutputStage &s : output_stages()) {
         if (!s.on(c.opt)) continue;
         if (c.opt.channel_link || c.high_band || fr_rate_) {
             *err = std::string(s.name) + (c.opt.channel_link ? " is not available yet while the channel link is on." :

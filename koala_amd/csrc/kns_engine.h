@@ -314,19 +314,16 @@ private:
     int hb_cur_ = 0;
     unsigned hb_epoch_ = 0;
     bool high_band_ready(const Call &c, std::string *err);  // the buffers, and the state cleared when the call's epoch is new
-    // what run_device is given: the frames [t0, t0 + T) of a call, their device buffers, and the call's reset table if it has one
-    struct ResetTable;
+    // what run_device is given: the frames [t0, t0 + T) of a call, their device buffers, and what the call has prepared for all of its slices
+    struct CallSetup;
     struct Slice {
         int t0, T;
         const int16_t *d_pcm;
         int16_t *d_out;
         bool allow_recompute;  // the synthesis kernel may rebuild the spectrum from d_pcm (false: d_out overlaps it)
-        ResetTable *resets;
-        const float *min_gain;  // the call's per-stream minimum gains on the device [Bpad] (begin_min_gain), nullptr: no limit in force
-        float *d_report = nullptr;  // the slice's frame report [B][T][4] (device-visible memory, rows T frames apart), nullptr: not asked for
-        int link = 0;  // the call's linked channels: channels() when StreamOptions::channel_link is set (then min_gain is not null), else 0
-        const float *profile = nullptr;  // the call's band profile on the device [Bpad][kProfileRow] (begin_band_profile; then min_gain is not null and link is 0), nullptr: neutral
-        bool comfort = false;  // the call's comfort noise: its two tables (cf_tab_, cfa_tab_) and run_comfort's counter values (then profile is not null)
+        float *d_report;       // the slice's frame report [B][T][4] (device-visible memory, rows T frames apart), nullptr: not asked for
+        CallSetup *call;       // begin_call's; not const: the first slice that needs the reset table uploads it
+        bool without_reset_table = false;  // the captured one-frame graph: the call's other tables, but never a reset table (run_call, at the capture)
     };
     bool run_device(const Slice &s, std::string *err);
     void *dalloc(size_t bytes, bool zero);
@@ -383,7 +380,7 @@ private:
     // staging for host-pointer calls: [B][Tmax * 256] each; chunked calls use them as two slots of [B][Tc * 256]
     int16_t *d_in_ = nullptr, *d_out_ = nullptr, *h_in_ = nullptr, *h_out_ = nullptr;
     // host-pointer calls with more than one sub-chunk: copy-in, compute and copy-out run on three streams
-    bool process_host_pipelined(const Call &c, bool pinned, ResetTable *resets, const float *min_gain, const float *profile, std::string *err);
+    bool process_host_pipelined(const Call &c, bool pinned, CallSetup *setup, std::string *err);
     std::vector<int> host_schedule(int T) const;  // its sub-chunk lengths
     std::vector<int> dev_host_sched_;             // developer override (KOALA_AMD_HOST_SCHED)
     // calls of several frames as a wavefront over (stage, frame): kns_engine.cpp, run_wave
@@ -410,16 +407,23 @@ private:
     int host_chunk_ = 1;
     size_t host_pipeline_min_bytes_ = 0;
 
-    // hipGraph of one host-pointer frame (copy-in, 23 kernels, copy-out); built on first use
-    hipGraphExec_t frame_graph_[64] = {};  // one per combination of the hidden-state / history / tail ping-pong indices, (bit 3) of
-                                           // "an attenuation limit is in force": the captured synthesis kernel is the plain or the kMinGain form,
-                                           // (bit 4) of "a frame report is asked for": the kReport forms, writing to the report staging,
-                                           // and (bit 5) of "a band profile is in force": the kProfile forms (bit 3 is set then)
+    // hipGraph of one host-pointer frame (copy-in, 23 kernels, copy-out); built on first use.  A captured frame has the state buffers it
+    // reads and writes, and the form of its synthesis kernel, baked in: one graph per combination of the bits below
+    enum FrameGraphBit {
+        kGraphHidden = 1, kGraphHistory = 2, kGraphTail = 4,  // the three ping-pong indices (a one-frame call flips the hidden state only, calls of several frames in between the other two as well)
+        kGraphMinGain = 8,   // an attenuation limit is in force: the kMinGain form, not the plain one
+        kGraphReport = 16,   // a frame report is asked for: the kReport forms, writing to the report staging
+        kGraphProfile = 32   // a band profile is in force: the kProfile forms (kGraphMinGain is set then)
+    };
+    int frame_graph_index(const CallSetup &s, bool report) const {  // the graph a one-frame call replays
+        return hs_cur_ * kGraphHidden | hist_cur_ * kGraphHistory | tail_cur_ * kGraphTail | (s.min_gain ? kGraphMinGain : 0) | (report ? kGraphReport : 0) | (s.profile ? kGraphProfile : 0);
+    }
+    hipGraphExec_t frame_graph_[2 * kGraphProfile] = {};
     // completion word of the zero-copy one-frame replays (kns_stft.hip, frame_done_kernel): the host spins on a word in page-locked
     // memory instead of sleeping in hipStreamSynchronize, whose wake-up is what made p99 drift away from p50 on a busy host
     unsigned *d_frame_count_ = nullptr, *h_frame_word_ = nullptr;
     unsigned frame_seq_ = 0;
-    bool frame_graph_signals_[64] = {};
+    bool frame_graph_signals_[2 * kGraphProfile] = {};
     bool spin_wait_ = true;
     bool use_graph_ = true, no_small_ = false, no_zero_copy_ = false, no_recompute_ = false, debug_taps_ = false;
     // developer switches (all read once in init() through dev_env(): compiled out of the product library)
@@ -455,7 +459,7 @@ private:
     };
     // Per-frame stream resets (kns_engine.cpp, begin_resets).  A call's packed table -- per (m-tile, frame) the rows that restart, uint32
     // [mtiles][T] -- goes through a slot of rs_ring_ to d_rs_ on the stream that runs the call's kernels, a frame-0 mask to d_rmask_.
-    // The table belongs to its call: process*() own it and hand it to run_device with every slice.
+    // The table belongs to its call: it is part of the call's CallSetup, which run_device is given with every slice.
     UploadRing rs_ring_, rsf_ring_, pk_ring_, fr_ring_;  // (fr_ring_: a fractional call's table; rsf_ring_: the sample-rate stages' copy of a call's reset flags; pk_ring_: a packet call's table)
     unsigned *d_rs_ = nullptr;
     struct ResetTable {
@@ -488,10 +492,35 @@ private:
     bool table_alloc(SettingTable *t, size_t row);  // the ring and the device table, both or neither
     bool put_table(SettingTable *t, size_t row, const void *rows, unsigned rev, const char *what, std::string *err);
     SettingTable mg_tab_, pf_tab_, lv_tab_, lm_tab_, cf_tab_, cfa_tab_;  // gains, band profile, leveller, limiter, comfort settings and amplitudes
-    // begin_min_gain / begin_band_profile: the device table a call's synthesis kernels read (nullptr: no limit / the neutral profile); a
-    // profiled call that is linked, carries the high band or comes without the gains is the owner's to refuse, and fails here
-    bool begin_min_gain(const Call &c, const float **table, std::string *err);
-    bool begin_band_profile(const Call &c, const float **table, std::string *err);
+    // The output stages behind the mask, in the order they have always been checked: what a refusal calls a stage, its buffers at first use
+    // and its setting tables (`rows`: the call's, nullptr: the stage is off).  refuse_stages: the first stage present is refused for `why`
+    enum StageBit { kStageLevel = 1, kStageLimiter = 2, kStageComfort = 4 };
+    struct OutputStage {
+        unsigned bit;                    // in CallSetup::stages
+        const char *name, *call, *what;  // "<name> is not ...", "<call> runs on ...", "... the buffers of <what>."
+        bool carries_profile;            // its kernels carry the band profile's clamp: such a call comes with the profile (and its own tables)
+        bool (Engine::*ready)(std::string *);
+        unsigned StreamOptions::*rev;
+        struct Table { SettingTable Engine::*tab; size_t row; const void *(*rows)(const StreamOptions &); } table[2];
+        bool on(const StreamOptions &o) const { return table[0].rows(o) != nullptr; }
+    };
+    static const OutputStage (&output_stages())[3];
+    static bool refuse_stages(const StreamOptions &o, const char *why, std::string *err);
+    // What a call has prepared, once, for all of its slices: the call's mutable state below its entry
+    struct CallSetup {
+        ResetTable resets;
+        const float *min_gain = nullptr;  // the per-stream minimum gains on the device [Bpad], nullptr: no limit in force
+        const float *profile = nullptr;   // the band profile on the device [Bpad][kProfileRow], nullptr: neutral (else min_gain is not null and link is 0)
+        const ComfortSetting *comfort_set = nullptr;  // comfort noise: its two tables (read beside run_comfort's counter values; then profile is not null), nullptr: off
+        const float *comfort_amp = nullptr;
+        int link = 0;                   // linked channels: channels() when StreamOptions::channel_link is set (then min_gain is not null), else 0
+        unsigned stages = 0;            // the StageBit of every output stage that is on
+        const uint8_t *ctl = nullptr;   // the stages' control rows on the device (control_rows), nullptr: no byte is set
+    };
+    // Fills the setup of the call about to run, before anything of it is enqueued and outside any capture: the refusals of a combination of
+    // Call members (the owner's to refuse by name first; a refused call enqueues nothing), then the reset table, the setting tables and the
+    // control rows, on the handle's stream in front of the call's kernels or graph replay.  device_rows: pcm / out are device memory
+    bool begin_call(const Call &c, bool device_rows, CallSetup *setup, std::string *err);
     // The control rows of a call with an output stage: `hold` and the reset flags as uint8 [B][T + 1], uploaded once per call, in front of its
     // first launch that reads them, and only when some byte is set (*ctl = nullptr otherwise).  One buffer [B][Tmax + 1] and one ring,
     // allocated by whichever stage is used first (ctl_ready)
@@ -501,10 +530,10 @@ private:
     bool control_rows(const Call &c, const uint8_t **ctl, std::string *err);
     // Output leveller (StreamOptions::level): the state [Bpad][2], allocated fresh by the first call that levels or by level_state and part
     // of every reset; the gain pairs [B][Tmax][2]; and the report [B][Tmax][4] of a call whose caller asked for none.  run_level: the two
-    // launches behind a device-pointer call's kernels
+    // launches behind a device-pointer call's kernels, for the stages and under the control rows of the call's setup
     float *d_lv_state_ = nullptr, *d_lv_gains_ = nullptr, *d_lv_rep_ = nullptr;
     bool level_ready(std::string *err);
-    bool run_level(const Call &c, const float *report, bool callers_report, const uint8_t *ctl, std::string *err);
+    bool run_level(const Call &c, const float *report, bool callers_report, const CallSetup &setup, std::string *err);
     // Peak limiter (StreamOptions::limiter): g of every stream [Bpad], allocated at 1 by the first call that limits or by limiter_state --
     // together with the leveller's buffers, whose gain pairs the limiter's launch reads -- and part of every reset.  run_level launches it in
     // level_apply_kernel's place
@@ -512,10 +541,10 @@ private:
     bool limiter_ready(std::string *err);
     // Comfort noise (StreamOptions::comfort): the counters [Bpad], allocated at 0 by the first call that fills or by comfort_state and part of
     // every reset; the counter values of a call's frames [Bpad][Tmax].  run_comfort: the counter's launch in front of a device-pointer
-    // call's kernels
+    // call's kernels, under the control rows of the call's setup
     uint32_t *d_cf_state_ = nullptr, *d_cf_n_ = nullptr;
     bool comfort_ready(std::string *err);
-    bool run_comfort(const Call &c, const uint8_t *ctl, std::string *err);
+    bool run_comfort(const Call &c, const CallSetup &setup, std::string *err);
     // level_state, limiter_state, comfort_state: N values of type T per stream, `fresh` on a handle that never used the stage
     template <class T, int N>
     Status stage_state(bool set, int count, const int32_t *streams, T *state, const T (&fresh)[N], T *Engine::*dev, bool (Engine::*ready)(std::string *), std::string *err);
