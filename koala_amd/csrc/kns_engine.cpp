@@ -744,13 +744,7 @@ Engine::~Engine() {
     if (h_in_) (void) hipHostFree(h_in_);
     if (h_out_) (void) hipHostFree(h_out_);
     if (h_report_) (void) hipHostFree(h_report_);
-    rs_ring_.release();
-    rsf_ring_.release();
-    recof_ring_.release();
-    for (SettingTable *t : {&mg_tab_, &pf_tab_, &lv_tab_, &lm_tab_, &cf_tab_, &cfa_tab_}) t->ring.release();
-    ctl_ring_.release();
-    pk_ring_.release();
-    fr_ring_.release();
+    for (Upload *u : uploads()) u->release();
     for (int i = 0; i < 4; ++i)
         if (aev_out_[i]) (void) hipEventDestroy(aev_out_[i]);
     for (int i = 0; i < 2; ++i) {
@@ -902,34 +896,39 @@ void Engine::launch_resets(const uint8_t *d_mask) {
     if (fr_rate_) launch_fractional_reset(fractional_state_args(), d_mask, stream_);
 }
 
-bool Engine::UploadRing::ready(size_t slot_bytes) {
-    if (host[0]) return true;
+bool Engine::Upload::ready(Engine *e, size_t bytes, bool zero) {
+    if (d) return true;
+    const bool pinned = host[0] != nullptr;  // (the ring of an earlier try whose dalloc failed)
     bool ok = true;
-    for (int i = 0; i < kResetRing && ok; ++i)
-        ok = hipHostMalloc(&host[i], slot_bytes, hipHostMallocDefault) == hipSuccess &&
+    for (int i = 0; i < kUploadRing && ok && !pinned; ++i)
+        ok = hipHostMalloc(&host[i], bytes, hipHostMallocDefault) == hipSuccess &&
              hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         (void) hipGetLastError();
         release();
+        return false;
     }
-    return ok;
+    d = e->dalloc(bytes, zero);
+    return d != nullptr;
 }
 
-int Engine::UploadRing::acquire() {
-    const int k = (int) (n % kResetRing);
-    if (pending[k] && hipEventSynchronize(ev[k]) != hipSuccess) return -1;
+void *Engine::Upload::take(int *slot) {
+    const int k = (int) (n % kUploadRing);
+    if (pending[k] && hipEventSynchronize(ev[k]) != hipSuccess) return nullptr;
     pending[k] = false;
     ++n;
-    return k;
+    *slot = k;
+    return host[k];
 }
 
-bool Engine::UploadRing::uploaded(int slot, hipStream_t stream) {
-    pending[slot] = hipEventRecord(ev[slot], stream) == hipSuccess;
+bool Engine::Upload::send(int slot, size_t bytes, hipStream_t stream, void *to) {
+    pending[slot] = hipMemcpyAsync(to ? to : d, host[slot], bytes, hipMemcpyHostToDevice, stream) == hipSuccess &&
+                    hipEventRecord(ev[slot], stream) == hipSuccess;
     return pending[slot];
 }
 
-void Engine::UploadRing::release() {
-    for (int i = 0; i < kResetRing; ++i) {
+void Engine::Upload::release() {
+    for (int i = 0; i < kUploadRing; ++i) {
         if (host[i]) (void) hipHostFree(host[i]);
         if (ev[i]) (void) hipEventDestroy(ev[i]);
         host[i] = nullptr;
@@ -941,10 +940,9 @@ void Engine::UploadRing::release() {
 // Per-frame stream resets of the call about to run (Call::resets, uint8 [B][T] host memory), before anything of the call is enqueued
 // (begin_call); `table` is the setup's, fresh.  Resets at frame 0 only: the reset kernel in front of the call, which then takes its normal route.
 // Resets at some frame t > 0 (refused for a several-frame front-end, whose feature history the reset arms do not rebuild): the mask is
-// packed per (m-tile, frame) into a page-locked ring slot -- bit r of word [mt][t] = stream 16 mt + r restarts right before frame t -- and
-// `table` says so; run_device uploads the slot on the stream of the call's kernels and reads it through the kernels' reset arms
-// (kRouteChunkedResets).  A slot is reused four calls later, after the copy that read it has completed (an event): the asynchronous
-// window is three calls, and a device-pointer caller waits only when it is four calls ahead of the GPU.
+// packed per (m-tile, frame) into a slot of rs_up_ -- bit r of word [mt][t] = stream 16 mt + r restarts right before frame t -- and
+// `table` says so; run_device sends the slot on the stream of the call's kernels and reads the table through the kernels' reset arms
+// (kRouteChunkedResets).  A slot is as large as the larger of the two things it may carry, the table and the frame-0 mask.
 bool Engine::begin_resets(int T, const uint8_t *mask, ResetTable *table, std::string *err) {
     if (!mask) return true;
     bool first = false, late = false;
@@ -959,26 +957,21 @@ bool Engine::begin_resets(int T, const uint8_t *mask, ResetTable *table, std::st
         return false;
     }
     const int mtb = Bpad_ / 16;
-    if (!d_rs_) {  // first use: the ring and the device table
-        const bool ok = rs_ring_.ready(std::max((size_t) mtb * Tmax_ * 4, (size_t) Bpad_));
-        unsigned *d = ok ? (unsigned *) dalloc((size_t) mtb * Tmax_ * 4, false) : nullptr;
-        if (!d) {
-            *err = "Failed to allocate the buffers of per-frame stream resets.";
-            return false;
-        }
-        d_rs_ = d;
+    if (!rs_up_.ready(this, std::max((size_t) mtb * Tmax_ * 4, (size_t) Bpad_))) {
+        *err = "Failed to allocate the buffers of per-frame stream resets.";
+        return false;
     }
-    const int k = rs_ring_.acquire();
-    if (k < 0) {
+    int k;
+    void *slot = rs_up_.take(&k);
+    if (!slot) {
         *err = hip_last_error();
         return false;
     }
     if (!late) {  // frame 0 only: the reset kernel on the call's stream, right in front of it
-        uint8_t *bytes = (uint8_t *) rs_ring_.host[k];
+        uint8_t *bytes = (uint8_t *) slot;
         memset(bytes, 0, (size_t) Bpad_);
         for (int b = 0; b < B_; ++b) bytes[b] = mask[(size_t) b * T] != 0;
-        const bool ok = hipMemcpyAsync(d_rmask_, bytes, (size_t) Bpad_, hipMemcpyHostToDevice, stream_) == hipSuccess &&
-                        rs_ring_.uploaded(k, stream_);
+        const bool ok = rs_up_.send(k, (size_t) Bpad_, stream_, d_rmask_);
         if (ok) launch_reset(reset_args(d_rmask_), stream_);
         const hipError_t e = hipGetLastError();
         if (!ok || e != hipSuccess) {
@@ -987,7 +980,7 @@ bool Engine::begin_resets(int T, const uint8_t *mask, ResetTable *table, std::st
         }
         return true;
     }
-    unsigned *w = (unsigned *) rs_ring_.host[k];
+    unsigned *w = (unsigned *) slot;
     memset(w, 0, (size_t) mtb * T * 4);
     table->frame.assign((size_t) T, 0);
     for (int b = 0; b < B_; ++b) {
@@ -1005,18 +998,11 @@ bool Engine::begin_resets(int T, const uint8_t *mask, ResetTable *table, std::st
     return true;
 }
 
-bool Engine::table_alloc(SettingTable *t, size_t row) {
-    if (t->d) return true;
-    t->row = row;
-    t->d = t->ring.ready((size_t) Bpad_ * row) ? dalloc((size_t) Bpad_ * row, false) : nullptr;
-    return t->d != nullptr;
-}
-
 // A per-stream setting of the call about to run (`rows`: host memory, B rows of `row` bytes), before anything of the call is enqueued and
-// outside any capture.  When the call's revision is not the one the device table holds, the rows go through a slot of the table's ring (rows
-// past B: zero) to the device on the handle's stream, where every kernel of the previous call is in front of the copy -- a call in flight
-// keeps the setting it was issued under -- and every kernel of this one behind it; an unchanged setting costs a call nothing.  The caller's
-// rows have been read when this returns; a device-pointer caller waits only when it is four changed tables ahead of the GPU.
+// outside any capture.  When the call's revision is not the one the device table holds, the rows go (rows past B: zero) to the device on
+// the handle's stream, where every kernel of the previous call is in front of the copy -- a call in flight keeps the setting it was issued
+// under -- and every kernel of this one behind it; an unchanged setting costs a call nothing.  The caller's rows have been read when this
+// returns.
 bool Engine::put_table(SettingTable *t, size_t row, const void *rows, unsigned rev, const char *what, std::string *err) {
     if (!table_alloc(t, row)) {
         (void) hipGetLastError();
@@ -1024,13 +1010,13 @@ bool Engine::put_table(SettingTable *t, size_t row, const void *rows, unsigned r
         return false;
     }
     if (t->valid && t->rev == rev) return true;
-    const int k = t->ring.acquire();
-    if (k >= 0) {
-        memcpy(t->ring.host[k], rows, (size_t) B_ * row);
-        memset((char *) t->ring.host[k] + (size_t) B_ * row, 0, (size_t) (Bpad_ - B_) * row);
+    int k;
+    char *slot = (char *) t->up.take(&k);
+    if (slot) {
+        memcpy(slot, rows, (size_t) B_ * row);
+        memset(slot + (size_t) B_ * row, 0, (size_t) (Bpad_ - B_) * row);
     }
-    if (k < 0 || hipMemcpyAsync(t->d, t->ring.host[k], (size_t) Bpad_ * row, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-        !t->ring.uploaded(k, stream_)) {
+    if (!slot || !t->up.send(k, (size_t) Bpad_ * row, stream_)) {
         *err = hip_last_error();
         t->valid = false;
         return false;
@@ -1090,15 +1076,15 @@ bool Engine::begin_call(const Call &c, bool device_rows, CallSetup *cs, std::str
     if (!begin_resets(c.T, c.resets, &cs->resets, err)) return false;
     if (o.min_gain && !put_table(&mg_tab_, 4, o.min_gain, o.min_gain_rev, "the per-stream attenuation limit", err)) return false;
     if (o.band_profile && !put_table(&pf_tab_, (size_t) kProfileRow * 4, o.band_profile, o.band_profile_rev, "the band profile", err)) return false;
-    cs->min_gain = o.min_gain ? (const float *) mg_tab_.d : nullptr;
-    cs->profile = o.band_profile ? (const float *) pf_tab_.d : nullptr;
+    cs->min_gain = o.min_gain ? (const float *) mg_tab_.up.d : nullptr;
+    cs->profile = o.band_profile ? (const float *) pf_tab_.up.d : nullptr;
     for (const OutputStage &s : output_stages()) {
         if (!(cs->stages & s.bit)) continue;
         if (!(this->*s.ready)(err)) return false;
         for (const OutputStage::Table &t : s.table)
             if (t.tab && !put_table(&(this->*t.tab), t.row, t.rows(o), o.*s.rev, s.what, err)) return false;
     }
-    if (cs->stages & kStageComfort) cs->comfort_set = (const ComfortSetting *) cf_tab_.d, cs->comfort_amp = (const float *) cfa_tab_.d;
+    if (cs->stages & kStageComfort) cs->comfort_set = (const ComfortSetting *) cf_tab_.up.d, cs->comfort_amp = (const float *) cfa_tab_.up.d;
     return !cs->stages || control_rows(c, &cs->ctl, err);
 }
 
@@ -1321,11 +1307,10 @@ bool Engine::run_device(const Slice &slice, std::string *err) {
     ResetTable *table = !slice.without_reset_table && slice.call->resets.slot >= 0 ? &slice.call->resets : nullptr;
     const bool resets = table && std::any_of(table->frame.begin() + slice.t0, table->frame.begin() + slice.t0 + T, [](uint8_t v) { return v != 0; });
     if (resets && !table->uploaded) {  // the call's table, on the stream of its kernels (its first sub-chunk that needs it)
-        (void) hipMemcpyAsync(d_rs_, rs_ring_.host[table->slot], (size_t) mtb * table->T * 4, hipMemcpyHostToDevice, stream_);
-        (void) rs_ring_.uploaded(table->slot, stream_);
+        (void) rs_up_.send(table->slot, (size_t) mtb * table->T * 4, stream_);
         table->uploaded = true;
     }
-    const unsigned *rs = resets ? d_rs_ : nullptr;
+    const unsigned *rs = resets ? (const unsigned *) rs_up_.d : nullptr;
     const int rs_pitch = table ? table->T : 0, rs_t0 = slice.t0;  // (where these frames are in the table)
 
     AnalysisArgs an;
@@ -2197,18 +2182,6 @@ fail:
 
 // ------------------------------------------------------------------------------------------------ handles that are not at 16 kHz
 
-bool Engine::rate_ready(std::string *err) {  // the device copy of a call's reset flags and its upload ring, at first use
-    if (d_rs_flags_) return true;
-    uint8_t *d = rsf_ring_.ready((size_t) B_ * Tmax_) ? (uint8_t *) dalloc((size_t) B_ * Tmax_, false) : nullptr;
-    if (!d) {
-        (void) hipGetLastError();
-        *err = "Failed to allocate the buffers of per-frame stream resets.";
-        return false;
-    }
-    d_rs_flags_ = d;
-    return true;
-}
-
 // High-band carry (Call::high_band): at the first such call the state's three ping-pong pairs and the engine's own report buffer; at that call and at
 // a call whose epoch is not the last one seen -- the owner turned the feature on again -- the state is cleared on the handle's stream, so the
 // high band is that of streams that begin with this call.
@@ -2253,16 +2226,18 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
     (void) hipSetDevice(device_);
     bool any = false;
     for (size_t i = 0; c.resets && i < (size_t) B_ * T && !any; ++i) any = c.resets[i] != 0;
-    if (any && !rate_ready(err)) return false;
     const uint8_t *flags = nullptr;
     if (any) {
-        const int k = rsf_ring_.acquire();
-        if (k < 0) goto fail;
-        memcpy(rsf_ring_.host[k], c.resets, (size_t) B_ * T);
-        if (hipMemcpyAsync(d_rs_flags_, rsf_ring_.host[k], (size_t) B_ * T, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-            !rsf_ring_.uploaded(k, stream_))
-            goto fail;
-        flags = d_rs_flags_;
+        if (!rsf_up_.ready(this, (size_t) B_ * Tmax_)) {
+            *err = "Failed to allocate the buffers of per-frame stream resets.";
+            return false;
+        }
+        int k;
+        void *slot = rsf_up_.take(&k);
+        if (!slot) goto fail;
+        memcpy(slot, c.resets, (size_t) B_ * T);
+        if (!rsf_up_.send(k, (size_t) B_ * T, stream_)) goto fail;
+        flags = (const uint8_t *) rsf_up_.d;
     }
     if (c.high_band && !high_band_ready(c, err)) return false;
     {
@@ -2307,7 +2282,7 @@ bool Engine::run_call_rate(const Call &c, std::string *err) {
         if (c.high_band) {
             HighBandArgs h;
             h.x = hb_x, h.y = d_in_, h.out = c.out, h.report = inner.report;
-            h.min_gain = c.opt.min_gain ? (const float *) mg_tab_.d : nullptr;  // (the inner call's begin_call has put the table on the stream)
+            h.min_gain = c.opt.min_gain ? (const float *) mg_tab_.up.d : nullptr;  // (the inner call's begin_call has put the table on the stream)
             h.resets = flags;
             h.xs = d_hb_x_[hb_cur_], h.ys = d_hb_y_[hb_cur_], h.ss = d_hb_s_[hb_cur_];
             h.xs_next = d_hb_x_[hb_cur_ ^ 1], h.ys_next = d_hb_y_[hb_cur_ ^ 1], h.ss_next = d_hb_s_[hb_cur_ ^ 1];
@@ -2326,12 +2301,6 @@ fail:
 
 // ------------------------------------------------------------------------------------------------ output leveller
 
-// The control rows' buffer and ring, at the first use of an output stage.
-bool Engine::ctl_ready() {
-    if (!d_ctl_) d_ctl_ = ctl_ring_.ready((size_t) B_ * (Tmax_ + 1)) ? (uint8_t *) dalloc((size_t) B_ * (Tmax_ + 1), false) : nullptr;
-    return d_ctl_ != nullptr;
-}
-
 // The call's `hold` and reset flags as one row of T + 1 bytes per stream (run_call: in front of the call's first launch), only when one of
 // them is set: the comfort counter's launch, the leveller's tracker and the limiter's launch read the same rows.
 bool Engine::control_rows(const Call &c, const uint8_t **ctl, std::string *err) {
@@ -2341,21 +2310,20 @@ bool Engine::control_rows(const Call &c, const uint8_t **ctl, std::string *err) 
     for (size_t i = 0; c.resets && i < (size_t) B_ * T && !any; ++i) any = c.resets[i] != 0;
     *ctl = nullptr;
     if (!any) return true;
-    const int k = ctl_ring_.acquire();
-    if (k >= 0) {
-        uint8_t *rows = (uint8_t *) ctl_ring_.host[k];
+    int k;
+    uint8_t *rows = (uint8_t *) ctl_up_.take(&k);
+    if (rows) {
         for (int b = 0; b < B_; ++b) {
             uint8_t *row = rows + (size_t) b * (T + 1);
             row[0] = c.hold && c.hold[b] ? 1 : 0;
             for (int t = 0; t < T; ++t) row[1 + t] = c.resets && c.resets[(size_t) b * T + t] ? 1 : 0;
         }
     }
-    if (k < 0 || hipMemcpyAsync(d_ctl_, ctl_ring_.host[k], (size_t) B_ * (T + 1), hipMemcpyHostToDevice, stream_) != hipSuccess ||
-        !ctl_ring_.uploaded(k, stream_)) {
+    if (!rows || !ctl_up_.send(k, (size_t) B_ * (T + 1), stream_)) {
         *err = hip_last_error();
         return false;
     }
-    *ctl = d_ctl_;
+    *ctl = (const uint8_t *) ctl_up_.d;
     return true;
 }
 
@@ -2424,7 +2392,7 @@ bool Engine::level_ready(std::string *err) {
 // limiter's launch, which applies the ramp too, in the place of level_apply_kernel.
 bool Engine::run_level(const Call &c, const float *report, bool callers_report, const CallSetup &setup, std::string *err) {
     LevelArgs a;
-    a.set = (const LevelSetting *) lv_tab_.d, a.state = d_lv_state_, a.ctl = setup.ctl;
+    a.set = (const LevelSetting *) lv_tab_.up.d, a.state = d_lv_state_, a.ctl = setup.ctl;
     a.report = report, a.report_out = callers_report ? (float *) report : nullptr;
     a.gains = d_lv_gains_, a.out = c.out;
     a.B = B_, a.T = c.T;
@@ -2433,7 +2401,7 @@ bool Engine::run_level(const Call &c, const float *report, bool callers_report, 
     } else {
         if (setup.stages & kStageLevel) launch_level_track(a, stream_);
         LimitArgs m;
-        m.set = (const LimiterSetting *) lm_tab_.d, m.state = d_lm_state_, m.ctl = setup.ctl;
+        m.set = (const LimiterSetting *) lm_tab_.up.d, m.state = d_lm_state_, m.ctl = setup.ctl;
         m.gains = setup.stages & kStageLevel ? d_lv_gains_ : nullptr, m.out = c.out;
         m.B = B_, m.T = c.T;
         launch_limit(m, stream_);
@@ -2541,25 +2509,23 @@ bool Engine::state_ready(std::string *err) {
     if (d_state_) return true;
     (void) hipSetDevice(device_);
     // (the records' version-1 part and the sample-rate stages' part are staged apart: the state kernels see the records they always saw)
-    uint8_t *d = (uint8_t *) dalloc((size_t) B_ * state_record_bytes(taps_), false);
-    int32_t *t = d ? (int32_t *) dalloc((size_t) Bpad_ * 4, false) : nullptr;
-    if (t && rate_ != kRate16k && !d_state_rs_) d_state_rs_ = (uint8_t *) dalloc((size_t) B_ * rs_record_bytes(rate_), false);
-    if (rate_ != kRate16k && !d_state_rs_) t = nullptr;
-    if (t && pk_max_ && !d_state_pk_) d_state_pk_ = (uint8_t *) dalloc((size_t) B_ * pk_record_bytes(rate_), false);
-    if (pk_max_ && !d_state_pk_) t = nullptr;
-    if (!d || !t || !recof_ring_.ready((size_t) Bpad_ * 4)) {
+    bool ok = recof_up_.ready(this, (size_t) Bpad_ * 4);
+    if (ok && rate_ != kRate16k && !d_state_rs_) d_state_rs_ = (uint8_t *) dalloc((size_t) B_ * rs_record_bytes(rate_), false);
+    ok = ok && (rate_ == kRate16k || d_state_rs_);
+    if (ok && pk_max_ && !d_state_pk_) d_state_pk_ = (uint8_t *) dalloc((size_t) B_ * pk_record_bytes(rate_), false);
+    ok = ok && (!pk_max_ || d_state_pk_);
+    uint8_t *d = ok ? (uint8_t *) dalloc((size_t) B_ * state_record_bytes(taps_), false) : nullptr;
+    if (!d) {
         // (what was allocated stays on the handle's lists and goes with the handle; the next call tries the rest again)
         (void) hipGetLastError();
         *err = "Failed to allocate the staging buffers of stream records.";
         return false;
     }
-    d_recof_ = t;
     d_state_ = d;
     return true;
 }
 
-// Checks a stream list (nullptr: 0 .. count - 1) and uploads its inverse -- stream -> record, -1 = not listed -- on the handle's stream
-// from the next slot of a page-locked ring (a slot is rewritten once the copy that read it four uploads back has completed).
+// Checks a stream list (nullptr: 0 .. count - 1); state_list uploads its inverse -- stream -> record, -1 = not listed -- on the handle's stream.
 Status Engine::check_stream_list(int count, const int32_t *streams, std::vector<int32_t> *inv, std::string *err) const {
     if (count < 1 || count > B_) {
         *err = "`count` " + std::to_string(count) + " is outside [1, " + std::to_string(B_) + "].";
@@ -2588,10 +2554,10 @@ Status Engine::state_list(int count, const int32_t *streams, std::string *err) {
     const Status listed = check_stream_list(count, streams, &inv, err);
     if (listed != Status::kOk) return listed;
     if (!state_ready(err)) return Status::kRuntime;
-    const int k = recof_ring_.acquire();
-    if (k >= 0) memcpy(recof_ring_.host[k], inv.data(), (size_t) Bpad_ * 4);
-    if (k < 0 || hipMemcpyAsync(d_recof_, recof_ring_.host[k], (size_t) Bpad_ * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-        !recof_ring_.uploaded(k, stream_)) {
+    int k;
+    void *slot = recof_up_.take(&k);
+    if (slot) memcpy(slot, inv.data(), (size_t) Bpad_ * 4);
+    if (!slot || !recof_up_.send(k, (size_t) Bpad_ * 4, stream_)) {
         *err = hip_last_error();
         return Status::kRuntime;
     }
@@ -2604,7 +2570,7 @@ StateArgs Engine::state_args() const {
     a.tail[0] = d_tail_[tail_cur_], a.tail[1] = d_tail_[tail_cur_ ^ 1];
     a.hstate[0] = d_hstate_[hs_cur_], a.hstate[1] = d_hstate_[hs_cur_ ^ 1];
     a.fhist = d_fhist_;
-    a.rec_of = d_recof_;
+    a.rec_of = (const int32_t *) recof_up_.d;
     a.records = d_state_;
     const StateHeader h{kStateMagic, pk_max_ ? kStateVersionPacket : rate_ == kRate16k ? kStateVersion : kStateVersionRate, (uint32_t) taps_,
                         (uint32_t) prec_, model_key_, rate_ == kRate16k && !pk_max_ ? 0u : (uint32_t) rate_, 0};
@@ -2630,7 +2596,7 @@ void Engine::launch_states(bool import, bool packet_part) {
     ResampleStateArgs a;
     for (int c = 0; c < 2; ++c) a.state_in[c] = d_rs_state_[0][rs_cur_ ^ c], a.state_out[c] = d_rs_state_[1][rs_cur_ ^ c];
     a.hist_in = rs_in_hist(rate_), a.hist_out = rs_out_hist(rate_);
-    a.rec_of = d_recof_;
+    a.rec_of = (const int32_t *) recof_up_.d;
     a.records = d_state_rs_;
     a.rec_bytes = (uint32_t) rs_record_bytes(rate_);
     a.Bpad = Bpad_;
@@ -2927,9 +2893,8 @@ bool Engine::enable_packets(int max_samples, std::string *err) {
     d_pk_in_ = (int16_t *) dalloc((size_t) B_ * K * F * 2, false);
     d_pk_out_ = (int16_t *) dalloc((size_t) B_ * K * F * 2, false);
     d_pk_rep_ = (float *) dalloc((size_t) B_ * K * 16, false);
-    d_pk_tab_ = (int32_t *) dalloc(tab_bytes, false);
-    if (!d_pk_pin_ || !d_pk_pout_ || !d_pk_fill_[0] || !d_pk_fill_[1] || !d_pk_in_ || !d_pk_out_ || !d_pk_rep_ || !d_pk_tab_ ||
-        !pk_ring_.ready(tab_bytes)) {
+    if (!d_pk_pin_ || !d_pk_pout_ || !d_pk_fill_[0] || !d_pk_fill_[1] || !d_pk_in_ || !d_pk_out_ || !d_pk_rep_ ||
+        !pk_up_.ready(this, tab_bytes)) {
         (void) hipGetLastError();
         *err = "Failed to allocate the buffers of a packet handle.";
         return false;
@@ -2943,7 +2908,7 @@ PacketStateArgs Engine::packet_state_args() const {
     PacketStateArgs a;
     a.pin = d_pk_pin_, a.pout = d_pk_pout_;
     a.fill_in = d_pk_fill_[0], a.fill_out = d_pk_fill_[1];
-    a.rec_of = d_recof_;
+    a.rec_of = (const int32_t *) recof_up_.d;
     a.records = d_state_pk_;
     a.rec_bytes = (uint32_t) pk_record_bytes(rate_);
     a.Bpad = Bpad_, a.F = rs_frame_length(rate_), a.import = 0;
@@ -2957,7 +2922,7 @@ PacketStateArgs Engine::packet_state_args() const {
 // format_in_kernel over the whole rows [B][max_samples] (the caller owns them), the call's table, the masked reset of `restart`,
 // packet_in_kernel, the sub-calls through process_frames -- routes, held streams, rate stages, attenuation limit and report as they are --
 // packet_out_kernel, and on a format handle format_out_kernel, which writes row b's first counts[b] elements only, from the call's table
-// (d_pk_tab_ starts with the counts).  A call without a sample (restarts only) moves and converts no samples.  Host pointers: the staging
+// (pk_up_'s starts with the counts).  A call without a sample (restarts only) moves and converts no samples.  Host pointers: the staging
 // stands in for the caller's device memory, and of what comes back only a row's first counts[b] elements and a stream's first k_b report
 // rows are copied on: the rest of the caller's bytes stay.
 Status Engine::run_packets(const PacketCall &c, std::string *err) { return fr_rate_ ? run_fractional(c, err) : run_packet_call(c, fmt_, ch_, err); }
@@ -3121,32 +3086,32 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string
     const int nsub = (int) cuts.size() - 1;
     // the call's table, and the restart mask behind it
     const size_t tab_ints = (size_t) Bpad_ + 2 + (size_t) Tmax_;
-    const int slot = pk_ring_.acquire();
-    if (slot < 0) {
+    int slot;
+    int32_t *tab = (int32_t *) pk_up_.take(&slot);
+    if (!tab) {
         *err = hip_last_error();
         return Status::kRuntime;
     }
-    int32_t *tab = (int32_t *) pk_ring_.host[slot];
     uint8_t *mask = (uint8_t *) (tab + tab_ints);
     memset(tab, 0, tab_ints * 4 + (size_t) Bpad_);
     memcpy(tab, c.counts, (size_t) B_ * 4);
     tab[Bpad_] = nsub;
     memcpy(tab + Bpad_ + 1, cuts.data(), cuts.size() * 4);
     for (int b = 0; any_restart && b < B_; ++b) mask[b] = c.restart[b] ? 1 : 0;
-    if (hipMemcpyAsync(d_pk_tab_, tab, tab_ints * 4 + (size_t) Bpad_, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-        !pk_ring_.uploaded(slot, stream_)) {
+    if (!pk_up_.send(slot, tab_ints * 4 + (size_t) Bpad_, stream_)) {
         *err = hip_last_error();
         return Status::kRuntime;
     }
+    const int32_t *d_tab = (const int32_t *) pk_up_.d;
     if (any_restart) {
-        launch_resets((const uint8_t *) (d_pk_tab_ + tab_ints));
+        launch_resets((const uint8_t *) (d_tab + tab_ints));
         for (int b = 0; b < B_; ++b)
             if (c.restart[b]) pk_fill_[b] = 0;
     }
     PacketArgs a;
     a.user_in = io.in16;
     a.user_out = io.out16;
-    a.tab = d_pk_tab_;
+    a.tab = d_tab;
     a.pin = d_pk_pin_, a.pout = d_pk_pout_;
     a.fill_in = d_pk_fill_[0], a.fill_out = d_pk_fill_[1];
     a.frames = d_pk_in_;
@@ -3182,7 +3147,7 @@ Status Engine::run_packet_call(const PacketCall &c, int fmt, int ch, std::string
         pk_fill_[b] = pk_fill_[b] + c.counts[b] - k[b] * F;
         if (c.frames) c.frames[b] = k[b];
     }
-    return packet_end(c, fmt, ch, io, d_pk_tab_, k.data(), kmax, err);
+    return packet_end(c, fmt, ch, io, d_tab, k.data(), kmax, err);
 }
 
 // ------------------------------------------------------------------------------------------------ packet handles at 44 100 and 22 050 Hz
@@ -3207,12 +3172,11 @@ bool Engine::enable_fractional(int rate, int max_samples, std::string *err) {
     d_fr_hist_[1] = (int16_t *) dalloc((size_t) Bpad_ * kFrOutHist * 2, true);
     d_fr_phase_[0] = (int32_t *) dalloc((size_t) Bpad_ * 4, true);
     d_fr_phase_[1] = (int32_t *) dalloc((size_t) Bpad_ * 4, true);
-    d_fr_tab_ = (int32_t *) dalloc(tab_bytes, true);
     const std::vector<float> h_in = fr_table(U, U, T), h_out = fr_table(kFrDown, kFrDown, kFrOutTaps);
     d_fr_taps_[0] = (float *) upload(h_in.data(), h_in.size() * 4);
     d_fr_taps_[1] = (float *) upload(h_out.data(), h_out.size() * 4);
-    if (!d_fr_in_ || !d_fr_out_ || !d_fr_hist_[0] || !d_fr_hist_[1] || !d_fr_phase_[0] || !d_fr_phase_[1] || !d_fr_tab_ || !d_fr_taps_[0] ||
-        !d_fr_taps_[1] || !fr_ring_.ready(tab_bytes)) {
+    if (!d_fr_in_ || !d_fr_out_ || !d_fr_hist_[0] || !d_fr_hist_[1] || !d_fr_phase_[0] || !d_fr_phase_[1] || !d_fr_taps_[0] || !d_fr_taps_[1] ||
+        !fr_up_.ready(this, tab_bytes, true)) {
         (void) hipGetLastError();
         *err = "Failed to allocate the buffers of a handle at " + std::to_string(rate) + " Hz.";
         return false;
@@ -3251,22 +3215,23 @@ Status Engine::run_fractional(const PacketCall &c, std::string *err) {
     PacketIo io;
     st = packet_begin(c, fmt_, ch_, kmax, any_restart, any_count, &io, &nothing, err);
     if (st != Status::kOk || nothing) return st;
-    const int slot = fr_ring_.acquire();
-    if (slot < 0) {
+    int slot;
+    int32_t *tab = (int32_t *) fr_up_.take(&slot);
+    if (!tab) {
         *err = hip_last_error();
         return Status::kRuntime;
     }
-    int32_t *tab = (int32_t *) fr_ring_.host[slot];
     uint8_t *mask = (uint8_t *) (tab + Bpad_);
     memset(tab, 0, (size_t) Bpad_ * 5);
     memcpy(tab, c.counts, (size_t) B_ * 4);
     for (int b = 0; any_restart && b < B_; ++b) mask[b] = c.restart[b] ? 1 : 0;
-    if (hipMemcpyAsync(d_fr_tab_, tab, (size_t) Bpad_ * 5, hipMemcpyHostToDevice, stream_) != hipSuccess || !fr_ring_.uploaded(slot, stream_)) {
+    if (!fr_up_.send(slot, (size_t) Bpad_ * 5, stream_)) {
         *err = hip_last_error();
         return Status::kRuntime;
     }
+    const int32_t *d_tab = (const int32_t *) fr_up_.d;
     if (any_restart) {
-        launch_resets((const uint8_t *) (d_fr_tab_ + Bpad_));
+        launch_resets((const uint8_t *) (d_tab + Bpad_));
         for (int b = 0; b < B_; ++b)
             if (c.restart[b]) pk_fill_[b] = 0, fr_phase_[b] = 0;
     }
@@ -3276,7 +3241,7 @@ Status Engine::run_fractional(const PacketCall &c, std::string *err) {
     FractionalArgs a;
     a.in = io.in16;
     a.out = d_fr_in_;
-    a.counts = d_fr_tab_;
+    a.counts = d_tab;
     a.hist = d_fr_hist_[0], a.phase = d_fr_phase_[0], a.taps = d_fr_taps_[0];
     a.in_stride = c.max_samples, a.out_stride = pk_max_, a.U = U;
     launch_fractional_in(a, B_, stream_);
@@ -3303,7 +3268,7 @@ Status Engine::run_fractional(const PacketCall &c, std::string *err) {
         fr_phase_[b] = (fr_phase_[b] + c.counts[b]) % kFrDown;
         if (c.frames) c.frames[b] = k[b];
     }
-    return packet_end(c, fmt_, ch_, io, d_fr_tab_, k.data(), kmax, err);
+    return packet_end(c, fmt_, ch_, io, d_tab, k.data(), kmax, err);
 }
 
 // ------------------------------------------------------------------------------------------------ sample formats

@@ -96,7 +96,7 @@ struct Call {
     const int16_t *pcm;
     int16_t *out;
     // Per-frame stream resets: host memory, uint8 [num_streams][T] (non-zero at [b][t]: stream b restarts from the fresh state right before
-    // frame t).  Consumed before the call returns -- packed into the reset ring (kns_engine.cpp, begin_resets) -- so the caller may
+    // frame t).  Consumed before the call returns -- packed into an upload slot (kns_engine.cpp, begin_resets) -- so the caller may
     // overwrite it then.  nullptr or all zero: the plain call.
     const uint8_t *resets = nullptr;
     // Held streams: host memory, uint8 [num_streams].  The streams with hold[b] != 0 are not advanced: their state after the call is bit for
@@ -258,17 +258,16 @@ private:
     // record (version 2), of reset() and of a call's per-frame resets.
     bool advance(const Call &c, std::string *err) { return rate_ == kRate16k ? run_call(c, err) : run_call_rate(c, err); }
     bool run_call_rate(const Call &c, std::string *err);
-    bool rate_ready(std::string *err);  // d_rs_flags_ and its ring
     // the state kernels of export / import / held streams: the engine's and, at such a rate, the stages'; packet_part: and a packet handle's
     // (not for held streams: a sub-call of a packet call does not touch the packetiser's state, whose two lengths differ inside a call)
     void launch_states(bool import, bool packet_part);
     void launch_resets(const uint8_t *d_mask);  // every reset kernel of the handle (d_mask: device [Bpad], null: every stream)
     // packet handles: the packetiser's state (kns_kernels.h, PacketArgs), the sub-calls' stacked frame matrices and reports
-    // [B][Tmax F] / [B][Tmax][4], the call table and its upload ring, and the HOST MIRROR of
+    // [B][Tmax F] / [B][Tmax][4], the call table (pk_up_) and the HOST MIRROR of
     // fill, from which a call is planned without a look at the device (updated by calls, resets and import_state)
     int pk_max_ = 0;
     int16_t *d_pk_pin_ = nullptr, *d_pk_pout_ = nullptr, *d_pk_in_ = nullptr, *d_pk_out_ = nullptr;
-    int32_t *d_pk_fill_[2] = {nullptr, nullptr}, *d_pk_tab_ = nullptr;
+    int32_t *d_pk_fill_[2] = {nullptr, nullptr};
     float *d_pk_rep_ = nullptr;
     uint8_t *d_state_pk_ = nullptr;  // the packet part of the staged stream records [B][pk_record_bytes]
     std::vector<int32_t> pk_fill_;
@@ -291,11 +290,11 @@ private:
     Status packet_begin(const PacketCall &c, int fmt, int ch, int kmax, bool any_restart, bool any_count, PacketIo *io, bool *nothing, std::string *err);
     Status packet_end(const PacketCall &c, int fmt, int ch, const PacketIo &io, const int32_t *d_counts, const int32_t *k, int kmax, std::string *err);
     // fractional handles: the rate, the caller's max_samples, the inner path's rows [B][pk_max_] on either side of the 16 kHz packet call,
-    // the stages' tables and per-stream state ([0]: in-stage, [1]: out-stage), the call table (int32 counts[Bpad], uint8 restart[Bpad])
-    // with its upload ring, and the HOST MIRROR of N mod 441, from which a call's inner counts are planned without a look at the device
+    // the stages' tables and per-stream state ([0]: in-stage, [1]: out-stage), the call table (fr_up_: int32 counts[Bpad], uint8
+    // restart[Bpad]), and the HOST MIRROR of N mod 441, from which a call's inner counts are planned without a look at the device
     int fr_rate_ = 0, fr_max_ = 0;
     int16_t *d_fr_in_ = nullptr, *d_fr_out_ = nullptr, *d_fr_hist_[2] = {nullptr, nullptr};
-    int32_t *d_fr_phase_[2] = {nullptr, nullptr}, *d_fr_tab_ = nullptr;
+    int32_t *d_fr_phase_[2] = {nullptr, nullptr};
     float *d_fr_taps_[2] = {nullptr, nullptr};
     std::vector<int32_t> fr_phase_;
     FractionalStateArgs fractional_state_args() const;
@@ -304,7 +303,6 @@ private:
     int16_t *d_rs_state_[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [in-stage, out-stage][ping-pong copy], [Bpad][hist] each
     int rs_cur_ = 0;
     std::vector<float> rs_taps_[2];     // the in-stage's and the out-stage's table h_U (kns_kernels.h)
-    uint8_t *d_rs_flags_ = nullptr;     // a call's per-frame resets on the device, uint8 [B][T], and their upload ring
     uint8_t *d_state_rs_ = nullptr;     // the stages' part of the staged stream records [B][rs_record_bytes]
     // high-band carry (Call::high_band; kns_kernels.h, HighBandArgs): the per-stream state as ping-pong pairs -- x [Bpad][hb_x_hist],
     // y [Bpad][kHbYHist], s' [Bpad][2] -- allocated (zeroed) by the first such call and part of reset(); the report [B][Tmax][4] of a call
@@ -444,52 +442,56 @@ private:
     int last_analysis_seg_ = 0, last_synth_seg_ = 0, last_synth_launches_ = 0;
 #endif
 
-    // A ring of page-locked upload slots, one per call that may still be in flight: a slot is handed out again once the copy that read
-    // it kResetRing uses ago has completed (an event per slot).  Allocated at first use, all slots or none; release() frees it (~Engine).
-    static constexpr int kResetRing = 4;
-    struct UploadRing {
-        void *host[kResetRing] = {};
-        hipEvent_t ev[kResetRing] = {};
-        bool pending[kResetRing] = {};  // a copy out of the slot has been enqueued since the slot was handed out
+    // A table that a call sends to the device in front of its kernels: the device buffer `d` and the ring of page-locked slots that feeds it,
+    // one slot per call that may still be in flight.  take() hands out the next slot for the caller to fill, once the copy that read it
+    // kUploadRing takes ago has completed (an event per slot); send() enqueues the slot's copy to `d` -- or to `to` -- on `stream` and records
+    // the slot's event there.  Four slots: the asynchronous window is three calls, and a device-pointer caller waits only when it is four
+    // uploads ahead of the GPU.  ready(): at first use the ring, all slots or none, then `d` through dalloc, so it goes with the handle's
+    // other allocations; after a failure the next call tries what is missing again.  release() frees the ring (~Engine, over uploads()).
+    static constexpr int kUploadRing = 4;
+    struct Upload {
+        void *d = nullptr;
+        void *host[kUploadRing] = {};
+        hipEvent_t ev[kUploadRing] = {};
+        bool pending[kUploadRing] = {};  // a copy out of the slot has been enqueued since the slot was handed out
         unsigned n = 0;
-        bool ready(size_t slot_bytes);
-        int acquire();                                // the next slot, once its last copy has completed; -1: HIP failure
-        bool uploaded(int slot, hipStream_t stream);  // a copy out of `slot` has just been enqueued on `stream`
+        // bytes: of a slot and of `d`; e: whose dalloc gives `d`; zero: `d` is cleared at allocation (the fractional call table only, as
+        // it has always been: every other table is written whole by its first upload)
+        bool ready(Engine *e, size_t bytes, bool zero = false);
+        void *take(int *slot);                                   // nullptr: HIP failure
+        bool send(int slot, size_t bytes, hipStream_t stream, void *to = nullptr);
         void release();
     };
-    // Per-frame stream resets (kns_engine.cpp, begin_resets).  A call's packed table -- per (m-tile, frame) the rows that restart, uint32
-    // [mtiles][T] -- goes through a slot of rs_ring_ to d_rs_ on the stream that runs the call's kernels, a frame-0 mask to d_rmask_.
+    // Per-frame stream resets (kns_engine.cpp, begin_resets): a call's packed table -- per (m-tile, frame) the rows that restart, uint32
+    // [mtiles][T] -- goes through rs_up_ on the stream that runs the call's kernels, a frame-0 mask through the same ring to d_rmask_.
     // The table belongs to its call: it is part of the call's CallSetup, which run_device is given with every slice.
-    UploadRing rs_ring_, rsf_ring_, pk_ring_, fr_ring_;  // (fr_ring_: a fractional call's table; rsf_ring_: the sample-rate stages' copy of a call's reset flags; pk_ring_: a packet call's table)
-    unsigned *d_rs_ = nullptr;
+    // rsf_up_: the sample-rate stages' copy of a call's reset flags, uint8 [B][T]; pk_up_, fr_up_: a packet call's and a fractional call's table
+    Upload rs_up_, rsf_up_, pk_up_, fr_up_;
     struct ResetTable {
-        int slot = -1, T = 0;        // the call's ring slot (-1: no stream restarts after frame 0, there is no table) and its length
+        int slot = -1, T = 0;        // the call's slot of rs_up_ (-1: no stream restarts after frame 0, there is no table) and its length
         bool uploaded = false;       // by the call's first run_device() that needed it
         std::vector<uint8_t> frame;  // [T]: some stream restarts at this frame of the call
     };
     bool begin_resets(int T, const uint8_t *mask, ResetTable *table, std::string *err);
     ResetArgs reset_args(const uint8_t *d_mask) const;  // the reset kernel's arguments (d_mask: device [Bpad], null: every stream)
 
-    // stream records (export_state / import_state / held streams): the device staging buffer [B_][state_bytes()], the stream -> record
-    // table on the device [Bpad_] and its upload ring
+    // stream records (export_state / import_state / held streams): the device staging buffer [B_][state_bytes()] and the stream -> record
+    // table, int32 [Bpad_]
     uint64_t model_key_ = 0;  // content hash of the parameters: the key of the shared weight image, the `model hash` of a record
     uint8_t *d_state_ = nullptr;
-    int32_t *d_recof_ = nullptr;
-    UploadRing recof_ring_;
-    // Per-stream settings (StreamOptions; DESIGN.md section 2, "Per-stream settings"): a feature's device table [Bpad][row] with its upload
-    // ring, and the owner's revision the table holds.  Configuration, not state: no reset, record or held stream touches a table.
+    Upload recof_up_;
+    // Per-stream settings (StreamOptions; DESIGN.md section 2, "Per-stream settings"): a feature's table [Bpad][row] and the owner's
+    // revision that the device holds.  Configuration, not state: no reset, record or held stream touches a table.
     // put_table: the table of the call about to run, on the handle's stream in front of the call's kernels or graph replay -- allocated at
-    // first use (`what`: the feature's name in the failure message), uploaded through a ring slot (rows past B: zero) when the call's
-    // revision is not the table's.  A table is never zeroed at allocation: all Bpad rows are uploaded, on the call's stream, before a kernel
-    // is given the pointer -- a memset on the handle's own stream would be unordered with that copy after set_stream.
+    // first use (`what`: the feature's name in the failure message), uploaded (rows past B: zero) when the call's revision is not the
+    // table's.  A table is never zeroed at allocation: all Bpad rows are uploaded, on the call's stream, before a kernel is given the
+    // pointer -- a memset on the handle's own stream would be unordered with that copy after set_stream.
     struct SettingTable {
-        void *d = nullptr;
-        UploadRing ring;
-        size_t row = 0;  // bytes per stream
+        Upload up;
         unsigned rev = 0;
         bool valid = false;
     };
-    bool table_alloc(SettingTable *t, size_t row);  // the ring and the device table, both or neither
+    bool table_alloc(SettingTable *t, size_t row) { return t->up.ready(this, (size_t) Bpad_ * row); }
     bool put_table(SettingTable *t, size_t row, const void *rows, unsigned rev, const char *what, std::string *err);
     SettingTable mg_tab_, pf_tab_, lv_tab_, lm_tab_, cf_tab_, cfa_tab_;  // gains, band profile, leveller, limiter, comfort settings and amplitudes
     // The output stages behind the mask, in the order they have always been checked: what a refusal calls a stage, its buffers at first use
@@ -522,12 +524,16 @@ private:
     // control rows, on the handle's stream in front of the call's kernels or graph replay.  device_rows: pcm / out are device memory
     bool begin_call(const Call &c, bool device_rows, CallSetup *setup, std::string *err);
     // The control rows of a call with an output stage: `hold` and the reset flags as uint8 [B][T + 1], uploaded once per call, in front of its
-    // first launch that reads them, and only when some byte is set (*ctl = nullptr otherwise).  One buffer [B][Tmax + 1] and one ring,
-    // allocated by whichever stage is used first (ctl_ready)
-    uint8_t *d_ctl_ = nullptr;
-    UploadRing ctl_ring_;
-    bool ctl_ready();
+    // first launch that reads them, and only when some byte is set (*ctl = nullptr otherwise).  One table [B][Tmax + 1], allocated by
+    // whichever stage is used first
+    Upload ctl_up_;
+    bool ctl_ready() { return ctl_up_.ready(this, (size_t) B_ * (Tmax_ + 1)); }
     bool control_rows(const Call &c, const uint8_t **ctl, std::string *err);
+    // every Upload of the handle, for ~Engine: a new table joins this list
+    std::vector<Upload *> uploads() {
+        return {&rs_up_, &rsf_up_, &pk_up_, &fr_up_, &recof_up_, &ctl_up_,
+                &mg_tab_.up, &pf_tab_.up, &lv_tab_.up, &lm_tab_.up, &cf_tab_.up, &cfa_tab_.up};
+    }
     // Output leveller (StreamOptions::level): the state [Bpad][2], allocated fresh by the first call that levels or by level_state and part
     // of every reset; the gain pairs [B][Tmax][2]; and the report [B][Tmax][4] of a call whose caller asked for none.  run_level: the two
     // launches behind a device-pointer call's kernels, for the stages and under the control rows of the call's setup

@@ -8,13 +8,15 @@ repeats after a warm-up.
       and one synchronise, timed by HIP events on the handles' stream.  The synthesis launch alone is read from the handles' own profile
       (pv_koala_batch_profile_*: events around every launch) in a second, shorter loop.
  (b2) the one-frame single-stream call (pv_koala_process, the hipGraph path): p50 / p99 of the host clock around the call, without a limit,
-      with gain 0.25, and again without (the plain graphs are still there).
+      with gain 0.25, again without (the plain graphs are still there), and with another gain before EVERY call: each such call uploads
+      its table, the path where the upload is the largest share of a call.  The setter stands outside the timed span.
 
 The prediction to hold the figures against: the arm adds 34 full-rate VALU instructions per lane and frame (17 products, 17 sums) to a
 kernel that issues roughly 1 700, about 2 % of the synthesis launch and 0.2 % of the bench step.
 
 (a), the bench's headline on this build against the parent commit's, is tools/ab.sh with the two libraries; its lines are added to the same
-file by hand, as are the file's first sections (assembly comparison, registers).  Writes the section "== 3. measured" of
+file by hand, as are the file's first sections (assembly comparison, registers).  --library: another build of the library (an A/B
+against a parent commit: the two alternate in one session); --one-frame-only: (b2) alone.  Writes the section "== 3. measured" of
 profiles/r09_min_gain.txt (or --out): what stands in front of that heading is kept.
 """
 import argparse
@@ -44,6 +46,8 @@ def main():
     ap.add_argument('--calls', type=int, default=0, help='calls per repeat (0: enough for about 20 ms)')
     ap.add_argument('--frames', type=int, default=4000, help='frames per phase of the single-stream measurement')
     ap.add_argument('--gain', type=float, default=0.25)
+    ap.add_argument('--library', default=None, help='alternative libpv_koala.so')
+    ap.add_argument('--one-frame-only', action='store_true')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r09_min_gain.txt'))
     a = ap.parse_args()
 
@@ -52,7 +56,7 @@ def main():
         sys.exit('min_gain_bench: no GPU (this tool measures; it has no CPU form)')
     import koala_amd
     import koala_amd.workload
-    koala_amd.build_native()
+    lib = a.library or koala_amd.build_native()
     model = koala_amd.default_model_path()
     lines = []
 
@@ -61,9 +65,9 @@ def main():
         lines.append(s)
 
     say('per-stream attenuation limit, bf16, %s, medians of %d repeats [10th .. 90th percentile]' % (torch.cuda.get_device_name(0), a.repeats))
-    for B, T in ((4096, 64), (1024, 64), (4096, 1)):
-        plain = koala_amd.create_batch('key', B, T, 'bf16', model_path=model)
-        limited = koala_amd.create_batch('key', B, T, 'bf16', model_path=model)
+    for B, T in () if a.one_frame_only else ((4096, 64), (1024, 64), (4096, 1)):
+        plain = koala_amd.create_batch('key', B, T, 'bf16', model_path=model, library_path=lib)
+        limited = koala_amd.create_batch('key', B, T, 'bf16', model_path=model, library_path=lib)
         limited.set_min_gain(a.gain)
         x = torch.from_numpy(np.ascontiguousarray(np.tile(koala_amd.workload.synth_streams(64, T, 1), (B // 64, 1)))).cuda()
         y = torch.zeros_like(x)
@@ -122,18 +126,20 @@ def main():
     # ---- the single-stream handle, one frame per call
     frame = np.ascontiguousarray(koala_amd.workload.synth_streams(1, 1, 2)[0])
     os.environ['KOALA_AMD_PRECISION'] = 'bf16'  # (the single-stream handle takes its precision from the environment)
-    k = koala_amd.create('key', model_path=model)
+    k = koala_amd.create('key', model_path=model, library_path=lib)
     say('(b2) pv_koala_process, one stream, one frame per call (hipGraph replay), %d calls per phase, host clock, us' % a.frames)
-    for name, g in (('no limit', 0.0), ('gain %g' % a.gain, a.gain), ('no limit again', 0.0)):
-        k.set_min_gain(g)
+    for name, g in (('no limit', 0.0), ('gain %g' % a.gain, a.gain), ('no limit again', 0.0), ('a new gain every call', None)):
+        k.set_min_gain(g or 0.0)
         v = []
         for i in range(200 + a.frames):
+            if g is None:
+                k.set_min_gain(a.gain + 0.001 * (i % 500))
             t0 = time.perf_counter()
             k.process(frame)
             if i >= 200:
                 v.append((time.perf_counter() - t0) * 1e6)
         v.sort()
-        say('    %-16s p50 %.1f   p90 %.1f   p99 %.1f' % (name, v[len(v) // 2], v[len(v) * 9 // 10], v[len(v) * 99 // 100]))
+        say('    %-22s p50 %.1f   p90 %.1f   p99 %.1f' % (name, v[len(v) // 2], v[len(v) * 9 // 10], v[len(v) * 99 // 100]))
     k.delete()
 
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
